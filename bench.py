@@ -6,7 +6,7 @@
 A *step* is one inner iteration of `richardson_lucy_MM` (lib/deconvolution.pyx:473-591) over one
 H x W x 3 fp32 frame; 5 steps make one outer iteration, which also pays for the `ut = u` copy and
 the residual-whiteness stop test (evaluated on device every outer iteration, `stop_test=2`: computed
-but never allowed to end the run, so that exactly K steps are timed).  Default workload =
+but never allowed to end the run, so that exactly K steps are timed; K must be a multiple of 5).  Default workload =
 BASELINE.json configs[2]: blind, 4096 x 4096 x 3, 15 x 15 initial PSF (the configuration the metric
 is quoted on); `--mode nonblind` gives the non-blind inner iteration on the same frame.  Inputs are
 synthetic and already resident in HBM when the timed region starts.
@@ -36,6 +36,30 @@ BYTES_PER_PX = {"synth_residual": 36.0, "backproject": 48.0, "update": 60.0, "ps
                 "update_synth": 72.0,
                 "synth_backproject": 84.0}  # update_synth: fused update + convolution, 4 reads + 2 writes; synth_backproject: A1 + A3 in one unit = S1 + S2 of SURVEY.md 8d (the residual is never materialised)
 ITER_BYTES_PER_PX = {"nonblind": 144.0, "blind": 204.0}
+DUMP_SAMPLE = 1 << 22   # `--dump-outputs`: float32 elements kept of a frame too large to write whole (16 MB; all files stay under 64 MB)
+
+
+def timed_steps(n):
+    """`--steps` in inner iterations: the library runs whole outer iterations of 5, so K must be a positive multiple of 5 (refused
+    otherwise, never rounded: exactly K steps are timed).  The untimed warm-up is rounded up to whole outer iterations instead."""
+    if n <= 0 or n % 5:
+        raise SystemExit("bench.py: --steps %d: steps are inner iterations, run 5 per outer iteration; give a positive multiple of 5" % n)
+    return n
+
+
+def dump_outputs(dirname, arrays):
+    """`--dump-outputs DIR`: what the timed run handed its caller, as DIR/<name>.npy (float32).  A frame of more than DUMP_SAMPLE
+    elements is written as `<name>_sample` (DUMP_SAMPLE flat positions drawn with seed 0, sorted, duplicates dropped: the same
+    positions in every run of the same arguments) plus `<name>_row_sums` (float64 sums over each row, every pixel counted)."""
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, np.float32)
+        if a.size <= DUMP_SAMPLE:
+            np.save(os.path.join(dirname, name + ".npy"), a)
+            continue
+        idx = np.unique(np.random.default_rng(0).integers(0, a.size, DUMP_SAMPLE))
+        np.save(os.path.join(dirname, name + "_sample.npy"), a.reshape(-1)[idx])
+        np.save(os.path.join(dirname, name + "_row_sums.npy"), a.sum(axis=1, dtype=np.float64))
 
 
 def labels(route, fuse=False):
@@ -292,7 +316,7 @@ def bench_bands(args, grp):
     M = N = args.size if args.size != 4096 else 12288
     MK = args.psf
     blind = args.mode == "blind"
-    steps, warm = ((args.steps + 4) // 5) * 5, ((args.warmup + 4) // 5) * 5
+    steps, warm = args.steps, ((args.warmup + 4) // 5) * 5
     conv = {"auto": 0, "vector": 1, "matrix": 2, "fft": 3}[args.conv]
     pad = MK // 2
     win = (M // 2 - 127, M // 2 + 128, N // 2 - 127, N // 2 + 128)      # 255-px window at the centre: straddles the bands for even N
@@ -351,7 +375,12 @@ def main():
     ap.add_argument("--no-preheat", action="store_true", help="skip the cold-start measurement and the 150-step clock pre-heat in front of the timed region")
     ap.add_argument("--bands", type=int, default=0, help="N > 0: ONE frame (--size, default 12288 here) split into N row bands, one rank per GPU "
                     "(lib.banded.BandRank: RCCL max / sum all-reduce + point-to-point halos); strong scaling, a secondary workload (SURVEY.md 8f N4)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write the u and PSF the timed run computed (rank 0's frame) "
+                    "as DIR/<name>.npy; frames above %d elements as a seeded sample plus float64 row sums" % DUMP_SAMPLE)
     args = ap.parse_args()
+    timed_steps(args.steps)
+    if args.dump_outputs and args.bands:
+        raise SystemExit("bench.py: --dump-outputs is not available with --bands (every rank holds only its own rows)")
 
     if args.bands:
         args.gpus = args.bands
@@ -367,8 +396,7 @@ def main():
         raise SystemExit(bench_bands(args, grp))
     M = N = args.size
     MK = args.psf
-    steps = ((args.steps + 4) // 5) * 5
-    warm = ((args.warmup + 4) // 5) * 5
+    steps, warm = args.steps, ((args.warmup + 4) // 5) * 5
     blind = args.mode == "blind"
     conv = {"auto": 0, "vector": 1, "matrix": 2, "fft": 3}[args.conv]
     if conv == 0 and os.environ.get("ICS_CONV_PATH", "")[:1] == "v":
@@ -424,6 +452,13 @@ def main():
     elapsed = time.perf_counter() - t0
     elapsed = grp.max(elapsed)
     assert st.inner_iterations == steps, (st.inner_iterations, steps)
+    if args.dump_outputs and grp.rank == 0:
+        # what richardson_lucy_MM's caller gets back from this run (lib/deconvolution.py): u in place, the PSF when blind, the image with tv_mode 1
+        u_out, _, psf_out = job.download()
+        outs = {"u": u_out, "psf": psf_out if blind else psf_true}
+        if args.tv_mode == 1:
+            outs["image"] = job.read(_native.BUF_IMAGE)
+        dump_outputs(args.dump_outputs, outs)
 
     # secondary measurement (not `value`): the other mode on the same resident frame, same schedule
     other = None
