@@ -6,6 +6,9 @@ import numpy as np
 
 import rl_mm_oracle as orc
 
+# oracle/make_golden_levels.py: the pyramid levels the fp16-split matrix cores serve under ICS_CONV_AUTO
+LEVEL_FIXTURES = ["nb_2048_k7", "nb_1448_k5", "nb_1024_k3", "nb_1448_k11", "nb_1061x1414_k9_corr", "bl_1024_k7", "nb_1024_k5_stop"]
+
 
 def load_golden(golden_dir, name):
     z = np.load(os.path.join(golden_dir, "rl_%s.npz" % name))
@@ -70,3 +73,53 @@ def psf_step_f32(psf, gradk, step, MK, correlation):
         return p, caller, dtpsf
     orc.normalize_kernel(p, MK)
     return p, p.copy(), dtpsf
+
+
+_large = {}
+
+
+def large_case(meta):
+    """orc.synth_case_large inputs of a fixture made by oracle/make_golden_{baseline,deep,levels}.py (one problem cached at a time)"""
+    key = (meta["M"], meta["N"], meta["MK"], meta["seed"], meta["blind"])
+    if key not in _large:
+        _large.clear()                      # one full-size problem in host memory at a time
+        _large[key] = orc.synth_case_large(meta["M"], meta["N"], meta["MK"], seed=meta["seed"], blind=bool(meta["blind"]))
+    return _large[key]
+
+
+def compare_samples(z, meta, tag, u, psf, gate, sums_tol):
+    """u and psf after a run against a sampled fixture (oracle/make_golden_deep.py keep()): crops, every n-th row and column of u
+    and the PSF within `gate` relative (of max |u_ref|), float64 moments and quadrant sums of the whole frame within `sums_tol`.
+    Returns (worst u error, psf error)."""
+    w = meta["where"]
+    c, s = w["centre"], w["seam"]
+    got = dict(centre=u[c[0]:c[1], c[2]:c[3]], seam=u[s[0]:s[1], s[2]:s[3]], corner=u[-w["corner"]:, -w["corner"]:], origin=u[:w["origin"], :w["origin"]])
+    if "u_rows_%s" % tag in z.files:
+        got.update(rows=u[::meta["row_step"]], cols=u[:, ::meta["row_step"]])
+    den = float(z["moments_%s" % tag][3])                               # max of the reference's u
+    errs = {k: float(np.max(np.abs(v.astype(np.float64) - z["u_%s_%s" % (k, tag)]))) / den for k, v in got.items()}
+    ep = rel_err(psf, z["psf_%s" % tag])
+    uf = u.astype(np.float64)
+    mom = np.array([uf.sum(), (uf ** 2).sum(), uf.min(), uf.max()])
+    h2, w2 = uf.shape[0] // 2, uf.shape[1] // 2
+    quad = np.array([[uf[a:a + h2, b:b + w2, ch].sum() for ch in range(3)] for a in (0, h2) for b in (0, w2)])
+    assert max(errs.values()) < gate, (tag, errs)
+    assert ep < gate, (tag, ep)
+    assert np.all(np.abs(mom - z["moments_%s" % tag]) <= sums_tol * np.abs(z["moments_%s" % tag]))
+    assert np.all(np.abs(quad - z["quadrants_%s" % tag]) <= sums_tol * np.abs(z["quadrants_%s" % tag]))
+    return max(errs.values()), ep
+
+
+def log_numbers(line):
+    return [float(t) for t in line.replace("|", " ").replace("=", " ").split() if t.replace(".", "").replace("-", "").isdigit()]
+
+
+def assert_log_matches(log, ref_log, rtol):
+    """the reference's own progress lines, line for line; a line that differs may differ only in its printed numbers (DoF extrema and
+    statistics printed with six decimals), within `rtol` / 2e-6 absolute"""
+    lines, ref = log.splitlines(), ref_log.splitlines()
+    assert len(lines) == len(ref), (lines, ref)
+    for lg, lr in zip(lines, ref):
+        if lg != lr:
+            vg, vr = log_numbers(lg), log_numbers(lr)
+            assert len(vg) == len(vr) and np.allclose(vg, vr, rtol=rtol, atol=2e-6), (lg, lr)

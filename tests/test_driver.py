@@ -110,9 +110,22 @@ def test_device_resident_driver_equals_the_host_driver(pyramid, preview, blur, c
     assert [l.split("=")[0] for l in strip(log_h)] == [l.split("=")[0] for l in strip(log_d)]   # same progress lines
 
 
+SMALL = dict(shape=(118, 141), K=5, mask=[60, 70], mask_size=61, iterations=3)
+# a 724 x 1024 picture with a 7-px blur: the non-blind levels (frames of 729 x 1029, 517 x 729 and 365 x 515, each with the final 7 x 7 PSF)
+# run on the fp16-split matrix cores under ICS_CONV_AUTO, the blind windows (257^2 / 7, 181^2 / 5, 129^2 / 3) on the small-frame
+# kernel.  Two outer iterations per call: `it > 1` (pyx:643) never holds, so no call takes a stop decision -- with three, the blind
+# windows' decisions have margins |M_r - M_r_prev| / M_r of 4e-6 ... 2e-5 here, below the reference's own fp32-FFT rounding.
+LEVELS = dict(shape=(724, 1024), K=7, mask=[362, 512], mask_size=255, iterations=2)
+
+
 @pytest.mark.gpu
-@pytest.mark.parametrize("pyramid,preview,blur", [(False, False, "static"), (True, False, "static"), (False, True, "static"), (False, False, "motion")])
-def test_device_resident_driver_against_the_oracle_solver(pyramid, preview, blur, capsys):
+@pytest.mark.parametrize("pyramid,preview,blur,picture", [
+    pytest.param(False, False, "static", SMALL, id="False-False-static"),
+    pytest.param(True, False, "static", SMALL, id="True-False-static"),
+    pytest.param(False, True, "static", SMALL, id="False-True-static"),
+    pytest.param(False, False, "motion", SMALL, id="False-False-motion"),
+    pytest.param(True, False, "static", LEVELS, id="True-False-static-724x1024-k7")])
+def test_device_resident_driver_against_the_oracle_solver(pyramid, preview, blur, picture, capsys):
     """SURVEY.md 8f N1 against an ORACLE run of the driver: `deblur_module(solver=<oracle richardson_lucy_MM>)` -- the host-frame
     driver with the pinned numpy restatement of lib/deconvolution.pyx doing every solver call (blind on the mask window, then
     the non-blind pass / preview; with `correlation` for motion blur) -- versus `deblur_module(device_resident=True)`, where
@@ -120,16 +133,18 @@ def test_device_resident_driver_against_the_oracle_solver(pyramid, preview, blur
     device kernel in both runs: the reference's skimage dependency is absent from the image, parity unpinned.)"""
     import deconvolve as dv
     import rl_mm_oracle as orc
-    case = orc.synth_case(118, 141, 5, seed=2)
+    K = picture["K"]
+    case = orc.synth_case(*picture["shape"], K, seed=2)
     pic = np.clip(case["image"] ** 2.2 * 255, 0, 255).astype(np.uint8)
-    kw = dict(mask=[60, 70], mask_size=61, display=False, iterations=3, pyramid=pyramid, save=False, preview=preview, blur=blur)
+    kw = dict(mask=picture["mask"], mask_size=picture["mask_size"], display=False, iterations=picture["iterations"], pyramid=pyramid,
+              save=False, preview=preview, blur=blur)
 
     def oracle_solver(image, u, psf, *args, **kwargs):
         return orc.richardson_lucy_MM(image, u, psf, *args, **kwargs)      # prints the reference's lines itself
 
-    out_o, psf_o = dv.deblur_module(pic, "o", ".", 5, solver=oracle_solver, **kw)
+    out_o, psf_o = dv.deblur_module(pic, "o", ".", K, solver=oracle_solver, **kw)
     log_o = capsys.readouterr().out
-    out_d, psf_d = dv.deblur_module(pic, "d", ".", 5, device_resident=True, **kw)
+    out_d, psf_d = dv.deblur_module(pic, "d", ".", K, device_resident=True, **kw)
     log_d = capsys.readouterr().out
     assert out_d.shape == out_o.shape
     ep = np.abs(psf_d - psf_o).max() / np.abs(psf_o).max()

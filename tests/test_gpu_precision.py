@@ -69,7 +69,7 @@ def run_conv(u, psf, conv):
     return out
 
 
-@pytest.mark.parametrize("MK", [15, 9, 31])
+@pytest.mark.parametrize("MK", [15, 9, 31, 3, 5, 7])
 def test_hot_pixel_1e4_inside_a_tile_keeps_22_bits_elsewhere(MK):
     rng = np.random.default_rng(MK)
     M, N = 300, 330
