@@ -168,6 +168,7 @@ struct ics_rl {
   // stop-test scratch (allocated for the window of the last run)
   float2* z; float2* tw; float* weights;
   int P, logP, wt, wb, wl, wr;
+  int Py, Px;                           // long-line path (a window side above 4096 px): per-axis transform sizes; 0 = the P x P path
   bool win_empty;
   float* h_scal;                        // pinned host mirror of scal (+ flags)
   bool uploaded;
@@ -713,7 +714,7 @@ extern "C" int ics_rl_exchange_rows(ics_rl* j, ics_group* g, int which, int send
 }
 
 // -------------------------------------------------------------------------------------------------
-// stop-test scratch: Gaussian window weights (pyx:393-404), twiddles, P x P x 3 complex buffer
+// stop-test scratch: Gaussian window weights (pyx:393-404), twiddles, P x P x 3 complex buffer (2 x 3 x H x Px on the long-line path)
 static int ensure_window(ics_rl* j, const ics_rl_params* p) {
   const int H = p->bottom - p->top, W = p->right - p->left;
   // an empty window: the reference slices error[top:bottom, left:right] into an empty array and every statistic is NaN
@@ -727,12 +728,21 @@ static int ensure_window(ics_rl* j, const ics_rl_params* p) {
   const int need = 2 * (H > W ? H : W) - 1;
   int P = 2, logP = 1;
   while (P < need) { P <<= 1; ++logP; }
-  if (P > 8192) return fail(ICS_ENOSUP, "stats window %dx%d needs a %d-point FFT (max 8192, i.e. windows up to 4096 px a side)", H, W, P);
+  // a side above 4096 px: the long-line path of ics_stats.hip, transform sizes per axis (an 8300 x 200 window must not take 32768^2)
+  const bool big = P > 8192;
+  int Py = 0, Px = 0;
+  if (big) {
+    Py = 64; Px = 64;
+    while (Py < 2 * H - 1) Py <<= 1;
+    while (Px < 2 * W - 1) Px <<= 1;
+    // a frame below 2 GiB has sides below 13 377 px: 2 * 13 376 - 1 < 32768, so no job gets here
+    if (Py > 32768 || Px > 32768) return fail(ICS_ENOSUP, "stats window %dx%d needs a %dx%d-point FFT (max 32768 a side)", H, W, Py, Px);
+  }
   // The cached key goes first: if an allocation below fails (z alone is 1.6 GB at P = 8192) the job must not keep the old key with
   // freed or half-built buffers -- jobs are reused (lib/deconvolution.py), and the next run with the previous window would pass the
   // cache check and launch the statistics kernels on them.
   auto drop = [&]() {
-    j->wt = j->wb = j->wl = j->wr = -1; j->P = 0; j->logP = 0;
+    j->wt = j->wb = j->wl = j->wr = -1; j->P = 0; j->logP = 0; j->Py = j->Px = 0;
     if (j->z) { j->ctx->pool.release(j->z); j->z = nullptr; }
     if (j->tw) { j->ctx->pool.release(j->tw); j->tw = nullptr; }
     if (j->weights) { j->ctx->pool.release(j->weights); j->weights = nullptr; }
@@ -740,15 +750,23 @@ static int ensure_window(ics_rl* j, const ics_rl_params* p) {
   drop();
   int rc;
   const int fail_at = ics_debug().fail_window_alloc.exchange(0, std::memory_order_relaxed);   // test hook: the fail_at-th allocation fails once
-  if ((rc = fail_at == 1 ? fail(ICS_ENOMEM, "stats window: allocation failed (test hook)") : dalloc(j->ctx, &j->z, (size_t)3 * P * P, false)) != ICS_OK) { drop(); return rc; }
-  if ((rc = fail_at == 2 ? fail(ICS_ENOMEM, "stats window: allocation failed (test hook)") : dalloc(j->ctx, &j->tw, (size_t)P / 2 + 1, false)) != ICS_OK) { drop(); return rc; }
-  if ((rc = fail_at == 3 ? fail(ICS_ENOMEM, "stats window: allocation failed (test hook)") : dalloc(j->ctx, &j->weights, (size_t)H * W, false)) != ICS_OK) { drop(); return rc; }
-  std::vector<float2> tw(P / 2 + 1);
-  for (int k = 0; k < P / 2; ++k) {
-    const double ang = -2.0 * M_PI * (double)k / (double)P;
-    tw[k] = make_float2((float)cos(ang), (float)sin(ang));
+  // long-line path: z holds the H rows that carry data, [3][H][Px], and their transpose (ics_stats.hip); tw = the full tables of both
+  // axes, [Py] then [Px]
+  const size_t nz = big ? (size_t)6 * H * Px : (size_t)3 * P * P, ntw = big ? (size_t)Py + Px : (size_t)P / 2 + 1;
+  if ((rc = fail_at == 1 ? fail(ICS_ENOMEM, "stats window: allocation of %zu bytes failed (test hook)", nz * sizeof(float2)) : dalloc(j->ctx, &j->z, nz, false)) != ICS_OK) { drop(); return rc; }
+  if ((rc = fail_at == 2 ? fail(ICS_ENOMEM, "stats window: allocation of %zu bytes failed (test hook)", ntw * sizeof(float2)) : dalloc(j->ctx, &j->tw, ntw, false)) != ICS_OK) { drop(); return rc; }
+  if ((rc = fail_at == 3 ? fail(ICS_ENOMEM, "stats window: allocation of %zu bytes failed (test hook)", (size_t)H * W * sizeof(float)) : dalloc(j->ctx, &j->weights, (size_t)H * W, false)) != ICS_OK) { drop(); return rc; }
+  std::vector<float2> tw(ntw);
+  if (big) {   // each entry from its own angle in double, stored as float (no recurrence)
+    for (int k = 0; k < Py; ++k) { const double ang = -2.0 * M_PI * (double)k / (double)Py; tw[k] = make_float2((float)cos(ang), (float)sin(ang)); }
+    for (int k = 0; k < Px; ++k) { const double ang = -2.0 * M_PI * (double)k / (double)Px; tw[Py + k] = make_float2((float)cos(ang), (float)sin(ang)); }
+  } else {
+    for (int k = 0; k < P / 2; ++k) {
+      const double ang = -2.0 * M_PI * (double)k / (double)P;
+      tw[k] = make_float2((float)cos(ang), (float)sin(ang));
+    }
+    tw[P / 2] = make_float2(0.f, 0.f);
   }
-  tw[P / 2] = make_float2(0.f, 0.f);
   // np.linspace(-1., 1., num, dtype=float32) then gaussian_weight(x, 0, 1) in float (pyx:35-36,397-401)
   auto serie = [](int num, std::vector<float>& out) {
     out.resize(num);
@@ -771,7 +789,7 @@ static int ensure_window(ics_rl* j, const ics_rl_params* p) {
   HIPCHK(hipMemcpyAsync(j->tw, tw.data(), tw.size() * sizeof(float2), hipMemcpyHostToDevice, j->ctx->stream));
   HIPCHK(hipMemcpyAsync(j->weights, w.data(), w.size() * sizeof(float), hipMemcpyHostToDevice, j->ctx->stream));
   HIPCHK(hipStreamSynchronize(j->ctx->stream));  // tw / w are stack-owned host vectors
-  j->P = P; j->logP = logP; j->wt = p->top; j->wb = p->bottom; j->wl = p->left; j->wr = p->right;
+  j->P = P; j->logP = logP; j->Py = Py; j->Px = Px; j->wt = p->top; j->wb = p->bottom; j->wl = p->left; j->wr = p->right;
   return ICS_OK;
 }
 
@@ -1343,6 +1361,7 @@ static int do_stats(ics_rl* j, const ics_rl_params* p, Prof& pr, int rearm = 0, 
   a.z = j->z; a.tw = j->tw; a.weights = j->weights;
   a.top = p->top; a.bottom = p->bottom; a.left = p->left; a.right = p->right;
   a.P = j->P; a.logP = j->logP; a.do_mr = p->stop_test != 0; a.geo = j->g;
+  a.Py = j->Py; a.Px = j->Px; a.twy = j->tw; a.twx = j->tw + j->Py;
   a.red = red_of(j); a.rearm = rearm;
   RC(pr.begin(ICS_K_STATS));
   HIPCHK(ics_launch_stats(a, st));

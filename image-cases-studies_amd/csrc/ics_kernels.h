@@ -222,6 +222,10 @@ struct IcsStatsArgs {
   int P, logP;
   int do_mr;
   IcsGeom geo;
+  // long-line path (a window side above 4096 px, ics_stats.hip): Py x Px transform, z = [3][H][Px] + its transpose [3][Px][H] complex; Py = 0 selects the P x P path
+  int Py, Px;
+  const float2* twy;   // [Py] exp(-2 pi i m / Py)
+  const float2* twx;   // [Px] exp(-2 pi i m / Px)
 };
 hipError_t ics_launch_stats(const IcsStatsArgs& a, hipStream_t s);
 hipError_t ics_launch_hasnan(const float* u, const IcsGeom& g, int* flag, hipStream_t s);

@@ -3,11 +3,13 @@
 //   A18 (lib/deconvolution.pyx:600-601): varu = std(u[window])^2,  Hu = ||error[window]||^2 / (n*3)
 //   A19 (lib/deconvolution.pyx:627-638): t = (e - mean e)/std e;  t /= max|t|;
 //        per channel  ac = convolve(t, rot180 t, "same");  M_r = mean(ac^2 * w)
-// The reference evaluates the autocorrelation with scipy's FFT convolution (pyx:632).  Here the
-// window (<= 1024 px) is zero-padded to a power of two P >= 2*max(H,W)-1 and autocorrelated by
+// The reference evaluates the autocorrelation with scipy's FFT convolution (pyx:632).  Here a
+// window of up to 4096 px a side is zero-padded to a power of two P >= 2*max(H,W)-1 (P <= 8192) and autocorrelated by
 // Wiener-Khinchin with a radix-2 Stockham FFT that runs entirely in LDS (one line per workgroup):
 // rows of the window, columns, |Z|^2 + inverse columns, inverse rows of the lags that are read.  3*P*P complex64 = 6 MB for a 255^2 window,
-// a few tens of microseconds per outer iteration, so the stop test never leaves the GPU.
+// a few tens of microseconds per outer iteration, so the stop test never leaves the GPU.  A larger window (a side above 4096 px, as
+// when the whole of a large frame is the window) takes the long-line path further down: Py x Px per axis, up to 32768 points, lines
+// above 8192 points split into in-LDS blocks.
 #include "ics_kernels.h"
 
 namespace {
@@ -138,14 +140,16 @@ __global__ __launch_bounds__(256) void k_mom2(IcsStatsArgs a) {
 //                sum ac^2 w  (pyx:633-638); the last workgroup out writes the scalars of the outer iteration
 // (Round 2 ran this as rows, columns, |Z|^2 + inverse columns, inverse rows, and a separate weighted sum: five launches and two more
 //  round trips of the 6 MB spectrum through L2 / HBM; as six separate element-wise + transform kernels before that.)
-__device__ __forceinline__ float2* fft_lines(float2* x, float2* y, int P, int logP, int C, int LP, const float2* __restrict__ tw, bool inverse) {
+// (ts: stride into the twiddle table, for a line of P points taken from the table of a transform ts times longer)
+__device__ __forceinline__ float2* fft_lines(float2* x, float2* y, int P, int logP, int C, int LP, const float2* __restrict__ tw, bool inverse,
+                                             int ts = 1) {
   const int t = P >> 1, tid = threadIdx.x, nthr = blockDim.x, logt = logP - 1;
   for (int s = 0, p = 1; s < logP; ++s, p <<= 1) {
     for (int q = tid; q < C * t; q += nthr) {
       const int cc = q >> logt, b = q & (t - 1);
       const int k = b & (p - 1);
       const int j = ((b - k) << 1) + k;
-      float2 w = tw[k * (t / p)];
+      float2 w = tw[k * (t / p) * ts];
       if (inverse) w.y = -w.y;
       const float2* xl = x + cc * LP; float2* yl = y + cc * LP;
       const float2 u0 = xl[b], v = xl[b + t];
@@ -280,6 +284,189 @@ __device__ void stats_final(const IcsStatsArgs& a) {
 }
 __global__ void k_stats_final(IcsStatsArgs a) { stats_final(a); }
 
+// ---- long-line path: a window side above 4096 px (Py or Px > 8192) ------------------------------------------------------
+// Same Wiener-Khinchin autocorrelation, transform sizes per axis (Py >= 2H - 1, Px >= 2W - 1, up to 32768).  A line of P = N2 * L
+// points (L <= 8192, the longest line two ping-pong buffers of LDS hold) is split by decimation in frequency:
+//   X[N2 k1 + k2] = FFT_L( y_k2 )[k1],   y_k2[n1] = sum_n2 x[n1 + L n2] * W_P^(k2 (n1 + L n2))
+// so block k2 of the spectrum is an in-LDS transform of a line the loader forms from N2 input points; the spectrum is kept in that
+// permuted order (|Z|^2 does not care), and the inverse undoes it:  x[m] = sum_k2 conj(W_P^(k2 m)) * IFFT_L(block k2)[m mod L].
+// The radix-N2 step runs in the loads and the combine in registers, so there is no pass of its own through HBM:
+//   k_big_rows : 3H rows of the normalised window -> z[plane][row][Px] (spectrum along x, permuted); one workgroup per row and block
+//   k_big_transpose : z -> zt[plane][column][row], 32 x 32 tiles through LDS, so that a column is a contiguous line
+//   k_big_cols : per column (C adjacent ones) and block of the y axis: forward transform, |Z|^2, inverse, combined in registers over the
+//                N2y blocks into the H lag rows the last pass reads; written back in place (a workgroup owns its columns)
+//   k_big_transpose : zt -> z, lag rows contiguous again
+//   k_big_mr   : per lag row: the N2x inverse blocks combined in registers for the W lags read, sum ac^2 w; the last workgroup writes
+//                the scalars (as k_fft_mr)
+// With N2 = 1 the twiddles are W^0 = 1 and an axis is the plain in-LDS transform.  z and zt hold the H rows that carry data only:
+// 2 x 3 H Px complex64, not 3 Py Px.  (The columns read straight from z, 8 bytes per row at a stride of 8 Px bytes, took 30 ms at
+// 4200^2; the two transposes cost 4 x 24 H Px bytes of traffic and make every other access a contiguous line.)  HBM traffic per
+// evaluation: z written by the rows, read and written by each transpose, zt read N2y times and written once by the columns, z read
+// once by the last pass -- (7 + N2y) * 24 H Px bytes (15 GB at 4200^2, 0.5 GB for 8300 x 200).
+#define ICS_BIG_ACC 16   // combine accumulators per thread: H * C / threads (columns) and W / threads (last pass) are <= 16 up to P = 32768
+
+__device__ __forceinline__ float2 cmul(float2 a, float2 b) { return make_float2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x); }
+__device__ __forceinline__ float2 cmulc(float2 a, float2 b) { return make_float2(a.x * b.x + a.y * b.y, a.y * b.x - a.x * b.y); }   // a * conj(b)
+
+__global__ void k_big_rows(IcsStatsArgs a, int L, int logL) {   // grid 3 H (Px / L), min(L / 2, 1024) threads, 2 L float2 of LDS
+  extern __shared__ __attribute__((aligned(16))) float2 sm[];
+  const IcsGeom& G = a.geo;
+  const Win w = make_win(a);
+  const int Px = a.Px, N2 = Px >> logL, tid = threadIdx.x, nthr = blockDim.x;
+  const int id = blockIdx.x / N2, k2 = blockIdx.x - id * N2;
+  const int plane = id / w.H, line = id - plane * w.H;
+  const float mean_e = mean_of(a.dacc[0], w.ne), std_e = std_of(a.dacc[3], w.ne);
+  const float mxk = ics_key2f(a.ukey[0]);
+  const float mx = (a.ukey[0] == 0xFFC00000u) ? mxk : __fdiv_rn(mxk, std_e);
+  const float* er = a.e + (ptrdiff_t)(a.top + G.pad + line) * G.pitch + 3 * (a.left + G.pad) + plane;
+  for (int n1 = tid; n1 < L; n1 += nthr) {
+    float2 v = make_float2(0.f, 0.f);
+    for (int n2 = 0; n2 < N2; ++n2) {
+      const int m = n1 + (n2 << logL);
+      if (m < w.W) {
+        const float x = __fdiv_rn(__fdiv_rn(__fsub_rn(er[3 * m], mean_e), std_e), mx);
+        const float2 t = a.twx[(k2 * m) & (Px - 1)];
+        v.x += x * t.x; v.y += x * t.y;
+      }
+    }
+    sm[n1] = v;
+  }
+  __syncthreads();
+  const float2* r = fft_lines(sm, sm + L, L, logL, 1, L, a.twx, false, N2);
+  float2* out = a.z + ((long)plane * w.H + line) * Px + ((long)k2 << logL);
+  for (int j = tid; j < L; j += nthr) out[j] = r[j];
+}
+
+// per plane: src [R][Cc] -> dst [Cc][R]
+__global__ __launch_bounds__(256) void k_big_transpose(const float2* __restrict__ src, float2* __restrict__ dst, int R, int Cc) {
+  __shared__ float2 tile[32][33];   // grid (ceil(Cc / 32), ceil(R / 32), 3), 256 threads
+  const long po = (long)blockIdx.z * R * Cc;
+  const int c0 = blockIdx.x * 32, r0 = blockIdx.y * 32, tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+  for (int k = ty; k < 32; k += 8)
+    if (r0 + k < R && c0 + tx < Cc) tile[k][tx] = src[po + (long)(r0 + k) * Cc + c0 + tx];
+  __syncthreads();
+  for (int k = ty; k < 32; k += 8)
+    if (c0 + k < Cc && r0 + tx < R) dst[po + (long)(c0 + k) * R + r0 + tx] = tile[tx][k];
+}
+
+// on zt = [3][Px][H]: column c of a plane is the contiguous line zt[plane][c][0 .. H)
+__global__ void k_big_cols(IcsStatsArgs a, int L, int logL, int C, int LP) {   // grid 3 Px / C, min(C L / 2, 1024) threads
+  extern __shared__ __attribute__((aligned(16))) float2 sm[];
+  const int Py = a.Py, Px = a.Px, N2 = Py >> logL, tid = threadIdx.x, nthr = blockDim.x;
+  const int H = a.bottom - a.top, n0 = H - H / 2, nq = H * C;
+  const int groups = Px / C;
+  const int plane = blockIdx.x / groups, c0 = (blockIdx.x - plane * groups) * C;
+  float2* base = a.z + (long)3 * H * Px + ((long)plane * Px + c0) * H;
+  float2* x = sm;
+  float2* y = sm + C * LP;
+  float2 acc[ICS_BIG_ACC];
+#pragma unroll
+  for (int q = 0; q < ICS_BIG_ACC; ++q) acc[q] = make_float2(0.f, 0.f);
+  for (int k2 = 0; k2 < N2; ++k2) {
+    for (int i = tid; i < C * L; i += nthr) {
+      const int cc = i >> logL, n1 = i & (L - 1);
+      float2 v = make_float2(0.f, 0.f);
+      for (int n2 = 0; n2 < N2; ++n2) {
+        const int r = n1 + (n2 << logL);
+        if (r < H) { const float2 d = cmul(base[(long)cc * H + r], a.twy[(k2 * r) & (Py - 1)]); v.x += d.x; v.y += d.y; }
+      }
+      x[cc * LP + n1] = v;
+    }
+    __syncthreads();
+    float2* f = fft_lines(x, y, L, logL, C, LP, a.twy, false, N2);
+    for (int i = tid; i < C * L; i += nthr) {
+      const int cc = i / L, j = i - cc * L;
+      const float2 v = f[cc * LP + j];
+      f[cc * LP + j] = make_float2(v.x * v.x + v.y * v.y, 0.f);
+    }
+    __syncthreads();
+    const float2* q = fft_lines(f, f == x ? y : x, L, logL, C, LP, a.twy, true, N2);
+#pragma unroll
+    for (int k = 0; k < ICS_BIG_ACC; ++k) {
+      const int i = tid + k * nthr;
+      if (i < nq) {
+        const int cc = i / H, l = i - cc * H;
+        const int r = l < n0 ? l : l + (Py - H);                 // lag row (l - H/2) mod Py
+        const float2 d = cmulc(q[cc * LP + (r & (L - 1))], a.twy[(k2 * r) & (Py - 1)]);
+        acc[k].x += d.x; acc[k].y += d.y;
+      }
+    }
+    __syncthreads();   // the next block's loads overwrite the LDS just read
+  }
+#pragma unroll
+  for (int k = 0; k < ICS_BIG_ACC; ++k) {
+    const int i = tid + k * nthr;
+    if (i < nq) base[i] = acc[k];                                // = zt[plane][c0 + i / H][i % H]
+  }
+}
+
+__global__ void k_big_mr(IcsStatsArgs a, int L, int logL) {   // grid 3 H, min(L / 2, 1024) threads, 2 L float2 of LDS
+  extern __shared__ __attribute__((aligned(16))) float2 sm[];
+  __shared__ double shd[16];
+  const int Py = a.Py, Px = a.Px, N2 = Px >> logL, tid = threadIdx.x, nthr = blockDim.x;
+  const int H = a.bottom - a.top, W = a.right - a.left, n0 = H - H / 2;
+  const int plane = blockIdx.x / H, l = blockIdx.x - plane * H;
+  const int r = l < n0 ? l + H / 2 : l - n0;                    // the weights' row of lag row l
+  const float2* row = a.z + ((long)plane * H + l) * Px;
+  float acc[ICS_BIG_ACC];
+#pragma unroll
+  for (int k = 0; k < ICS_BIG_ACC; ++k) acc[k] = 0.f;
+  for (int k2 = 0; k2 < N2; ++k2) {
+    for (int j = tid; j < L; j += nthr) sm[j] = row[((long)k2 << logL) + j];
+    __syncthreads();
+    const float2* x = fft_lines(sm, sm + L, L, logL, 1, L, a.twx, true, N2);
+#pragma unroll
+    for (int k = 0; k < ICS_BIG_ACC; ++k) {
+      const int b = tid + k * nthr;
+      if (b < W) {
+        const int col = (b - W / 2 + Px) & (Px - 1);
+        acc[k] += cmulc(x[col & (L - 1)], a.twx[(k2 * col) & (Px - 1)]).x;
+      }
+    }
+    __syncthreads();
+  }
+  const float inv = 1.0f / ((float)Py * (float)Px);
+  double s = 0.0;
+#pragma unroll
+  for (int k = 0; k < ICS_BIG_ACC; ++k) {
+    const int b = tid + k * nthr;
+    if (b < W) { const float ac = acc[k] * inv; s += (double)__fmul_rn(__fmul_rn(ac, ac), a.weights[r * W + b]); }
+  }
+  s = block_sum(s, shd);
+  if (tid == 0) {
+    atomicAdd(a.dacc + 5, s);
+    __threadfence();
+    if (atomicAdd(a.ukey + 1, 1u) == gridDim.x - 1) { __threadfence(); stats_final(a); }
+  }
+}
+
+hipError_t launch_stats_big(const IcsStatsArgs& a, hipStream_t s) {
+  const int H = a.bottom - a.top, W = a.right - a.left;
+  auto lg = [](int v) { int k = 0; while ((1 << k) < v) ++k; return k; };
+  const int Ly = a.Py < 8192 ? a.Py : 8192, Lx = a.Px < 8192 ? a.Px : 8192, logLy = lg(Ly), logLx = lg(Lx);
+  const int C = Ly <= 1024 ? 4 : (Ly <= 2048 ? 2 : 1);          // as k_fft_cols (Ly, Lx >= 64 here)
+  const int LP = Ly + (C > 1 ? 4 : 0);
+  auto clampt = [](int v) { return v < 64 ? 64 : (v > 1024 ? 1024 : v); };
+  const int tc = clampt(C * (Ly / 2)), tx = clampt(Lx / 2);
+  if ((H * C + tc - 1) / tc > ICS_BIG_ACC || (W + tx - 1) / tx > ICS_BIG_ACC) return hipErrorInvalidValue;   // not reachable for P <= 32768
+  const size_t lds_c = 2 * (size_t)C * LP * sizeof(float2), lds_x = 2 * (size_t)Lx * sizeof(float2);
+  if (lds_c > 64 * 1024 || lds_x > 64 * 1024) {
+    static std::atomic<bool> cfg[3][ICS_MAX_DEVICES];
+    const int dev = ics_current_device();
+    hipError_t e = ics_configure_lds(cfg[0], dev, k_big_rows, 132 * 1024);
+    if (e == hipSuccess) e = ics_configure_lds(cfg[1], dev, k_big_cols, 132 * 1024);
+    if (e == hipSuccess) e = ics_configure_lds(cfg[2], dev, k_big_mr, 132 * 1024);
+    if (e != hipSuccess) return e;
+  }
+  hipLaunchKernelGGL(k_big_rows, dim3(3 * H * (a.Px / Lx)), dim3(tx), lds_x, s, a, Lx, logLx);
+  float2* zt = a.z + (size_t)3 * H * a.Px;
+  hipLaunchKernelGGL(k_big_transpose, dim3(a.Px / 32, (H + 31) / 32, 3), dim3(256), 0, s, a.z, zt, H, a.Px);
+  hipLaunchKernelGGL(k_big_cols, dim3(3 * (a.Px / C)), dim3(tc), lds_c, s, a, Ly, logLy, C, LP);
+  hipLaunchKernelGGL(k_big_transpose, dim3((H + 31) / 32, a.Px / 32, 3), dim3(256), 0, s, zt, a.z, a.Px, H);
+  hipLaunchKernelGGL(k_big_mr, dim3(3 * H), dim3(tx), lds_x, s, a, Lx, logLx);   // its last workgroup writes the scalars
+  return hipSuccess;
+}
+
 __global__ __launch_bounds__(256) void k_hasnan(const float* u, IcsGeom G, int* flag) {
   const int ngx = G.tiles_x * 16;
   const long total = (long)G.uM * ngx;
@@ -302,7 +489,10 @@ hipError_t ics_launch_stats(const IcsStatsArgs& a, hipStream_t s) {
   int gb = (ne + 256 * ICS_MOM_BATCH - 1) / (256 * ICS_MOM_BATCH); if (gb < 1) gb = 1; if (gb > 512) gb = 512;
   hipLaunchKernelGGL(k_mom1, dim3(gb), dim3(256), 0, s, a);
   hipLaunchKernelGGL(k_mom2, dim3(gb), dim3(256), 0, s, a);
-  if (a.do_mr) {
+  if (a.do_mr && a.Py > 0) {
+    const hipError_t e = launch_stats_big(a, s);
+    if (e != hipSuccess) return e;
+  } else if (a.do_mr) {
     const int P = a.P, H = a.bottom - a.top;
     const int C = P < 4 ? 1 : (P <= 1024 ? 4 : (P <= 2048 ? 2 : 1));   // columns per workgroup (LDS: 2 * C * LP * 8 bytes); P >= 2
     const int LP = P + (C > 1 ? 4 : 0);                       // line pitch in LDS: the transposing accesses spread over the banks
