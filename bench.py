@@ -16,8 +16,12 @@ own frame (seed = rank), nothing is exchanged during the iterations, and the onl
 the barrier / max-over-ranks of the contract below (RCCL).  value = N * pixels * K / max-rank time.
 
 One JSON line on rank 0, with `roofline` (dominant kernel: algorithmic bytes per launch over its
-HIP-event duration, against 8 TB/s) and `cpu_baseline` (the numpy/scipy port of the reference loop in
-oracle/, timed on the host cores on a bounded sample).
+HIP-event duration in the timed run, against 8 TB/s).  A plain run does only what that line needs: frame
+synthesis, the cold start and clock pre-heat in front of the warm-up, the W + K steps, `--dump-outputs`.
+`--full` adds everything measured beside the headline, each block still subject to its `--no-*` switch:
+`cpu_baseline` (the numpy/scipy port of the reference loop in oracle/, timed on the host cores on a
+bounded sample), the other mode on the same frame, the `sustained` block, and at the default workload the
+other product paths, the other BASELINE.json configurations and `deblur_module` end to end.
 """
 import argparse
 import json
@@ -365,13 +369,15 @@ def main():
     ap.add_argument("--mode", choices=["blind", "nonblind"], default="blind")
     ap.add_argument("--size", type=int, default=4096)
     ap.add_argument("--psf", type=int, default=15)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-other-mode", action="store_true", help="skip the secondary (untimed for `value`) run of the other mode")
-    ap.add_argument("--no-other-configs", action="store_true", help="skip the secondary lines for BASELINE.json configs[1], configs[3] and the TV variants")
+    ap.add_argument("--full", action="store_true", help="also measure everything beside the headline (cpu_baseline, other mode, sustained, other "
+                    "product paths / configurations, deblur_module end to end); a plain run measures the headline alone")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip cpu_baseline")
+    ap.add_argument("--no-other-mode", action="store_true", help="with --full: skip the secondary (untimed for `value`) run of the other mode")
+    ap.add_argument("--no-other-configs", action="store_true", help="with --full: skip the secondary lines for BASELINE.json configs[1], configs[3] and the TV variants")
     ap.add_argument("--tv-mode", type=int, default=0, help="0 = shipped loop (TV term dead, the parity-pinned path); 1 = build-defined active MM-TV")
     ap.add_argument("--fuse", action="store_true", help="fused update+convolution kernel (opt-in; measured slower)")
     ap.add_argument("--no-profile", action="store_true", help="do not bracket kernels with HIP events in the timed region")
-    ap.add_argument("--no-sustained", action="store_true", help="skip the `sustained` block (25 + 200 extra steps after the timed region)")
+    ap.add_argument("--no-sustained", action="store_true", help="with --full: skip the `sustained` block (25 + 200 extra steps after the timed region)")
     ap.add_argument("--no-preheat", action="store_true", help="skip the cold-start measurement and the 150-step clock pre-heat in front of the timed region")
     ap.add_argument("--bands", type=int, default=0, help="N > 0: ONE frame (--size, default 12288 here) split into N row bands, one rank per GPU "
                     "(lib.banded.BandRank: RCCL max / sum all-reduce + point-to-point halos); strong scaling, a secondary workload (SURVEY.md 8f N4)")
@@ -460,9 +466,9 @@ def main():
             outs["image"] = job.read(_native.BUF_IMAGE)
         dump_outputs(args.dump_outputs, outs)
 
-    # secondary measurement (not `value`): the other mode on the same resident frame, same schedule
+    # secondary measurement (not `value`; --full): the other mode on the same resident frame, same schedule
     other = None
-    if grp.size == 1 and not args.no_other_mode:
+    if grp.size == 1 and args.full and not args.no_other_mode:
         omode = "nonblind" if blind else "blind"
         job.upload(image, u0, psf_true if blind else psf_uniform)
         po = job.params(*win, 1e9, steps // 5, 1e-3, 10000.0, not blind, 0, 3, stop_test=2, profile=0, fuse=int(args.fuse), tv_mode=args.tv_mode, conv=conv)
@@ -478,9 +484,9 @@ def main():
 
     # beside `value` (never instead of it): a SUSTAINED measurement -- 25 warm-up + 200 timed steps whatever --steps / --warmup were --
     # with its own kernel table.  A 20-step run after 5 warm-up steps is timed while the clocks still ramp (NOTES_r02.md section 4a);
-    # this block is what the per-kernel fractions in DESIGN.md are quoted from.
+    # this block is what the per-kernel fractions in DESIGN.md are quoted from (--full).
     sustained = None
-    if grp.size == 1 and not args.no_sustained:
+    if grp.size == 1 and args.full and not args.no_sustained:
         run(25, 0)
         ctx.synchronize()
         ts = time.perf_counter()
@@ -554,8 +560,8 @@ def main():
             "rccl": rccl,
             "other_mode_same_frame": other,
         }
-        if grp.size == 1 and not args.no_other_configs and args.size == 4096 and args.psf == 15 and args.tv_mode == 0 and not args.fuse:
-            # secondary lines (never `value`): the other BASELINE.json configurations and the build-defined TV variants they name
+        if grp.size == 1 and args.full and not args.no_other_configs and args.size == 4096 and args.psf == 15 and args.tv_mode == 0 and not args.fuse:
+            # secondary lines (never `value`; --full): the other BASELINE.json configurations and the build-defined TV variants they name
             out["conv_rel_err_vs_f64"] = conv_rel_err(ctx, MK)
             # since round 6 the headline's default path is fp32 throughout (transform tiles); the same workload on the other two kernel families,
             # every round, beside it: packed-fp32 vector convolutions + fp32-MFMA gradient, and the matrix cores with fp16x2-split operands
@@ -582,7 +588,7 @@ def main():
             out["other_configs"] = oc
             out["deblur_module_end_to_end"] = {"4096^2 blur 15, reference defaults (iterations=20)": deblur_end_to_end(4096, 15, 20),
                                                "2048^2 blur 15, reference defaults (iterations=20)": deblur_end_to_end(2048, 15, 20)}
-        if not args.no_cpu_baseline and grp.size == 1:   # (rank 0 at N = 1 only)
+        if args.full and not args.no_cpu_baseline and grp.size == 1:   # (rank 0 at N = 1 only)
             out["cpu_baseline"] = cpu_baseline(args.mode, MK, M)
         print(json.dumps(out))
     grp.close()

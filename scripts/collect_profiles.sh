@@ -6,13 +6,13 @@ R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/prof
 rm -rf $O; mkdir -p $O
 cd $R
-python3 bench.py > $O/bench_blind.json 2> $O/bench_blind.err
-python3 bench.py --mode nonblind --no-other-configs > $O/bench_nonblind.json 2> $O/bench_nonblind.err
-python3 bench.py --steps 20 --warmup 5 --no-other-configs --no-cpu-baseline > $O/bench_blind_driver_style_20_steps.json 2>/dev/null
-python3 bench.py --conv vector --no-cpu-baseline --no-other-configs > $O/bench_blind_vector.json 2>/dev/null
-ICS_FUSED_GRADK=0 python3 bench.py --no-cpu-baseline --no-other-configs > $O/bench_blind_two_kernel_gradk.json 2>/dev/null
+python3 bench.py --full > $O/bench_blind.json 2> $O/bench_blind.err
+python3 bench.py --full --mode nonblind --no-other-configs > $O/bench_nonblind.json 2> $O/bench_nonblind.err
+python3 bench.py --full --steps 20 --warmup 5 --no-other-configs --no-cpu-baseline > $O/bench_blind_driver_style_20_steps.json 2>/dev/null
+python3 bench.py --full --conv vector --no-cpu-baseline --no-other-configs > $O/bench_blind_vector.json 2>/dev/null
+ICS_FUSED_GRADK=0 python3 bench.py --full --no-cpu-baseline --no-other-configs > $O/bench_blind_two_kernel_gradk.json 2>/dev/null
 cd /tmp
-ARGS="$R/bench.py --no-cpu-baseline --no-other-configs --no-other-mode"
+ARGS="$R/bench.py --full --no-cpu-baseline --no-other-configs --no-other-mode"
 rocprofv3 --kernel-trace --stats -d $O/kt -- python3 $ARGS > /dev/null 2>&1
 SHORT="$ARGS --steps 5 --warmup 0 --no-profile --no-sustained"
 rocprofv3 --kernel-trace --pmc FETCH_SIZE -d $O/fetch -- python3 $SHORT > /dev/null 2>&1

@@ -7,7 +7,7 @@ R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/prof_${SIZE}_${PSF}
 rm -rf $O; mkdir -p $O
 cd $R
-CFG="--size $SIZE --psf $PSF --mode $MODE --no-cpu-baseline --no-other-configs --no-other-mode"
+CFG="--full --size $SIZE --psf $PSF --mode $MODE --no-cpu-baseline --no-other-configs --no-other-mode"
 python3 bench.py $CFG --steps 40 --warmup 10 > $O/bench.json 2> $O/bench.err
 cd /tmp
 rocprofv3 --kernel-trace --stats -d $O/kt -- python3 $R/bench.py $CFG --steps 40 --warmup 10 --no-sustained > /dev/null 2>&1
