@@ -173,12 +173,6 @@ struct ics_rl {
   float* h_scal;                        // pinned host mirror of scal (+ flags)
   bool uploaded;
   bool ut_is_u;                         // majoriser aliased to u (first inner iteration of an outer one, no copy made yet)
-  // one hipGraph per outer iteration (small frames, use_graph): the launches of an outer iteration depend on which of the three
-  // frames is u / ut / spare (the rotation of do_update has period 3), so up to three executables, valid for one parameter set
-  struct Graph { float *u, *ut, *u2; hipGraphExec_t exec; };
-  std::vector<Graph> graphs;
-  ics_rl_params graph_sig;              // the parameters baked into the captured kernel arguments
-  int graph_epoch;                      // ... and the state of the debug switches they were captured under
   // profiling
   std::vector<hipEvent_t> ev;
   struct EvPair { int b, e, cls; };     // a bracketed launch group: events ev[b] .. ev[e]
@@ -190,7 +184,7 @@ struct ics_rl {
   hipEvent_t ev_begin, ev_end;
   // FFT-tile pipeline (round 5; ics_conv_fft.hip, ics_planar.hip): channel-planar mirrors of the frames (ics_common.h), allocated by the
   // first run that uses it.  A mirror belongs to a BUFFER, not to a role: u / ut / u2 and e / e2 rotate as pointers, the table is looked
-  // up by the HWC pointer's value.  fft_on = a run / stage on the pipeline is in progress: the do_* helpers work on the mirrors and
+  // up by the HWC pointer's value.  fft_on = the mirrors hold the live frames of a run / stage on the pipeline (its route's `tiles`):
   // pack_weights also builds the two spectra.
   struct Twin { float* hwc; float* pl; };
   Twin twins[8];
@@ -229,28 +223,27 @@ extern "C" size_t ics_rl_params_size(void) { return sizeof(ics_rl_params); }
 extern "C" size_t ics_rl_stats_size(void) { return sizeof(ics_rl_stats); }
 
 // test / measurement switches (ics_common.h IcsDebug): exported, deliberately absent from include/ics_hip.h
-static std::atomic<int> g_debug_epoch{0};   // bumped by every ics_debug_set: captured graphs carry the switches' effects in their kernel arguments
-extern "C" int ics_debug_set(const char* name, int value) {
-  if (!name) return -1;
+static std::atomic<int>* debug_switch(const char* name) {
   IcsDebug& d = ics_debug();
-  struct { const char* n; std::atomic<int>* v; } tab[] = {
+  const struct { const char* n; std::atomic<int>* v; } tab[] = {
       {"max_wgs", &d.max_wgs}, {"dynamic_tiles", &d.dynamic_tiles}, {"conv_rs", &d.conv_rs}, {"conv_nh", &d.conv_nh}, {"conv_path", &d.conv_path},
       {"fused_gradk", &d.fused_gradk}, {"update_wg_per_cu", &d.update_wg_per_cu}, {"update_kernel", &d.update_kernel}, {"fused_rs", &d.fused_rs},
-      {"planar_image", &d.planar_image}, {"pam_exact", &d.pam_exact}, {"fail_window_alloc", &d.fail_window_alloc}, {"graph", &d.graph}, {"pool_limit_mb", &d.pool_limit_mb}, {"overlap", &d.overlap}, {"fft_gradk", &d.fft_gradk}, {"fft_fused", &d.fft_fused}, {"fft_conv2", &d.fft_conv2}, {"fft_rot", &d.fft_rot}, {"small_iter", &d.small_iter}, {"small_trace", &d.small_trace}, {"fail_small_launch", &d.fail_small_launch}};
+      {"planar_image", &d.planar_image}, {"pam_exact", &d.pam_exact}, {"fail_window_alloc", &d.fail_window_alloc}, {"pool_limit_mb", &d.pool_limit_mb}, {"overlap", &d.overlap}, {"fft_gradk", &d.fft_gradk}, {"fft_fused", &d.fft_fused}, {"fft_conv2", &d.fft_conv2}, {"fft_rot", &d.fft_rot}, {"small_iter", &d.small_iter}, {"small_trace", &d.small_trace}, {"fail_small_launch", &d.fail_small_launch}};
   for (auto& t : tab)
-    if (strcmp(t.n, name) == 0) { t.v->store(value, std::memory_order_relaxed); g_debug_epoch.fetch_add(1, std::memory_order_relaxed); return 0; }
-  return -1;
+    if (strcmp(t.n, name) == 0) return t.v;
+  return nullptr;
+}
+extern "C" int ics_debug_set(const char* name, int value) {
+  std::atomic<int>* v = name ? debug_switch(name) : nullptr;
+  if (!v) return -1;
+  v->store(value, std::memory_order_relaxed);
+  return 0;
 }
 extern "C" int ics_debug_get(const char* name, int* value) {
-  if (!name || !value) return -1;
-  IcsDebug& d = ics_debug();
-  struct { const char* n; std::atomic<int>* v; } tab[] = {
-      {"max_wgs", &d.max_wgs}, {"dynamic_tiles", &d.dynamic_tiles}, {"conv_rs", &d.conv_rs}, {"conv_nh", &d.conv_nh}, {"conv_path", &d.conv_path},
-      {"fused_gradk", &d.fused_gradk}, {"update_wg_per_cu", &d.update_wg_per_cu}, {"update_kernel", &d.update_kernel}, {"fused_rs", &d.fused_rs},
-      {"planar_image", &d.planar_image}, {"pam_exact", &d.pam_exact}, {"fail_window_alloc", &d.fail_window_alloc}, {"graph", &d.graph}, {"pool_limit_mb", &d.pool_limit_mb}, {"overlap", &d.overlap}, {"fft_gradk", &d.fft_gradk}, {"fft_fused", &d.fft_fused}, {"fft_conv2", &d.fft_conv2}, {"fft_rot", &d.fft_rot}, {"small_iter", &d.small_iter}, {"small_trace", &d.small_trace}, {"fail_small_launch", &d.fail_small_launch}};
-  for (auto& t : tab)
-    if (strcmp(t.n, name) == 0) { *value = t.v->load(std::memory_order_relaxed); return 0; }
-  return -1;
+  std::atomic<int>* v = name && value ? debug_switch(name) : nullptr;
+  if (!v) return -1;
+  *value = v->load(std::memory_order_relaxed);
+  return 0;
 }
 extern "C" const char* ics_last_error(void) { return g_err; }
 
@@ -383,7 +376,6 @@ extern "C" void ics_rl_destroy(ics_rl* j) {
   if (j->spec_conv) j->ctx->pool.release(j->spec_conv);
   if (j->spec_corr) j->ctx->pool.release(j->spec_corr);
   if (j->fspec) j->ctx->pool.release(j->fspec);
-  for (auto& g : j->graphs) hipGraphExecDestroy(g.exec);
   for (int i = 0; i < 2; ++i) { if (j->ev_body[i]) hipEventDestroy(j->ev_body[i]); if (j->ev_stats[i]) hipEventDestroy(j->ev_stats[i]); }
   if (j->h_scal) hipHostFree(j->h_scal);
   for (hipEvent_t e : j->ev) hipEventDestroy(e);
@@ -882,16 +874,24 @@ extern "C" int ics_rl_allreduce_gradk(ics_rl* j, ics_group* g) {
 }
 
 
-// ICS_CONV_AUTO: matrix-core kernels where they exist and win (ics_conv_mfma_preferred); env ICS_CONV_PATH=vector|matrix
-// overrides AUTO
-static bool use_matrix_conv(const ics_rl* j, const ics_rl_params* p) {
-  if (!j->bt_conv) return false;
-  if (p->conv == ICS_CONV_VECTOR) return false;
-  if (p->conv == ICS_CONV_MATRIX) return true;
-  const int env = ics_debug().conv_path.load(std::memory_order_relaxed);
-  // (ICS_CONV_PATH=fft where the tiles do not run -- single stages, tv_mode 1, PSF sizes above 65: what AUTO would take)
-  return env == 2 || ((env == 0 || env == 3) && ics_conv_mfma_preferred(j->g.K));
-}
+// ---- routing ------------------------------------------------------------------------------------------------------------------------
+// Which kernels a run or a stage launches is decided in ONE place, resolve_route (below check_params), from the geometry, the parameters,
+// the weight tables the job owns, its sticky fallbacks and the routing switches (ics_common.h IcsDebug: conv_path, fused_gradk,
+// planar_image, fft_gradk, fft_fused, fft_conv2, small_iter, overlap -- read nowhere else).  ics_rl_run and ics_rl_stage resolve it once and
+// hand it to the do_* helpers, which dispatch on it; ics_rl_describe copies it.  Family numbers: those of ics_rl_route (include/ics_hip.h).
+enum { CONV_MATRIX = 1, CONV_BLOCKS = 2, CONV_PACKED = 3, CONV_SIZED = 4, CONV_TILES = 5, CONV_SMALL = 6 };
+enum { GK_FUSED_MATRIX = 1, GK_MATRIX = 2, GK_SPLIT = 3, GK_FP32 = 4, GK_SIZED = 5, GK_TILES = 6, GK_FUSED_TILES = 7, GK_SMALL = 8 };
+struct Route {
+  bool tiles;           // the FFT-tile pipeline on the planar mirrors (conv family 5)
+  bool conv2;           // ... with A1 + A3 as one unit per tile pair (do_conv2)
+  bool small;           // the cooperative small-frame iteration, one launch per outer iteration (conv family 6, gradient family 8), with its plan
+  IcsSmallPlan plan;
+  int conv;             // modes 0 / 1 on the HWC frames: CONV_MATRIX, CONV_BLOCKS, CONV_PACKED or CONV_SIZED
+  int gradk;            // the PSF gradient, GK_FUSED_MATRIX ... GK_FUSED_TILES (resolved for non-blind parameters too: the stage API)
+  bool image_acc;       // the residual's epilogues read the accumulator-order copy of the image where their tile height has one (ics_image_acc.h)
+  bool acc_order;       // ... and a run of these parameters does (ics_rl_route.image_in_accumulator_order)
+  bool overlap;         // the statistics of outer iteration i on the second stream beside iteration i + 1; else a drain at every outer boundary
+};
 
 // The FFT-tile pipeline (ics_conv_fft.hip; round 5): A1 / A3 / A11 as LDS-resident 128 x 128 overlap-save transforms on planar mirrors,
 // fp32 throughout, with the update pass and the matrix-core PSF gradient on the mirrors as well.  Shipped loop only (tv_mode 0, fuse 0),
@@ -935,49 +935,6 @@ static bool fft_preferred(const IcsGeom& g, bool blind) {
 // mirrors: a frame accepted just under the 2 GiB frame limit can have a mirror whose last plane ends beyond 2^31 bytes -- loads there
 // would read 0, stores would be dropped, silently (e.g. 18784 x 9256 with a 33 x 33 PSF).  Such shapes never take the tiles.
 static bool fft_mirror_fits(const IcsGeom& g) { return ics_planar_floats(g) * sizeof(float) < 0x7FFFFFFFull; }
-static bool pam_on_tiles(const ics_rl* j, const ics_rl_params* p, bool in_run) {   // the routing rule of the PAM kinds (tv_mode 2 / 3)
-  if (!ics_conv_fft_supported(j->g.K) || p->fuse || !in_run || !fft_mirror_fits(j->g)) return false;        // (single stages of the TV variants run on the HWC kernels)
-  if (p->tv_mode != ICS_TV_PAM_ISO && p->tv_mode != ICS_TV_PAM_COLLAB) return false;
-  if (p->conv == ICS_CONV_FFT) return true;
-  if (p->conv != ICS_CONV_AUTO) return false;
-  const int env = ics_debug().conv_path.load(std::memory_order_relaxed);
-  if (env == 3) return true;
-  // bench.py --tv-mode 2, ICS_CONV_PATH=matrix -> fft (measured with the convolutions and the gradient on the tiles only), ms per inner iteration: 1448^2 / 31 blind 0.357 -> 0.297; 2048^2 / 21 blind 0.470 -> 0.396,
-  // non-blind 0.271 -> 0.259; 4096^2 / 19 blind 1.563 -> 1.132; 1100^2 / 45 blind 0.432 -> 0.310
-  // round 6: the shipped loop's thresholds -- the same kernels but for the epilogue's operands -- except below 6 Mpx at 15 x 15 and less, where the
-  // TV term's own pass on the planes tips it back (bench.py --tv-mode 2, ms per inner iteration, matrix cores -> tiles: 4096^2 / 15 blind 0.873 -> 0.780,
-  // tv_mode 3 0.869 -> 0.794; 2048^2 / 15 non-blind 0.176 -> 0.190, blind 0.261 -> 0.293)
-  const long px = (long)j->g.uM * j->g.uN;
-  return env == 0 && fft_preferred(j->g, p->blind != 0) && (j->g.K >= 17 || px >= 6000000L);
-}
-static bool use_fft_pipeline(const ics_rl* j, const ics_rl_params* p, bool in_run) {
-  if (p->tv_mode != ICS_TV_SHIPPED) return pam_on_tiles(j, p, in_run);   // PAM kinds: TV term, back-projection epilogue and update on the mirrors too
-  if (!(ics_conv_fft_supported(j->g.K) || ics_conv_fft_blk_supported(j->g.K)) || p->fuse || !fft_mirror_fits(j->g)) return false;      // (87 ... 255: tap blocks on the tiles)
-  if (p->conv == ICS_CONV_FFT) return true;
-  if (p->conv != ICS_CONV_AUTO || !in_run) return false;
-  const int env = ics_debug().conv_path.load(std::memory_order_relaxed);
-  if (env == 3) return true;
-  return env == 0 && fft_preferred(j->g, p->blind != 0);
-}
-
-// tv_mode 1 rewrites the image in every inner iteration (pyx:547-549 live): a copy would have to be rebuilt each time
-static bool use_image_acc(const ics_rl_params* p) {
-  return p->tv_mode != ICS_TV_MM_ACTIVE && ics_debug().planar_image.load(std::memory_order_relaxed) != 0;
-}
-
-// The run-time-sized fp32 kernels (ics_big.hip) are the only ones above 63, and under ICS_CONV_AUTO they take over from the packed-fp32
-// kernels compiled per size wherever the matrix-core kernels are not built or not chosen (51 .. 63; 39 .. 49 with ICS_CONV_PATH=...): they
-// beat them (shipped loop, 2048^2 non-blind, ms per pass, compiled -> run-time-sized): synthesis
-// 39: 0.626 -> 0.594, 45: 0.829 -> 0.756, 55: 1.238 -> 1.013, 63: 1.71 -> 1.27; back-projection (incl. the separate maxima pass)
-// 39: 0.975 -> 0.716, 45: 1.348 -> 0.915, 55: 2.109 -> 1.233, 63: 2.88 -> 1.52.  ICS_CONV_VECTOR keeps the compiled kernels
-// (tests/test_gpu_stages.py drives them at every size).
-static bool use_big_conv(const ics_rl* j, const ics_rl_params* p, int mode) {
-  const int K = j->g.K;
-  if (ics_big_supported(K)) return true;
-  if (mode == 2 || p->conv != ICS_CONV_AUTO || p->tv_mode != ICS_TV_SHIPPED || K < 39) return false;
-  return ics_debug().conv_path.load(std::memory_order_relaxed) != 1;   // ICS_CONV_PATH=vector: as ICS_CONV_VECTOR
-}
-
 // PSF sizes 51 ... 127 on the matrix cores (ICS_CONV_AUTO / ICS_CONV_MATRIX, shipped loop): a convolution is linear in its taps, so
 // the K x K PSF is cut into blk_n x blk_n blocks of Kb x Kb taps (Kb odd, <= 33: sizes k_conv_mfma is built for); block (qa, qb) is
 //     out_q[y][x] = sum_{a',b' < Kb} W[qa Kb + a'][qb Kb + b'] * in'[y + a' - Kb/2][x + b' - Kb/2],   in' = in shifted by (qa Kb + Kb/2 - pad, ...)
@@ -985,12 +942,6 @@ static bool use_big_conv(const ics_rl* j, const ics_rl_params* p, int mode) {
 // own pad: all three pointers move by pad - Kb/2 so that this is the image origin).  The blocks are summed as a chain through the
 // kernels' own operand frames, alternating between the result frame and a scratch frame (do_conv_blocks); the maxima of A7 are taken
 // over the sum by k_band_reduce.  2048^2, 63 x 63: 1.24 / 1.50 ms (run-time-sized fp32 kernel) -> see NOTES_r03.md 4c.
-static bool use_block_conv(const ics_rl* j, const ics_rl_params* p, int mode) {
-  if (!j->blk_conv || mode == 2 || p->tv_mode != ICS_TV_SHIPPED || p->conv == ICS_CONV_VECTOR) return false;
-  if (psf_blocks_only(j->g.K)) return true;   // (no other path: ICS_CONV_PATH does not apply)
-  return p->conv == ICS_CONV_MATRIX || ics_debug().conv_path.load(std::memory_order_relaxed) != 1;
-}
-
 static int do_conv_blocks(ics_rl* j, int mode, const ics_rl_params* p, int slot, Prof& pr) {
   const IcsGeom& G = j->g;
   const int Kb = j->blk_kb, nb = j->blk_n, padb = Kb / 2, pad = G.pad;
@@ -1080,12 +1031,6 @@ static int do_conv_fft(ics_rl* j, int mode, const ics_rl_params* p, int slot, Pr
 #ifndef ICS_CONV2_MAX_K
 #define ICS_CONV2_MAX_K 25
 #endif
-static bool use_conv2(const ics_rl* j, const ics_rl_params* p) {
-  if (!j->fft_on || p->tv_mode == ICS_TV_MM_ACTIVE || p->fuse) return false;      // (shipped loop and the PAM kinds, whose epilogue takes u and T)
-  const int sw = ics_debug().fft_conv2.load(std::memory_order_relaxed);
-  if (sw == 0 || j->conv2_off || !ics_conv2_fft_supported(j->g)) return false;
-  return sw == 2 || j->g.K <= ICS_CONV2_MAX_K;
-}
 static int do_conv2(ics_rl* j, const ics_rl_params* p, int slot, Prof& pr) {
   if (!j->fspec) RC(dalloc(j->ctx, &j->fspec, ics_conv2_fft_fspec_floats(j->g), false));
   if (!j->fspec_valid) {
@@ -1127,9 +1072,10 @@ static int do_conv_fft_window(ics_rl* j, const ics_rl_params* p, Prof& pr) {
   return ICS_OK;
 }
 
-static int do_conv(ics_rl* j, int mode, const ics_rl_params* p, int slot, int want_dof, Prof& pr) {
-  if (j->fft_on && mode != 2) return do_conv_fft(j, mode, p, slot, pr);
-  if (use_block_conv(j, p, mode)) return do_conv_blocks(j, mode, p, slot, pr);
+static int do_conv(ics_rl* j, const Route& r, int mode, const ics_rl_params* p, int slot, int want_dof, Prof& pr) {
+  if (r.tiles && mode != 2) return do_conv_fft(j, mode, p, slot, pr);
+  const int fam = mode == 2 ? (ics_big_supported(j->g.K) ? CONV_SIZED : CONV_PACKED) : r.conv;   // (mode 2, the update fused with A1 + A2: fp32 kernels only)
+  if (fam == CONV_BLOCKS) return do_conv_blocks(j, mode, p, slot, pr);
   IcsConvArgs a;
   a.g = j->g; a.lambd = p->lambd;
   if (mode == 1) { a.in = org(j, j->e); a.w = j->wcorr; a.out = org(j, j->gr); }
@@ -1139,16 +1085,16 @@ static int do_conv(ics_rl* j, int mode, const ics_rl_params* p, int slot, int wa
   a.gr = org(j, j->gr); a.u_out = org(j, j->u2); a.scal = j->scal; a.dofkeys = dof_of(j);
   a.tv = (p->tv_mode != ICS_TV_SHIPPED && j->tvf) ? org(j, j->tvf) : nullptr; a.tv_kind = a.tv ? p->tv_mode : 0;
   a.step = p->step_factor; a.blind = p->blind; a.want_dof = want_dof;
-  const bool matrix = mode != 2 && use_matrix_conv(j, p);
+  const bool matrix = fam == CONV_MATRIX;
   a.bt = matrix ? (mode == 1 ? j->bt_corr : j->bt_conv) : nullptr;
   a.facc[0] = a.facc[1] = nullptr;
-  if (matrix && mode == 0 && use_image_acc(p)) {   // the image operand of the residual in accumulator order (ics_image_acc.h)
+  if (matrix && mode == 0 && r.image_acc) {   // the image operand of the residual in accumulator order (ics_image_acc.h)
     const int rs = ics_conv_mfma_rs(j->g.K, j->g);
     if (rs) { RC(ensure_image_acc(j, rs)); a.facc[rs == 2 ? 0 : 1] = j->facc[rs == 2 ? 0 : 1]; }
   }
   a.sched = matrix ? j->sched : nullptr;   // counters of the dynamic tile walk: the launcher decides per launch (ics_conv_mfma.hip)
   RC(pr.begin(mode == 0 ? ICS_K_SYNTH : (mode == 1 ? ICS_K_BACKPROJECT : ICS_K_UPDATE_SYNTH)));
-  if (!matrix && use_big_conv(j, p, mode)) {   // run-time-sized kernels (ics_big.hip); the maxima of A7 as a pass of their own
+  if (fam == CONV_SIZED) {   // run-time-sized kernels (ics_big.hip); the maxima of A7 as a pass of their own
     HIPCHK(ics_launch_conv_big(mode, a, j->psf, j->ctx->stream));
     if (mode == 1) HIPCHK(ics_launch_band_reduce(a.out, a.u, a.ut, j->g, p->lambd, 0, j->g.uM, a.red, j->ctx->stream));
   } else if (matrix) HIPCHK(ics_launch_conv_mfma(mode, a, j->ctx->stream));
@@ -1158,7 +1104,7 @@ static int do_conv(ics_rl* j, int mode, const ics_rl_params* p, int slot, int wa
   return ICS_OK;
 }
 
-static int do_update(ics_rl* j, const ics_rl_params* p, int slot, int want_dof, Prof& pr) {
+static int do_update(ics_rl* j, const Route& r, const ics_rl_params* p, int slot, int want_dof, Prof& pr) {
   IcsUpdateArgs a;
   a.u = org(j, j->u); a.ut = org(j, ut_of(j)); a.g = org(j, j->gr); a.f = org(j, j->f);
   a.u_out = org(j, j->ut_is_u ? j->u2 : j->u);
@@ -1167,7 +1113,7 @@ static int do_update(ics_rl* j, const ics_rl_params* p, int slot, int want_dof, 
   a.step = p->step_factor; a.lambd = p->lambd; a.blind = p->blind; a.want_dof = want_dof; a.geo = j->g;
   if (a.tv_kind == ICS_TV_MM_ACTIVE) image_changed(j);          // pyx:547-549: this update also steps the image
   RC(pr.begin(ICS_K_UPDATE));
-  if (j->fft_on) {   // the same pass on the planar mirrors (bit-identical arithmetic, ics_planar.hip)
+  if (r.tiles) {   // the same pass on the planar mirrors (bit-identical arithmetic, ics_planar.hip)
     a.u = porg(j, j->u); a.ut = porg(j, ut_of(j)); a.g = porg(j, j->gr); a.f = porg(j, j->f);
     a.u_out = porg(j, j->ut_is_u ? j->u2 : j->u); a.f_rw = nullptr;
     if (!a.u || !a.ut || !a.g || !a.f || !a.u_out) return fail(ICS_ESTATE, "FFT pipeline: a frame has no planar mirror");
@@ -1189,11 +1135,11 @@ static int ensure_tv(ics_rl* j) {
   return rc;
 }
 
-static int do_tvterm(ics_rl* j, const ics_rl_params* p, int slot, Prof& pr) {
+static int do_tvterm(ics_rl* j, const Route& r, const ics_rl_params* p, int slot, Prof& pr) {
   IcsTvTermArgs a;
   a.u = org(j, j->u); a.ut = org(j, ut_of(j)); a.f = org(j, j->f); a.tv = org(j, j->tvf);
   a.red = red_of(j) + slot * ICS_RED_STRIDE; a.epsilon = p->blind ? 1e-2f : 1e-6f; a.kind = p->tv_mode; a.geo = j->g;
-  if (j->fft_on) {   // PAM kinds on the planar mirrors (the kernel reads u and writes T; ut and f are not touched by these kinds)
+  if (r.tiles) {   // PAM kinds on the planar mirrors (the kernel reads u and writes T; ut and f are not touched by these kinds)
     a.u = porg(j, j->u); a.tv = porg(j, j->tvf); a.planar = 1;
     if (!a.u || !a.tv) return fail(ICS_ESTATE, "FFT pipeline: a frame has no planar mirror");
   }
@@ -1203,29 +1149,14 @@ static int do_tvterm(ics_rl* j, const ics_rl_params* p, int slot, Prof& pr) {
   return ICS_OK;
 }
 
-// The PSF gradient has its own choice: the matrix-core kernel wins at every size it is built for (K <= 31; at K = 19, 21,
-// where AUTO keeps the packed-fp32 convolutions, 0.35 vs 0.97 ms at 4096^2)
-static bool use_matrix_gradk(const ics_rl* j, const ics_rl_params* p) {
-  if (!ics_gradk_mfma_supported(j->g.K) || p->conv == ICS_CONV_VECTOR) return false;
-  if (p->conv == ICS_CONV_MATRIX || j->fft_on) return true;   // (the FFT pipeline's gradient reads the mirrors: matrix-core kernel only)
-  return ics_debug().conv_path.load(std::memory_order_relaxed) != 1;
-}
-
 // PSF sizes 33 ... 127: the fp16-split matrix-core gradient is built for up to 31 x 31 taps (2 x 2 blocks of 16; a third block row does
 // not fit its registers), the fp32-MFMA kernel that took over above runs at a third of its rate.  The gradient is a sum over pixels
 // per tap, so the K x K taps split into blocks of at most 31 x 31 -- rows / columns [0, 31), [31, 62), ... -- each a gradient of its own:
 //   gradk[a0 + a'][b0 + b'] = sum E[y][x] * U'[y + pad' - a'][x + pad' - b'],   U' = U shifted by (pad - a0 - pad', pad - b0 - pad')
 // i.e. the 31 x 31 (or, for the small corner block, 15 x 15) kernel on a shifted frame pointer with a geometry that differs in K and
 // pad only; the frames' aprons (16 * ceil(K / 16) rows / pixels) cover the shifts.  4096^2, 45 x 45: 1.92 -> 1.22 ms.
-static bool use_split_gradk(const ics_rl* j, const ics_rl_params* p) {
-  const int K = j->g.K;
-  if (K < 33 || p->conv == ICS_CONV_VECTOR) return false;
-  if (psf_blocks_only(K) || j->fft_on) return true;
-  return p->conv == ICS_CONV_MATRIX || ics_debug().conv_path.load(std::memory_order_relaxed) != 1;
-}
-
 // (33 ... 49: 2 x 2 blocks; 51 ... 127: up to 5 x 5 -- 2048^2: 63 x 63 0.98 -> 0.8 ms, 65 x 65 3.3 -> 0.8, 127 x 127 16.3 -> 2.3)
-static int do_gradk_split(ics_rl* j, Prof& pr) {
+static int do_gradk_split(ics_rl* j, bool planar, Prof& pr) {
   const int K = j->g.K, pad = j->g.pad, L = 31, n = (K + L - 1) / L;
   RC(pr.begin(ICS_K_PSF_GRADIENT));
   for (int qa = 0; qa < n; ++qa)
@@ -1234,7 +1165,7 @@ static int do_gradk_split(ics_rl* j, Prof& pr) {
       const int Ks = (La <= 15 && Lb <= 15) ? 15 : 31, pads = Ks / 2, nt = Ks == 15 ? 16 : 32;
       IcsGradkArgs a;
       a.geo = j->g; a.geo.K = Ks; a.geo.pad = pads;
-      a.planar = j->fft_on ? 1 : 0;
+      a.planar = planar ? 1 : 0;
       if (a.planar) { a.e = porg(j, j->e); a.u = porg(j, j->u) + (ptrdiff_t)(pad - a0 - pads) * ics_ppitch(j->g) + (pad - b0 - pads); }
       else { a.e = org(j, j->e); a.u = org(j, j->u) + (ptrdiff_t)(pad - a0 - pads) * j->g.pitch + 3 * (pad - b0 - pads); }
       a.partial = j->partial;
@@ -1250,11 +1181,10 @@ static int do_gradk_split(ics_rl* j, Prof& pr) {
   return ICS_OK;
 }
 
-// the FFT-tile pipeline's own PSF gradient (k_gradk_fft): two forward transforms per tile pair, products added up in the frequency domain
-static bool use_fft_gradk(const ics_rl* j) { return j->fft_on && ics_debug().fft_gradk.load(std::memory_order_relaxed) != 0; }
-
-static int do_gradk(ics_rl* j, const ics_rl_params* p, Prof& pr) {
-  if (use_fft_gradk(j)) {
+// A13 on the route's gradient kernels (a stage of a fused family: the kernel that family fuses with A11)
+static int do_gradk(ics_rl* j, const Route& r, Prof& pr) {
+  const int fam = r.gradk == GK_FUSED_MATRIX ? GK_MATRIX : (r.gradk == GK_FUSED_TILES ? GK_TILES : r.gradk);
+  if (fam == GK_TILES) {   // the FFT-tile pipeline's own PSF gradient (k_gradk_fft): two forward transforms per tile pair, products added up in the frequency domain
     RC(pr.begin(ICS_K_PSF_GRADIENT));
     if (ics_conv_fft_blk_supported(j->g.K)) {   // one launch per block of lags
       int nb, kb;
@@ -1266,23 +1196,20 @@ static int do_gradk(ics_rl* j, const ics_rl_params* p, Prof& pr) {
     RC(pr.end());
     return ICS_OK;
   }
-  if (use_split_gradk(j, p)) return do_gradk_split(j, pr);
+  if (fam == GK_SPLIT) return do_gradk_split(j, r.tiles, pr);
   IcsGradkArgs a;
   a.e = org(j, j->e); a.u = org(j, j->u); a.partial = j->partial; a.geo = j->g; a.planar = 0;
-  if (j->fft_on) { a.e = porg(j, j->e); a.u = porg(j, j->u); a.planar = 1; }
+  if (r.tiles) { a.e = porg(j, j->e); a.u = porg(j, j->u); a.planar = 1; }
   RC(pr.begin(ICS_K_PSF_GRADIENT));
-  if (ics_big_supported(j->g.K) && !j->fft_on) HIPCHK(ics_launch_gradk_big(a, j->gradk_blocks, j->ctx->stream));
-  else if (use_matrix_gradk(j, p)) HIPCHK(ics_launch_gradk_mfma(a, j->gradk_blocks, j->ctx->stream));
+  if (fam == GK_SIZED) HIPCHK(ics_launch_gradk_big(a, j->gradk_blocks, j->ctx->stream));
+  else if (fam == GK_MATRIX) HIPCHK(ics_launch_gradk_mfma(a, j->gradk_blocks, j->ctx->stream));
   else HIPCHK(ics_launch_gradk(a, j->gradk_blocks, j->ctx->stream));
   HIPCHK(ics_launch_gradk_reduce(j->partial, j->gradk_blocks, j->gradk, j->g, j->ctx->stream));
   RC(pr.end());
   return ICS_OK;
 }
 
-// A11 + A13 as one three-transform unit on the tiles (k_synth_gradk_fft): wherever the pipeline takes its gradient on the tiles
-static bool use_fused_fft(const ics_rl* j, const ics_rl_params* p) {
-  return use_fft_gradk(j) && ics_conv_fft_supported(j->g.K) && !p->fuse && !(p->flags & ICS_FLAG_NO_FUSED_GRADK) && ics_debug().fft_fused.load(std::memory_order_relaxed) != 0;
-}
+// A11 + A13 as one three-transform unit on the tiles (k_synth_gradk_fft)
 static int do_synth_gradk_fft(ics_rl* j, const ics_rl_params* p, int store_all, Prof& pr) {
   const float *u = porg(j, j->u), *f = porg(j, j->f);
   float* e = porg(j, j->e);
@@ -1297,14 +1224,8 @@ static int do_synth_gradk_fft(ics_rl* j, const ics_rl_params* p, int store_all, 
 #ifndef ICS_FUSED_DEFAULT_RS
 #define ICS_FUSED_DEFAULT_RS 4
 #endif
-// A11 + A13 in one kernel where it exists (matrix-core path, MK <= 15): ics_synth_gradk_mfma.hip
-static bool use_fused_gradk(const ics_rl* j, const ics_rl_params* p) {
-  if (!ics_synth_gradk_supported(j->g.K) || !j->bt_conv || j->fft_on) return false;
-  if (p->flags & ICS_FLAG_NO_FUSED_GRADK) return false;
-  return ics_debug().fused_gradk.load(std::memory_order_relaxed) != 0 && use_matrix_conv(j, p) && use_matrix_gradk(j, p);
-}
-
-static int do_synth_gradk(ics_rl* j, const ics_rl_params* p, int store_all, Prof& pr) {
+// A11 + A13 in one kernel (matrix-core path, MK <= 15): ics_synth_gradk_mfma.hip
+static int do_synth_gradk(ics_rl* j, const Route& r, const ics_rl_params* p, int store_all, Prof& pr) {
   IcsFusedArgs a;
   a.u = org(j, j->u); a.f = org(j, j->f); a.e_out = org(j, j->e); a.bt = j->bt_conv; a.partial = j->partial; a.g = j->g;
   a.wy0 = p->top + j->g.pad; a.wy1 = p->bottom + j->g.pad; a.wx0 = p->left + j->g.pad; a.wx1 = p->right + j->g.pad;
@@ -1316,7 +1237,7 @@ static int do_synth_gradk(ics_rl* j, const ics_rl_params* p, int store_all, Prof
   const int frs = ics_debug().fused_rs.load(std::memory_order_relaxed);
   a.rs = frs == 2 || frs == 4 ? frs : ((long)j->g.tiles_x * j->g.tiles_y <= 2500 ? 2 : ICS_FUSED_DEFAULT_RS);
   a.facc = nullptr;
-  if (use_image_acc(p)) { RC(ensure_image_acc(j, a.rs)); a.facc = j->facc[a.rs == 2 ? 0 : 1]; }
+  if (r.image_acc) { RC(ensure_image_acc(j, a.rs)); a.facc = j->facc[a.rs == 2 ? 0 : 1]; }
   int nblocks = j->gradk_blocks;
   if (a.rs == 2) {
     const int tiles32 = ((j->g.N + 63) / 64) * ((j->g.M + 31) / 32);
@@ -1344,14 +1265,14 @@ static int do_majorize(ics_rl* j, Prof& pr) {
   return ICS_OK;
 }
 
-static int do_stats(ics_rl* j, const ics_rl_params* p, Prof& pr, int rearm = 0, hipStream_t st = nullptr) {
+static int do_stats(ics_rl* j, const Route& r, const ics_rl_params* p, Prof& pr, int rearm = 0, hipStream_t st = nullptr) {
   if (!st) st = j->ctx->stream;
   if (j->win_empty) {
     static const float nan3[3] = {nanf(""), nanf(""), nanf("")};   // M_r, Hu, varu
     HIPCHK(hipMemcpyAsync(j->scal + ICS_SC_MR, nan3, sizeof nan3, hipMemcpyHostToDevice, j->ctx->stream));
     return ICS_OK;
   }
-  if (j->fft_on) {   // A18 / A19 read HWC frames: bring the window of e and u over from the mirrors (u-frame rows [top, bottom + 2 pad))
+  if (r.tiles) {   // A18 / A19 read HWC frames: bring the window of e and u over from the mirrors (u-frame rows [top, bottom + 2 pad))
     const int pad2 = 2 * j->g.pad;
     HIPCHK(ics_launch_planar_convert(false, pl_of(j, j->e), j->e, j->g, false, p->top, p->bottom + pad2, p->left, p->right + pad2, st));
     HIPCHK(ics_launch_planar_convert(false, pl_of(j, j->u), j->u, j->g, false, p->top, p->bottom + pad2, p->left, p->right + pad2, st));
@@ -1402,20 +1323,92 @@ static int check_params(ics_rl* j, const ics_rl_params* p) {
   return ICS_OK;
 }
 
-// Small frames (ics_small.hip): every (tile, channel) of the u-frame on a compute unit of its own, the operands of the five inner iterations
-// resident in LDS, ONE cooperative launch per outer iteration instead of 25 - 30.  What ICS_CONV_AUTO picks for the shipped loop when the
-// frame is small enough (3 x tiles of 32 or 64 <= compute units, operands <= 160 KB of LDS: up to ~290^2 at 31 x 31, ~570^2 at 15 x 15);
-// an explicit ICS_CONV_* request, ICS_CONV_PATH or the debug switch `small_iter` = 0 keep the multi-launch families.
-static bool use_small_iter(const ics_rl* j, const ics_rl_params* p, IcsSmallPlan* plan = nullptr) {
-  if (p->conv != ICS_CONV_AUTO || p->tv_mode != ICS_TV_SHIPPED || p->fuse || j->fft_on || j->small_off) return false;
-  if (ics_debug().conv_path.load(std::memory_order_relaxed) != 0 || !ics_debug().small_iter.load(std::memory_order_relaxed)) return false;
-  // non-blind (two convolutions and two barriers per inner iteration): measured level with the multi-launch path at 255^2 for PSF sizes up to 15 (0.029 ms
-  // either way), ahead of it from 17 x 17 (255^2 / 23: 0.057 -> 0.041) and on frames up to ~160^2 at every size (128^2 / 7: 0.022 -> 0.018)
-  if (!p->blind && j->g.K < 17 && (long)j->g.uM * j->g.uN > 26000L) return false;
-  IcsSmallPlan pl;
-  if (!ics_small_plan(j->g, j->ctx ? j->ctx->cus : 256, &pl, ics_debug().small_iter.load(std::memory_order_relaxed) == 2)) return false;
-  if (plan) *plan = pl;
-  return true;
+// The routing table (see "routing" above).  in_run: ics_rl_run / ics_rl_describe rather than a single stage.  tiles_allowed = false: the
+// mirrors did not fit the device (ics_rl_run), or a stage that does not run on them (ics_rl_stage).
+static Route resolve_route(const ics_rl* j, const ics_rl_params* p, bool in_run, bool tiles_allowed) {
+  const IcsDebug& d = ics_debug();
+  auto sw = [](const std::atomic<int>& v) { return v.load(std::memory_order_relaxed); };
+  // ICS_CONV_PATH: what ICS_CONV_AUTO resolves to, 0 default, 1 vector, 2 matrix, 3 fft (where the tiles do not run -- single stages, tv_mode 1,
+  // PSF sizes above 65 -- what AUTO would take)
+  const int path = sw(d.conv_path), small_sw = sw(d.small_iter), conv2_sw = sw(d.fft_conv2), overlap_sw = sw(d.overlap);
+  const bool fused_sw = sw(d.fused_gradk) != 0, fft_gradk_sw = sw(d.fft_gradk) != 0, fft_fused_sw = sw(d.fft_fused) != 0, planar_sw = sw(d.planar_image) != 0;
+  const IcsGeom& g = j->g;
+  const int K = g.K;
+  const int cus = j->ctx ? j->ctx->cus : 256;   // (no HIP call on this path: ics_describe has no context and assumes an MI355X's 256 CUs)
+  const long px = (long)g.uM * g.uN;
+  const bool blind = p->blind != 0, fuse = p->fuse != 0, autoc = p->conv == ICS_CONV_AUTO, vector = p->conv == ICS_CONV_VECTOR, matrix_req = p->conv == ICS_CONV_MATRIX;
+  const bool shipped = p->tv_mode == ICS_TV_SHIPPED, pam = p->tv_mode == ICS_TV_PAM_ISO || p->tv_mode == ICS_TV_PAM_COLLAB;
+  Route r{};
+
+  // The transform tiles: the shipped loop (87 ... 255: tap blocks on the tiles) and, inside ics_rl_run, the PAM kinds -- TV term, back-projection
+  // epilogue and update on the mirrors too (single stages of the TV variants run on the HWC kernels).  Never fused, never beyond the mirrors' 2 GiB.
+  const bool tiles_built = shipped ? ics_conv_fft_supported(K) || ics_conv_fft_blk_supported(K) : pam && in_run && ics_conv_fft_supported(K);
+  if (tiles_allowed && tiles_built && !fuse && fft_mirror_fits(g)) {
+    if (p->conv == ICS_CONV_FFT) r.tiles = true;
+    // PAM kinds: bench.py --tv-mode 2, ICS_CONV_PATH=matrix -> fft (measured with the convolutions and the gradient on the tiles only), ms per inner iteration: 1448^2 / 31 blind 0.357 -> 0.297; 2048^2 / 21 blind 0.470 -> 0.396,
+    // non-blind 0.271 -> 0.259; 4096^2 / 19 blind 1.563 -> 1.132; 1100^2 / 45 blind 0.432 -> 0.310
+    // round 6: the shipped loop's thresholds -- the same kernels but for the epilogue's operands -- except below 6 Mpx at 15 x 15 and less, where the
+    // TV term's own pass on the planes tips it back (bench.py --tv-mode 2, ms per inner iteration, matrix cores -> tiles: 4096^2 / 15 blind 0.873 -> 0.780,
+    // tv_mode 3 0.869 -> 0.794; 2048^2 / 15 non-blind 0.176 -> 0.190, blind 0.261 -> 0.293)
+    else if (autoc && in_run) r.tiles = path == 3 || (path == 0 && fft_preferred(g, blind) && (!pam || K >= 17 || px >= 6000000L));
+  }
+  r.conv2 = r.tiles && conv2_sw != 0 && !j->conv2_off && ics_conv2_fft_supported(g) && (conv2_sw == 2 || K <= ICS_CONV2_MAX_K);
+
+  // Modes 0 / 1 on the HWC frames.  ICS_CONV_AUTO: the matrix-core kernels where they exist and win (ics_conv_mfma_preferred); PSF sizes 51 ... 127 as
+  // tap blocks on them (do_conv_blocks; 129 ... 255: no other path, ICS_CONV_PATH does not apply), shipped loop.  The run-time-sized fp32 kernels
+  // (ics_big.hip) are the only ones above 63, and under ICS_CONV_AUTO they take over from the packed-fp32 kernels compiled per size wherever the
+  // matrix-core kernels are not built or not chosen (51 .. 63; 39 .. 49 with ICS_CONV_PATH=...): they beat them (shipped loop, 2048^2 non-blind,
+  // ms per pass, compiled -> run-time-sized): synthesis 39: 0.626 -> 0.594, 45: 0.829 -> 0.756, 55: 1.238 -> 1.013, 63: 1.71 -> 1.27;
+  // back-projection (incl. the separate maxima pass) 39: 0.975 -> 0.716, 45: 1.348 -> 0.915, 55: 2.109 -> 1.233, 63: 2.88 -> 1.52.
+  // ICS_CONV_VECTOR keeps the compiled kernels (tests/test_gpu_stages.py drives them at every size).
+  const bool matrix = j->bt_conv && !vector && (matrix_req || path == 2 || ((path == 0 || path == 3) && ics_conv_mfma_preferred(K)));
+  if (j->blk_conv && shipped && !vector && (psf_blocks_only(K) || matrix_req || path != 1)) r.conv = CONV_BLOCKS;
+  else if (matrix) r.conv = CONV_MATRIX;
+  else if (ics_big_supported(K) || (autoc && shipped && K >= 39 && path != 1)) r.conv = CONV_SIZED;
+  else r.conv = CONV_PACKED;
+
+  // The PSF gradient has its own choice: the matrix-core kernel wins at every size it is built for (K <= 31; at K = 19, 21, where AUTO keeps the
+  // packed-fp32 convolutions, 0.35 vs 0.97 ms at 4096^2), and the tile pipeline's gradient reads the mirrors: matrix-core kernel only.  Fused with
+  // A11 where that exists (k_synth_gradk: matrix-core path, K <= 15; k_synth_gradk_fft: the tiles), from 33 on as 31 x 31 blocks (do_gradk_split).
+  const bool matrix_gk = ics_gradk_mfma_supported(K) && !vector && (matrix_req || r.tiles || path != 1);
+  const bool fusable = !fuse && !(p->flags & ICS_FLAG_NO_FUSED_GRADK), fft_gk = r.tiles && fft_gradk_sw;
+  if (fusable && !r.tiles && ics_synth_gradk_supported(K) && fused_sw && matrix && matrix_gk) r.gradk = GK_FUSED_MATRIX;
+  else if (fusable && fft_gk && ics_conv_fft_supported(K) && fft_fused_sw) r.gradk = GK_FUSED_TILES;
+  else if (fft_gk) r.gradk = GK_TILES;
+  else if (K >= 33 && !vector && (psf_blocks_only(K) || r.tiles || matrix_req || path != 1)) r.gradk = GK_SPLIT;
+  else if (ics_big_supported(K)) r.gradk = GK_SIZED;
+  else r.gradk = matrix_gk ? GK_MATRIX : GK_FP32;
+
+  // Small frames (ics_small.hip): every (tile, channel) of the u-frame on a compute unit of its own, the operands of the five inner iterations
+  // resident in LDS, ONE cooperative launch per outer iteration instead of 25 - 30.  What ICS_CONV_AUTO picks for the shipped loop when the
+  // frame is small enough (3 x tiles of 32 or 64 <= compute units, operands <= 160 KB of LDS: up to ~290^2 at 31 x 31, ~570^2 at 15 x 15);
+  // an explicit ICS_CONV_* request, ICS_CONV_PATH or the debug switch `small_iter` = 0 keep the multi-launch families.
+  // Non-blind (two convolutions and two barriers per inner iteration): measured level with the multi-launch path at 255^2 for PSF sizes up to 15 (0.029 ms
+  // either way), ahead of it from 17 x 17 (255^2 / 23: 0.057 -> 0.041) and on frames up to ~160^2 at every size (128^2 / 7: 0.022 -> 0.018).
+  r.small = autoc && shipped && !fuse && !r.tiles && !j->small_off && path == 0 && small_sw != 0 && (blind || K >= 17 || px <= 26000L) &&
+            ics_small_plan(g, cus, &r.plan, small_sw == 2);
+
+  // tv_mode 1 rewrites the image in every inner iteration (pyx:547-549 live): a copy would have to be rebuilt each time
+  r.image_acc = p->tv_mode != ICS_TV_MM_ACTIVE && planar_sw;
+  r.acc_order = !r.small && r.image_acc && ((!r.tiles && r.conv == CONV_MATRIX && ics_conv_mfma_rs(K, g, cus) != 0) || (blind && r.gradk == GK_FUSED_MATRIX));
+
+  // Statistics of outer iteration i overlapped with iteration i + 1 (ics_rl_run).  Not with the opt-in fused update + convolution (its
+  // own u ping-pong), not with tv_mode 1 (the image is stepped too: nothing to fall back on), not with an empty window, not for a
+  // single iteration.  Debug switch `overlap` = 0 restores the drain at every outer boundary.
+  // Measured (MI355X, ms per inner iteration, drained -> overlapped): non-blind 512^2 / 9x9 0.044 -> 0.040 (0.060 -> 0.040 after a long run of
+  // small launches, when the device has clocked down), non-blind 2048^2 / 15x15 0.160 -> 0.152; blind 4096^2 / 15x15 0.808 -> 0.804 without
+  // and 0.810 -> 0.821 with event brackets in the timed region: on frames that fill the device the statistics' small kernels only compete
+  // with the persistent workgroups of the convolutions.
+  // Re-measured at the end of round 4 on two boxes, drained -> overlapped: non-blind 512^2 0.045 -> 0.040, 1024^2 0.080 -> 0.073, 1448^2 0.103 -> 0.096,
+  // 2048^2 level, 2560^2 0.218 -> 0.223, 2900^2 0.270 -> 0.277, 3072^2 0.320 -> 0.333; blind 255^2 0.066 -> 0.066 ... 0.070 (the copies of the PSF
+  // and the event bubble of an outer boundary weigh as much as the drain they replace), 512^2 0.073 -> 0.077, 1024^2 0.114 -> 0.111, 1536^2
+  // level, 2048^2 0.227 -> 0.232, 2560^2 0.333 -> 0.341.  Hence by default (switch = 1): non-blind up to 4.5 Mpx, blind between 0.6 and 2.5 Mpx;
+  // everywhere with switch = 2.  (Round 6: on the transform tiles -- one persistent 1024-thread workgroup per CU -- the statistics' small kernels
+  // fit beside the iteration's at every size: 4096^2 / 15, drained -> second stream: blind 0.6713 -> 0.6591 ms, non-blind 0.4734 -> 0.4629; the
+  // cooperative iteration kernel of small frames leaves room beside it as well: blind 255^2 / 15 0.060 -> 0.052 ms.)
+  if (!fuse && p->tv_mode != ICS_TV_MM_ACTIVE && !j->win_empty && p->iterations >= 2)
+    r.overlap = overlap_sw == 2 || (overlap_sw == 1 && (r.tiles || r.small || (blind ? px >= 600000L && px <= 2500000L : px <= 4500000L)));
+  return r;
 }
 
 static int ensure_small(ics_rl* j, const IcsSmallPlan& pl) {
@@ -1471,80 +1464,21 @@ static int do_small_iter(ics_rl* j, const ics_rl_params* p, const IcsSmallPlan& 
   return ICS_OK;
 }
 
-// One submission per outer iteration (round 4).  deblur_module runs its blind phase on a 255-px window at every pyramid level
-// (deconvolve.py:138-141,277-286): 15 ... 35 launches of 5 ... 15 us each per outer iteration, where the host's launch calls and
-// the gaps between dependent dispatches weigh as much as the kernels.  The launches of an outer iteration (pyx:462-638: five inner
-// iterations, the statistics, the copy of the scalars to the pinned host mirror) are captured once per frame rotation and replayed
-// with hipGraphLaunch.  Not with profiling (events between the kernels), not with the opt-in fused update + convolution (its own
-// ping-pong), not with an empty window (host-side NaN upload).  Default: frames up to 1.2 Mpx; debug switch `graph` = 0 / 1 forces.
-static bool use_graph(const ics_rl* j, const ics_rl_params* p) {
-  if (p->profile || p->fuse || j->win_empty || use_fft_pipeline(j, p, true) || use_small_iter(j, p)) return false;
-  const int g = ics_debug().graph.load(std::memory_order_relaxed);
-  if (g >= 0) return g != 0;
-  return (long)j->g.uM * j->g.uN <= 1200000L;
-}
-
-// Statistics of outer iteration i overlapped with iteration i + 1 (ics_rl_run).  Not with the opt-in fused update + convolution (its
-// own u ping-pong), not with tv_mode 1 (the image is stepped too: nothing to fall back on), not with an empty window, not for a
-// single iteration.  Debug switch `overlap` = 0 restores the drain at every outer boundary.
-// Measured (MI355X, ms per inner iteration, drained -> overlapped): non-blind 512^2 / 9x9 0.044 -> 0.040 (0.060 -> 0.040 after a long run of
-// small launches, when the device has clocked down), non-blind 2048^2 / 15x15 0.160 -> 0.152; blind 4096^2 / 15x15 0.808 -> 0.804 without
-// and 0.810 -> 0.821 with event brackets in the timed region: on frames that fill the device the statistics' small kernels only compete
-// with the persistent workgroups of the convolutions.
-// Re-measured at the end of round 4 on two boxes, drained -> overlapped: non-blind 512^2 0.045 -> 0.040, 1024^2 0.080 -> 0.073, 1448^2 0.103 -> 0.096,
-// 2048^2 level, 2560^2 0.218 -> 0.223, 2900^2 0.270 -> 0.277, 3072^2 0.320 -> 0.333; blind 255^2 0.066 -> 0.066 ... 0.070 (the copies of the PSF
-// and the event bubble of an outer boundary weigh as much as the drain they replace), 512^2 0.073 -> 0.077, 1024^2 0.114 -> 0.111, 1536^2
-// level, 2048^2 0.227 -> 0.232, 2560^2 0.333 -> 0.341.  Hence by default (switch = 1): non-blind up to 4.5 Mpx, blind between 0.6 and 2.5 Mpx;
-// everywhere with switch = 2.
-// Switch = 3 (opt-in): the same loop with the statistics queued on the job's OWN stream: no concurrency, but iteration i + 1 is still queued
-// before M_r(i) reaches the host, so the device does not idle through the host's round trip at an outer boundary.  Measured: never slower,
-// 0 ... 1.5 % faster (blind 4096^2 0.8145 -> 0.8075 ms, blind 512^2 0.075 -> 0.072, 255^2 0.066 -> 0.065, the rest level) -- less than the
-// outer iteration a run wastes when its stop test fires (1 / n of a run that stops after n), and a frame more per job: not the default.
-// Returns 0: drain at every outer boundary, 1: statistics on the second stream, 2: look-ahead on the job's stream.
-#ifndef ICS_LOOKAHEAD_DEFAULT
-#define ICS_LOOKAHEAD_DEFAULT 0
-#endif
-static int use_overlap(const ics_rl* j, const ics_rl_params* p) {
-  if (p->fuse || p->tv_mode == ICS_TV_MM_ACTIVE || j->win_empty || p->iterations < 2) return 0;
-  const int sw = ics_debug().overlap.load(std::memory_order_relaxed);
-  const long px = (long)j->g.uM * j->g.uN;
-  if (sw == 2) return 1;
-  if (sw == 3) return 2;
-  if (sw != 1) return 0;
-  // (round 6: on the transform tiles -- one persistent 1024-thread workgroup per CU -- the statistics' small kernels fit beside the iteration's at
-  //  every size: 4096^2 / 15, drained -> second stream: blind 0.6713 -> 0.6591 ms, non-blind 0.4734 -> 0.4629; look-ahead on the job's own stream 0.669 / 0.470)
-  if (j->fft_on || use_small_iter(j, p)) return 1;   // (the cooperative iteration kernel of small frames leaves room beside it as well: blind 255^2 / 15 0.060 -> 0.052 ms)
-  if (p->blind ? (px >= 600000L && px <= 2500000L) : px <= 4500000L) return 1;
-  return ICS_LOOKAHEAD_DEFAULT ? 2 : 0;
-}
-
-// ics_rl_describe / ics_describe: the routing predicates above, as the launches below evaluate them
+// ics_rl_describe / ics_describe: the route ics_rl_run resolves for these parameters
 static int describe_impl(ics_rl* j, const ics_rl_params* p, ics_rl_route* r) {
   if (!r) return fail(ICS_EINVAL, "route is NULL");
   if (r->struct_size != sizeof(ics_rl_route)) return fail(ICS_EINVAL, "ics_rl_route.struct_size = %u, expected %zu", r->struct_size, sizeof(ics_rl_route));
   RC(check_params(j, p));
-  memset(r, 0, sizeof *r);
+  const Route rt = resolve_route(j, p, true, true);
+  memset(r, 0, sizeof *r);   // (graph: always 0)
   r->struct_size = sizeof(ics_rl_route);
-  const bool fft = use_fft_pipeline(j, p, true);
-  struct Flag { ics_rl* j; bool was; ~Flag() { j->fft_on = was; } } flag{j, j->fft_on};   // (the gradient's predicates read it)
-  j->fft_on = fft;
-  const bool blocks = !fft && use_block_conv(j, p, 0), matrix = !fft && !blocks && use_matrix_conv(j, p);
-  const bool small = !fft && use_small_iter(j, p);
-  r->conv_family = small ? 6 : (fft ? 5 : (blocks ? 2 : (matrix ? 1 : (use_big_conv(j, p, 0) ? 4 : 3))));
-  r->conv_fp16_split = !small && (blocks || matrix);
-  if (p->blind && small) r->gradk_family = 8;
-  else if (p->blind) {
-    const bool fused = !p->fuse && use_fused_gradk(j, p);
-    if (fused) r->gradk_family = 1;
-    else if (use_fused_fft(j, p)) r->gradk_family = 7;
-    else if (use_fft_gradk(j)) r->gradk_family = 6;
-    else if (use_split_gradk(j, p)) r->gradk_family = 3;
-    else if (ics_big_supported(j->g.K)) r->gradk_family = 5;
-    else r->gradk_family = use_matrix_gradk(j, p) ? 2 : 4;
-    r->gradk_fp16_split = r->gradk_family <= 3;
+  r->conv_family = rt.small ? CONV_SMALL : (rt.tiles ? CONV_TILES : rt.conv);
+  r->conv_fp16_split = r->conv_family == CONV_MATRIX || r->conv_family == CONV_BLOCKS;
+  if (p->blind) {
+    r->gradk_family = rt.small ? GK_SMALL : rt.gradk;
+    r->gradk_fp16_split = r->gradk_family <= GK_SPLIT;
   }
-  r->image_in_accumulator_order = small ? 0 : (matrix && use_image_acc(p) && ics_conv_mfma_rs(j->g.K, j->g, j->ctx ? j->ctx->cus : 256) != 0) || (r->gradk_family == 1 && use_image_acc(p));   // (no HIP call on this path: ics_describe has no context and assumes an MI355X's 256 CUs)
-  r->graph = use_graph(j, p) ? 1 : 0;
+  r->image_in_accumulator_order = rt.acc_order;
   return ICS_OK;
 }
 extern "C" int ics_rl_describe(ics_rl* j, const ics_rl_params* p, ics_rl_route* r) { return describe_impl(j, p, r); }
@@ -1581,25 +1515,25 @@ extern "C" int ics_rl_run(ics_rl* j, const ics_rl_params* p, ics_rl_stats* st) {
   // error return inside the overlapped loop used to skip the drain), and the FFT pipeline's flag is cleared
   struct Drain { ics_ctx* c; ~Drain() { if (c->stream2) (void)hipStreamSynchronize(c->stream2); } } drain{j->ctx};
   FftScope fft_scope{j};
-  if (use_fft_pipeline(j, p, true)) {   // the frames live as channel-planar mirrors for the duration of the run (ics_planar.hip)
+  // the route, resolved once (again without the tiles if their mirrors do not fit); the other fallbacks edit it, the overlap decision stays
+  Route r = resolve_route(j, p, true, true);
+  if (r.tiles) {   // the frames live as channel-planar mirrors for the duration of the run (ics_planar.hip)
     j->fft_on = true;
     int rc_pl = ensure_planar(j);
     // the mirrors are 7 - 8 more frame-sized buffers: when they do not fit and the tiles were AUTO's choice, the run goes on on the HWC
     // kernels, which need nothing more (an explicit ICS_CONV_FFT, and the PAM kinds' explicit request, report the failure)
-    if (rc_pl == ICS_ENOMEM && p->conv == ICS_CONV_AUTO) { j->fft_on = false; (void)hipGetLastError(); }
+    if (rc_pl == ICS_ENOMEM && p->conv == ICS_CONV_AUTO) { j->fft_on = false; (void)hipGetLastError(); r = resolve_route(j, p, true, false); }
     else if (rc_pl != ICS_OK) return rc_pl;
   }
-  if (j->fft_on) {
+  if (r.tiles) {
     RC(to_planar(j, j->u, s));
     if (!j->plf_valid) { RC(to_planar(j, j->f, s)); j->plf_valid = true; }
     fft_scope.back = true;
     // mode 2's image spectra are 1.6 frames more (128 KB per unit): when they do not fit, the run takes A1 and A3 as two kernels instead
-    if (use_conv2(j, p) && !j->fspec && dalloc(j->ctx, &j->fspec, ics_conv2_fft_fspec_floats(j->g), false) != ICS_OK) { j->fspec = nullptr; j->conv2_off = true; (void)hipGetLastError(); }
+    if (r.conv2 && !j->fspec && dalloc(j->ctx, &j->fspec, ics_conv2_fft_fspec_floats(j->g), false) != ICS_OK) { j->fspec = nullptr; j->conv2_off = true; r.conv2 = false; (void)hipGetLastError(); }
   }
-  IcsSmallPlan small_plan;
-  bool small = use_small_iter(j, p, &small_plan);
-  if (small && ensure_small(j, small_plan) != ICS_OK) { small = false; (void)hipGetLastError(); }   // (AUTO's choice: the multi-launch path needs nothing more)
-  if (small) { HIPCHK(hipMemsetAsync(j->small_bar, 0, (size_t)ICS_SMALL_BAR_WORDS * sizeof(unsigned long long), s)); j->small_gen = 0; j->small_bak = false; }
+  if (r.small && ensure_small(j, r.plan) != ICS_OK) { r.small = false; (void)hipGetLastError(); }   // (AUTO's choice: the multi-launch path needs nothing more)
+  if (r.small) { HIPCHK(hipMemsetAsync(j->small_bar, 0, (size_t)ICS_SMALL_BAR_WORDS * sizeof(unsigned long long), s)); j->small_gen = 0; j->small_bak = false; }
   {  // everything but the caller's in-fields is overwritten
     ics_rl_stats in = *st;
     memset(st, 0, sizeof *st);
@@ -1632,9 +1566,9 @@ extern "C" int ics_rl_run(ics_rl* j, const ics_rl_params* p, ics_rl_stats* st) {
     j->ev_chain = -1;
     if (p->fuse) RC(do_majorize(j, pr));                      // pyx:462 (explicit copy only for the fused path)
     else j->ut_is_u = true;                                   // pyx:462 without a copy (see ut_of)
-    if (small) {   // one cooperative launch for the INNER inner iterations (ics_small.hip)
-      if (do_small_iter(j, p, small_plan, INNER, p->profile > 0 ? pr_on : pr_off) == ICS_OK) { inner_done += INNER; return ICS_OK; }
-      small = false; j->small_off = true; (void)hipGetLastError();   // refused by the runtime: this job runs the multi-launch path from here on
+    if (r.small) {   // one cooperative launch for the INNER inner iterations (ics_small.hip)
+      if (do_small_iter(j, p, r.plan, INNER, p->profile > 0 ? pr_on : pr_off) == ICS_OK) { inner_done += INNER; return ICS_OK; }
+      r.small = false; j->small_off = true; (void)hipGetLastError();   // refused by the runtime: this job runs the multi-launch path from here on
       RC(pack_weights(j, 0, 0.f, 0, s));   // (the weight tables of the multi-launch kernels follow the PSF the cooperative launches have stepped so far)
       if (j->small_bak) {   // (the copy of the PSF the refused launch was to take)
         const size_t npsf = (size_t)3 * j->g.K * j->g.K;
@@ -1644,41 +1578,39 @@ extern "C" int ics_rl_run(ics_rl* j, const ics_rl_params* p, ics_rl_stats* st) {
       }
     }
     const bool fuse = p->fuse != 0;
-    const bool fused_gk = p->blind && !fuse && use_fused_gradk(j, p);
-    const bool fused_fft = p->blind && !fuse && use_fused_fft(j, p);
-    // (blind without the fused A11 + A13 unit: A11 rewrites the whole residual frame, nothing more to do; either way the window is there)
-    const bool conv2 = use_conv2(j, p);
+    const bool fused_gk = r.gradk == GK_FUSED_MATRIX, fused_fft = r.gradk == GK_FUSED_TILES;
+    // (mode 2 of the tiles, blind without the fused A11 + A13 unit: A11 rewrites the whole residual frame, nothing more to do; either way the window is there)
     bool have_e = false;  // error already produced by a fused update+synth kernel
     for (int itt = 0; itt < INNER; ++itt) {                   // pyx:473
       const int last = itt == INNER - 1;
       // profile = k: bracket the launches of every k-th inner iteration only (k = 1: all).  Event records
       // between dependent kernels cost ~4 % of a 4096^2 blind iteration, a sample of them does not.
       Prof& pr = (p->profile > 0 && inner_done % p->profile == 0) ? pr_on : pr_off;
-      if (conv2) {
-        if (tv) RC(do_tvterm(j, p, itt, pr));                 // (PAM kinds: T of u, read by the back-projection's epilogue)
+      if (r.conv2) {
+        if (tv) RC(do_tvterm(j, r, p, itt, pr));              // (PAM kinds: T of u, read by the back-projection's epilogue)
         RC(do_conv2(j, p, itt, pr));                          // A1 + A2 + A3 (+A7) in one unit per tile pair; the residual frame is not written ...
         if (!p->blind && last) RC(do_conv_fft_window(j, p, pr));   // ... so the statistics' window of it is (blind: A11 rewrites it, do_synth_gradk_fft)
       } else {
-      if (!have_e) RC(do_conv(j, 0, p, itt, 0, pr));          // A1+A2
+      if (!have_e) RC(do_conv(j, r, 0, p, itt, 0, pr));       // A1+A2
       have_e = false;
-      if (tv) RC(do_tvterm(j, p, itt, pr));                   // pyx:495-496 (live only in tv_mode 1)
-      RC(do_conv(j, 1, p, itt, 0, pr));                       // A3 (+A7)
+      if (tv) RC(do_tvterm(j, r, p, itt, pr));                // pyx:495-496 (live only in tv_mode 1)
+      RC(do_conv(j, r, 1, p, itt, 0, pr));                    // A3 (+A7)
       }
       if (p->blind) {                                         // pyx:555
-        if (fuse) RC(do_conv(j, 2, p, itt, last, pr));        // A5-A10 fused with A11
+        if (fuse) RC(do_conv(j, r, 2, p, itt, last, pr));     // A5-A10 fused with A11
         else {
-          RC(do_update(j, p, itt, last, pr));
-          if (fused_gk) RC(do_synth_gradk(j, p, 0, pr));      // A11 + A12 + A13, e' stays on chip
+          RC(do_update(j, r, p, itt, last, pr));
+          if (fused_gk) RC(do_synth_gradk(j, r, p, 0, pr));   // A11 + A12 + A13, e' stays on chip
           else if (fused_fft) RC(do_synth_gradk_fft(j, p, 0, pr));   // the same on the transform tiles
-          else RC(do_conv(j, 0, p, itt, 0, pr));
+          else RC(do_conv(j, r, 0, p, itt, 0, pr));
         }
-        if (fuse || !(fused_gk || fused_fft)) RC(do_gradk(j, p, pr));   // A12+A13
+        if (!(fused_gk || fused_fft)) RC(do_gradk(j, r, pr));   // A12+A13
         RC(do_psf(j, p, pr));                                 // A14-A17
       } else if (fuse && !last) {
-        RC(do_conv(j, 2, p, itt, 0, pr));                     // A5-A10 fused with A1+A2 of itt+1
+        RC(do_conv(j, r, 2, p, itt, 0, pr));                  // A5-A10 fused with A1+A2 of itt+1
         have_e = true;
       } else {
-        RC(do_update(j, p, itt, last, pr));                   // A5,A6,A8,A10 (outer boundary: stats need u and e)
+        RC(do_update(j, r, p, itt, last, pr));                // A5,A6,A8,A10 (outer boundary: stats need u and e)
       }
       ++inner_done;
     }
@@ -1686,30 +1618,10 @@ extern "C" int ics_rl_run(ics_rl* j, const ics_rl_params* p, ics_rl_stats* st) {
   };
   // ... and its statistics (A18 + A19) with the copy of the scalars to the pinned host mirror `hs`, on stream `st`
   auto enqueue_stats = [&](hipStream_t st, float* hs, Prof& prs) -> int {
-    RC(do_stats(j, p, prs, 1, st));
+    RC(do_stats(j, r, p, prs, 1, st));
     HIPCHK(hipMemcpyAsync(hs, j->scal, ICS_SC_COUNT * 4, hipMemcpyDeviceToHost, st));
     return ICS_OK;
   };
-  auto enqueue_outer = [&]() -> int {
-    RC(enqueue_body());
-    return enqueue_stats(s, j->h_scal, pr);
-  };
-  // One hipGraph launch per outer iteration (use_graph): everything captured carries the parameters in its kernel arguments, so the
-  // executables live as long as the parameter set (and the debug switches) stay what they were.
-  const bool graphs_on = use_graph(j, p);
-  if (graphs_on) {
-    ics_rl_params sig;
-    memset(&sig, 0, sizeof sig);
-    sig.top = p->top; sig.bottom = p->bottom; sig.left = p->left; sig.right = p->right; sig.tau = p->tau; sig.step_factor = p->step_factor;
-    sig.lambd = p->lambd; sig.blind = p->blind; sig.correlation = p->correlation; sig.channels = p->channels; sig.tv_mode = p->tv_mode;
-    sig.stop_test = p->stop_test; sig.conv = p->conv; sig.flags = p->flags;
-    const int epoch = g_debug_epoch.load(std::memory_order_relaxed);
-    if (!j->graphs.empty() && (memcmp(&sig, &j->graph_sig, sizeof sig) != 0 || epoch != j->graph_epoch)) {
-      for (auto& g : j->graphs) hipGraphExecDestroy(g.exec);
-      j->graphs.clear();
-    }
-    j->graph_sig = sig; j->graph_epoch = epoch;
-  }
   // what the host does once the scalars of an outer iteration are in `hs`: traces, stop decision (pyx:643-654), progress callback
   auto consume = [&](const float* hs) {
     if (it > 0) M_r_prev = M_r;                               // pyx:623-624
@@ -1734,8 +1646,7 @@ extern "C" int ics_rl_run(ics_rl* j, const ics_rl_params* p, ics_rl_stats* st) {
     if (p->progress && p->progress(p->progress_user, it, stop, dmin, dmax, M_r, Hu, varu) != 0 && !stop) stop = 2;
   };
   j->par = 0;
-  const int ovl = graphs_on ? 0 : use_overlap(j, p);
-  if (ovl) {
+  if (r.overlap) {
     // ---- statistics of iteration i on a second stream, iteration i + 1 already running on the job's stream (round 4) -------------------
     // The stop decision of iteration i needs M_r(i) on the host, so until round 3 the device drained at every outer boundary: five
     // small dependent kernels (0.06 ms) and a round trip with nothing else in flight -- a quarter of a 512^2 step, 7 % at 2048^2.
@@ -1745,7 +1656,7 @@ extern "C" int ics_rl_run(ics_rl* j, const ics_rl_params* p, ics_rl_stats* st) {
     // iteration i + 1 is undone: its u is dropped for the majoriser frame (= u(i)), the PSF comes back from the copy taken when i + 1
     // started.  At most one outer iteration is ever ahead, and only the run's last decision costs a wasted one.
     ics_ctx* c = j->ctx;
-    if (ovl == 1 && !c->stream2) {   // lowest priority: the statistics take what the iteration's kernels leave free
+    if (!c->stream2) {   // lowest priority: the statistics take what the iteration's kernels leave free
       int lo = 0, hi = 0;
       HIPCHK(hipDeviceGetStreamPriorityRange(&lo, &hi));
       HIPCHK(hipStreamCreateWithPriority(&c->stream2, hipStreamNonBlocking, lo));
@@ -1753,16 +1664,16 @@ extern "C" int ics_rl_run(ics_rl* j, const ics_rl_params* p, ics_rl_stats* st) {
     if (!j->ev_body[0])
       for (int i = 0; i < 2; ++i) { HIPCHK(hipEventCreateWithFlags(&j->ev_body[i], hipEventDisableTiming)); HIPCHK(hipEventCreateWithFlags(&j->ev_stats[i], hipEventDisableTiming)); }
     if (!j->e2) RC(dalloc(c, &j->e2, j->frame_floats));
-    if (j->fft_on) RC(ensure_planar(j));                     // (a mirror for e2 as well)
+    if (r.tiles) RC(ensure_planar(j));                       // (a mirror for e2 as well)
     const size_t npsf = (size_t)3 * j->g.K * j->g.K;
     if (p->blind && !j->psf_bak) RC(dalloc(c, &j->psf_bak, 2 * npsf, false));
-    const hipStream_t st2 = ovl == 1 ? c->stream2 : s;      // where the statistics run
+    const hipStream_t st2 = c->stream2;                     // where the statistics run
     Prof pr_s2{j, p->profile != 0, st2};
     size_t ev_mark[2] = {0, 0}, ev_done = 0;
     int enq = 0;                                              // outer iterations queued; `it` = outer iterations whose scalars were consumed
     auto undo = [&]() -> int {                                // drops iteration enq - 1 (queued, possibly running)
       HIPCHK(hipStreamSynchronize(s));
-      if (st2 != s) HIPCHK(hipStreamSynchronize(st2));
+      HIPCHK(hipStreamSynchronize(st2));
       { float* t = j->u; j->u = j->ut; j->ut = t; }           // the majoriser frame of the dropped iteration is u of the one before
       { float* t = j->e; j->e = j->e2; j->e2 = t; }
       if (p->blind) {
@@ -1780,17 +1691,15 @@ extern "C" int ics_rl_run(ics_rl* j, const ics_rl_params* p, ics_rl_stats* st) {
       j->par = enq & 1;
       if (enq > 0) {
         { float* t = j->e; j->e = j->e2; j->e2 = t; }         // the statistics of the previous iteration read the other frame
-        if (p->blind && small) j->small_bak = true;           // (the cooperative kernel takes the copy itself: two launches and a queue switch less per outer iteration)
+        if (p->blind && r.small) j->small_bak = true;           // (the cooperative kernel takes the copy itself: two launches and a queue switch less per outer iteration)
         else if (p->blind) {
           HIPCHK(hipMemcpyAsync(j->psf_bak, j->psf, npsf * 4, hipMemcpyDeviceToDevice, s));
           HIPCHK(hipMemcpyAsync(j->psf_bak + npsf, j->psf_caller, npsf * 4, hipMemcpyDeviceToDevice, s));
         }
       }
       RC(enqueue_body());
-      if (st2 != s) {
-        HIPCHK(hipEventRecord(j->ev_body[enq & 1], s));
-        HIPCHK(hipStreamWaitEvent(st2, j->ev_body[enq & 1], 0));
-      }
+      HIPCHK(hipEventRecord(j->ev_body[enq & 1], s));
+      HIPCHK(hipStreamWaitEvent(st2, j->ev_body[enq & 1], 0));
       RC(enqueue_stats(st2, j->h_scal + (enq & 1) * (ICS_SC_COUNT + 4), pr_s2));
       HIPCHK(hipEventRecord(j->ev_stats[enq & 1], st2));
       ev_mark[enq & 1] = j->ev_pairs.size();
@@ -1808,7 +1717,7 @@ extern "C" int ics_rl_run(ics_rl* j, const ics_rl_params* p, ics_rl_stats* st) {
       consume(j->h_scal + ((enq - 1) & 1) * (ICS_SC_COUNT + 4));
     }
     HIPCHK(hipStreamSynchronize(s));
-    if (st2 != s) HIPCHK(hipStreamSynchronize(st2));
+    HIPCHK(hipStreamSynchronize(st2));
     RC(pr.collect_range(ms, launches, ev_done, j->ev_pairs.size()));
     j->ev_used = 0; j->ev_pairs.clear(); j->ev_chain = -1;
     j->par = 0;
@@ -1818,36 +1727,15 @@ extern "C" int ics_rl_run(ics_rl* j, const ics_rl_params* p, ics_rl_stats* st) {
       HIPCHK(hipMemsetAsync(j->red, 0, 8 * ICS_RED_STRIDE * sizeof(uint32_t), s));
       RC(reset_dofkeys(j));
     }
-    if (graphs_on && it > 0) {   // (the first outer iteration of a call runs eagerly: first launches configure kernels and build lazily-allocated copies)
-      hipGraphExec_t exec = nullptr;
-      for (auto& g : j->graphs) if (g.u == j->u && g.ut == j->ut && g.u2 == j->u2) exec = g.exec;
-      if (exec) {
-        HIPCHK(hipGraphLaunch(exec, s));
-        float* old_ut = j->ut;                                // the rotation the captured do_update performed (period 3)
-        j->ut = j->u; j->u = j->u2; j->u2 = old_ut; j->ut_is_u = false;
-        inner_done += INNER;
-      } else {
-        ics_rl::Graph g{j->u, j->ut, j->u2, nullptr};
-        HIPCHK(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-        const int rc_body = enqueue_outer();
-        hipGraph_t graph = nullptr;
-        const hipError_t e_end = hipStreamEndCapture(s, &graph);   // always: the stream must leave capture mode whatever the body returned
-        if (rc_body != ICS_OK) { if (graph) hipGraphDestroy(graph); return rc_body; }
-        if (e_end != hipSuccess) return fail(ICS_EHIP, "hipStreamEndCapture: %s", hipGetErrorString(e_end));
-        const hipError_t e_inst = hipGraphInstantiate(&g.exec, graph, nullptr, nullptr, 0);
-        hipGraphDestroy(graph);
-        if (e_inst != hipSuccess) return fail(ICS_EHIP, "hipGraphInstantiate: %s", hipGetErrorString(e_inst));
-        j->graphs.push_back(g);
-        HIPCHK(hipGraphLaunch(g.exec, s));
-      }
-    } else RC(enqueue_outer());
+    RC(enqueue_body());
+    RC(enqueue_stats(s, j->h_scal, pr));
     // (the wait's wake-up is not what the device idles on here: an event before the statistics + polling through them measured the
     //  same iteration time, 0.8178 vs 0.8185 ms at 4096^2 and 0.1573 vs 0.1562 at 2048^2 non-blind)
     HIPCHK(hipStreamSynchronize(s));
     RC(pr.collect(ms, launches));
     consume(j->h_scal);
   }
-  if (j->fft_on) { RC(from_planar(j, j->u, s)); RC(from_planar(j, j->e, s)); fft_scope.back = false; }   // the HWC frames are the job's state between calls
+  if (r.tiles) { RC(from_planar(j, j->u, s)); RC(from_planar(j, j->e, s)); fft_scope.back = false; }   // the HWC frames are the job's state between calls
   HIPCHK(ics_launch_hasnan(org(j, j->u), j->g, j->flags + 1, s));
   HIPCHK(hipEventRecord(j->ev_end, s));
   int hflags[4] = {0, 0, 0, 0};
@@ -1877,9 +1765,10 @@ extern "C" int ics_rl_stage(ics_rl* j, int stage, const ics_rl_params* p) {
   // conv = ICS_CONV_FFT through the stage API (tests): the stage runs on the mirrors, every frame is copied over before and the frames a
   // stage writes are copied back after -- slow and simple; ics_rl_run converts at its boundaries only
   FftScope fft_scope{j};
-  const bool fft_stage = use_fft_pipeline(j, p, false) && (stage == ICS_STAGE_SYNTH_RESIDUAL || stage == ICS_STAGE_BACKPROJECT || stage == ICS_STAGE_UPDATE ||
-                                                            stage == ICS_STAGE_PSF_GRADIENT || stage == ICS_STAGE_PSF_UPDATE || stage == ICS_STAGE_SYNTH_GRADK || stage == ICS_STAGE_SYNTH_BACKPROJECT);
-  if (fft_stage) {
+  const bool tile_stage = stage == ICS_STAGE_SYNTH_RESIDUAL || stage == ICS_STAGE_BACKPROJECT || stage == ICS_STAGE_UPDATE || stage == ICS_STAGE_PSF_GRADIENT ||
+                          stage == ICS_STAGE_PSF_UPDATE || stage == ICS_STAGE_SYNTH_GRADK || stage == ICS_STAGE_SYNTH_BACKPROJECT;
+  const Route r = resolve_route(j, p, false, tile_stage);
+  if (r.tiles) {
     j->fft_on = true;
     RC(ensure_planar(j));
     for (float* h : {j->u, j->ut, j->gr, j->f, j->e}) RC(to_planar(j, h, s));
@@ -1888,35 +1777,35 @@ extern "C" int ics_rl_stage(ics_rl* j, int stage, const ics_rl_params* p) {
   struct StageBack {   // (runs before fft_scope clears the flag: declared after it)
     ics_rl* j; bool on; hipStream_t s;
     ~StageBack() { if (on) { for (float* h : {j->u, j->gr, j->e}) (void)from_planar(j, h, s); (void)hipStreamSynchronize(s); } }
-  } stage_back{j, fft_stage, s};
+  } stage_back{j, r.tiles, s};
   switch (stage) {
     case ICS_STAGE_SYNTH_RESIDUAL:
       RC(pack_weights(j, 0, 0.f, 0, s));
-      RC(do_conv(j, 0, p, 0, 0, pr));
+      RC(do_conv(j, r, 0, p, 0, 0, pr));
       break;
     case ICS_STAGE_BACKPROJECT:
       RC(pack_weights(j, 0, 0.f, 0, s));
       // (in tv_mode 1 ICS_STAGE_TVTERM runs first and owns the reset: its keys live in the same slot)
       if (p->tv_mode == ICS_TV_SHIPPED) HIPCHK(hipMemsetAsync(j->red, 0, 8 * ICS_RED_STRIDE * sizeof(uint32_t), s));
       else RC(ensure_tv(j));
-      RC(do_conv(j, 1, p, 0, 0, pr));
+      RC(do_conv(j, r, 1, p, 0, 0, pr));
       break;
     case ICS_STAGE_UPDATE:
       RC(reset_dofkeys(j));
-      RC(do_update(j, p, 0, 1, pr));
+      RC(do_update(j, r, p, 0, 1, pr));
       break;
     case ICS_STAGE_TVTERM:
       if (p->tv_mode == ICS_TV_SHIPPED) return fail(ICS_EINVAL, "ICS_STAGE_TVTERM needs tv_mode != ICS_TV_SHIPPED");
       RC(ensure_tv(j));
       HIPCHK(hipMemsetAsync(j->red, 0, 8 * ICS_RED_STRIDE * sizeof(uint32_t), s));
-      RC(do_tvterm(j, p, 0, pr));
+      RC(do_tvterm(j, r, p, 0, pr));
       break;
     case ICS_STAGE_UPDATE_SYNTH:
       RC(pack_weights(j, 0, 0.f, 0, s));
       RC(reset_dofkeys(j));
-      RC(do_conv(j, 2, p, 0, 1, pr));
+      RC(do_conv(j, r, 2, p, 0, 1, pr));
       break;
-    case ICS_STAGE_PSF_GRADIENT: RC(do_gradk(j, p, pr)); break;
+    case ICS_STAGE_PSF_GRADIENT: RC(do_gradk(j, r, pr)); break;
     case ICS_STAGE_BAND_REDUCE:
       if (p->tv_mode != ICS_TV_SHIPPED) return fail(ICS_ENOSUP, "row bands are built for the shipped loop (tv_mode 0)");
       if (p->band_row0 < 0 || p->band_row1 > j->g.uM || p->band_row0 >= p->band_row1) return fail(ICS_EINVAL, "band rows [%d, %d) outside the %d u rows", p->band_row0, p->band_row1, j->g.uM);
@@ -1928,18 +1817,18 @@ extern "C" int ics_rl_stage(ics_rl* j, int stage, const ics_rl_params* p) {
       HIPCHK(ics_launch_band_mask_e(org(j, j->e), j->g, p->band_row0, p->band_row1, s));
       break;
     case ICS_STAGE_SYNTH_GRADK:
-      if (j->fft_on && !ics_conv_fft_supported(j->g.K)) return fail(ICS_ENOSUP, "ICS_STAGE_SYNTH_GRADK on the tiles: the fused unit is built for PSF sizes that fit one tile (<= 85); above, A11 and A13 run as tap blocks");
-      if (j->fft_on) {   // conv = ICS_CONV_FFT: the fused unit of the transform tiles, every tile stores its residual
+      if (r.tiles && !ics_conv_fft_supported(j->g.K)) return fail(ICS_ENOSUP, "ICS_STAGE_SYNTH_GRADK on the tiles: the fused unit is built for PSF sizes that fit one tile (<= 85); above, A11 and A13 run as tap blocks");
+      if (r.tiles) {   // conv = ICS_CONV_FFT: the fused unit of the transform tiles, every tile stores its residual
         RC(pack_weights(j, 0, 0.f, 0, s));
         RC(do_synth_gradk_fft(j, p, 1, pr));
         break;
       }
       if (!ics_synth_gradk_supported(j->g.K) || !j->bt_conv) return fail(ICS_ENOSUP, "ICS_STAGE_SYNTH_GRADK is built for PSF sizes <= 15");
       RC(pack_weights(j, 0, 0.f, 0, s));
-      RC(do_synth_gradk(j, p, 1, pr));
+      RC(do_synth_gradk(j, r, p, 1, pr));
       break;
     case ICS_STAGE_SYNTH_BACKPROJECT:
-      if (!j->fft_on || p->tv_mode != ICS_TV_SHIPPED || !ics_conv2_fft_supported(j->g))
+      if (!r.tiles || p->tv_mode != ICS_TV_SHIPPED || !ics_conv2_fft_supported(j->g))
         return fail(ICS_ENOSUP, "ICS_STAGE_SYNTH_BACKPROJECT needs params.conv = ICS_CONV_FFT, tv_mode 0 and a PSF of at most 57 x 57");
       RC(pack_weights(j, 0, 0.f, 0, s));
       HIPCHK(hipMemsetAsync(j->red, 0, 8 * ICS_RED_STRIDE * sizeof(uint32_t), s));
@@ -1951,7 +1840,7 @@ extern "C" int ics_rl_stage(ics_rl* j, int stage, const ics_rl_params* p) {
       HIPCHK(hipMemsetAsync(j->dacc, 0, 8 * sizeof(double), s));
       HIPCHK(hipMemsetAsync(j->ukey, 0, 2 * sizeof(uint32_t), s));
       RC(ensure_window(j, p));
-      RC(do_stats(j, p, pr));
+      RC(do_stats(j, r, p, pr));
       break;
     default: return fail(ICS_EINVAL, "unknown stage %d", stage);
   }

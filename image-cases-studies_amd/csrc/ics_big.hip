@@ -4,7 +4,7 @@
 // are FFTs).  The tuned kernels of this library are compiled per size (matrix cores to 37, packed fp32 to 63); beyond that these
 // two kernels take the size at run time.  Plain fp32 FMA streams out of LDS -- built to be correct and to keep the arithmetic units
 // busy, not tuned per size: at 4096^2 a 65x65 convolution is 4.2e11 flop per pass.  Under ICS_CONV_AUTO they also serve the upper part
-// of the compiled range where they are the faster ones (ics_api.hip, use_big_conv).
+// of the compiled range where they are the faster ones (ics_api.hip, resolve_route).
 //
 //   k_conv_big  : out[y, x, c] = sum_{a,b<K} W[a, b, c] * in[y + a - pad, x + b - pad, c]   (u-frame coordinates, as ics_conv.hip)
 //                 W = rot180(psf), out = error - image on the M x N interior (mode 0: pyx:477-488)

@@ -110,7 +110,7 @@ struct IcsDebug {
   std::atomic<int> pam_exact;         // ICS_PAM_EXACT         1 = the TV term of ALL three extended kinds (tv_mode 1, 2, 3) with IEEE sqrt / division per value
   std::atomic<int> fail_window_alloc; // (test hook)           n = the n-th allocation of the next ensure_window() fails once with ICS_ENOMEM
   std::atomic<int> pool_limit_mb;     // ICS_POOL_LIMIT_MB     cap of a context's cache of freed device blocks in MiB (-1: a quarter of the device memory; 0: no caching)
-  std::atomic<int> overlap;           // ICS_OVERLAP           0 = drain at every outer boundary, 1 (default) = statistics on a second stream where that measured ahead (use_overlap, ics_api.hip), 2 = second stream always, 3 = look-ahead with the statistics on the job's own stream
+  std::atomic<int> overlap;           // ICS_OVERLAP           0 = drain at every outer boundary, 1 (default) = statistics on a second stream where that measured ahead (resolve_route, ics_api.hip), 2 = second stream always
   std::atomic<int> fft_gradk;         // ICS_FFT_GRADK         0 = the FFT-tile pipeline takes its PSF gradient on the matrix cores (k_gradk_mfma on the mirrors) instead of on the tiles
   std::atomic<int> fft_fused;         // ICS_FFT_FUSED         0 = the FFT-tile pipeline runs A11 and A13 as two kernels (k_conv_fft<0> + k_gradk_fft) instead of the fused three-transform unit
   std::atomic<int> fft_conv2;         // ICS_FFT_CONV2         0 = the FFT-tile pipeline runs A1 and A3 as two kernels; 1 (default) = as one unit per tile pair (k_conv_fft<2>) for the PSF sizes it pays for; 2 = wherever it is built
@@ -118,7 +118,6 @@ struct IcsDebug {
   std::atomic<int> small_iter;        // ICS_SMALL_ITER        0 = small frames run the multi-launch families instead of the cooperative iteration kernel (ics_small.hip); 2 = 64-pixel tiles too; default 1, 0 under rocprofv3
   std::atomic<int> fail_small_launch; // (test hook)           1 = the next cooperative launch of the small-frame kernel is refused once (the job falls back to the multi-launch path)
   std::atomic<int> small_trace;       // ICS_SMALL_TRACE       1 = every cooperative launch is followed by a drain and a phase timeline on stderr
-  std::atomic<int> graph;             // ICS_GRAPH             0 (default) never, 1 always, -1 frames <= 1.2 Mpx: one hipGraph launch per outer iteration (measured: no gain, NOTES_r04.md 4d)
   static int env_int(const char* name, int dflt) { const char* e = getenv(name); return (e && e[0]) ? atoi(e) : dflt; }
   IcsDebug() {
     max_wgs = env_int("ICS_TEST_MAX_WGS", 0);
@@ -147,7 +146,6 @@ struct IcsDebug {
     small_iter = env_int("ICS_SMALL_ITER", profiler ? 0 : 1);
     small_trace = env_int("ICS_SMALL_TRACE", 0);
     fail_small_launch = 0;
-    graph = env_int("ICS_GRAPH", 0);
     overlap = env_int("ICS_OVERLAP", 1);
     pool_limit_mb = env_int("ICS_POOL_LIMIT_MB", -1);
   }

@@ -234,8 +234,8 @@ int ics_rl_run(ics_rl *job, const ics_rl_params *params, ics_rl_stats *stats);
  * tiles: single stages run on them only under an explicit params.conv = ICS_CONV_FFT with tv_mode 0 -- under ICS_CONV_AUTO, and for the PAM
  * kinds, a stage-driven loop such as lib/banded.py runs the matrix-core / vector kernels where ics_rl_run would take the tiles; describe
  * such a loop with params.conv = ICS_CONV_MATRIX.)  Inputs: (PSF size, params.conv, tv_mode, fuse,
- * flags, the ICS_CONV_PATH override): the library's own routing predicates, so that a benchmark labels its precision and traffic
- * figures from what actually runs.  Families:  convolutions A1/A3 -- 1 fp16-split matrix cores (whole PSF), 2 the same as tap blocks
+ * flags, the ICS_CONV_PATH override): the route ics_rl_run resolves and launches from, so that a benchmark labels its precision and
+ * traffic figures from what actually runs.  Families:  convolutions A1/A3 -- 1 fp16-split matrix cores (whole PSF), 2 the same as tap blocks
  * (PSF > 49), 3 packed-fp32 kernels compiled per size, 4 run-time-sized fp32 kernels (ics_big.hip), 5 fp32 transform tiles on planar
  * mirrors (ics_conv_fft.hip), 6 the cooperative small-frame iteration kernel (ics_small.hip: the five inner iterations of an outer one in
  * ONE launch, a tile of a channel per compute unit, fp32 FMAs; frames up to ~290 px a side, PSF <= 31, shipped loop, ICS_CONV_AUTO only;
@@ -249,7 +249,7 @@ typedef struct ics_rl_route {
   int conv_family, conv_fp16_split;
   int gradk_family, gradk_fp16_split;
   int image_in_accumulator_order; /* the residual kernels read the read-only accumulator-order copy of the image (ics_image_acc.h) */
-  int graph;                      /* ics_rl_run submits one hipGraph per outer iteration (small frames; ICS_GRAPH=0|1 overrides) */
+  int graph;                      /* kept for the layout: always 0 */
 } ics_rl_route;
 int ics_rl_describe(ics_rl *job, const ics_rl_params *params, ics_rl_route *route);
 /* The same for a shape alone -- no device and no job needed (a benchmark or a test labels its lines before anything is allocated). */

@@ -182,7 +182,7 @@ def test_big_psf_refusals():
 
 @pytest.mark.parametrize("MK", [45, 51, 59, 63])
 def test_auto_path_above_37_against_the_kernels_compiled_per_size(MK):
-    """ICS_CONV_AUTO (csrc/ics_api.hip): matrix-core kernels to 49 x 49, ics_big.hip (use_big_conv) above; ICS_CONV_VECTOR keeps the
+    """ICS_CONV_AUTO (csrc/ics_api.hip): matrix-core kernels to 49 x 49, ics_big.hip (resolve_route) above; ICS_CONV_VECTOR keeps the
     packed-fp32 kernels compiled per size.  Both against float64 direct sums with the same gate, and against each other."""
     from lib import _native as nv
     M, N = 70 + MK, 131

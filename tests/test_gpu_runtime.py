@@ -82,40 +82,6 @@ def test_callback_return_value_stops_the_run_and_params_are_left_alone():
         job.close()
 
 
-@pytest.mark.parametrize("blind,tv_mode,MK", [(False, 0, 9), (True, 0, 9), (True, 0, 21), (False, 1, 7), (True, 2, 15), (True, 3, 15)])
-def test_graph_replay_is_bit_identical_to_eager_launches(blind, tv_mode, MK, debug_switch):
-    """One hipGraph launch per outer iteration (use_graph, csrc/ics_api.hip): 8 outer iterations cross the three-frame rotation of
-    u / ut / spare twice, so every captured executable is replayed at least once; u, psf, the traces and the stop-test scalars must
-    be those of the eager launches bit for bit.  Then a second call on the same job with other parameters (lambd): the executables
-    of the first parameter set must not be replayed."""
-    from lib import _native as nv
-    M, N = 150, 131
-    case = orc.synth_case(M, N, MK, seed=7, blind=blind)
-    win = orc.default_window(M, N, MK)
-    out = {}
-    debug_switch("small_iter", 0)      # (graphs belong to the multi-launch families: the cooperative small-frame kernel is one launch per outer iteration already)
-    for graph in (0, 1):
-        debug_switch("graph", graph)
-        job = nv.RLJob(M, N, MK)
-        try:
-            res = []
-            for lambd in (1e4, 3e3):
-                job.upload(case["image"], case["u0"], case["psf0"])
-                p = job.params(*win, 1e9, 8, 1e-3, lambd, blind, tv_mode=tv_mode, stop_test=2)      # (evaluate the stop test, never stop: all 8 iterations run)
-                assert job.describe(p).graph == graph
-                st = job.run(p)
-                u, psf, _ = job.download()
-                res.append((u, psf, np.array(st.trace_M_r[:8]), np.array(st.trace_Hu[:8]), np.array(st.trace_dof_max[:8]), st.inner_iterations))
-            out[graph] = res
-        finally:
-            job.close()
-    for a, b in zip(out[0], out[1]):
-        assert a[5] == b[5] == 40
-        for x, y in zip(a[:5], b[:5]):
-            assert np.array_equal(x, y, equal_nan=True)
-    assert not np.array_equal(out[1][0][0], out[1][1][0])       # the second parameter set did change the result
-
-
 def test_stats_window_allocation_failure_leaves_the_job_usable(debug_switch):
     """ensure_window freed its buffers, failed to reallocate, and kept the OLD window key -- the next run with the
     previous window passed the cache check and launched the statistics kernels on freed / NULL buffers.  Window A, a failing window B
@@ -163,19 +129,19 @@ def test_statistics_overlapped_with_the_next_iteration_change_nothing(golden_dir
     blind M_r > M_r_prev), that run to the end, and with the correlation quirk (the caller's PSF frozen after the first step)."""
     z, meta = load_golden(golden_dir, name)
     res = {}
-    for ov in (0, 2, 3):
+    for ov in (0, 2):
         debug_switch("overlap", ov)
         u, psf, log, st = _run(z, meta, iters)
         res[ov] = (u, psf, log, st.iterations_done, st.stopped, st.inner_iterations, np.array(st.trace_M_r[:st.trace_len]), np.array(st.trace_Hu[:st.trace_len]),
                    np.array(st.trace_varu[:st.trace_len]), np.array(st.trace_dof_min[:st.trace_len]), np.array(st.trace_dof_max[:st.trace_len]), st.M_r, st.Hu, st.varu)
     a = res[0]
     print("%s: %d of %d outer iterations, stopped = %d" % (name, a[3], iters, a[4]))
-    for b in (res[2], res[3]):       # 2: statistics on the second stream; 3: look-ahead on the job's own stream
-        assert a[3:6] == b[3:6] and a[5] == 5 * a[3]
-        assert a[2] == b[2]                                                  # the printed lines
-        for x, y in zip(a[:2] + a[6:11], b[:2] + b[6:11]):
-            assert np.array_equal(x, y, equal_nan=True)
-        assert a[11:] == b[11:] or all(np.isnan(v) for v in a[11:] + b[11:])
+    b = res[2]                       # statistics on the second stream
+    assert a[3:6] == b[3:6] and a[5] == 5 * a[3]
+    assert a[2] == b[2]                                                  # the printed lines
+    for x, y in zip(a[:2] + a[6:11], b[:2] + b[6:11]):
+        assert np.array_equal(x, y, equal_nan=True)
+    assert a[11:] == b[11:] or all(np.isnan(v) for v in a[11:] + b[11:])
 
 
 def test_abort_under_overlap_drops_the_iteration_that_was_ahead(debug_switch):
@@ -213,7 +179,7 @@ def test_long_overlapped_run_equals_the_drained_one(debug_switch, blind, tv_mode
     case = orc.synth_case(M, N, MK, seed=5, blind=blind)
     win = orc.default_window(M, N, MK)
     out = {}
-    for ov in (0, 2, 3):
+    for ov in (0, 2):
         debug_switch("overlap", ov)
         job = nv.RLJob(M, N, MK)
         try:
@@ -223,6 +189,5 @@ def test_long_overlapped_run_equals_the_drained_one(debug_switch, blind, tv_mode
             out[ov] = job.download() + (np.array(st.trace_M_r[:150]), np.array(st.trace_dof_max[:150]), np.array(st.trace_varu[:150]))
         finally:
             job.close()
-    for ov in (2, 3):
-        for x, y in zip(out[0], out[ov]):
-            assert np.array_equal(x, y, equal_nan=True)
+    for x, y in zip(out[0], out[2]):
+        assert np.array_equal(x, y, equal_nan=True)
