@@ -1272,10 +1272,12 @@ static int do_stats(ics_rl* j, const Route& r, const ics_rl_params* p, Prof& pr,
     HIPCHK(hipMemcpyAsync(j->scal + ICS_SC_MR, nan3, sizeof nan3, hipMemcpyHostToDevice, j->ctx->stream));
     return ICS_OK;
   }
-  if (r.tiles) {   // A18 / A19 read HWC frames: bring the window of e and u over from the mirrors (u-frame rows [top, bottom + 2 pad))
+  if (r.tiles) {   // A18 / A19 read HWC frames: bring the window of e and u over from the mirrors (u-frame rows [top, bottom + 2 pad); to the
+                   // frame's end where the u window's stop is negative and numpy counts it from there, ics_stats.hip make_win)
     const int pad2 = 2 * j->g.pad;
-    HIPCHK(ics_launch_planar_convert(false, pl_of(j, j->e), j->e, j->g, false, p->top, p->bottom + pad2, p->left, p->right + pad2, st));
-    HIPCHK(ics_launch_planar_convert(false, pl_of(j, j->u), j->u, j->g, false, p->top, p->bottom + pad2, p->left, p->right + pad2, st));
+    const int y1 = p->bottom < j->g.pad ? j->g.uM : p->bottom + pad2, x1 = p->right < j->g.pad ? j->g.uN : p->right + pad2;
+    HIPCHK(ics_launch_planar_convert(false, pl_of(j, j->e), j->e, j->g, false, p->top, y1, p->left, x1, st));
+    HIPCHK(ics_launch_planar_convert(false, pl_of(j, j->u), j->u, j->g, false, p->top, y1, p->left, x1, st));
   }
   IcsStatsArgs a;
   a.e = org(j, j->e); a.u = org(j, j->u); a.scal = j->scal; a.dofkeys = dof_of(j); a.dacc = j->dacc; a.ukey = j->ukey;

@@ -42,6 +42,7 @@
 #include "ics_kernels.h"
 #include "ics_tw128.h"
 #include <algorithm>
+#include <mutex>
 #include <vector>
 
 #define ICS_FFT_P 128
@@ -1699,15 +1700,23 @@ hipError_t ics_launch_conv2_fft(const IcsConvArgs& c, const float* spec_conv, co
   // the bottom row on 86 workgroups while 170 idle: 0.293 -> 0.281 ms with the walk started half way).  Of eight starting points the one with
   // the lightest most-loaded workgroup is taken (workgroup of walk position k = k mod grid); the choice depends on the geometry and the grid
   // only and is kept for the next launch.  Order only: results do not change.
+  // The kept choice is one record (geometry, grid and rot together) read and written under a mutex: jobs of other geometries run
+  // concurrently from several host threads (lib/banded.py: one per band), and a rot read apart from its own key could lie beyond this
+  // launch's unit list, where walk_unit would send positions past the end and drop their units.
   if (ics_debug().fft_rot.load(std::memory_order_relaxed)) {
-    static std::atomic<long long> cache_key{-1};
-    static std::atomic<int> cache_rot{0};
+    struct RotCache { int M = -1, N = -1, K = -1, grid = -1, rot = 0; };
+    static std::mutex cache_mu;
+    static RotCache cache;
     const int dev = ics_current_device();
     int grid = ics_device_cus(dev);
     if (const int mw = ics_debug().max_wgs.load(std::memory_order_relaxed); mw > 0 && grid > mw) grid = mw;
     if (grid > a.nunits) grid = a.nunits;
-    const long long key = ((long long)c.g.M << 40) ^ ((long long)c.g.N << 16) ^ ((long long)c.g.K << 8) ^ (long long)grid;
-    if (cache_key.load(std::memory_order_acquire) == key) a.rot = cache_rot.load(std::memory_order_relaxed);
+    RotCache hit;
+    {
+      std::lock_guard<std::mutex> lk(cache_mu);
+      hit = cache;
+    }
+    if (hit.M == c.g.M && hit.N == c.g.N && hit.K == c.g.K && hit.grid == grid) a.rot = hit.rot;
     else {
       std::vector<unsigned char> ring((size_t)a.nunits);
       for (int n = 0; n < a.nunits; ++n) ring[n] = icsfft::unit_is_border(a, icsfft::decode_unit(a, n)) ? 1 : 0;
@@ -1723,9 +1732,13 @@ hipError_t ics_launch_conv2_fft(const IcsConvArgs& c, const float* spec_conv, co
         if (best_cost < 0 || cost < best_cost) { best_cost = cost; best = a.rot; }
       }
       a.rot = best;
-      cache_rot.store(best, std::memory_order_relaxed); cache_key.store(key, std::memory_order_release);
+      RotCache fresh;
+      fresh.M = c.g.M; fresh.N = c.g.N; fresh.K = c.g.K; fresh.grid = grid; fresh.rot = best;
+      std::lock_guard<std::mutex> lk(cache_mu);
+      cache = fresh;
     }
   }
+  if (a.rot < 0 || a.rot >= a.nunits) a.rot = 0;   // (a start point outside the list would drop units; any inside it only reorders the walk)
   return ics_launch_conv_fft_args(2, a, s);
 }
 // ---- tap blocks (PSF sizes above ICS_FFT_MAX_K) ------------------------------------------------------------------------------------------------

@@ -46,7 +46,11 @@ struct Win {
 __device__ __forceinline__ Win make_win(const IcsStatsArgs& a) {
   Win w;
   w.H = a.bottom - a.top; w.W = a.right - a.left;
-  w.Hu = (a.bottom - a.geo.pad) - (a.top + a.geo.pad); w.Wu = (a.right - a.geo.pad) - (a.left + a.geo.pad);
+  // u window: numpy's slice u[top + pad:bottom - pad, left + pad:right - pad] (pyx:600), whose negative stop counts from the end of the u-frame
+  // (a window that ends less than pad rows / columns into the image: the reference then takes the rows / columns down to uM - (pad - bottom))
+  const int yb = a.bottom - a.geo.pad < 0 ? a.bottom - a.geo.pad + a.geo.uM : a.bottom - a.geo.pad;
+  const int xb = a.right - a.geo.pad < 0 ? a.right - a.geo.pad + a.geo.uN : a.right - a.geo.pad;
+  w.Hu = yb - (a.top + a.geo.pad); w.Wu = xb - (a.left + a.geo.pad);
   if (w.Hu < 0) w.Hu = 0;
   if (w.Wu < 0) w.Wu = 0;
   w.ne = w.H * w.W * 3; w.nu = w.Hu * w.Wu * 3;

@@ -104,7 +104,10 @@ typedef struct ics_rl_params {
                                    all) and the per-outer kernels with HIP events on the job's stream;
                                    per-kernel averages are reported in ics_rl_stats         */
   int fuse;                     /* 1: the image update of inner iteration i is fused in front of the next
-                                   convolution (one kernel, u ping-pong, bit-identical results).  Default 0:
+                                   convolution (one kernel, u ping-pong; the fused kernel is an fp32 one: bit-identical results on the fp32 routes;
+                                   on a matrix-core route A1 then takes fp32 products instead of fp16-split ones
+                                   after the first inner iteration of an outer one, so results differ there in
+                                   rounding (<= 1e-5 relative, tests/test_gpu_route_matrix.py).  Default 0:
                                    measured SLOWER on MI355X at 4096^2/15x15 (0.67 ms vs 0.28 + 0.19 ms),
                                    the 1.8x halo recompute with two IEEE divisions per element outweighs
                                    the saved frame pass (NOTES_r01.md section 4)                            */
