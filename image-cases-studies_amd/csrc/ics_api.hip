@@ -226,7 +226,7 @@ extern "C" size_t ics_rl_stats_size(void) { return sizeof(ics_rl_stats); }
 static std::atomic<int>* debug_switch(const char* name) {
   IcsDebug& d = ics_debug();
   const struct { const char* n; std::atomic<int>* v; } tab[] = {
-      {"max_wgs", &d.max_wgs}, {"dynamic_tiles", &d.dynamic_tiles}, {"conv_rs", &d.conv_rs}, {"conv_nh", &d.conv_nh}, {"conv_path", &d.conv_path},
+      {"max_wgs", &d.max_wgs}, {"dynamic_tiles", &d.dynamic_tiles}, {"conv_rs", &d.conv_rs}, {"conv_path", &d.conv_path},
       {"fused_gradk", &d.fused_gradk}, {"update_wg_per_cu", &d.update_wg_per_cu}, {"update_kernel", &d.update_kernel}, {"fused_rs", &d.fused_rs},
       {"planar_image", &d.planar_image}, {"pam_exact", &d.pam_exact}, {"fail_window_alloc", &d.fail_window_alloc}, {"pool_limit_mb", &d.pool_limit_mb}, {"overlap", &d.overlap}, {"fft_gradk", &d.fft_gradk}, {"fft_fused", &d.fft_fused}, {"fft_conv2", &d.fft_conv2}, {"fft_rot", &d.fft_rot}, {"small_iter", &d.small_iter}, {"small_trace", &d.small_trace}, {"fail_small_launch", &d.fail_small_launch}};
   for (auto& t : tab)
@@ -482,7 +482,7 @@ static int pack_weights(ics_rl* j, int do_step, float step, int correlation, hip
   a.correlation = correlation; a.do_step = do_step;
   HIPCHK(ics_launch_psf(a, s));
   if (j->blk_conv) HIPCHK(ics_launch_pack_blocks(j->psf, j->g.K, j->blk_kb, j->blk_n, j->blk_conv, j->blk_corr, ics_conv_mfma_table_floats(j->blk_kb), s));
-  if (j->fft_on) {   // conj(DFT2(W)) / 128^2 of both orientations (PSF sizes above 97: of every tap block)
+  if (j->fft_on) {   // conj(DFT2(W)) / 128^2 of both orientations (PSF sizes above 85: of every tap block)
     int nb = 0, kb = 0;
     if (ics_conv_fft_blk_supported(j->g.K)) ics_conv_fft_blk_shape(j->g.K, &nb, &kb);
     HIPCHK(ics_launch_fft_spectrum(j->psf, j->g.K, j->spec_conv, j->spec_corr, s, nb, kb));
@@ -901,12 +901,8 @@ struct Route {
 //  shrinks: 62 pixels a side at 67, 32 at 97 -- against the matrix cores' tap blocks, profiles/r06_ab_fft_bigk.txt, non-blind / blind:
 //  1024^2 67: 0.659 -> 0.160 / 1.270 -> 0.332;  2048^2 67: 1.894 -> 0.333 / 3.621 -> 0.609;  97: 2.455 -> 0.793 / 5.182 -> 1.494;
 //  4096^2 67: 6.774 -> 1.059 / 12.78 -> 1.746;  85: 7.822 -> 1.676 / 14.43 -> 2.895;  97: 9.011 -> 2.848 / 18.46 -> 4.989)
-#ifndef ICS_FFT_AUTO_MAX_K
-#define ICS_FFT_AUTO_MAX_K 85
-#endif
-#ifndef ICS_FFT_BLK_MIN_PX
-#define ICS_FFT_BLK_MIN_PX 500000L
-#endif
+static constexpr int ICS_FFT_AUTO_MAX_K = 85;
+static constexpr long ICS_FFT_BLK_MIN_PX = 500000L;
 static bool fft_preferred(const IcsGeom& g, bool blind) {
   // measured on MI355X (NOTES_r05.md): per-pass time of the transform tiles is set by the tile count (128 - K + 1 valid pixels a side),
   // the Toeplitz matrix-core kernels pay K^2.  scripts/ab_fft.py at the end of round 5, ms per inner iteration, matrix cores -> tiles
@@ -1028,9 +1024,7 @@ static int do_conv_fft(ics_rl* j, int mode, const ics_rl_params* p, int slot, Pr
 // 0.156 -> 0.136;  25: 0.109 -> 0.100 / 0.172 -> 0.161;  2048^2 15: 0.186 -> 0.154 / 0.293 -> 0.250;  21: 0.187 -> 0.178 / 0.294 -> 0.281;  25: 0.201 -> 0.175 / 0.319 -> 0.283;
 // 31: 0.184 -> 0.230 / 0.306 -> 0.351;  4096^2 9: 0.572 -> 0.470 / 0.775 -> 0.668;  15: 0.581 -> 0.518 / 0.797 -> 0.714 (another box: 0.576 -> 0.485 / 0.794 -> 0.686);
 // 21: 0.600 -> 0.561 / 0.828 -> 0.774;  25: level / 0.867 -> 0.859;  31: 0.636 -> 0.735 / 0.909 -> 0.990.
-#ifndef ICS_CONV2_MAX_K
-#define ICS_CONV2_MAX_K 25
-#endif
+static constexpr int ICS_CONV2_MAX_K = 25;
 static int do_conv2(ics_rl* j, const ics_rl_params* p, int slot, Prof& pr) {
   if (!j->fspec) RC(dalloc(j->ctx, &j->fspec, ics_conv2_fft_fspec_floats(j->g), false));
   if (!j->fspec_valid) {
@@ -1221,9 +1215,7 @@ static int do_synth_gradk_fft(ics_rl* j, const ics_rl_params* p, int store_all, 
   return ICS_OK;
 }
 
-#ifndef ICS_FUSED_DEFAULT_RS
-#define ICS_FUSED_DEFAULT_RS 4
-#endif
+static constexpr int ICS_FUSED_DEFAULT_RS = 4;
 // A11 + A13 in one kernel (matrix-core path, MK <= 15): ics_synth_gradk_mfma.hip
 static int do_synth_gradk(ics_rl* j, const Route& r, const ics_rl_params* p, int store_all, Prof& pr) {
   IcsFusedArgs a;

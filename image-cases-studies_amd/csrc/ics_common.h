@@ -100,7 +100,6 @@ struct IcsDebug {
   std::atomic<int> max_wgs;           // ICS_TEST_MAX_WGS      cap on persistent workgroups, 0 = none (tests: many tiles per workgroup)
   std::atomic<int> dynamic_tiles;     // ICS_DYNAMIC_TILES     -1 launcher decides, 0 static walk, 1 dynamic tile claiming
   std::atomic<int> conv_rs;           // ICS_TEST_CONV_RS      0 launcher decides, 2 / 4 = force 32- / 64-row tiles where both are built
-  std::atomic<int> conv_nh;           // ICS_TEST_CONV_NH      harness builds only: 1 = 4-wave form of the K >= 23 kernels
   std::atomic<int> conv_path;         // ICS_CONV_PATH         what ICS_CONV_AUTO resolves to: 0 default, 1 vector, 2 matrix, 3 fft (transform tiles, ics_conv_fft.hip)
   std::atomic<int> fused_gradk;       // ICS_FUSED_GRADK       0 = two-kernel A11 + A13 (like ICS_FLAG_NO_FUSED_GRADK)
   std::atomic<int> update_wg_per_cu;  // ICS_UPDATE_WG_PER_CU  0 launcher decides
@@ -123,7 +122,6 @@ struct IcsDebug {
     max_wgs = env_int("ICS_TEST_MAX_WGS", 0);
     dynamic_tiles = env_int("ICS_DYNAMIC_TILES", -1);
     conv_rs = env_int("ICS_TEST_CONV_RS", 0);
-    conv_nh = env_int("ICS_TEST_CONV_NH", 0);
     const char* cp = getenv("ICS_CONV_PATH");
     conv_path = !cp ? 0 : (cp[0] == 'v' ? 1 : (cp[0] == 'm' ? 2 : (cp[0] == 'f' ? 3 : 0)));
     fused_gradk = env_int("ICS_FUSED_GRADK", 1);
@@ -181,8 +179,7 @@ __device__ __forceinline__ float ics_dof_ratio(float g, float f) {
 // Persistent tile walks (ics_conv_mfma.hip, ics_synth_gradk_mfma.hip): workgroup b runs on XCD b % nb and walks the band of tiles
 // [ics_band_begin(x), ics_band_begin(x + 1)) of its XCD x.  A band's share of the tiles follows the number of workgroups that walk it
 // (grid / nb, or one more for the first grid % nb XCDs).  With equal shares, 85 tiles dealt to 85 workgroups gave two XCDs 11 tiles
-// and 10 workgroups: one workgroup walked two tiles and a 255^2 back-projection took 16 us instead of 10 (phase timeline,
-// tools/bench_conv_mfma.hip -DICS_MFMA_TRACE).
+// and 10 workgroups: one workgroup walked two tiles and a 255^2 back-projection took 16 us instead of 10 (phase timeline).
 __host__ __device__ inline int ics_band_begin(int ntiles, int grid, int nb, int x) {
   const int q = grid / nb, r = grid - q * nb;
   return (int)((long)ntiles * (q * x + (x < r ? x : r)) / grid);

@@ -27,10 +27,6 @@
 // (DESIGN.md), so this path is VALU by design.
 #include "ics_common.h"
 
-#ifndef ICS_CONV_NTY32
-#define ICS_CONV_NTY32 1
-#endif
-
 namespace {
 
 template <int K, int R, int NTY = 16>
@@ -430,7 +426,7 @@ hipError_t launch_one(const IcsConvArgs& a, hipStream_t s) {
 template <int K>
 hipError_t launch_k(int mode, const IcsConvArgs& a, hipStream_t s) {
   // NTY = 32 (512 threads, 64x64-px tile, 2 workgroups = 16 waves per CU) when its LDS image fits twice
-  constexpr int NTY = (2 * ConvCfg<K, 2, 32>::LDS_BYTES <= 160 * 1024 && ICS_CONV_NTY32) ? 32 : 16;
+  constexpr int NTY = 2 * ConvCfg<K, 2, 32>::LDS_BYTES <= 160 * 1024 ? 32 : 16;
   if (mode == 2) {
     if constexpr (K <= 31) return launch_one<K, 2, 2, NTY>(a, s);
     else return hipErrorInvalidValue;  // the opt-in fused kernel is only built for PSF sizes <= 31

@@ -46,10 +46,9 @@
 #include <vector>
 
 #define ICS_FFT_P 128
-#ifndef ICS_FFT_MAX_K
-#define ICS_FFT_MAX_K 85        /* largest PSF size ONE tile takes (44 valid pixels a side); above it the PSF is cut into tap blocks (k_conv_fft_blk), which measured
-                                   ahead from about there: 4096^2 non-blind 85 one tile 1.68 ms, 97 one tile 2.85, 99 as 2 x 2 blocks 1.59 */
-#endif
+// largest PSF size ONE tile takes (44 valid pixels a side); above it the PSF is cut into tap blocks (k_conv_fft_blk), which measured ahead
+// from about there: 4096^2 non-blind 85 one tile 1.68 ms, 97 one tile 2.85, 99 as 2 x 2 blocks 1.59
+constexpr int ICS_FFT_MAX_K = 85;
 #define ICS_FFT_PITCH 136
 #define ICS_FFT_TWS 17         /* the twiddle table behind the tile: T[j][k1] = w^(j k1), j < 8, k1 < 16, rows of 17 entries (34 dwords: the eight j of a
                                   wave's lanes fall into different banks), so that a lane's fifteen reads are ONE address + immediate offsets */
@@ -60,9 +59,7 @@
 typedef float v2f __attribute__((ext_vector_type(2)));
 typedef float v4f __attribute__((ext_vector_type(4)));
 
-#ifndef ICS_FFT_HD
 #define ICS_FFT_HD __host__ __device__ __forceinline__
-#endif
 
 #if defined(__HIP_DEVICE_COMPILE__)
 #define ICS_FFT_UNIFORM(x) __builtin_amdgcn_readfirstlane(x)
@@ -88,29 +85,14 @@ namespace icsfft {
 // s_waitcnt vmcnt(n) for the register prefetch of the next unit does not degrade to vmcnt(0) behind the epilogue's stores.
 // The host pass (CPU emulation, tools/bench_conv_fft.hip) indexes pointers.
 #define ICS_FFT_NONE 0x20000000
-// Measurement hooks (per-wave phase timeline, ablations): empty in the library; the harness builds of tools/bench_conv_fft.hip define
-// ICS_FFT_PROBES and get their bodies from tools/ics_conv_fft_probe.h.
-#ifdef ICS_FFT_PROBES
-#include "tools/ics_conv_fft_probe.h"
-#else
-#define ICS_FFT_PROBE_SKIP_LOAD(KIND, vi, si)
-#define ICS_FFT_PROBE_SKIP_STORE(v, vi, si)
-#define ICS_FFT_PROBE_SKIP_MATH() do { } while (0)
-#define ICS_FFT_PROBE_COLUMN_PASS(x) do { x } while (0)
-#define ICS_FFT_PROBE_TRACE_DECL() do { } while (0)
-#define ICS_FFT_STAMP(i) do { } while (0)
-#define ICS_FFT_PROBE_TRACE_NEXT() do { } while (0)
-#define ICS_FFT_PROBE_STAGGER() do { } while (0)
-#endif
 #if defined(__HIP_DEVICE_COMPILE__)
 typedef __amdgpu_buffer_rsrc_t gbuf;
 __device__ __forceinline__ gbuf make_gbuf(const void* p) { return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, 0x7FFFFFFF, 0x00020000); }
 __device__ __forceinline__ float ld_f32(gbuf b, int vi, int si) { return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(b, 4 * vi, 4 * si, 0)); }
 __device__ __forceinline__ void st_f32(gbuf b, int vi, int si, float v) { __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(int, v), b, 4 * vi, 4 * si, 0); }
 __device__ __forceinline__ v2f ld_v2f(gbuf b, int vi, int si) { return __builtin_bit_cast(v2f, __builtin_amdgcn_raw_buffer_load_b64(b, 8 * vi, 8 * si, 0)); }
-template <int KIND = 0>   // (KIND: which class of access this is -- spectrum 1, operands 2 / 16, window 4 -- for the harness' ablation hook)
+template <int KIND = 0>   // (KIND: which class of access this is -- spectrum 1, operands 2 / 16, window 4)
 __device__ __forceinline__ v4f ld_f32x4(gbuf b, int vi, int si) {
-  ICS_FFT_PROBE_SKIP_LOAD(KIND, vi, si)
   return __builtin_bit_cast(v4f, __builtin_amdgcn_raw_buffer_load_b128(b, 4 * vi, 4 * si, 0));
 }
 typedef uint32_t u4v __attribute__((ext_vector_type(4)));
@@ -121,7 +103,6 @@ typedef uint32_t u4v __attribute__((ext_vector_type(4)));
 //  (tools/bench_conv_fft.hip found it: the first pixel of the quads of lanes 12-15 of every row group but the first).  Keeping the data
 //  alive across two wait states costs nothing here: eight stores per thread and unit)
 __device__ __forceinline__ void st_f32x4(gbuf b, int vi, int si, v4f v) {
-  ICS_FFT_PROBE_SKIP_STORE(v, vi, si)
   __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u4v, v), b, 4 * vi, 4 * si, 0);
   asm volatile("s_nop 2" :: "v"(v) : "memory");
 }
@@ -225,7 +206,6 @@ template <int DIR> ICS_FFT_HD void fft4_r2(v2f& a0, v2f& a1, v2f& a2, v2f& a3) {
 
 // 8 points, natural order in, natural order out.  n = 2 n1 + n2, k = k1 + 4 k2.
 template <int DIR> ICS_FFT_HD void fft8(v2f (&v)[8]) {
-  ICS_FFT_PROBE_SKIP_MATH();
   constexpr float R = 0.70710678118654752440f;
   v2f e0 = v[0], e1 = v[2], e2 = v[4], e3 = v[6], o0 = v[1], o1 = v[3], o2 = v[5], o3 = v[7];
   fft4<DIR>(e0, e1, e2, e3);
@@ -241,7 +221,6 @@ template <int DIR> ICS_FFT_HD void fft8(v2f (&v)[8]) {
 
 // 16 points, natural order in, natural order out.  n = 4 n1 + n2, k = k1 + 4 k2.
 template <int DIR> ICS_FFT_HD void fft16(v2f (&v)[16]) {
-  ICS_FFT_PROBE_SKIP_MATH();
   constexpr float C1 = 0.92387953251128675613f, S1 = 0.38268343236508977173f, R = 0.70710678118654752440f;
   v2f a[4][4];   // a[n2][k1]
 #pragma unroll
@@ -293,7 +272,6 @@ struct IcsFftArgs {
                             // not the bottom tile row, whose units are the outer ring's four-transform ones).  Order only: results do not change
   int wy0, wy1, wx0, wx1;   // k_synth_gradk_fft: the stop-test window in u-frame coordinates -- the residual is stored to its frame for the tiles
   int store_all;            // that touch it (pyx:600-601, 627 read nothing else of it), or for every tile (single stage)
-  long long* trace;         // harness builds with -DICS_FFT_TRACE: [workgroup][unit round][wave][10] shader-clock stamps, else unused
 };
 
 namespace icsfft {
@@ -471,7 +449,7 @@ ICS_FFT_HD void stage_c(const v2f* rd, v2f* lds, const v2f* twl, int tid) {
 
 // The spectrum values a thread multiplies by in stage D: row -> ky, kx = q + 8 s + 16 k2 (from L2: 384 KB for the three channels).  Requested
 // in front of stage C: requested inside stage D, in two batches of eight with a wait each, the last wave left stage D 17 k shader clocks
-// after the first (per-wave timeline, tools/bench_conv_fft.hip -DICS_FFT_TRACE).  (Requested a whole unit ahead -- in front of the
+// after the first (per-wave timeline).  (Requested a whole unit ahead -- in front of the
 // previous unit's stores, which vmcnt makes every later load wait for -- they took stage D to 2 k clocks, but 32 registers alive across
 // stages A-C spilled the window prefetch: measured slower.)
 // Layout (k_fft_spectrum writes it): the sixteen values of a thread as eight 16-byte pairs, [channel][pair l = 4 s + k2 / 2][thread] -- a wave's
@@ -743,7 +721,7 @@ ICS_FFT_HD void load_ops(const IcsFftArgs& a, const Mem& mem, const Unit& u, int
 #pragma unroll
   for (int i = i0; i < i1; ++i) {
     const int vo = i < rows ? va : ICS_FFT_NONE;
-    if (t == 0) {   // (ablation kinds: 2 = tile 0's operands and mode 0's image, 16 = tile 1's)
+    if (t == 0) {
       o.a[t][i] = ld_f32x4<2>(mem.u, vo, 32 * i * mem.lu.pitch);
       o.b[t][i] = pam ? ld_f32x4<2>(mem.tv, vo, 32 * i * mem.ltv.pitch) : ld_f32x4<2>(mem.ut, vo, 32 * i * mem.lut.pitch);
     } else {
@@ -901,15 +879,6 @@ __device__ __forceinline__ int opaque(int x) { asm volatile("" : "+v"(x)); retur
 // workgroup barrier that waits for this wave's LDS traffic only (__syncthreads() also waits for the global loads and stores in flight)
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
-#ifndef ICS_FFT_M2_ORDER
-#define ICS_FFT_M2_ORDER 1   /* mode 2: 0 = the second halves of the weight spectra requested in front of stage D's first pass, 1 = behind it */
-#endif
-#ifndef ICS_FFT_M1_EARLY
-#define ICS_FFT_M1_EARLY 1      // mode 1: row groups of tile 1's operands requested before stage F already (0: all at the start of the epilogue)
-#endif
-#ifndef ICS_FFT_M1_WIN
-#define ICS_FFT_M1_WIN 0        // mode 1: tile 1 of the next window requested at the start of the epilogue instead of between its passes
-#endif
 template <int MODE, bool TV>
 __global__ __launch_bounds__(ICS_FFT_THREADS) void k_conv_fft(IcsFftArgs a) {
   extern __shared__ __attribute__((aligned(16))) v2f lds[];
@@ -921,14 +890,12 @@ __global__ __launch_bounds__(ICS_FFT_THREADS) void k_conv_fft(IcsFftArgs a) {
   // workgroup b runs on XCD b % 8 (observed dispatch): consecutive unit slots q go to one XCD, so the three channel units of a tile pair
   // (n = 3 pair + c) share that XCD's L2.  Affects speed only.
   const int q = (G & 7) ? (int)blockIdx.x : (int)(blockIdx.x & 7) * (G >> 3) + (int)(blockIdx.x >> 3);
-  ICS_FFT_PROBE_TRACE_DECL();
   uint32_t accg[3] = {0u, 0u, 0u}, accu[3] = {0u, 0u, 0u};   // the workgroup's maxima as order-preserving keys (0 = nothing seen, NaN = largest)
   // A unit's window is requested one unit ahead (registers).  It enters the tile buffer -- and runs its stage A -- at the END of the unit
   // before it, behind that unit's stores: there the compiler knows exactly what is in flight (the window loads, then the stores) and waits
   // with vmcnt(n_stores).  (Consumed at the top of the loop the wait became vmcnt(0): the loop header merges the first entry, where
   // nothing follows the loads.)
   v4f pw[2][4];
-  ICS_FFT_PROBE_STAGGER();
   if (q < a.nunits) {
     load_window(a, mem, decode_unit(a, walk_unit(a, q)), opaque(tid), pw);
     store_window(pw, lds, opaque(tid));
@@ -938,11 +905,9 @@ __global__ __launch_bounds__(ICS_FFT_THREADS) void k_conv_fft(IcsFftArgs a) {
   for (int k = q; k < a.nunits; k += G) {
     const int n = walk_unit(a, k);
     const Unit u = decode_unit(a, n);
-    ICS_FFT_STAMP(0);
     lds_barrier();
-    ICS_FFT_STAMP(1);
-    ICS_FFT_PROBE_COLUMN_PASS(stage_b<1>(lds, opaque(tid)); lds_barrier(););
-    ICS_FFT_STAMP(2);
+    stage_b<1>(lds, opaque(tid));
+    lds_barrier();
     if (MODE == 2) {
       // A1 + A3 in one unit (see stage_d2_half): interior tiles stay in the frequency domain between the two convolutions
       if (!unit_is_border(a, u)) {
@@ -953,18 +918,10 @@ __global__ __launch_bounds__(ICS_FFT_THREADS) void k_conv_fft(IcsFftArgs a) {
         load_spectrum_half<1>(mem.spec1, 8 * u.c, opaque(tid), 0, s1);
         stage_c<4>(lds, lds, twl, opaque(tid));
         wave_sync();
-#if ICS_FFT_M2_ORDER == 0
-        v2f s0b[8], s1b[8];                                                  // the second halves of the weight spectra (L2) behind the first pass of stage D
-        load_spectrum_half<1>(mem.spec, 8 * u.c, opaque(tid), 1, s0b);
-        load_spectrum_half<1>(mem.spec1, 8 * u.c, opaque(tid), 1, s1b);
         stage_d2_half(s0, s1, fs[0], lds, opaque(tid), 0);
-        stage_d2_half(s0b, s1b, fs[1], lds, opaque(tid), 1);
-#else
-        stage_d2_half(s0, s1, fs[0], lds, opaque(tid), 0);
-        load_spectrum_half<1>(mem.spec, 8 * u.c, opaque(tid), 1, s0);
+        load_spectrum_half<1>(mem.spec, 8 * u.c, opaque(tid), 1, s0);         // the second halves of the weight spectra behind the first pass
         load_spectrum_half<1>(mem.spec1, 8 * u.c, opaque(tid), 1, s1);
         stage_d2_half(s0, s1, fs[1], lds, opaque(tid), 1);
-#endif
         wave_sync();
       } else {
         // the outer ring: conv, residual with its mask in the tile buffer, then the correlation (four transforms, as the two kernels)
@@ -1003,11 +960,9 @@ __global__ __launch_bounds__(ICS_FFT_THREADS) void k_conv_fft(IcsFftArgs a) {
     load_spectrum(mem, u.c, opaque(tid), sp);      // (stage C's arithmetic covers their trip to L2; inside stage D the waves queued up on it)
     stage_c(lds, lds, twl, opaque(tid));
     wave_sync();
-    ICS_FFT_STAMP(3);
     stage_d(sp, lds, opaque(tid));
     wave_sync();
     }
-    ICS_FFT_STAMP(4);
     load_window(a, mem, decode_unit(a, walk_unit(a, k + G)), opaque(tid), pw, 0, MODE == 0 ? 2 : 1);   // next unit (beyond the last one: dropped accesses); mode 1 holds 64 operand registers through stage G and requests the second tile behind it
     stage_e(lds, lds, twl, opaque(tid));
     v4f fimg[2][4];
@@ -1015,22 +970,17 @@ __global__ __launch_bounds__(ICS_FFT_THREADS) void k_conv_fft(IcsFftArgs a) {
     if (MODE == 0) load_image(a, mem, u, opaque(tid), fimg);
     else {
       load_ops<TV>(a, mem, u, opaque(tid), 0, ops);
-      if (ICS_FFT_M1_EARLY > 0) load_ops<TV>(a, mem, u, opaque(tid), 1, ops, 0, ICS_FFT_M1_EARLY);   // (stages F and G leave registers for part of tile 1's operands)
+      load_ops<TV>(a, mem, u, opaque(tid), 1, ops, 0, 1);   // (stages F and G leave registers for the first row group of tile 1's operands)
     }
     lds_barrier();
-    ICS_FFT_STAMP(5);
-    ICS_FFT_PROBE_COLUMN_PASS(stage_b<-1>(lds, opaque(tid)); lds_barrier(););
-    ICS_FFT_STAMP(6);
+    stage_b<-1>(lds, opaque(tid));
+    lds_barrier();
     stage_g(lds, opaque(tid));
     lds_barrier();
-    ICS_FFT_STAMP(7);
     // row-quad epilogue, row group by row group (at most one group's raw values alive beside the operands).  Mode 1 has two operand
     // frames: it requests those of the second tile here and takes its maxima in a second pass, and the second tile of the next unit's
     // window goes out between the passes (registers: 128 per thread with 1024 of them).
-    if (MODE >= 1) {
-      load_ops<TV>(a, mem, u, opaque(tid), 1, ops, ICS_FFT_M1_EARLY, 4);
-      if (ICS_FFT_M1_WIN) load_window(a, mem, decode_unit(a, walk_unit(a, k + G)), opaque(tid), pw, 1, 2);
-    }
+    if (MODE >= 1) load_ops<TV>(a, mem, u, opaque(tid), 1, ops, 1, 4);
     Maxima mx; maxima_init(mx);
     v4f res[4][2];
     // lane address and row-group count of the two tiles ONCE per unit (as eight store_quad calls the address arithmetic of the epilogue
@@ -1072,21 +1022,18 @@ __global__ __launch_bounds__(ICS_FFT_THREADS) void k_conv_fft(IcsFftArgs a) {
         else { maxima_quad<TV>(a, u, te, 0, i, res[i][0], ops, mx, qo[0], false); store_quad_at(a, mem, qo[0], false, i, res[i][0]); }
         asm volatile("" ::: "memory");
       }
-      if (!ICS_FFT_M1_WIN) load_window(a, mem, decode_unit(a, walk_unit(a, k + G)), opaque(tid), pw, 1, 2);
+      load_window(a, mem, decode_unit(a, walk_unit(a, k + G)), opaque(tid), pw, 1, 2);
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         if (edge) { maxima_quad<TV>(a, u, te, 1, i, res[i][1], ops, mx, qo[1], true); store_quad_at(a, mem, qo[1], true, i, res[i][1]); }
         else { maxima_quad<TV>(a, u, te, 1, i, res[i][1], ops, mx, qo[1], false); store_quad_at(a, mem, qo[1], false, i, res[i][1]); }
       }
     }
-    ICS_FFT_STAMP(8);
     if (k + G < a.nunits) {
       store_window(pw, lds, opaque(tid));      // (the slots this thread just read)
       lds_barrier();
       stage_a(lds, opaque(tid));
     }
-    ICS_FFT_STAMP(9);
-    ICS_FFT_PROBE_TRACE_NEXT();
     if (MODE >= 1) {   // (u.c is uniform)
       uint32_t kg, ku;
       maxima_keys(mx, kg, ku);
@@ -1343,9 +1290,6 @@ __global__ __launch_bounds__(ICS_FFT_THREADS) void k_fft_image_spectrum(IcsFftAr
 // Registers (1024 threads: 128): acc and T stay alive through the unit, so the sixteen-point stages run in their lean forms and the
 // two prefetches sit beside eight-point stages only: the image quads are requested behind stage G's last LDS write (in flight through the
 // barrier), the next unit's window in front of the second stage D.
-#ifndef ICS_FFT_FUSED_IMG_EARLY
-#define ICS_FFT_FUSED_IMG_EARLY 2
-#endif
 template <int DUMMY>
 __global__ __launch_bounds__(ICS_FFT_THREADS) void k_synth_gradk_fft(IcsFftArgs a, float* __restrict__ partial) {
   extern __shared__ __attribute__((aligned(16))) v2f lds[];
@@ -1389,9 +1333,9 @@ __global__ __launch_bounds__(ICS_FFT_THREADS) void k_synth_gradk_fft(IcsFftArgs 
       // the image quads in two halves of two row groups: the first is requested behind stage G's last LDS write (in flight through the
       // barrier), the second in front of the first half's arithmetic -- 96 registers of spectra and image beside the epilogue otherwise
       v4f fimg[2][4];
-      load_image_rows(a, mem, u, opaque(tid), fimg, 0, ICS_FFT_FUSED_IMG_EARLY);
+      load_image_rows(a, mem, u, opaque(tid), fimg, 0, 2);
       lds_barrier();
-      load_image_rows(a, mem, u, opaque(tid), fimg, ICS_FFT_FUSED_IMG_EARLY, 4);
+      load_image_rows(a, mem, u, opaque(tid), fimg, 2, 4);
       QuadOut qo[2];
       const int te = opaque(tid);
 #pragma unroll
@@ -1537,14 +1481,13 @@ void ics_conv_fft_blk_shape(int K, int* blk_n, int* blk_k) {
 
 hipError_t ics_launch_fft_spectrum(const float* psf, int K, float* spec_conv, float* spec_corr, hipStream_t s, int blk_n, int blk_k) {
   const int nb = blk_n > 0 ? blk_n : 1, Kb = blk_n > 0 ? blk_k : K;
-  const size_t lds = (256 + (size_t)Kb * 32 * 2) * sizeof(double);   // 35 KB at 65, 52 KB at 97
+  const size_t lds = (256 + (size_t)Kb * 32 * 2) * sizeof(double);   // 35 KB at 65, 46 KB at 85
   hipLaunchKernelGGL(icsfft::k_fft_spectrum, dim3(96, nb * nb), dim3(256), lds, s, psf, K, reinterpret_cast<v2f*>(spec_conv), reinterpret_cast<v2f*>(spec_corr), nb, Kb);
   return hipGetLastError();
 }
 
 void ics_conv_fft_fill_args(int mode, const IcsConvArgs& c, const float* spec, IcsFftArgs* a, int blk_n = 0, int blk_k = 0) {
   a->c = c;
-  a->trace = nullptr;
   a->planar = 0;
   a->wy0 = a->wy1 = a->wx0 = a->wx1 = 0; a->store_all = 0;
   a->wpad = c.g.pad; a->fspec = nullptr; a->spec1 = nullptr; a->lag_y = a->lag_x = 0; a->rot = 0;

@@ -51,68 +51,6 @@
 #include <stdlib.h>
 #include <type_traits>
 
-#ifndef ICS_MFMA_INTERLEAVE
-#define ICS_MFMA_INTERLEAVE 1
-#endif
-#ifndef ICS_EPI_LOAD_AUX
-#define ICS_EPI_LOAD_AUX 0    /* cache policy of the epilogue operand loads (2 = nt measured slower: the update pass that follows finds less of u / ut in the memory-side cache) */
-#endif
-#ifndef ICS_EPI_LOAD_AUX0
-#define ICS_EPI_LOAD_AUX0 ICS_EPI_LOAD_AUX   /* the same for mode 0 (image operand) */
-#endif
-#ifndef ICS_RAW_AUX
-#define ICS_RAW_AUX 0         /* cache policy of the tile loads */
-#endif
-#ifndef ICS_EPI_STORE_AUX
-#define ICS_EPI_STORE_AUX 0
-#endif
-#ifndef ICS_EPI_TB
-#define ICS_EPI_TB(mode) ((mode) == 0 ? 4 : 2)   /* mode 1 carries two operand frames: two batches keep it spill-free */
-#endif
-#ifndef ICS_EPI_EARLY1
-#define ICS_EPI_EARLY1 1      /* 16-row tiles (small frames, one tile per workgroup), mode 0: the image operand of the residual is requested with the tile's rows, at the top of the kernel (-0.2 us of 6.9).  The same for mode 1's u / majoriser operands measured +0.7 ... 1.5 us -- more requests in front of the rows the kernel waits for -- and is not built */
-#endif
-#ifndef ICS_EPI_EARLY
-#define ICS_EPI_EARLY 1       /* mode 0, 32-row tiles, accumulator-order image: request the image operand BEFORE the matrix phase (130 of 168 VGPRs in use: room for its 24) */
-#endif
-#ifndef ICS_MFMA_PAIRS
-#define ICS_MFMA_PAIRS 2   /* two-window sizes up to 33 x 33 (8-wave kernels): two kernel rows per three MFMA windows, see MCfg::PAIR.
-                              1: the two waves of a column block split the accumulator sets (t = half, half + 2), all kernel rows each;
-                              2: they split the row pairs (items) and keep all four sets: a B fragment then serves four sets */
-#endif
-#ifndef ICS_MFMA_WSPLIT
-#define ICS_MFMA_WSPLIT 1   /* see MCfg::WSPLIT */
-#endif
-#ifndef ICS_MFMA_NO_RS1
-#define ICS_MFMA_NO_RS1 0
-#endif
-#ifndef ICS_MFMA_ALL_RS
-#define ICS_MFMA_ALL_RS 0  /* tools/: build both tile heights for every PSF size (ICS_TEST_CONV_RS=2|4 then picks one) */
-#endif
-#ifndef ICS_MFMA_ABLATE
-#define ICS_MFMA_ABLATE 0  /* tools/bench_conv_mfma.hip: 1 = no MFMA loop, 2 = no conversion, 4 = no epilogue, 64 = two of the three split terms only */
-#endif
-
-// phase timing probe (tools/bench_conv_mfma.hip -DICS_MFMA_TIMING): per-wave cycle totals between the marks
-#ifdef ICS_MFMA_TIMING
-__device__ unsigned long long ics_mfma_ticks[11];
-#define ICS_TICK_INIT unsigned long long tk_prev = __builtin_readcyclecounter(), tk_acc[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0}
-#define ICS_TICK(i) do { const unsigned long long tk_now = __builtin_readcyclecounter(); tk_acc[i] += tk_now - tk_prev; tk_prev = tk_now; } while (0)
-#define ICS_TICK_FLUSH do { if ((threadIdx.x & 63) == 0) { for (int i = 0; i < 10; ++i) atomicAdd(&ics_mfma_ticks[i], tk_acc[i]); atomicAdd(&ics_mfma_ticks[10], 1ull); } } while (0)
-#elif defined(ICS_MFMA_TRACE)
-// phase timeline (tools/bench_conv_mfma.hip -DICS_MFMA_TRACE): lane 0 of every wave records (100 MHz wall clock << 8 | mark)
-// at each mark; entry 0 = HW_ID | XCC_ID << 32.  1024 entries per wave.
-__device__ unsigned long long* ics_trace_buf;
-#define ICS_TICK_INIT unsigned long long* tr_ = ics_trace_buf + ((size_t)blockIdx.x * 4 + wv) * 1024; int tri_ = 0; \
-  if (lane == 0) { tr_[tri_++] = (unsigned long long)__builtin_amdgcn_s_getreg(63492) | ((unsigned long long)__builtin_amdgcn_s_getreg(63508) << 32); tr_[tri_++] = (wall_clock64() << 8) | 15; }
-#define ICS_TICK(i) do { if (lane == 0 && tri_ < 1023) tr_[tri_++] = (wall_clock64() << 8) | (i); } while (0)
-#define ICS_TICK_FLUSH do { if (lane == 0) tr_[tri_] = 0; } while (0)
-#else
-#define ICS_TICK_INIT
-#define ICS_TICK(i)
-#define ICS_TICK_FLUSH
-#endif
-
 namespace {
 
 typedef _Float16 h8 __attribute__((ext_vector_type(8)));
@@ -154,29 +92,26 @@ struct MCfg {
   static constexpr int WROWB = (2 * (K + 17) + 3) & ~3;
   static constexpr int WZERO = (K + 7) / 2;      // first all-zero dword of a row
   static constexpr int WLDS = 3 * K * 2 * WROWB; // = the global weight table built by k_psf (ics_common.h), copied verbatim
-  // PAIR_ITEMS, where the LDS has room (K <= 31): the weight rows are kept as FOUR plain rows per (channel, kernel row) instead of
-  // one hi / lo dword-interleaved row -- hi and lo, each once as it is and once moved up by one half.  A lane then finds its 8
+  // Row pairs (round 4).  With two windows a kernel row costs 2 x 32 columns of MFMA depth for its 16 + K - 1 <= 48 input columns,
+  // and the matrix loop of these kernels runs at 85 % of the MFMA issue rate (without it 0.35 of 1.07 ms at 6144^2 / 31 x 31, with
+  // two of the three split terms 0.83).  Two consecutive kernel rows a, a + 1 of one accumulator set read input rows r and r + 1;
+  // their 2 x 48 columns fill THREE 32-deep windows exactly:
+  //     window 0 = row r cols [0, 32) | window m = row r cols [32, 48) + row r + 1 cols [0, 16) | window 2 = row r + 1 cols [16, 48)
+  // -- 24 % fewer MFMAs at K = 31.  The mixed window's A fragment takes lane groups 0, 1 from one LDS row class and 2, 3 from the next
+  // (a per-lane base address), its B fragment likewise from the weight rows of a and a + 1.  The two waves of a column block split the
+  // row pairs (items) and keep all four accumulator sets, so that a B fragment serves four sets; their partial sums are exchanged as in
+  // the classic row split.
+  static constexpr bool PAIR = NH == 2 && RS == 4 && (16 + K - 1 > 32) && (16 + K - 1 <= 48);
+  // WSPLIT, for the row pairs where the LDS has room (K <= 31): the weight rows are kept as FOUR plain rows per (channel, kernel row)
+  // instead of one hi / lo dword-interleaved row -- hi and lo, each once as it is and once moved up by one half.  A lane then finds its 8
   // consecutive halves dword-aligned in the copy of its parity and reads them with two 4-byte-aligned 8-byte loads per split term
   // (ds_read2_b32) straight into the MFMA operand registers: 4 LDS instructions and no funnel shift per B fragment instead of
   // 5 + 8 (the pair loops run at the wave's issue limit: 2.5 other instructions per MFMA, profiles/r04_6144_31_mfma_counters.json).
-  static constexpr bool WSPLIT_WANTED = ICS_MFMA_PAIRS == 2 && ICS_MFMA_WSPLIT && NH_ == 2 && RS_ == 4 && (16 + K - 1 > 32) && (16 + K - 1 <= 48);
-  static constexpr bool WSPLIT = WSPLIT_WANTED && (size_t)SCRATCH + 256 + 2 * WLDS <= 160 * 1024;
+  static constexpr bool WSPLIT = PAIR && (size_t)SCRATCH + 256 + 2 * WLDS <= 160 * 1024;
   static constexpr int WLDS_USED = WSPLIT ? 2 * WLDS : WLDS;
   static constexpr size_t LDS_BYTES = SCRATCH + 256 + WLDS_USED;
   static constexpr int WGS_CAP = RS == 4 ? 2 : 3;                      // register budget: 256 / 168 VGPRs
   static constexpr int WGS = (160 * 1024 / LDS_BYTES) < WGS_CAP ? (160 * 1024 / LDS_BYTES) : WGS_CAP;   // workgroups (of 4 waves) per CU
-  // Row pairs (round 4).  With two windows a kernel row costs 2 x 32 columns of MFMA depth for its 16 + K - 1 <= 48 input columns,
-  // and the matrix loop of these kernels runs at 85 % of the MFMA issue rate (without it 0.35 of 1.07 ms at 6144^2 / 31 x 31, with
-  // two of the three split terms 0.83: tools/bench_conv_mfma.hip -DICS_MFMA_ABLATE=64).  Two consecutive kernel rows a, a + 1 of one
-  // accumulator set read input rows r and r + 1; their 2 x 48 columns fill THREE 32-deep windows exactly:
-  //     window 0 = row r cols [0, 32) | window m = row r cols [32, 48) + row r + 1 cols [0, 16) | window 2 = row r + 1 cols [16, 48)
-  // -- 24 % fewer MFMAs at K = 31.  The mixed window's A fragment takes lane groups 0, 1 from one LDS row class and 2, 3 from the next
-  // (a per-lane base address), its B fragment likewise from the weight rows of a and a + 1.  A fragment pair (q, q + 1) then serves
-  // the accumulator sets t = q - a with a EVEN only, so the two waves of a column block no longer split the kernel rows but the
-  // sets: wave `half` owns t = half and half + 2 for all rows -- no exchange of partial sums, two workgroup barriers less per tile.
-  static constexpr bool PAIR = ICS_MFMA_PAIRS && NH == 2 && RS == 4 && (16 + K - 1 > 32) && (16 + K - 1 <= 48);
-  static constexpr bool PAIR_SETS = PAIR && ICS_MFMA_PAIRS == 1;   // waves own accumulator sets (no exchange of partial sums)
-  static constexpr bool PAIR_ITEMS = PAIR && ICS_MFMA_PAIRS == 2;  // waves own row pairs, all four sets (partial sums exchanged as in the classic split)
   static constexpr int NQ = K + RS - 1;          // fragments per (channel, column block)
   static constexpr int XG = LCOLS / 4;           // 4-pixel groups per staged row
   static constexpr int NTASK = LROWS * XG;
@@ -217,7 +152,7 @@ __device__ __forceinline__ void load_raw(f32x4u (&v)[C::NIT][3], __amdgpu_buffer
     const int row = t / C::XG, xg = t - row * C::XG;
     const int toff = 4 * (row * pitch + 12 * xg);
 #pragma unroll
-    for (int h = 0; h < 3; ++h) v[k][h] = __builtin_bit_cast(f32x4u, __builtin_amdgcn_raw_buffer_load_b128(rs, toff + 16 * h, soff, ICS_RAW_AUX));
+    for (int h = 0; h < 3; ++h) v[k][h] = __builtin_bit_cast(f32x4u, __builtin_amdgcn_raw_buffer_load_b128(rs, toff + 16 * h, soff, 0));
   }
 }
 
@@ -240,7 +175,6 @@ __global__ __launch_bounds__(256 * NH) __attribute__((amdgpu_waves_per_eu(MCfg<K
   const int cb = wv & 3, half = wv >> 2;                      // column block of this wave; which kernel rows it takes (NH = 2)
   const int lane = tid & 63, li = lane & 15, lg = lane >> 4;
   const int pitch = a.g.pitch;
-  ICS_TICK_INIT;
 
   // persistent tile walk: workgroup b runs on XCD b % 8 (observed dispatch); every XCD owns one contiguous
   // band of tiles so that the halos shared by neighbouring tiles hit in that XCD's L2
@@ -285,8 +219,9 @@ __global__ __launch_bounds__(256 * NH) __attribute__((amdgpu_waves_per_eu(MCfg<K
   }
   // 16-row tiles are what frames with fewer tiles than compute units get: every workgroup runs ONE tile and the kernel's time is its chain
   // of dependent round trips, so the synthesis' image operand travels with the rows instead of behind the matrix phase (on frames that fill
-  // the device the same move measured nothing: other workgroups cover the latency there; ICS_EPI_EARLY1 above for the back-projection).
-  constexpr bool EARLY1 = ICS_EPI_EARLY1 != 0 && RS == 1 && NH == 1 && MODE == 0;
+  // the device the same move measured nothing: other workgroups cover the latency there; -0.2 us of 6.9 here).  The same for the
+  // back-projection's u / majoriser operands measured +0.7 ... 1.5 us -- more requests in front of the rows the kernel waits for.
+  constexpr bool EARLY1 = RS == 1 && NH == 1 && MODE == 0;
   const __amdgpu_buffer_rsrc_t rs_f = make_rsrc(MODE == 0 ? a.f : a.u);
   const __amdgpu_buffer_rsrc_t rs_t = make_rsrc(MODE == 0 ? a.f : a.ut);
   u3 pre1[4];
@@ -297,7 +232,7 @@ __global__ __launch_bounds__(256 * NH) __attribute__((amdgpu_waves_per_eu(MCfg<K
       const int tide = opaque(tid);
       const int voff = 4 * (4 * C::RS * ((tide >> 4) & 3) * pitch + 3 * (tide & 15)), sb = 4 * (y0 * pitch + 3 * (x0 + 16 * cb));
 #pragma unroll
-      for (int r = 0; r < 4; ++r) pre1[r] = __builtin_amdgcn_raw_buffer_load_b96(rs_f, voff, sb + 4 * C::RS * r * pitch, ICS_EPI_LOAD_AUX0);
+      for (int r = 0; r < 4; ++r) pre1[r] = __builtin_amdgcn_raw_buffer_load_b96(rs_f, voff, sb + 4 * C::RS * r * pitch, 0);
     }
   };
   bool first1 = true;
@@ -325,7 +260,6 @@ __global__ __launch_bounds__(256 * NH) __attribute__((amdgpu_waves_per_eu(MCfg<K
       for (int k = 0; k < WPT; ++k) { const int i = tid + k * C::NT; if (i < C::WLDS / 4) ldsW[i] = wreg[k]; }
     }
   }
-  ICS_TICK(8);
   // lane constants of the B operand: in window h this lane's 8 consecutive halves start at half
   // bo = 32h + 8*lg - li + 15 of the zero-padded row; it reads the five dwords that contain them and funnel-shifts
   // by the parity (v_alignbit).  (Gathering them from a row image with ds_bpermute cost ~5 LDS cycles per bpermute.)
@@ -383,7 +317,7 @@ __global__ __launch_bounds__(256 * NH) __attribute__((amdgpu_waves_per_eu(MCfg<K
 #pragma unroll
       for (int k = 0; k < C::NIT; ++k) {
         const int t = tidc + k * C::NT;
-        if (t < C::NTASK && !((ICS_MFMA_ABLATE & 2) && k > 0)) {
+        if (t < C::NTASK) {
           const int row = t / C::XG, xg = t - row * C::XG;
           const int rc = row % C::RS;
           const int crow = (rc == 0 ? 0 : (rc == 1 ? C::cls_base(1) : (rc == 2 ? C::cls_base(2) : C::cls_base(3)))) + row / C::RS;
@@ -410,13 +344,12 @@ __global__ __launch_bounds__(256 * NH) __attribute__((amdgpu_waves_per_eu(MCfg<K
       }
     }
     __syncthreads();
-    ICS_TICK(0);
 
     // ---- request the next tile's rows: in flight during the whole matrix phase (the loop below issues no
     // vector-memory loads -- they return in order, a weight load behind this prefetch would wait for it) -----
     // mode 0, 32-row tiles: the image operand of this tile's residual (accumulator order, ics_image_acc.h) is requested here, ahead
-    // of the next tile's rows (loads return in order), and is there when the matrix phase ends
-    constexpr bool EARLY = ICS_EPI_EARLY && MODE == 0 && RS == 2 && NH == 1;
+    // of the next tile's rows (loads return in order), and is there when the matrix phase ends (130 of 168 VGPRs in use: room for its 24)
+    constexpr bool EARLY = MODE == 0 && RS == 2 && NH == 1;
     u4 fpre[3][C::RS];
     const float* faccp0 = (MODE == 0 && C::RS != 1) ? a.facc[C::RS == 2 ? 0 : 1] : nullptr;
     if (EARLY && faccp0 != nullptr && x0 + 16 * cb < xend) {
@@ -425,7 +358,7 @@ __global__ __launch_bounds__(256 * NH) __attribute__((amdgpu_waves_per_eu(MCfg<K
 #pragma unroll
       for (int c = 0; c < 3; ++c)
 #pragma unroll
-        for (int t = 0; t < C::RS; ++t) fpre[c][t] = __builtin_amdgcn_raw_buffer_load_b128(rs_a0, lv, sb0 + (c * C::RS + t) * 1024, ICS_EPI_LOAD_AUX0);
+        for (int t = 0; t < C::RS; ++t) fpre[c][t] = __builtin_amdgcn_raw_buffer_load_b128(rs_a0, lv, sb0 + (c * C::RS + t) * 1024, 0);
     }
     if (EARLY1 && !first1) request1(tile);   // (a workgroup's further tiles, if any: ahead of the matrix phase)
     first1 = false;
@@ -438,12 +371,10 @@ __global__ __launch_bounds__(256 * NH) __attribute__((amdgpu_waves_per_eu(MCfg<K
     }
     __builtin_amdgcn_sched_barrier(0);
 
-    ICS_TICK(7);
     // ---- Toeplitz MFMA loop ----------------------------------------------------------------------------
     // (The two-window kernels, K >= 19, need the whole q loop unrolled for this -- the Makefile raises the pragma-unroll
     //  threshold for this file; with the default threshold the loop stayed rolled, the B fragments went to scratch and
     //  the kernel was 5x slower: 3.3 vs 0.51 ms at 4096^2 / 31x31.)
-    constexpr bool INTERLEAVE = ICS_MFMA_INTERLEAVE != 0;
     f4 acc[3][C::RS];
 #pragma unroll
     for (int ch = 0; ch < 3; ++ch)
@@ -454,7 +385,7 @@ __global__ __launch_bounds__(256 * NH) __attribute__((amdgpu_waves_per_eu(MCfg<K
       constexpr int A0 = decltype(a0c)::value, A1 = decltype(a1c)::value;
       constexpr int Q0 = A0, Q1 = A1 + C::RS - 1;   // fragments q = Q0 .. Q1 - 1 meet these rows
 #pragma unroll
-      for (int ch = 0; ch < ((ICS_MFMA_ABLATE & 1) ? 0 : 3); ++ch) {
+      for (int ch = 0; ch < 3; ++ch) {
         // (re-hidden per tile and channel: the weight reads are tile-invariant and would otherwise be hoisted out
         //  of the tile loop, hundreds of live registers)
         uint32_t wb[C::NCH];
@@ -468,7 +399,7 @@ __global__ __launch_bounds__(256 * NH) __attribute__((amdgpu_waves_per_eu(MCfg<K
         // B fragments in two halves: the raw dwords of kernel row q + 1 are requested before the MFMAs of step q and
         // funnel-shifted behind them.  The reads are volatile: as plain loads they were sunk to the shifts, and the wave
         // waited out the LDS latency in front of every step's MFMAs (466 cycles per step for 192 cycles of MFMA,
-        // tools/bench_conv_mfma.hip -DICS_MFMA_TRACE).
+        // phase timeline of the matrix loop).
         typedef uint32_t u2 __attribute__((ext_vector_type(2)));
         typedef const volatile __attribute__((address_space(3))) u2* lds_vu2p;
         u2 rawB[C::NCH][5];   // (hi, lo) dword pairs: the table interleaves the two split terms dword by dword
@@ -477,7 +408,7 @@ __global__ __launch_bounds__(256 * NH) __attribute__((amdgpu_waves_per_eu(MCfg<K
           for (int h = 0; h < C::NCH; ++h) {
             const lds_vu2p r = reinterpret_cast<lds_vu2p>(wb[h] + (uint32_t)((ch * K + ka) * 2 * C::WROWB));
 #pragma unroll
-            for (int d = 0; d < 5; ++d) rawB[h][d] = (ICS_MFMA_ABLATE & 32) ? (u2){0x3c003c00u + ka + d, 0x3c003c00u + d} : r[d];
+            for (int d = 0; d < 5; ++d) rawB[h][d] = r[d];
           }
         };
         auto finishB = [&](int ka) {
@@ -508,16 +439,13 @@ __global__ __launch_bounds__(256 * NH) __attribute__((amdgpu_waves_per_eu(MCfg<K
           for (int h = 0; h < C::NCH; ++h) { Nh[h] = Ah[h]; Nl[h] = Al[h]; }
           if (q + 1 < Q1) {
             const int off = (C::cls_base((q + 1) % C::RS) + (q + 1) / C::RS) * C::ROWB;
-            if (!(ICS_MFMA_ABLATE & 16)) {   // 16: timing probe without the A-fragment reads
 #pragma unroll
-              for (int h = 0; h < C::NCH; ++h) {
-                Nh[h] = *reinterpret_cast<const h8*>(ph + off + 64 * h);
-                Nl[h] = *reinterpret_cast<const h8*>(pl + off + 64 * h);
-              }
+            for (int h = 0; h < C::NCH; ++h) {
+              Nh[h] = *reinterpret_cast<const h8*>(ph + off + 64 * h);
+              Nl[h] = *reinterpret_cast<const h8*>(pl + off + 64 * h);
             }
           }
           if (q + 1 < A1) issueB(q + 1);
-          if (!INTERLEAVE) __builtin_amdgcn_sched_barrier(0);   // ...all requested before the step's MFMAs start
           // three split terms x windows; the (up to) 4 accumulators of a pass are independent
 #pragma unroll
           for (int term = 0; term < 3; ++term) {
@@ -527,180 +455,45 @@ __global__ __launch_bounds__(256 * NH) __attribute__((amdgpu_waves_per_eu(MCfg<K
               for (int t = 0; t < C::RS; ++t) {
                 const int ka = q - t;
                 if (ka < A0 || ka >= A1) continue;
-                if ((ICS_MFMA_ABLATE & 64) && term == 2) continue;   // timing probe: a third of the MFMAs less (results wrong)
                 const h8 av = term == 2 ? Al[h] : Ah[h];
                 const h8 bv = term == 1 ? Bl[ka][h] : Bh[ka][h];
                 acc[ch][t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(av, bv, acc[ch][t], 0, 0, 0);
               }
             }
           }
-          if (!INTERLEAVE) __builtin_amdgcn_sched_barrier(0);   // ...and consumed behind them
           if (q + 1 < A1) finishB(q + 1);
 #pragma unroll
           for (int h = 0; h < C::NCH; ++h) { Ah[h] = Nh[h]; Al[h] = Nl[h]; }
           // issue order inside the step: the LDS reads go into the shadows of the first MFMAs (an MFMA holds the matrix
           // pipe for 16 cycles, the wave can issue an independent instruction meanwhile), the funnel shifts into the
           // shadows of the last ones; as three blocks (reads | MFMAs | shifts) a step cost their sum
-          if (INTERLEAVE) {
-            int nt = 0;
+          int nt = 0;
 #pragma unroll
-            for (int t = 0; t < C::RS; ++t) nt += (q - t >= A0 && q - t < A1) ? 1 : 0;
-            const int nm = 3 * C::NCH * nt;                                             // MFMAs of this step
-            const int nr = ((q + 1 < Q1) ? 2 * C::NCH : 0) + ((q + 1 < A1) ? 5 * C::NCH : 0);   // LDS reads
-            const int nv = (q + 1 < A1) ? 8 * C::NCH : 0;                               // funnel shifts
-            const int tail = nv ? (nm > 4 ? 4 : nm) : 0;                                // MFMAs that cover the shifts
-            const int head = nm - tail;
+          for (int t = 0; t < C::RS; ++t) nt += (q - t >= A0 && q - t < A1) ? 1 : 0;
+          const int nm = 3 * C::NCH * nt;                                             // MFMAs of this step
+          const int nr = ((q + 1 < Q1) ? 2 * C::NCH : 0) + ((q + 1 < A1) ? 5 * C::NCH : 0);   // LDS reads
+          const int nv = (q + 1 < A1) ? 8 * C::NCH : 0;                               // funnel shifts
+          const int tail = nv ? (nm > 4 ? 4 : nm) : 0;                                // MFMAs that cover the shifts
+          const int head = nm - tail;
 #pragma unroll
-            for (int i = 0; i < (head > nr ? head : nr); ++i) {
-              if (i < head) __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-              if (i < nr) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-            }
+          for (int i = 0; i < (head > nr ? head : nr); ++i) {
+            if (i < head) __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+            if (i < nr) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+          }
 #pragma unroll
-            for (int i = 0; i < tail; ++i) {
-              __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+          for (int i = 0; i < tail; ++i) {
+            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
 #pragma unroll
-              for (int j = 0; j < (nv / 2 + tail - 1) / tail; ++j) __builtin_amdgcn_sched_group_barrier(0x002, 2, 0);
-            }
+            for (int j = 0; j < (nv / 2 + tail - 1) / tail; ++j) __builtin_amdgcn_sched_group_barrier(0x002, 2, 0);
           }
           __builtin_amdgcn_sched_barrier(0);   // keep each step's prefetches in that step (register pressure)
         }
       }
     };
-    // MCfg::PAIR: accumulator sets H and H + 2 of this wave, all kernel rows: pairs (2s, 2s + 1), s < NP, then the single row K - 1
-    // (classic two windows).  Step s' works on the fragments f = 2s' + H, f + 1: set H takes item s', set H + 2 item s' - 1 (same
-    // fragments, since (2s' - 2) + (H + 2) = f), so the B fragments of an item are built once and used in two consecutive steps.
-    auto matrix_phase_pairs = [&](auto hc) {
-      constexpr int H = decltype(hc)::value;
-      constexpr int NP = (K - 1) / 2;
-      typedef uint32_t u2 __attribute__((ext_vector_type(2)));
-      typedef const volatile __attribute__((address_space(3))) u2* lds_vu2p;
-      // B windows of a lane: start half bo of the zero-padded weight row (as in the classic loop), four kinds:
-      //   0: Toeplitz rows [0, 32) of row a      1: rows [32, 64) of row a (single row only)      2: rows [16, 48) of row a + 1
-      //   3 (mixed): lane groups 0, 1 rows [32, 48) of row a, lane groups 2, 3 rows [0, 16) of row a + 1
-      const uint32_t wbase = (uint32_t)(uintptr_t)(lds_u32p)(lds + C::SCRATCH + 256);
-      auto wof = [&](int bo, int rowadd) -> uint32_t {
-        const bool z = bo < 8 || bo > K + 14;
-        return wbase + 8u * (uint32_t)(z ? C::WZERO : ((bo - 8) >> 1)) + (z ? 0u : (uint32_t)(rowadd * 2 * C::WROWB));
-      };
-      uint32_t wk[4] = {wof(8 * lg - li + 15, 0), wof(32 + 8 * lg - li + 15, 0), wof(16 + 8 * lg - li + 15, 0),
-                        lg < 2 ? wof(32 + 8 * lg - li + 15, 0) : wof(8 * (lg - 2) - li + 15, 1)};
-      const uint32_t sh = (uint32_t)((8 * lg - li + 15) & 1) * 16u;   // (every start above has this parity)
-      // A fragments: `base_h` = lane row li, columns 16 cb + 8 lg of LDS row 0.  The mixed fragment's lane groups 2, 3 sit 16
-      // columns to the left in the NEXT input row: the distance between the LDS rows of fragments f and f + 1 depends on f mod 4
-      // only (row classes), and f mod 4 is H or H + 2 here -- two per-lane offsets
-      constexpr int DA = (C::cls_base((H + 1) % 4) + (H + 1) / 4 - C::cls_base(H % 4) - H / 4) * C::ROWB;
-      constexpr int DB = (C::cls_base((H + 3) % 4) + (H + 3) / 4 - C::cls_base((H + 2) % 4) - (H + 2) / 4) * C::ROWB;
-      int mixA = lg < 2 ? 64 : DA - 32, mixB = lg < 2 ? 64 : DB - 32;
-      asm volatile("" : "+v"(mixA), "+v"(mixB));
-#pragma unroll
-      for (int ch = 0; ch < ((ICS_MFMA_ABLATE & 1) ? 0 : 3); ++ch) {
-        uint32_t wb[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) { wb[k] = wk[k]; asm volatile("" : "+v"(wb[k])); }
-        const unsigned char* ph = base_h + (2 * ch) * C::PLANE;
-        const unsigned char* pl = ph + C::PLANE;
-        // item i < NP: pair (2i, 2i + 1) -> kinds 0, 3, 2; item NP: single row K - 1 -> kinds 0, 1
-        u2 rawB[3][5];
-        h8 Bc[3][2], Bp[3][2];                       // [window][hi, lo] of the current item (set H) and of the previous one (set H + 2)
-        auto issueB = [&](int item) {
-          const int a = 2 * item;
-          const int kinds[3] = {0, item < NP ? 3 : 1, 2};
-#pragma unroll
-          for (int w = 0; w < (item < NP ? 3 : 2); ++w) {
-            const int arow = a + (w == 2 ? 1 : 0);   // (the mixed window adds its second row per lane, in wk[3])
-            const lds_vu2p r = reinterpret_cast<lds_vu2p>(wb[kinds[w]] + (uint32_t)((ch * K + arow) * 2 * C::WROWB));
-#pragma unroll
-            for (int d = 0; d < 5; ++d) rawB[w][d] = r[d];
-          }
-        };
-        auto finishB = [&](int item, h8 (&B)[3][2]) {
-#pragma unroll
-          for (int w = 0; w < (item < NP ? 3 : 2); ++w) {
-            const u2* d = rawB[w];
-            u4 wh = {__builtin_amdgcn_alignbit(d[1].x, d[0].x, sh), __builtin_amdgcn_alignbit(d[2].x, d[1].x, sh),
-                     __builtin_amdgcn_alignbit(d[3].x, d[2].x, sh), __builtin_amdgcn_alignbit(d[4].x, d[3].x, sh)};
-            u4 wl = {__builtin_amdgcn_alignbit(d[1].y, d[0].y, sh), __builtin_amdgcn_alignbit(d[2].y, d[1].y, sh),
-                     __builtin_amdgcn_alignbit(d[3].y, d[2].y, sh), __builtin_amdgcn_alignbit(d[4].y, d[3].y, sh)};
-            B[w][0] = __builtin_bit_cast(h8, wh);
-            B[w][1] = __builtin_bit_cast(h8, wl);
-          }
-        };
-        // A fragments of step s': [0] row f cols [0, 32), [1] mixed (item < NP) or row f cols [32, 64) (single), [2] row f + 1 cols [16, 48)
-        auto loadA = [&](int sp, h8 (&A)[3][2], bool need_pair, bool need_single, h8 (&A1)[2]) {
-          const int f = 2 * sp + H;
-          const int off = (C::cls_base(f % 4) + f / 4) * C::ROWB;
-          const int off1 = (C::cls_base((f + 1) % 4) + (f + 1) / 4) * C::ROWB;
-          A[0][0] = *reinterpret_cast<const h8*>(ph + off); A[0][1] = *reinterpret_cast<const h8*>(pl + off);
-          if (need_pair) {
-            const int mix = (f % 4 == H) ? mixA : mixB;
-            A[1][0] = *reinterpret_cast<const h8*>(ph + off + mix); A[1][1] = *reinterpret_cast<const h8*>(pl + off + mix);
-            A[2][0] = *reinterpret_cast<const h8*>(ph + off1 + 32); A[2][1] = *reinterpret_cast<const h8*>(pl + off1 + 32);
-          }
-          if (need_single) { A1[0] = *reinterpret_cast<const h8*>(ph + off + 64); A1[1] = *reinterpret_cast<const h8*>(pl + off + 64); }
-        };
-        // which items run at step sp: set H item sp (pair if sp < NP, single if sp == NP), set H + 2 item sp - 1
-        auto pair_at = [](int sp) { return sp < NP || (sp >= 1 && sp - 1 < NP); };
-        auto single_at = [](int sp) { return sp == NP || sp - 1 == NP; };
-        h8 Ac[3][2], As[2];
-        issueB(0);
-        loadA(0, Ac, pair_at(0), single_at(0), As);
-        finishB(0, Bc);
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int sp = 0; sp <= NP + 1; ++sp) {
-          h8 An[3][2], Asn[2];
-#pragma unroll
-          for (int w = 0; w < 3; ++w) { An[w][0] = Ac[w][0]; An[w][1] = Ac[w][1]; }
-          Asn[0] = As[0]; Asn[1] = As[1];
-          if (sp + 1 <= NP + 1) loadA(sp + 1, An, pair_at(sp + 1), single_at(sp + 1), Asn);
-          if (sp + 1 <= NP) issueB(sp + 1);
-          int nm = 0;
-          // three split terms; the two sets' accumulators alternate
-#pragma unroll
-          for (int term = 0; term < 3; ++term) {
-            const int ia = term == 2 ? 1 : 0, ib = term == 1 ? 1 : 0;
-#pragma unroll
-            for (int w = 0; w < 3; ++w) {
-              if ((ICS_MFMA_ABLATE & 64) && term == 2) continue;
-              // set H: item sp
-              if (sp < NP) { acc[ch][H] = __builtin_amdgcn_mfma_f32_16x16x32_f16(Ac[w][ia], Bc[w][ib], acc[ch][H], 0, 0, 0); ++nm; }
-              else if (sp == NP && w < 2) { acc[ch][H] = __builtin_amdgcn_mfma_f32_16x16x32_f16(w == 0 ? Ac[0][ia] : As[ia], Bc[w][ib], acc[ch][H], 0, 0, 0); ++nm; }
-              // set H + 2: item sp - 1
-              if (sp >= 1 && sp - 1 < NP) { acc[ch][H + 2] = __builtin_amdgcn_mfma_f32_16x16x32_f16(Ac[w][ia], Bp[w][ib], acc[ch][H + 2], 0, 0, 0); ++nm; }
-              else if (sp - 1 == NP && w < 2) { acc[ch][H + 2] = __builtin_amdgcn_mfma_f32_16x16x32_f16(w == 0 ? Ac[0][ia] : As[ia], Bp[w][ib], acc[ch][H + 2], 0, 0, 0); ++nm; }
-            }
-          }
-#pragma unroll
-          for (int w = 0; w < 3; ++w) { Bp[w][0] = Bc[w][0]; Bp[w][1] = Bc[w][1]; }
-          if (sp + 1 <= NP) finishB(sp + 1, Bc);
-#pragma unroll
-          for (int w = 0; w < 3; ++w) { Ac[w][0] = An[w][0]; Ac[w][1] = An[w][1]; }
-          As[0] = Asn[0]; As[1] = Asn[1];
-          if (ICS_MFMA_INTERLEAVE) {   // LDS reads behind the first MFMAs of the step, the funnel shifts behind the last four
-            int nr = 0, nv = 0;
-            if (sp + 1 <= NP + 1) nr += 2 + (pair_at(sp + 1) ? 4 : 0) + (single_at(sp + 1) ? 2 : 0);
-            if (sp + 1 <= NP) { nr += 5 * (sp + 1 < NP ? 3 : 2); nv = 8 * (sp + 1 < NP ? 3 : 2); }
-            const int tail = nv ? (nm > 4 ? 4 : nm) : 0, head = nm - tail;
-#pragma unroll
-            for (int i = 0; i < (head > nr ? head : nr); ++i) {
-              if (i < head) __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-              if (i < nr) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-            }
-#pragma unroll
-            for (int i = 0; i < tail; ++i) {
-              __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-#pragma unroll
-              for (int j = 0; j < (nv / 2 + tail - 1) / tail; ++j) __builtin_amdgcn_sched_group_barrier(0x002, 2, 0);
-            }
-          }
-          __builtin_amdgcn_sched_barrier(0);
-        }
-      }
-    };
-    // MCfg::PAIR_ITEMS: this wave takes the items [I0, I1] (item i < NP = row pair (2i, 2i + 1), item NP = the single row K - 1) for
+    // MCfg::PAIR: this wave takes the items [I0, I1] (item i < NP = row pair (2i, 2i + 1), item NP = the single row K - 1) for
     // ALL four accumulator sets.  Fragment step f serves the sets t = f mod 2 and t + 2 with the items (f - t) / 2; an item's B
     // fragments are built once and used in the four steps f = 2i .. 2i + 3 -- half the weight-row reads and funnel shifts per
-    // MFMA of the per-set split above (which ran at the wave's issue limit: 2.8 other instructions per MFMA, 1.00 of 1.06 ms).
+    // MFMA of the per-set split it replaced (which ran at the wave's issue limit: 2.8 other instructions per MFMA, 1.00 of 1.06 ms).
     auto matrix_phase_items = [&](auto i0c, auto i1c) {
       constexpr int I0 = decltype(i0c)::value, I1 = decltype(i1c)::value;
       constexpr int NP = (K - 1) / 2;
@@ -725,7 +518,7 @@ __global__ __launch_bounds__(256 * NH) __attribute__((amdgpu_waves_per_eu(MCfg<K
       auto mixoff = [&](int c4) { return 64 + (mixsel & ((C::cls_base((c4 + 1) % 4) + (c4 + 1) / 4 - C::cls_base(c4)) * C::ROWB - 96)); };
       constexpr int F0 = 2 * I0, F1 = 2 * I1 + 3;            // fragment steps of this wave
 #pragma unroll
-      for (int ch = 0; ch < ((ICS_MFMA_ABLATE & 1) ? 0 : 3); ++ch) {
+      for (int ch = 0; ch < 3; ++ch) {
         uint32_t wb[4];
 #pragma unroll
         for (int k = 0; k < 4; ++k) { wb[k] = wk[k]; asm volatile("" : "+v"(wb[k])); }
@@ -815,7 +608,6 @@ __global__ __launch_bounds__(256 * NH) __attribute__((amdgpu_waves_per_eu(MCfg<K
             const int ia = term == 2 ? 1 : 0, ib = term == 1 ? 1 : 0;
 #pragma unroll
             for (int w = 0; w < 3; ++w) {
-              if ((ICS_MFMA_ABLATE & 64) && term == 2) continue;
 #pragma unroll
               for (int tt = 0; tt < 2; ++tt) {
                 const int t = (f & 1) + 2 * tt;
@@ -830,22 +622,21 @@ __global__ __launch_bounds__(256 * NH) __attribute__((amdgpu_waves_per_eu(MCfg<K
 #pragma unroll
           for (int w = 0; w < 3; ++w) { Ac[w][0] = An[w][0]; Ac[w][1] = An[w][1]; }
           As[0] = Asn[0]; As[1] = Asn[1];
-          if (ICS_MFMA_INTERLEAVE) {
-            int nr = 0, nv = 0;
-            if (f + 1 <= F1) nr += 2 + (pair_at(f + 1) ? 4 : 0) + (single_at(f + 1) ? 2 : 0);
-            if (newB) { const int nw = (f + 1) / 2 < NP ? 3 : 2; nr += (C::WSPLIT ? 4 : 5) * nw; nv = C::WSPLIT ? 0 : 8 * nw; }
-            const int tail = nv ? (nm > 4 ? 4 : nm) : 0, head = nm - tail;
+          // LDS reads behind the first MFMAs of the step, the funnel shifts behind the last four
+          int nr = 0, nv = 0;
+          if (f + 1 <= F1) nr += 2 + (pair_at(f + 1) ? 4 : 0) + (single_at(f + 1) ? 2 : 0);
+          if (newB) { const int nw = (f + 1) / 2 < NP ? 3 : 2; nr += (C::WSPLIT ? 4 : 5) * nw; nv = C::WSPLIT ? 0 : 8 * nw; }
+          const int tail = nv ? (nm > 4 ? 4 : nm) : 0, head = nm - tail;
 #pragma unroll
-            for (int i = 0; i < (head > nr ? head : nr); ++i) {
-              if (i < head) __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-              if (i < nr) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-            }
+          for (int i = 0; i < (head > nr ? head : nr); ++i) {
+            if (i < head) __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+            if (i < nr) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+          }
 #pragma unroll
-            for (int i = 0; i < tail; ++i) {
-              __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+          for (int i = 0; i < tail; ++i) {
+            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
 #pragma unroll
-              for (int j = 0; j < (nv / 2 + tail - 1) / tail; ++j) __builtin_amdgcn_sched_group_barrier(0x002, 2, 0);
-            }
+            for (int j = 0; j < (nv / 2 + tail - 1) / tail; ++j) __builtin_amdgcn_sched_group_barrier(0x002, 2, 0);
           }
           __builtin_amdgcn_sched_barrier(0);
         }
@@ -853,19 +644,17 @@ __global__ __launch_bounds__(256 * NH) __attribute__((amdgpu_waves_per_eu(MCfg<K
     };
     const bool has_out = x0 + 16 * cb < xend;   // wave-uniform: a column block right of the output carries none
     if (has_out) {
-      if constexpr (C::PAIR_ITEMS) {
+      if constexpr (C::PAIR) {
         constexpr int NPI = (K - 1) / 2, ISPLIT = (NPI + 1) / 2;          // items 0 .. ISPLIT - 1 | ISPLIT .. NPI (the single row included)
         if (half == 0) matrix_phase_items(std::integral_constant<int, 0>{}, std::integral_constant<int, ISPLIT - 1>{});
         else matrix_phase_items(std::integral_constant<int, ISPLIT>{}, std::integral_constant<int, NPI>{});
-      } else if constexpr (C::PAIR_SETS) {
-        if (half == 0) matrix_phase_pairs(std::integral_constant<int, 0>{}); else matrix_phase_pairs(std::integral_constant<int, 1>{});
       } else {
         if (NH == 1) matrix_phase(std::integral_constant<int, 0>{}, std::integral_constant<int, K>{});
         else if (half == 0) matrix_phase(std::integral_constant<int, 0>{}, std::integral_constant<int, C::KSPLIT>{});
         else matrix_phase(std::integral_constant<int, C::KSPLIT>{}, std::integral_constant<int, K>{});
       }
     }
-    if (NH == 2 && !C::PAIR_SETS) {
+    if (NH == 2) {
       // partial sums of the two halves: a wave keeps the accumulator sets t = 2 half, 2 half + 1 and hands the other two to its
       // partner through the plane space (free once every wave has left the matrix phase)
       lds_barrier();
@@ -884,12 +673,11 @@ __global__ __launch_bounds__(256 * NH) __attribute__((amdgpu_waves_per_eu(MCfg<K
       lds_barrier();
       if (half == 0) exchange(std::integral_constant<int, 0>{}, false); else exchange(std::integral_constant<int, 1>{}, false);
     }
-    ICS_TICK(1);
     // ---- epilogue straight from the accumulators: lane (li, lg) holds, for each channel, the 16 rows
     // t + 16*lg + 4*r of pixel column 16*wv + li, i.e. one 12-byte HWC pixel per (t, r): operands arrive and
     // results leave as dwordx3 (16 lanes = 192 contiguous bytes of a row), no LDS transpose and no workgroup
     // barrier between the matrix phase and the stores -- the four waves drift apart and overlap their phases.
-    if (has_out && !(ICS_MFMA_ABLATE & 4)) {
+    if (has_out) {
       const float sc = inv_w * inv_x;   // powers of two
       const int tide = opaque(tid);
       const int eli = tide & 15, elg = (tide >> 4) & 3;
@@ -909,11 +697,10 @@ __global__ __launch_bounds__(256 * NH) __attribute__((amdgpu_waves_per_eu(MCfg<K
       const int acc_voff = 16 * (tide & 63);
       const int acc_sb = (tile * 4 + cb) * (3 * C::RS * 1024);                  // bytes: [tile][cb][ch][t][lane] float4
       auto run_epi = [&](auto tbc, auto tvc, auto tloc) {
-      // accumulator sets of this wave: all of them (NH = 1), two consecutive ones (NH = 2), or TLO and TLO + 2 (row pairs, MCfg::PAIR).
-      // The loops below run over slots i = 0 .. NS - 1 <-> set TLO + i * TSTEP; written with `t` running over [TLO, THI) in steps of TSTEP.
-      constexpr int TSTEP = C::PAIR_SETS ? 2 : 1, NS = C::RS / NH;
-      constexpr int TLO = decltype(tloc)::value, THI = TLO + NS * TSTEP;
-      constexpr int TB = (decltype(tbc)::value < NS ? decltype(tbc)::value : NS) * TSTEP;   // sets per batch, in units of t
+      // accumulator sets of this wave: all of them (NH = 1) or two consecutive ones (NH = 2), t running over [TLO, THI)
+      constexpr int NS = C::RS / NH;
+      constexpr int TLO = decltype(tloc)::value, THI = TLO + NS;
+      constexpr int TB = decltype(tbc)::value < NS ? decltype(tbc)::value : NS;   // sets per batch
       constexpr bool TVOP = decltype(tvc)::value;
       // PAM kinds (tv_kind 2, 3): the frame this kernel writes is G = T + lambd * gradu itself -- the update pass then reads u and G
       // only (no T, no majoriser, no image: 3 frame transits instead of 5), and T is read exactly once, here
@@ -922,45 +709,43 @@ __global__ __launch_bounds__(256 * NH) __attribute__((amdgpu_waves_per_eu(MCfg<K
       for (int t0 = TLO; t0 < THI; t0 += TB) {
       u3 eop[EOPS][C::RS][4], eopT[C::RS][4];
 #pragma unroll
-      for (int t = t0; t < t0 + TB; t += TSTEP)
+      for (int t = t0; t < t0 + TB; ++t)
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           const int so = sb + 4 * (t + C::RS * r) * pitch;
-          if (ICS_MFMA_ABLATE & 8) { eop[0][t][r] = (u3){0u, 0u, 0u}; eop[EOPS - 1][t][r] = (u3){0u, 0u, 0u}; continue; }
           if (MODE == 0 && use_acc) continue;   // requested below, per (channel, t)
           if (EARLY1) { eop[0][t][r] = pre1[r]; continue; }
-          eop[0][t][r] = __builtin_amdgcn_raw_buffer_load_b96(rs_f, voff, so, (MODE == 0 ? ICS_EPI_LOAD_AUX0 : ICS_EPI_LOAD_AUX));
-          if (MODE == 1 && !pam) eop[EOPS - 1][t][r] = __builtin_amdgcn_raw_buffer_load_b96(rs_t, voff, so, ICS_EPI_LOAD_AUX);   // (PAM has no majoriser term)
-          if (MODE == 1 && TVOP) eopT[t][r] = __builtin_amdgcn_raw_buffer_load_b96(rs_tv, voff, so, ICS_EPI_LOAD_AUX);
+          eop[0][t][r] = __builtin_amdgcn_raw_buffer_load_b96(rs_f, voff, so, 0);   // (nt loads measured slower: the update pass that follows finds less of u / ut in the memory-side cache)
+          if (MODE == 1 && !pam) eop[EOPS - 1][t][r] = __builtin_amdgcn_raw_buffer_load_b96(rs_t, voff, so, 0);   // (PAM has no majoriser term)
+          if (MODE == 1 && TVOP) eopT[t][r] = __builtin_amdgcn_raw_buffer_load_b96(rs_tv, voff, so, 0);
         }
-      if (MODE == 0 && use_acc && !(ICS_MFMA_ABLATE & 8)) {
+      if (MODE == 0 && use_acc) {
         // the image in accumulator order (ics_image_acc.h): one 16-byte load per (channel, accumulator set) instead of four 12-byte ones
 #pragma unroll
-        for (int t = t0; t < t0 + TB; t += TSTEP)
+        for (int t = t0; t < t0 + TB; ++t)
 #pragma unroll
           for (int c = 0; c < 3; ++c) {
-            const u4 v = EARLY ? fpre[c][t] : __builtin_amdgcn_raw_buffer_load_b128(rs_acc, acc_voff, acc_sb + (c * C::RS + t) * 1024, ICS_EPI_LOAD_AUX0);
+            const u4 v = EARLY ? fpre[c][t] : __builtin_amdgcn_raw_buffer_load_b128(rs_acc, acc_voff, acc_sb + (c * C::RS + t) * 1024, 0);
 #pragma unroll
             for (int r = 0; r < 4; ++r) eop[0][t][r][c] = v[r];
           }
       }
-      if (t0 == TLO) ICS_TICK(3);
       if (MODE == 1 && t0 == TLO && !pam) {
         // the back-projection itself needs no operand: all 16 rows are stored behind the first batch of requests, in the
         // shadow of their latency (u and ut only feed the step-size reductions)
 #pragma unroll
-        for (int t = TLO; t < THI; t += TSTEP)
+        for (int t = TLO; t < THI; ++t)
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
             const int y = y0 + t + 4 * C::RS * elg + C::RS * r;
-            if (y < a.g.uM && colx < a.g.uN && !(ICS_MFMA_ABLATE & 8)) {
+            if (y < a.g.uM && colx < a.g.uN) {
               const u3 e = {__float_as_uint(acc[0][t][r] * sc), __float_as_uint(acc[1][t][r] * sc), __float_as_uint(acc[2][t][r] * sc)};
-              __builtin_amdgcn_raw_buffer_store_b96(e, rs_o, voff, sb + 4 * (t + C::RS * r) * pitch, ICS_EPI_STORE_AUX);
+              __builtin_amdgcn_raw_buffer_store_b96(e, rs_o, voff, sb + 4 * (t + C::RS * r) * pitch, 0);
             }
           }
       }
 #pragma unroll
-      for (int t = t0; t < t0 + TB; t += TSTEP)
+      for (int t = t0; t < t0 + TB; ++t)
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           const int y = y0 + t + 4 * C::RS * elg + C::RS * r;
@@ -970,15 +755,15 @@ __global__ __launch_bounds__(256 * NH) __attribute__((amdgpu_waves_per_eu(MCfg<K
           for (int c = 0; c < 3; ++c) av[c] = acc[c][t][r] * sc;
           if (MODE == 0) {
             // error = synth - image on the M x N interior (pyx:488); the border ring of the frame stays 0
-            if (y >= C::PAD && y < C::PAD + a.g.M && colx >= C::PAD && colx < C::PAD + a.g.N && (!(ICS_MFMA_ABLATE & 8) || av[0] + av[1] + av[2] == 12345.678f)) {
+            if (y >= C::PAD && y < C::PAD + a.g.M && colx >= C::PAD && colx < C::PAD + a.g.N) {
               u3 e;
 #pragma unroll
               for (int c = 0; c < 3; ++c) e[c] = __float_as_uint(__fsub_rn(av[c], __uint_as_float(eop[0][t][r][c])));
-              __builtin_amdgcn_raw_buffer_store_b96(e, rs_o, voff, so, ICS_EPI_STORE_AUX);
+              __builtin_amdgcn_raw_buffer_store_b96(e, rs_o, voff, so, 0);
             }
           } else {
             // gradu over the whole u-frame + reductions for the step size (pyx:519,523-524)
-            if (y < a.g.uM && colx < a.g.uN && (!(ICS_MFMA_ABLATE & 8) || av[0] + av[1] + av[2] == 12345.678f)) {
+            if (y < a.g.uM && colx < a.g.uN) {
               const float lambd = a.lambd;
               u3 gout;
 #pragma unroll
@@ -999,7 +784,7 @@ __global__ __launch_bounds__(256 * NH) __attribute__((amdgpu_waves_per_eu(MCfg<K
                 gout[c] = __float_as_uint(g);
               }
               rflags |= 64u;
-              if (pam) __builtin_amdgcn_raw_buffer_store_b96(gout, rs_o, voff, so, ICS_EPI_STORE_AUX);
+              if (pam) __builtin_amdgcn_raw_buffer_store_b96(gout, rs_o, voff, so, 0);
             }
           }
         }
@@ -1007,16 +792,14 @@ __global__ __launch_bounds__(256 * NH) __attribute__((amdgpu_waves_per_eu(MCfg<K
       };
       auto run_all = [&](auto tloc) {
         if (MODE == 1 && a.tv_kind != 0) run_epi(std::integral_constant<int, 1>{}, std::true_type{}, tloc);
-        else run_epi(std::integral_constant<int, ICS_EPI_TB(MODE)>{}, std::false_type{}, tloc);
+        else run_epi(std::integral_constant<int, MODE == 0 ? 4 : 2>{}, std::false_type{}, tloc);   // mode 1 carries two operand frames: two batches keep it spill-free
       };
-      if (NH == 1 || half == 0) run_all(std::integral_constant<int, 0>{}); else run_all(std::integral_constant<int, C::PAIR_SETS ? 1 : C::RS / 2>{});
+      if (NH == 1 || half == 0) run_all(std::integral_constant<int, 0>{}); else run_all(std::integral_constant<int, C::RS / 2>{});
     }
-    ICS_TICK(5);
     // (the next tile's first barrier, after the per-wave maxima, also orders this tile's fragment reads
     //  before the next conversion overwrites the planes)
   }
 
-  ICS_TICK(6);
   if (a.sched && tid == 0) {   // the last workgroup out re-arms the counters for the next launch
     if (atomicAdd(a.sched + 8, 1u) == gridDim.x - 1) {
 #pragma unroll
@@ -1049,8 +832,6 @@ __global__ __launch_bounds__(256 * NH) __attribute__((amdgpu_waves_per_eu(MCfg<K
       if (m > a.red[slot]) atomicMax(a.red + slot, m);
     }
   }
-  ICS_TICK(9);
-  ICS_TICK_FLUSH;
 }
 
 template <int K, int MODE, int RS, int NH = 1>
@@ -1063,9 +844,6 @@ hipError_t launch_one(const IcsConvArgs& a, hipStream_t s) {
   const int ncu = ics_device_cus(dev);
   const int ntiles = MODE == 0 ? ((a.g.N + C::TW - 1) / C::TW) * ((a.g.M + C::TH - 1) / C::TH) : a.g.tiles_x * ((a.g.uM + C::TH - 1) / C::TH);
   int grid = C::WGS * ncu;                   // persistent workgroups: as many as fit the LDS of a CU
-#ifdef ICS_GRID_WGS
-  grid = ICS_GRID_WGS * ncu;
-#endif
   if (grid > ntiles) grid = ntiles;
   // test hook: fewer persistent workgroups, so that small frames make every workgroup walk several tiles (next-tile
   // prefetch, band split) -- tests/test_gpu_rl.py::test_blind_golden_576x520_multi_tile_walk
@@ -1090,16 +868,13 @@ hipError_t launch_one(const IcsConvArgs& a, hipStream_t s) {
 //   0.184 / 0.218, K = 19 0.347 / 0.405 -> 0.325 / 0.364, K = 21 -5 % / -9 %, K = 23 .. 31 +10 .. 14 % (one workgroup per CU
 //   either way, and the A-fragment reads then bound the step); 1024^2 .. 3072^2, K <= 15: RS = 2 ahead by 3 .. 30 % (finer
 //   tiles balance the 256 CUs better).  Hence: K >= 23 -> 4; K = 15 .. 21 -> 2; K <= 13 -> 2 up to 3000 tiles of 64 x 64, else 4.
-#ifndef ICS_MFMA_39_NH2
-#define ICS_MFMA_39_NH2 1
-#endif
 template <int K> struct TileRs {
-  static constexpr bool has2 = ICS_MFMA_ALL_RS || K <= 21 || K >= 39;   // 39 .. 49: the planes of a 64-row tile do not fit the LDS
-  static constexpr bool has4 = ICS_MFMA_ALL_RS || K <= 13 || (K >= 23 && K <= 37);
+  static constexpr bool has2 = K <= 21 || K >= 39;   // 39 .. 49: the planes of a 64-row tile do not fit the LDS
+  static constexpr bool has4 = K <= 13 || (K >= 23 && K <= 37);
   // 16-row tiles (fragment rows 1 apart, one accumulator set; round 4) for frames that do not give every CU a 32-row tile: the 255-px
   // windows of deblur_module's blind phase (45 tiles of 32 x 64 on 256 CUs) and 512^2 (128).  A fragment read then feeds 3 MFMAs only --
   // irrelevant where a kernel is one chain of dependent round trips per workgroup; what counts is that the chain is half as long.
-  static constexpr bool has1 = !ICS_MFMA_NO_RS1 && K <= 15;
+  static constexpr bool has1 = K <= 15;
 };
 // does this frame take the 16-row tiles?  (fewer 32-row tiles than compute units)
 template <int K>
@@ -1122,7 +897,7 @@ hipError_t launch_k(int mode, const IcsConvArgs& a, hipStream_t s) {
     rs2 = frs == 2 ? true : (frs == 4 ? false : rs2);
   }
   if constexpr (TileRs<K>::has2) {
-    if constexpr (K >= 39 && ICS_MFMA_39_NH2) {   // 39 .. 49: 32-row tiles with the kernel rows split between two waves per column block
+    if constexpr (K >= 39) {   // 39 .. 49: 32-row tiles with the kernel rows split between two waves per column block
       if (rs2 || !TileRs<K>::has4) return mode == 0 ? launch_one<K, 0, 2, 2>(a, s) : launch_one<K, 1, 2, 2>(a, s);
     } else {
       if (rs2 || !TileRs<K>::has4) return mode == 0 ? launch_one<K, 0, 2>(a, s) : launch_one<K, 1, 2>(a, s);
@@ -1131,12 +906,11 @@ hipError_t launch_k(int mode, const IcsConvArgs& a, hipStream_t s) {
   if constexpr (TileRs<K>::has4) {
     if constexpr (K >= 23) {
       // one workgroup per CU: 8 waves, kernel rows split between the two waves of a column block (MCfg NH = 2).  Measured against the
-      // 4-wave form (ICS_TEST_CONV_NH=1 in a build with ICS_MFMA_ALL_RS): 4096^2 K = 23 0.417 / 0.485 -> 0.390 / 0.448 ms,
-      // 6144^2 K = 31 1.089 / 1.266 -> 1.077 / 1.197 ms
-      const int fnh = ICS_MFMA_ALL_RS ? ics_debug().conv_nh.load(std::memory_order_relaxed) : 0;
-      if (fnh != 1) return mode == 0 ? launch_one<K, 0, 4, 2>(a, s) : launch_one<K, 1, 4, 2>(a, s);
+      // 4-wave form: 4096^2 K = 23 0.417 / 0.485 -> 0.390 / 0.448 ms, 6144^2 K = 31 1.089 / 1.266 -> 1.077 / 1.197 ms
+      return mode == 0 ? launch_one<K, 0, 4, 2>(a, s) : launch_one<K, 1, 4, 2>(a, s);
+    } else {
+      return mode == 0 ? launch_one<K, 0, 4>(a, s) : launch_one<K, 1, 4>(a, s);
     }
-    if constexpr (K < 23 || ICS_MFMA_ALL_RS) return mode == 0 ? launch_one<K, 0, 4>(a, s) : launch_one<K, 1, 4>(a, s);
   }
   return hipErrorInvalidValue;
 }
@@ -1211,7 +985,7 @@ int ics_conv_mfma_rs(int K, const IcsGeom& g, int cus) {   // cus < 0: the curre
   if (K <= 15) {   // 16-row tiles on small frames (TileRs::has1): no accumulator-order image for them
     const int frs = ics_debug().conv_rs.load(std::memory_order_relaxed);
     const long t32 = (long)((g.N + 63) / 64) * ((g.M + 31) / 32);
-    if (!ICS_MFMA_NO_RS1 && (frs == 1 || (frs == 0 && t32 < (long)(cus >= 0 ? cus : ics_device_cus(ics_current_device()))))) return 0;
+    if ((frs == 1 || (frs == 0 && t32 < (long)(cus >= 0 ? cus : ics_device_cus(ics_current_device()))))) return 0;
   }
   bool rs2 = K <= 21 && (K >= 15 || (long)g.tiles_x * g.tiles_y <= 3000);
   if (K <= 13) {   // both heights are built
@@ -1226,9 +1000,6 @@ size_t ics_conv_mfma_table_floats(int K) { return (size_t)3 * K * 2 * (((2 * (K 
 
 hipError_t ics_launch_conv_mfma(int mode, const IcsConvArgs& a, hipStream_t s) {
   if ((mode != 0 && mode != 1) || !a.bt) return hipErrorInvalidValue;
-#ifdef ICS_MFMA_ONLY_K   /* experiments: one PSF size per build (scripts/isa_one.sh) */
-  return a.g.K == ICS_MFMA_ONLY_K ? launch_k<ICS_MFMA_ONLY_K>(mode, a, s) : hipErrorInvalidValue;
-#else
   switch (a.g.K) {
     case 3: return launch_k<3>(mode, a, s);
     case 5: return launch_k<5>(mode, a, s);
@@ -1240,6 +1011,5 @@ hipError_t ics_launch_conv_mfma(int mode, const IcsConvArgs& a, hipStream_t s) {
     case 17: return launch_k<17>(mode, a, s);
     default: return a.g.K <= 27 ? ics_launch_conv_mfma_part1(mode, a, s) : (a.g.K <= 37 ? ics_launch_conv_mfma_part2(mode, a, s) : ics_launch_conv_mfma_part3(mode, a, s));
   }
-#endif
 }
 #endif

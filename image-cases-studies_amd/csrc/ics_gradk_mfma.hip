@@ -28,13 +28,6 @@
 #include "ics_kernels.h"
 #include <type_traits>
 
-#ifndef ICS_GRADK_U_AUX
-#define ICS_GRADK_U_AUX 0   /* cache policy of the tile loads (2 = nt) */
-#endif
-#ifndef ICS_GRADK_E_AUX
-#define ICS_GRADK_E_AUX 0
-#endif
-
 namespace {
 
 typedef _Float16 h8 __attribute__((ext_vector_type(8)));
@@ -43,9 +36,9 @@ typedef float f4 __attribute__((ext_vector_type(4)));
 typedef uint32_t u4 __attribute__((ext_vector_type(4)));
 typedef float f32x4u __attribute__((ext_vector_type(4), aligned(4)));
 
-#ifndef ICS_GRADK_SLICE
-#define ICS_GRADK_SLICE 12   /* priority slices between the two workgroups of a CU, 2^12 x 10 ns (ics_prio_turn, ics_common.h); 0: off.  6144^2 / 31x31: 0.782 (off) -> 0.755 (2^10) -> 0.747 ms (2^12); 4096^2 / 23x23 0.359 -> 0.342 */
-#endif
+// priority slices between the two workgroups of a CU, 2^12 x 10 ns (ics_prio_turn, ics_common.h).  6144^2 / 31x31: 0.782 (off) -> 0.755 (2^10)
+// -> 0.747 ms (2^12); 4096^2 / 23x23 0.359 -> 0.342
+constexpr int ICS_GRADK_SLICE = 12;
 template <int NB>
 struct GCfg {
   static constexpr int TW = 64, NT = 16 * NB;        // U columns per tile; taps per axis (padded to 16 NB)
@@ -187,14 +180,14 @@ __device__ __forceinline__ void load_tile(f32x4u (&pu)[GCfg<NB>::UIT][3], f32x4u
     if (k * C::NTH >= ntask) break;                       // wave-uniform
     int v = tid + k * C::NTH; v = v < ntask ? v : ntask - 1;
     const int row = v / C::UXG, xg = v - row * C::UXG;
-    load_group<PL, ICS_GRADK_U_AUX>(pu[k], rs_u, 4 * (row * pitch + 4 * XM * xg), su, plane_bytes);
+    load_group<PL, 0>(pu[k], rs_u, 4 * (row * pitch + 4 * XM * xg), su, plane_bytes);
   }
   const int se = 4 * ((G.ay + y0) * pitch + XM * (G.ax + x0 - 8 * NB));
 #pragma unroll
   for (int k = 0; k < C::EIT; ++k) {
     int v = tid + k * C::NTH; v = v < C::ETASK ? v : C::ETASK - 1;
     const int row = v / C::EXG, xg = v - row * C::EXG;
-    load_group<PL, ICS_GRADK_E_AUX>(pe[k], rs_e, 4 * (row * pitch + 4 * XM * xg), se, plane_bytes);
+    load_group<PL, 0>(pe[k], rs_e, 4 * (row * pitch + 4 * XM * xg), se, plane_bytes);
   }
 }
 

@@ -81,7 +81,7 @@ bool ics_conv_fft_supported(int K);
 size_t ics_conv_fft_spectrum_floats();                                        // per orientation
 // (blk_n > 0: the spectra of blk_n x blk_n tap blocks of blk_k x blk_k taps, block q at spec + q * ics_conv_fft_spectrum_floats())
 hipError_t ics_launch_fft_spectrum(const float* psf, int K, float* spec_conv, float* spec_corr, hipStream_t s, int blk_n = 0, int blk_k = 0);
-// PSF sizes above the single-tile range (99 ... 255): the convolutions and the PSF gradient as tap blocks on the tiles -- the blocks' products
+// PSF sizes above the single-tile range (87 ... 255): the convolutions and the PSF gradient as tap blocks on the tiles -- the blocks' products
 // are summed in the frequency domain, one inverse transform per unit (k_conv_fft_blk); modes 0 and 1 of the shipped loop
 bool ics_conv_fft_blk_supported(int K);
 void ics_conv_fft_blk_shape(int K, int* blk_n, int* blk_k);

@@ -4,23 +4,13 @@
 #include "ics_kernels.h"
 #include "ics_tv.h"
 
-#ifndef ICS_UPDATE_U
-#define ICS_UPDATE_U 4   /* wave segments (1 KiB per frame each) per loop iteration of k_update_rows */
-#endif
-#ifndef ICS_PSF_THREADS
-#define ICS_PSF_THREADS 1024
-#endif
-#ifndef ICS_UPDATE_U_TV
-#define ICS_UPDATE_U_TV 4   /* the same for the active MM-TV form (five frames read, two written) */
-#endif
-#ifndef ICS_UPDATE_NT
-#define ICS_UPDATE_NT 15  /* streaming (nt) loads in k_update_rows: bit 0 u, 1 ut, 2 g, 3 f */
-#endif
-#ifndef ICS_GRADK_WAVES
-#define ICS_GRADK_WAVES 4   /* waves per k_gradk workgroup (4 or 8: measured equal, 0.28 ms at 4096^2) */
-#endif
-
 namespace {
+
+constexpr int ICS_UPDATE_U = 4;      // wave segments (1 KiB per frame each) per loop iteration of k_update_rows
+constexpr int ICS_UPDATE_U_TV = 4;   // the same for the active MM-TV form (five frames read, two written)
+constexpr int ICS_PSF_THREADS = 1024;
+constexpr int ICS_GRADK_WAVES = 4;   // waves per k_gradk workgroup (4 or 8: measured equal, 0.28 ms at 4096^2)
+constexpr int ICS_TVMM_SEG = 8;
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
@@ -206,27 +196,11 @@ __device__ __forceinline__ float pam_term(const float (&n)[3][20], int i, int c,
 // the image is flattest, i.e. where the differences cancel), everything behind them uses v_rcp_f32 / v_sqrt_f32 (1 ulp).  Within
 // ~1e-6 of the IEEE form relative to max |T| (gate 1e-5, tests/test_tv_mode.py); ICS_PAM_EXACT=1 / debug switch pam_exact (one switch for all
 // three extended kinds, tv_mode 1, 2 and 3: ics_launch_tvterm) selects the IEEE form.  n = rows (y-1, y, y+1) of the 20-float windows, i = index of the centre float.
-#ifndef ICS_TVMM_SEG
-#define ICS_TVMM_SEG 8
-#endif
-#ifndef ICS_TVMM_F64_DIFF
-#define ICS_TVMM_F64_DIFF 0   /* second differences as double sums (round 3's first form) */
-#endif
 struct IcsStencil2 { float udx, udy, udd, uda; };
 __device__ __forceinline__ IcsStencil2 ics_second_differences(const float (&n)[3][20], int i) {
-#if ICS_TVMM_F64_DIFF
-  const double m2c = -2.0 * (double)n[1][i];
-  const float inv = 0.707106769f;   // 1 / 1.41421354f rounded to float
-  IcsStencil2 s;
-  s.udx = (float)((m2c + (double)n[0][i]) + (double)n[2][i]);
-  s.udy = (float)((m2c + (double)n[1][i - 3]) + (double)n[1][i + 3]);
-  s.udd = (float)((m2c + (double)n[0][i - 3]) + (double)n[2][i + 3]) * inv;
-  s.uda = (float)((m2c + (double)n[0][i + 3]) + (double)n[2][i - 3]) * inv;
-  return s;
-#else
   // (a - c) + (b - c) in fp32: where the neighbours lie within a factor two of the centre -- every place where the differences
-  // cancel, i.e. where the term is large -- both differences are exact (Sterbenz) and the sum is rounded once, which is what the
-  // double form above returns; elsewhere the result is within an ulp of it.  A third fewer vector instructions per value.
+  // cancel, i.e. where the term is large -- both differences are exact (Sterbenz) and the sum is rounded once, which is what a
+  // double sum returns; elsewhere the result is within an ulp of it.  A third fewer vector instructions per value than the double form.
   const float c = n[1][i];
   const float inv = 0.707106769f;   // 1 / 1.41421354f rounded to float
   IcsStencil2 s;
@@ -235,7 +209,6 @@ __device__ __forceinline__ IcsStencil2 ics_second_differences(const float (&n)[3
   s.udd = __fadd_rn(__fsub_rn(n[0][i - 3], c), __fsub_rn(n[2][i + 3], c)) * inv;
   s.uda = __fadd_rn(__fsub_rn(n[0][i + 3], c), __fsub_rn(n[2][i - 3], c)) * inv;
   return s;
-#endif
 }
 __device__ __forceinline__ float ics_tv_mm_term_fast(const float (&nu)[3][20], const float (&nt)[3][20], int i, float eps) {
   const float a1 = 6.82842731f, a2 = 4.82842731f;            // 4 (1 + 1/sqrt 2), 2 (1 + sqrt 2)
@@ -891,10 +864,11 @@ __global__ __launch_bounds__(256) void k_update_rows(IcsUpdateArgs a) {
       const ptrdiff_t o = (ptrdiff_t)ys[s] * G.pitch + f0s[s];
       const f32x4* pu = reinterpret_cast<const f32x4*>(a.u + o); const f32x4* pt = reinterpret_cast<const f32x4*>(a.ut + o);
       const f32x4* pg = reinterpret_cast<const f32x4*>(a.g + o); const f32x4* pf = reinterpret_cast<const f32x4*>(a.f + o);
-      uq[s] = (ICS_UPDATE_NT & 1) ? __builtin_nontemporal_load(pu) : *pu;
-      if (TVK != 2) tq[s] = (ICS_UPDATE_NT & 2) ? __builtin_nontemporal_load(pt) : *pt;
-      gq[s] = (ICS_UPDATE_NT & 4) ? __builtin_nontemporal_load(pg) : *pg;
-      if (TVK != 2) fq[s] = (ICS_UPDATE_NT & 8) ? __builtin_nontemporal_load(pf) : *pf;
+      // streaming (nt) loads: every frame is read once per pass
+      uq[s] = __builtin_nontemporal_load(pu);
+      if (TVK != 2) tq[s] = __builtin_nontemporal_load(pt);
+      gq[s] = __builtin_nontemporal_load(pg);
+      if (TVK != 2) fq[s] = __builtin_nontemporal_load(pf);
       if (TVK == 1) Tq[s] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(a.tv + o));
     }
 #pragma unroll
@@ -952,8 +926,7 @@ __global__ __launch_bounds__(256) void k_update_rows(IcsUpdateArgs a) {
       }
       if (f0 + 3 < rowf) {
         const f32x4 w = {un4[0], un4[1], un4[2], un4[3]};
-        if (ICS_UPDATE_NT & 16) __builtin_nontemporal_store(w, reinterpret_cast<f32x4*>(a.u_out + o));
-        else *reinterpret_cast<f32x4*>(a.u_out + o) = w;
+        *reinterpret_cast<f32x4*>(a.u_out + o) = w;
       } else {
 #pragma unroll
         for (int e = 0; e < 4; ++e)
@@ -1080,7 +1053,7 @@ hipError_t ics_launch_update(const IcsUpdateArgs& a, hipStream_t s) {
   const long total = (long)a.geo.uM * a.geo.tiles_x * 16;
   long blocks = (total + 255) / 256;
   // Few long-lived workgroups stream best here.  k_update_rows at 4096^2 (4 reads + 1 write, 1.0 GB), segments per loop
-  // iteration x workgroups per CU: 3x2 0.173 ms, 4x2 0.167, 4x3 0.164, 4x4 0.170, 6x2 0.164, 6x4 0.180 (scripts/sweep_update.sh).
+  // iteration x workgroups per CU: 3x2 0.173 ms, 4x2 0.167, 4x3 0.164, 4x4 0.170, 6x2 0.164, 6x4 0.180.
   // ... and at smaller frames fewer still: 2048^2 0.0568 / 0.0526 / 0.0565 ms and 3072^2 0.119 / 0.099 / 0.102 ms with 1 / 2 / 3 per CU,
   // 1024^2 0.0252 / 0.0265 / 0.0299
   const long px = (long)a.geo.uM * a.geo.uN;

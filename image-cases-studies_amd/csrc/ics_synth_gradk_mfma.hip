@@ -33,50 +33,19 @@
 #include "ics_image_acc.h"
 #include <type_traits>
 
-#ifndef ICS_FUSED_INTERLEAVE
-#define ICS_FUSED_INTERLEAVE 1
-#endif
-
-// Measurement hooks (phase timing, timeline, ablations): empty in the library; the harness builds of tools/bench_synth_gradk.hip define
-// ICS_FUSED_PROBES and get their bodies from tools/ics_synth_gradk_probe.h.
-#ifdef ICS_FUSED_PROBES
-#include "tools/ics_synth_gradk_probe.h"
-#else
-#define FTICK_INIT
-#define FTICK(i)
-#define FTICK_FLUSH
-#define ICS_FUSED_ABL(mask) 0
-#endif
-#ifndef ICS_FUSED_GK_INTERLEAVE
-#define ICS_FUSED_GK_INTERLEAVE 1
-#endif
 // Fair shares for the workgroups of one CU.  The walk is static (the partial sums of a workgroup must not depend on timing), every
 // workgroup has the same number of tiles, and the CU's arbiter serves the OLDEST wave first: of the two workgroups that share a CU (blocks b
 // and b + CUs) the first-dispatched one walked its 8 tiles of a 4096^2 frame in 199 us, the other needed 256 -- 37 us per tile beside its
-// mate, 20 alone on a half-empty CU for the last 57 us (phase timeline, tools/bench_synth_gradk.hip -DICS_FUSED_TRACE,
-// scripts/dbg/trace_teams.py).  Priority now alternates between the mates in slices of 2^ICS_FUSED_SLICE ticks of the 100 MHz wall clock
+// mate, 20 alone on a half-empty CU for the last 57 us (phase timeline).  Priority now alternates between the mates in slices of
+// 2^FUSED_SLICE ticks of the 100 MHz wall clock
 // (ics_prio_turn, ics_common.h: s_setprio behind the barriers of the tile).  Scheduling only: results are bit-identical.
 // 4096^2, 15x15, 64-row form (tools/bench_synth_gradk.hip, sustained): 0.2744 -> 0.2616 ms with slices of 2^10 ticks (2^7: 0.262, 2^12: 0.262,
 // 2^14: 0.266; the younger mate always first: 0.275); the mates now end at 219 / 233 us instead of 199 / 256.
-#ifndef ICS_FUSED_SLICE
-#define ICS_FUSED_SLICE 10   /* 0: off */
-#endif
 // (the 32-row form, three mates: every slice length measured slower than none, 0.2646 -> 0.267 ... 0.273 ms; it keeps the arbiter's order)
-#define ICS_FUSED_TURN(team, nteams) ics_prio_turn(ICS_FUSED_SLICE, team, nteams)
-#ifndef ICS_FUSED_PRIO
-#define ICS_FUSED_PRIO 0
-#endif
-#ifndef ICS_FUSED_F01
-#define ICS_FUSED_F01 0   /* image operand of channels 0 and 1 in one dwordx2 request (0: one dword request per channel) */
-#endif
-
-#ifndef ICS_FUSED_WSPLIT
-#define ICS_FUSED_WSPLIT 0   /* measured: stand-alone harness 0.2749 -> 0.2622 ms (-4.6 %), inside the iteration 0.2739 -> 0.2767 (same box, two
-                                libraries alternating): the restaging of a channel's rows from the global table sits on the critical path between the
-                                two barriers there.  Built, correct (every fused-kernel test with the 64-row form forced), default off. */
-#endif
 
 namespace {
+
+constexpr int FUSED_SLICE = 10;
 
 typedef _Float16 h8 __attribute__((ext_vector_type(8)));
 typedef _Float16 h4 __attribute__((ext_vector_type(4)));
@@ -123,14 +92,9 @@ struct FCfg {
   static constexpr int WZERO = (K + 7) / 2;
   static constexpr int WLDS = 3 * K * 2 * WROWB;
   static constexpr int WOFF = SCR + 256;
-  // ICS_FUSED_WSPLIT (round 4): the weight rows of ONE channel at a time, as four plain rows per kernel row -- hi, lo, hi moved up one
-  // half, lo moved up one half -- so that a lane finds its 8 halves dword-aligned in the copy of its parity and reads them with two
-  // ds_read2_b32 per split term straight into the operand registers: 4 LDS instructions and no funnel shift per B fragment instead of
-  // 5 + 8 (ics_conv_mfma.hip, MCfg::WSPLIT).  All three channels in that form would need 11.5 KB where 5.8 KB are free; one channel
-  // (3.8 KB) is restaged from the global table between the two barriers every channel already has.
-  static constexpr bool WSPLIT = ICS_FUSED_WSPLIT != 0;
-  static constexpr int WLDS_USED = WSPLIT ? K * 4 * WROWB : WLDS;
-  static constexpr size_t LDS_BYTES = WOFF + WLDS_USED;
+  // (the weight rows of ics_conv_mfma.hip's MCfg::WSPLIT form, restaged one channel at a time between the barriers, measured slower
+  //  inside the iteration: 0.2739 -> 0.2767 ms -- the restaging sits on the critical path between the two barriers of a channel)
+  static constexpr size_t LDS_BYTES = WOFF + WLDS;
   static constexpr int NQ = K + 3;
   static constexpr int XG = LCOLS / 4;
   static constexpr int NTASK = LROWS * XG;
@@ -157,23 +121,11 @@ __device__ __forceinline__ int opaque(int x) { asm volatile("" : "+v"(x)); retur
 
 // workgroup barrier that orders LDS traffic only.  __syncthreads() also waits for every outstanding global load (vmcnt(0)):
 // with the image operand or the next tile's rows in flight it stalled the whole workgroup for an HBM round trip.
-__device__ __forceinline__ void lds_barrier() {
-  if (ICS_FUSED_ABL(128)) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  else asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-}
-// harness hooks (ICS_FUSED_ABL, a constant 0 in the library): the matrix instruction, or a stand-in that keeps its operands alive; the funnel shift or its first operand
-__device__ __forceinline__ f4 f_mfma32(h8 a, h8 b, f4 c) {
-  if (ICS_FUSED_ABL(64)) { asm volatile("" :: "v"(a), "v"(b)); return c; }
-  return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
-}
-__device__ __forceinline__ f4 f_mfma16(h4 a, h4 b, f4 c) {
-  if (ICS_FUSED_ABL(64)) { asm volatile("" :: "v"(a), "v"(b)); return c; }
-  return __builtin_amdgcn_mfma_f32_16x16x16f16(a, b, c, 0, 0, 0);
-}
-__device__ __forceinline__ uint32_t f_align(uint32_t hi, uint32_t lo, uint32_t sh) {
-  if (ICS_FUSED_ABL(32)) return lo;
-  return __builtin_amdgcn_alignbit(hi, lo, sh);
-}
+__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+// the matrix instructions and the funnel shift, short
+__device__ __forceinline__ f4 f_mfma32(h8 a, h8 b, f4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0); }
+__device__ __forceinline__ f4 f_mfma16(h4 a, h4 b, f4 c) { return __builtin_amdgcn_mfma_f32_16x16x16f16(a, b, c, 0, 0, 0); }
+__device__ __forceinline__ uint32_t f_align(uint32_t hi, uint32_t lo, uint32_t sh) { return __builtin_amdgcn_alignbit(hi, lo, sh); }
 
 template <typename C>
 __device__ __forceinline__ void load_raw(f32x4u (&v)[C::NIT][3], __amdgpu_buffer_rsrc_t rs, int soff, int tid, int pitch) {
@@ -244,42 +196,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   {
     u4* z = reinterpret_cast<u4*>(lds);
     for (int i = tid; i < C::WOFF / 16; i += C::NT) z[i] = (u4){0u, 0u, 0u, 0u};
-    if (!C::WSPLIT) {
-      uint32_t* ldsW = reinterpret_cast<uint32_t*>(lds + C::WOFF);
-      const uint32_t* tab = reinterpret_cast<const uint32_t*>(a.bt);
-      for (int i = tid; i < C::WLDS / 4; i += C::NT) ldsW[i] = tab[i];
-    }
+    uint32_t* ldsW = reinterpret_cast<uint32_t*>(lds + C::WOFF);
+    const uint32_t* tab = reinterpret_cast<const uint32_t*>(a.bt);
+    for (int i = tid; i < C::WLDS / 4; i += C::NT) ldsW[i] = tab[i];
   }
   const float inv_w = *reinterpret_cast<const float*>(reinterpret_cast<const unsigned char*>(a.bt) + C::WLDS);
-  // WSPLIT: the weight rows of channel `ch` from the global table (hi dword d at 2d, lo at 2d + 1 of a (c, a) block) into the four plain
-  // rows; one dword position per thread (K * WROWB / 4 <= 256), requested (wq_issue) ahead of the work it hides behind, stored (wq_store)
-  // before the barrier that precedes the convolution of that channel
-  typedef uint32_t wq2 __attribute__((ext_vector_type(2)));
-  wq2 wq_a = {0u, 0u}, wq_b = {0u, 0u};
-  auto wq_issue = [&](int ch) {
-    if (!C::WSPLIT) return;
-    constexpr int RD = C::WROWB / 4;
-    static_assert(!C::WSPLIT || K * RD <= C::NT, "one dword position per thread");
-    const int t0 = opaque(tid);
-    const int i = t0 < K * RD ? t0 : K * RD - 1;
-    const int ar = i / RD, d = i - ar * RD;
-    const wq2* src = reinterpret_cast<const wq2*>(reinterpret_cast<const uint32_t*>(a.bt) + (ch * K + ar) * 2 * RD) + d;
-    wq_a = src[0];
-    wq_b = d + 1 < RD ? src[1] : (wq2){0u, 0u};
-  };
-  auto wq_store = [&]() {
-    if (!C::WSPLIT) return;
-    constexpr int RD = C::WROWB / 4;
-    const int i = opaque(tid);
-    if (i < K * RD) {
-      const int ar = i / RD, d = i - ar * RD;
-      uint32_t* dst = reinterpret_cast<uint32_t*>(lds + C::WOFF) + ar * 4 * RD + d;
-      dst[0] = wq_a.x; dst[RD] = wq_a.y;
-      dst[2 * RD] = __builtin_amdgcn_alignbit(wq_b.x, wq_a.x, 16); dst[3 * RD] = __builtin_amdgcn_alignbit(wq_b.y, wq_a.y, 16);
-    }
-  };
-  wq_issue(0);
-  wq_store();
 
   // ---- lane constants --------------------------------------------------------------------------------------------
   typedef const __attribute__((address_space(3))) uint32_t* lds_u32p;
@@ -290,8 +211,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     const int bo = 8 * lg - li + 15;
     const bool bzero = bo < 8 || bo > K + 14;
     wsh = bzero ? 0u : (uint32_t)(bo & 1) * 16u;
-    if (C::WSPLIT) wa0 = lds0 + (uint32_t)C::WOFF + 4u * (uint32_t)(bzero ? C::WZERO : ((bo & 1) * 2 * (C::WROWB / 4) + ((bo - 8 - (bo & 1)) >> 1)));
-    else wa0 = lds0 + (uint32_t)C::WOFF + 8u * (uint32_t)(bzero ? C::WZERO : ((bo - 8) >> 1));
+    wa0 = lds0 + (uint32_t)C::WOFF + 8u * (uint32_t)(bzero ? C::WZERO : ((bo - 8) >> 1));
     asm volatile("" : "+v"(wa0));
   }
   // convolution, A operand: lane row li of column block wv, 8 halves at 16 wv + 8 lg
@@ -342,7 +262,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     load_raw<C>(raw, rs_in, 4 * ((a.g.ay + TORG + tyi * C::TH - C::PAD) * pitch + 3 * (a.g.ax + TORG + txi * C::TW - C::PAD)), tid, pitch);
   }
   __syncthreads();   // LDS initialised
-  FTICK_INIT;
   constexpr int MATES = 2;                                                      // workgroups per CU
   const int team = (int)gridDim.x >= MATES ? (int)blockIdx.x / ((int)gridDim.x / MATES) % MATES : 0;
 
@@ -365,12 +284,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
       m = ics_wave_max_f32(m);
       if (lane == 0) fscr[wv] = m;
       lds_barrier();     // S0: also orders the previous tile's last gradient phase before the planes are rewritten
-      ICS_FUSED_TURN(team, MATES);
+      ics_prio_turn(FUSED_SLICE, team, MATES);
 #pragma unroll
       for (int w = 0; w < C::NW; ++w) m = __builtin_fmaxf(m, fscr[w]);
       pow2_scale(__builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, m))), s_x, inv_x);
     }
-    FTICK(0);
     const float sc = inv_w * inv_x;
 
     // lane part of the epilogue addresses (image operand, optional e' store): pixel column 16 wv + li, rows 16 lg + ...
@@ -381,11 +299,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     const int sb = 4 * (y0 * pitch + 3 * (x0 + 16 * wv));
 
     // image operand.  With the accumulator-order copy (a.facc, ics_image_acc.h): four 16-byte loads per channel, requested right
-    // before the channel's convolution and consumed behind it.  Without (tv_mode 1 rewrites the image every iteration): channels 0
-    // and 1 arrive together from the HWC frame (16 dwordx2 requests instead of 32 dword requests per lane: the TA processes a
-    // request per instruction, and 48 stride-12 dword requests per lane and tile cost 0.037 ms of the 0.29), channel 1 waits in 16
-    // registers across gradk(0) and conv(1); channel 2 is requested on its own before conv(2)
-    uint32_t fop[4][4], fop1[ACC ? 1 : 4][4];
+    // before the channel's convolution and consumed behind it.  Without (tv_mode 1 rewrites the image every iteration): 16 dword
+    // requests per lane and channel from the HWC frame, at the same place
+    uint32_t fop[4][4];
     constexpr bool use_acc = ACC;
     const __amdgpu_buffer_rsrc_t rs_acc = make_rsrc(a.facc);
     const int acc_voff = 16 * (tide & 63);
@@ -398,39 +314,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         for (int r = 0; r < 4; ++r) fop[t][r] = v[r];
       }
     };
-    auto load_f01 = [&]() {
-      if constexpr (ACC) return;
-      else if (ICS_FUSED_ABL(16)) {
-#pragma unroll
-        for (int t = 0; t < 4; ++t)
-#pragma unroll
-          for (int r = 0; r < 4; ++r) { fop[t][r] = 0u; fop1[t][r] = 0u; }
-        return;
-      }
-#pragma unroll
-      for (int t = 0; t < 4; ++t)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const u2 v = __builtin_amdgcn_raw_buffer_load_b64(rs_f, voff, sb + 4 * (t + 4 * r) * pitch, 0);
-          fop[t][r] = v.x; fop1[t][r] = v.y;
-        }
-    };
-    auto take_f1 = [&]() {
-      if constexpr (!ACC) {
-#pragma unroll
-        for (int t = 0; t < 4; ++t)
-#pragma unroll
-          for (int r = 0; r < 4; ++r) fop[t][r] = fop1[t][r];
-      }
-    };
     auto load_f = [&](int ch) {
-      if (ICS_FUSED_ABL(16)) {
-#pragma unroll
-        for (int t = 0; t < 4; ++t)
-#pragma unroll
-          for (int r = 0; r < 4; ++r) fop[t][r] = 0u;
-        return;
-      }
 #pragma unroll
       for (int t = 0; t < 4; ++t)
 #pragma unroll
@@ -445,7 +329,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
       constexpr uint32_t PB = (uint32_t)((ch & 1) * 2 * C::PLANE);
 #pragma unroll
       for (int t = 0; t < 4; ++t) acc[t] = (f4){0.f, 0.f, 0.f, 0.f};
-      if (ICS_FUSED_ABL(2)) return;
       typedef const __attribute__((address_space(3))) h8* lds_h8p;
       typedef const volatile __attribute__((address_space(3))) u2* lds_vu2p;
       uint32_t wb = wa0; asm volatile("" : "+v"(wb));
@@ -453,24 +336,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
       h8 Bh[K], Bl[K];
       u2 rawB[5];
       auto issueB = [&](int ka) {
-        if constexpr (C::WSPLIT) {   // (inline asm: as C++ loads the pairs are merged into ds_read2_b64 at 4-byte alignment, which gfx950 executes very slowly)
-          const uint32_t ad = wb + (uint32_t)(ka * 4 * C::WROWB);
-          constexpr int RD = C::WROWB / 4;
-          u2 h01, h23, l01, l23;
-          asm volatile("ds_read2_b32 %0, %1 offset1:1" : "=v"(h01) : "v"(ad));
-          asm volatile("ds_read2_b32 %0, %1 offset0:2 offset1:3" : "=v"(h23) : "v"(ad));
-          asm volatile("ds_read2_b32 %0, %1 offset0:%2 offset1:%3" : "=v"(l01) : "v"(ad), "n"(RD), "n"(RD + 1));
-          asm volatile("ds_read2_b32 %0, %1 offset0:%2 offset1:%3" : "=v"(l23) : "v"(ad), "n"(RD + 2), "n"(RD + 3));
-          Bh[ka] = __builtin_bit_cast(h8, (u4){h01.x, h01.y, h23.x, h23.y});
-          Bl[ka] = __builtin_bit_cast(h8, (u4){l01.x, l01.y, l23.x, l23.y});
-          return;
-        }
         const lds_vu2p r = reinterpret_cast<lds_vu2p>(wb + (uint32_t)((ch * K + ka) * 2 * C::WROWB));
 #pragma unroll
         for (int d = 0; d < 5; ++d) rawB[d] = r[d];
       };
       auto finishB = [&](int ka) {
-        if constexpr (C::WSPLIT) { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); return; }   // (asm results are not tracked by the compiler's s_waitcnt insertion)
         const u2* d = rawB;
         const u4 wh = {f_align(d[1].x, d[0].x, wsh), f_align(d[2].x, d[1].x, wsh),
                        f_align(d[3].x, d[2].x, wsh), f_align(d[4].x, d[3].x, wsh)};
@@ -483,7 +353,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
       h8 Ah = *reinterpret_cast<lds_h8p>(ca + PB), Al = *reinterpret_cast<lds_h8p>(ca + PB + C::PLANE);
       finishB(0);
       __builtin_amdgcn_sched_barrier(0);
-      if (ICS_FUSED_PRIO & 2) __builtin_amdgcn_s_setprio(1);
 #pragma unroll
       for (int q = 0; q < C::NQ; ++q) {
         h8 Nh = Ah, Nl = Al;
@@ -503,26 +372,24 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
           }
         if (q + 1 < K) finishB(q + 1);
         Ah = Nh; Al = Nl;
-        if (ICS_FUSED_INTERLEAVE) {
-          int nt = 0;
+        int nt = 0;
 #pragma unroll
-          for (int t = 0; t < 4; ++t) nt += (q - t >= 0 && q - t < K) ? 1 : 0;
-          const int nm = 3 * nt;
-          const int nr = ((q + 1 < C::NQ) ? 2 : 0) + ((q + 1 < K) ? (C::WSPLIT ? 4 : 5) : 0);
-          const int nv = (q + 1 < K && !C::WSPLIT) ? 8 : 0;
-          const int tail = nv ? (nm > 4 ? 4 : nm) : 0;
-          const int head = nm - tail;
+        for (int t = 0; t < 4; ++t) nt += (q - t >= 0 && q - t < K) ? 1 : 0;
+        const int nm = 3 * nt;
+        const int nr = ((q + 1 < C::NQ) ? 2 : 0) + ((q + 1 < K) ? 5 : 0);
+        const int nv = (q + 1 < K) ? 8 : 0;
+        const int tail = nv ? (nm > 4 ? 4 : nm) : 0;
+        const int head = nm - tail;
 #pragma unroll
-          for (int i = 0; i < (head > nr ? head : nr); ++i) {
-            if (i < head) __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-            if (i < nr) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-          }
+        for (int i = 0; i < (head > nr ? head : nr); ++i) {
+          if (i < head) __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+          if (i < nr) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+        }
 #pragma unroll
-          for (int i = 0; i < tail; ++i) {
-            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+        for (int i = 0; i < tail; ++i) {
+          __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
 #pragma unroll
-            for (int j = 0; j < (nv / 2 + tail - 1) / tail; ++j) __builtin_amdgcn_sched_group_barrier(0x002, 2, 0);
-          }
+          for (int j = 0; j < (nv / 2 + tail - 1) / tail; ++j) __builtin_amdgcn_sched_group_barrier(0x002, 2, 0);
         }
         __builtin_amdgcn_sched_barrier(0);
       }
@@ -548,7 +415,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     // ---- e' -> fp16 (hi, lo) planes: a lane packs (hi | lo << 16), swaps with its column neighbour and stores one dword --
     auto write_e = [&](float s_e) {
       typedef __attribute__((address_space(3))) uint32_t* lds_wp;
-      if (ICS_FUSED_ABL(4)) return;
       const bool odd = (li & 1) != 0;
 #pragma unroll
       for (int t = 0; t < 4; ++t)
@@ -586,7 +452,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
       for (int h = 0; h < 2; ++h)
 #pragma unroll
         for (int X = 0; X < 2; ++X) g[h][X] = (f4){0.f, 0.f, 0.f, 0.f};
-      if (ICS_FUSED_ABL(1)) { tot[ch][0] += scale; return; }
       uint32_t gav[2], gbv[3];
 #pragma unroll
       for (int j = 0; j < 2; ++j) { gav[j] = ga[j]; asm volatile("" : "+v"(gav[j])); }
@@ -644,7 +509,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
       for (int X = 0; X < 2; ++X) { Ah[X] = nAh[X]; Al[X] = nAl[X]; }
       A2h = nA2h; A2l = nA2l;
       __builtin_amdgcn_sched_barrier(0);
-      if (ICS_FUSED_PRIO & 1) __builtin_amdgcn_s_setprio(1);
 #pragma unroll
       for (int i = 0; i < 16; ++i) {
         const int hp = i & 1;
@@ -671,7 +535,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
             A2h = nA2h; A2l = nA2l;
           }
         }
-        if (ICS_FUSED_GK_INTERLEAVE && i + 1 < 16) {
+        if (i + 1 < 16) {
           // 9 MFMAs; LDS reads of the next row: 13 e' dword pairs, + 4 + 2 u fragments when it opens a pair; 20 funnel shifts
           if (hp) {
 #pragma unroll
@@ -693,7 +557,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         }
         __builtin_amdgcn_sched_barrier(0);
       }
-      if (ICS_FUSED_PRIO & 1) __builtin_amdgcn_s_setprio(0);
       // block D1 (odd residual rows): row m = tap m.  Block D0 (even rows): row m = tap m - 1, i.e. tap a sits one row further down:
       // row a + 1 = register r + 1 of the same lane, or -- for r = 3 -- register 0 of the lane 16 above (rows 4 lg + r).  That one
       // crosses lanes: it is accumulated apart (`carry`) and joins its tap in the final cross-wave reduction, which goes through LDS anyway.
@@ -710,44 +573,31 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     unsigned char* const up = lds + C::UOFF;
     convert_channel<C, 0>(raw, s_x, up, opaque(tid));
     lds_barrier();                                                     // planes of channel 0 visible
-    FTICK(1);
-    if (use_acc) load_acc(0); else if (ICS_FUSED_F01) load_f01(); else load_f(0);
+    if (use_acc) load_acc(0); else load_f(0);
     conv_phase(std::integral_constant<int, 0>{});
-    FTICK(2);
     float s_e, inv_e, me;
 
 #define ICS_FUSED_CHANNEL(CH)                                                                                           \
     me = residual(CH);                                                                                                  \
     if (lane == 0) fscr[8 + 4 * (CH) + wv] = me;                                                                        \
-    FTICK(3);                                                                                                           \
     lds_barrier();     /* tile maximum; every wave is past the previous gradient phase: e' planes and u buffer free */  \
-    FTICK(4);                                                                                                           \
-    wq_issue(((CH) + 1) % 3);   /* every wave is past conv(CH): the weight rows of the next channel may take its place */          \
     me = __builtin_fmaxf(__builtin_fmaxf(fscr[8 + 4 * (CH)], fscr[9 + 4 * (CH)]), __builtin_fmaxf(fscr[10 + 4 * (CH)], fscr[11 + 4 * (CH)])); \
     pow2_scale(__builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, me))), s_e, inv_e);      \
-    write_e(s_e);                                                                                                       \
-    wq_store();
+    write_e(s_e);
 
     ICS_FUSED_CHANNEL(0)
-    if (!(ICS_FUSED_ABL(8))) convert_channel<C, 1>(raw, s_x, up + 2 * C::PLANE, opaque(tid));
-    FTICK(5);
+    convert_channel<C, 1>(raw, s_x, up + 2 * C::PLANE, opaque(tid));
     lds_barrier();                                                     // e'(0) and planes(1) visible
-    FTICK(6);
-    ICS_FUSED_TURN(team, MATES);
+    ics_prio_turn(FUSED_SLICE, team, MATES);
     gradk_phase(std::integral_constant<int, 0>{}, inv_x * inv_e);
-    FTICK(7);
-    if (use_acc) load_acc(1); else if (ICS_FUSED_F01) take_f1(); else load_f(1);
+    if (use_acc) load_acc(1); else load_f(1);
     conv_phase(std::integral_constant<int, 1>{});
-    FTICK(2);
 
     ICS_FUSED_CHANNEL(1)
-    if (!(ICS_FUSED_ABL(8))) convert_channel<C, 2>(raw, s_x, up, opaque(tid));
-    FTICK(5);
+    convert_channel<C, 2>(raw, s_x, up, opaque(tid));
     lds_barrier();                                                     // e'(1) and planes(2) visible
-    FTICK(6);
-    ICS_FUSED_TURN(team, MATES);
+    ics_prio_turn(FUSED_SLICE, team, MATES);
     gradk_phase(std::integral_constant<int, 1>{}, inv_x * inv_e);
-    FTICK(7);
     if (use_acc) load_acc(2); else load_f(2);
     // the rows of the next tile: in flight during conv(2), gradk(2) (no vector-memory loads in there; the image operand of
     // channel 2 was requested before them and returns first).  (Spreading the 21 requests of a lane over the steps of conv(2)
@@ -758,21 +608,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
       load_raw<C>(raw, rs_in, 4 * ((a.g.ay + TORG + nyi * C::TH - C::PAD) * pitch + 3 * (a.g.ax + TORG + nxi * C::TW - C::PAD)), opaque(tid), pitch);
     }
     __builtin_amdgcn_sched_barrier(0);
-    FTICK(8);
     conv_phase(std::integral_constant<int, 2>{});
-    FTICK(2);
 
     ICS_FUSED_CHANNEL(2)
-    FTICK(5);
     lds_barrier();                                                     // e'(2) visible
-    FTICK(6);
-    ICS_FUSED_TURN(team, MATES);
+    ics_prio_turn(FUSED_SLICE, team, MATES);
     gradk_phase(std::integral_constant<int, 2>{}, inv_x * inv_e);
-    FTICK(7);
 #undef ICS_FUSED_CHANNEL
   }
 
-  FTICK_FLUSH;
   // ---- cross-wave reduction (fixed order) and partial write, one channel per pass ------------------------------------
   float* red = reinterpret_cast<float*>(lds);   // [wave][256]: element (row = 4*lg + r, col = li) at [r*64 + lane]; then [wave][64] carries
   float* dst = a.partial + (size_t)blockIdx.x * (3 * 16 * 16);
@@ -811,13 +655,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 //     wave with one-row-deep software pipelines and copies of the operand registers (130 VGPRs in the gradient loop alone);
 //     here a wave requests an operand chunk, waits, shifts, issues its three MFMAs, and the two other waves of the SIMD fill
 //     the gaps -- 70 VGPRs in the gradient loop, which is what makes the third workgroup fit.
-// The ablation of the 64-row kernel that motivates it (tools/bench_synth_gradk.hip -DICS_FUSED_ABLATE, 4096^2, K = 15): without any
-// MFMA the kernel still takes 0.177 of its 0.265 ms -- a wave issues 6.2 k instructions per tile (25 k cycles of its 59 k) and
+// What motivates it, measured on the 64-row kernel at 4096^2, K = 15: without any MFMA the kernel still takes 0.177 of its 0.265 ms -- a wave issues 6.2 k instructions per tile (25 k cycles of its 59 k) and
 // stalls for the rest; two waves per SIMD leave that unhidden.
 // =====================================================================================================================
-#ifndef ICS_FUSED2_PREFETCH
-#define ICS_FUSED2_PREFETCH 0   /* measured: 0 (request at the start of the tile, 137 VGPRs) 0.2624 ms, 1 0.2669, 2 (ahead of conv(2), 167 VGPRs + spills) 0.2658 */
-#endif
 template <int K>
 struct FCfg2 {
   static constexpr int PAD = K / 2;
@@ -949,7 +789,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
   const float inv_w = *reinterpret_cast<const float*>(reinterpret_cast<const unsigned char*>(a.bt) + C::WLDS);
   __syncthreads();   // LDS initialised
   // (no priority slices here: with three workgroups per CU every slice length, and a rotation in which one mate steps back, measured slower
-  //  than the arbiter's own order -- ICS_FUSED_TURN above)
+  //  than the arbiter's own order -- FUSED_SLICE above)
 
 #pragma unroll 1
   for (; tile < band1; tile += nx) {
@@ -1201,6 +1041,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
     lds_barrier();                                                     // e'(1) and planes(2) visible
     gradk_phase(std::integral_constant<int, 1>{}, inv_x * inv_e);
     load_img(2);
+    // the rows of the next tile, requested at its start (behind gradk(2)): the other two workgroups of the CU cover the latency (137 VGPRs,
+    // 0.2624 ms; in flight during gradk(2) 0.2669, during conv(2) and gradk(2) 0.2658 with 167 VGPRs + spills)
     auto prefetch = [&]() {
       if (tile + nx < band1) {
         const int nt = tile + nx;
@@ -1208,14 +1050,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
         load_raw2<C>(raw, rs_in, 4 * ((a.g.ay + TORG + nyi * C::TH - C::PAD) * pitch + 3 * (a.g.ax + TORG + nxi * C::TW - C::PAD)), opaque(tid), pitch);
       }
     };
-    if (ICS_FUSED2_PREFETCH == 2) prefetch();                          // the rows of the next tile: in flight during conv(2), gradk(2)
     conv_phase(std::integral_constant<int, 2>{});
 
     ICS_FUSED2_CHANNEL(2)
     lds_barrier();                                                     // e'(2) visible
-    if (ICS_FUSED2_PREFETCH == 1) prefetch();                          // ... during gradk(2) only
     gradk_phase(std::integral_constant<int, 2>{}, inv_x * inv_e);
-    if (ICS_FUSED2_PREFETCH == 0) prefetch();                          // ... not at all: the other two workgroups of the CU cover the latency
+    prefetch();
 #undef ICS_FUSED2_CHANNEL
   }
 

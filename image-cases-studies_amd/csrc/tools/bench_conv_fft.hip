@@ -709,36 +709,6 @@ int gpu(int M, int K, int N, int reps) {
     for (int i = 0; i < reps; ++i) CK(ics_launch_conv_fft_args(mode, fa, 0));
     CK(hipEventRecord(e1, 0)); CK(hipEventSynchronize(e1));
     float ms; CK(hipEventElapsedTime(&ms, e0, e1));
-#ifdef ICS_FFT_TRACE
-    {
-      long long* dtr; const size_t nt = (size_t)256 * 16 * 16 * 10;
-      CK(hipMalloc(&dtr, nt * 8)); CK(hipMemset(dtr, 0, nt * 8));
-      fa.trace = dtr;
-      CK(ics_launch_conv_fft_args(mode, fa, 0)); CK(hipDeviceSynchronize());
-      std::vector<long long> tr(nt);
-      CK(hipMemcpy(tr.data(), dtr, nt * 8, hipMemcpyDeviceToHost));
-      static const char* nm[9] = {"barrier", "B", "C", "D spec", "E + loads", "F", "G", "epilogue", "A of next"};
-      // per stamp: when the FIRST and the LAST of the 16 waves pass it, relative to the unit's first stamp (mean over units)
-      double first[10] = {0}, last[10] = {0}, own[9] = {0}; int cnt = 0;
-      for (int b = 0; b < 256; b += 5)
-        for (int r = 1; r < 8; ++r) {   // rounds 1..7 of every fifth workgroup
-          const long long* t = &tr[(((size_t)b * 16 + r) * 16) * 10];
-          if (!t[9] || !t[0]) continue;
-          long long t0 = t[0];
-          for (int w = 0; w < 16; ++w) t0 = t[w * 10] < t0 ? t[w * 10] : t0;
-          for (int i = 0; i < 10; ++i) {
-            long long f = t[i], l = t[i];
-            for (int w = 0; w < 16; ++w) { f = t[w * 10 + i] < f ? t[w * 10 + i] : f; l = t[w * 10 + i] > l ? t[w * 10 + i] : l; }
-            first[i] += (double)(f - t0); last[i] += (double)(l - t0);
-          }
-          for (int i = 0; i < 9; ++i) { double s = 0; for (int w = 0; w < 16; ++w) s += (double)(t[w * 10 + i + 1] - t[w * 10 + i]); own[i] += s / 16; }
-          ++cnt;
-        }
-      printf("  phase timeline (shader clocks from the unit's start, mean of %d units; first wave / last wave to pass each mark; mean time a wave spends in the phase):\n", cnt);
-      for (int i = 0; i < 9; ++i) printf("    %-10s ends %6.0f / %6.0f   own %6.0f\n", nm[i], first[i + 1] / cnt, last[i + 1] / cnt, own[i] / cnt);
-      fa.trace = nullptr; hipFree(dtr);
-    }
-#endif
     printf("  mode %d: %.4f ms per launch (%d launches), %d units, %.2f us per unit and CU\n", mode, ms / reps, reps, fa.nunits, 1e3 * ms / reps / ((fa.nunits + 255) / 256));
   }
   {   // the PSF gradient on the tiles

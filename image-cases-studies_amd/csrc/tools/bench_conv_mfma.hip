@@ -1,15 +1,7 @@
 // bench_conv_mfma.hip -- stand-alone timing harness for the matrix-core convolution (ics_conv_mfma.hip) at
-// 4096^2 x 3, 15x15 PSF; built in variants (-DICS_MFMA_ABLATE=mask) to see which phase bounds the kernel.
-//   hipcc -O3 -std=c++17 --offload-arch=gfx950 -ffp-contract=off -I.. [-DICS_MFMA_ABLATE=m] bench_conv_mfma.hip -o bench_conv_mfma
-#ifdef ICS_BENCH_SMALL_K   /* K <= 17 only (seconds to build): the other parts' entry points are stubs */
-#define ICS_MFMA_PART 0
-#endif
+// 4096^2 x 3, 15x15 PSF, the kernels as the library builds them.
+//   hipcc -O3 -std=c++17 --offload-arch=gfx950 -ffp-contract=off -I.. bench_conv_mfma.hip -o bench_conv_mfma
 #include "../ics_conv_mfma.hip"
-#ifdef ICS_BENCH_SMALL_K
-hipError_t ics_launch_conv_mfma_part1(int, const IcsConvArgs&, hipStream_t) { return hipErrorInvalidValue; }
-hipError_t ics_launch_conv_mfma_part2(int, const IcsConvArgs&, hipStream_t) { return hipErrorInvalidValue; }
-hipError_t ics_launch_conv_mfma_part3(int, const IcsConvArgs&, hipStream_t) { return hipErrorInvalidValue; }
-#endif
 #include <stdio.h>
 #include <stdlib.h>
 #include <vector>
@@ -57,11 +49,6 @@ int main(int argc, char** argv) {
       printf("occupancy (workgroups per CU) K=15, 32-row tiles: mode 0 %d, mode 1 %d, LDS %zu B\n", nb0, nb1, (size_t)MCfg<15, 2>::LDS_BYTES);
     }
   }
-#ifdef ICS_MFMA_TRACE
-  unsigned long long* trace; const size_t trace_n = (size_t)1024 * 4 * 1024;   // up to 1024 workgroups
-  hipMalloc(&trace, trace_n * 8); hipMemset(trace, 0, trace_n * 8);
-  hipMemcpyToSymbol(HIP_SYMBOL(ics_trace_buf), &trace, sizeof trace);
-#endif
   hipEvent_t e0, e1; hipEventCreate(&e0); hipEventCreate(&e1);
   for (int mode = 0; mode < 2; ++mode) {
     // long runs: the first milliseconds after idle are timed at ramping clocks, and a sustained loop of this kernel sits at
@@ -72,36 +59,7 @@ int main(int argc, char** argv) {
     for (int i = 0; i < reps; ++i) ics_launch_conv_mfma(mode, a, 0);
     hipEventRecord(e1); hipEventSynchronize(e1);
     float ms; hipEventElapsedTime(&ms, e0, e1);
-    printf("ablate=%d mode %d: %.4f ms\n", ICS_MFMA_ABLATE, mode, ms / reps);
-#ifdef ICS_MFMA_TRACE
-    {  // one more launch, traced
-      hipMemset(trace, 0, trace_n * 8);
-      ics_launch_conv_mfma(mode, a, 0); hipDeviceSynchronize();
-      std::vector<unsigned long long> ht(trace_n);
-      hipMemcpy(ht.data(), trace, trace_n * 8, hipMemcpyDeviceToHost);
-      char nm[256]; snprintf(nm, sizeof nm, "%s/trace_mode%d.bin", getenv("ICS_TRACE_DIR") ? getenv("ICS_TRACE_DIR") : ".", mode);
-      FILE* fp = fopen(nm, "wb");
-      if (fp) {  // compact: per wave only the used entries
-        for (size_t w = 0; w < trace_n / 1024; ++w) {
-          const unsigned long long* t = ht.data() + w * 1024; int n = 0; while (n < 1024 && t[n]) ++n;
-          if (!n) continue;
-          unsigned long long hdr[2] = {w, (unsigned long long)n}; fwrite(hdr, 8, 2, fp); fwrite(t, 8, n, fp);
-        }
-        fclose(fp);
-      }
-    }
-#endif
-#ifdef ICS_MFMA_TIMING
-    {
-      unsigned long long h[11]; hipMemcpyFromSymbol(h, HIP_SYMBOL(ics_mfma_ticks), sizeof h);
-      const double tiles = (double)g.tiles_x * g.tiles_y * 4 * 23;   // wave-tiles over the 23 launches of this mode
-      const char* nm[10] = {"convert+sync", "mfma loop", "wait sync C", "epi operand issue", "wait sync D", "epilogue", "wait sync E", "prefetch issue", "transposes (LDS)", "-"};
-      double tot = 0; for (int i = 0; i < 10; ++i) tot += (double)h[i];
-      for (int i = 0; i < 9; ++i) printf("   %-18s %8.0f cycles / wave-tile  (%4.1f %%)\n", nm[i], h[i] / tiles, 100.0 * h[i] / tot);
-      printf("   total %.0f cycles / wave-tile, %llu waves\n", tot / tiles, h[10]);
-      unsigned long long z[11] = {0}; hipMemcpyToSymbol(HIP_SYMBOL(ics_mfma_ticks), z, sizeof z);
-    }
-#endif
+    printf("mode %d: %.4f ms\n", mode, ms / reps);
   }
   return 0;
 }
