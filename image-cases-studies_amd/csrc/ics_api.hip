@@ -116,6 +116,7 @@ struct ics_ctx {
   hipEvent_t pin_ev = nullptr;
   bool pin_used = false;
   static constexpr size_t PIN_DOUBLES = 8192;
+  bool ev_pending = false;  // ev0 / ev1 were recorded by a queued image filter: ics_ctx_last_kernel_ms reads them on demand
 };
 
 // at least `bytes` of device scratch that persists between calls (no hipMalloc / hipFree per filter call)
@@ -309,6 +310,12 @@ extern "C" int ics_ctx_synchronize(ics_ctx* c) {
 
 extern "C" int ics_ctx_last_kernel_ms(ics_ctx* c, float* ms) {
   if (!c || !ms) return fail(ICS_EINVAL, "NULL argument");
+  if (c->ev_pending) {   // a queued ics_img_convolve / _usm / _bilateral recorded ev0 / ev1 and did not wait for them
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipEventSynchronize(c->ev1));
+    HIPCHK(hipEventElapsedTime(&c->last_ms, c->ev0, c->ev1));
+    c->ev_pending = false;
+  }
   *ms = c->last_ms;
   return ICS_OK;
 }
@@ -1901,14 +1908,14 @@ extern "C" int ics_tv(ics_ctx* c, const float* u, int M, int N, float eps, int o
 
 // Rank-1 test: kern == outer(col, row)?  Every window of lib/utils.py (uniform, gaussian, kaiser, poisson) is an outer product
 // normalised by its sum; the two 1-D factors are taken through the largest element.
-static bool rank1_factors(const double* k, int KH, int KW, std::vector<double>& col, std::vector<double>& row) {
+static bool rank1_factors(const double* k, int KH, int KW, std::vector<double>& col, std::vector<double>& row, double tol = 4e-16) {
   int r = 0, c = 0; double m = 0.0;
   for (int i = 0; i < KH; ++i) for (int j = 0; j < KW; ++j) if (fabs(k[i * KW + j]) > m) { m = fabs(k[i * KW + j]); r = i; c = j; }
   if (m == 0.0 || KH == 1 || KW == 1) return false;
   const double piv = k[r * KW + c];
   for (int i = 0; i < KH; ++i)
     for (int j = 0; j < KW; ++j)
-      if (fabs(k[i * KW + j] * piv - k[i * KW + c] * k[r * KW + j]) > 4e-16 * m * m) return false;
+      if (fabs(k[i * KW + j] * piv - k[i * KW + c] * k[r * KW + j]) > tol * m * m) return false;
   col.resize(KH); row.resize(KW);
   for (int i = 0; i < KH; ++i) col[i] = k[i * KW + c] / piv;
   for (int j = 0; j < KW; ++j) row[j] = k[r * KW + j];
@@ -2167,6 +2174,105 @@ extern "C" int ics_img_resize(const ics_img* src, int OH, int OW, ics_img** out)
   if (e == hipSuccess && nw && !staged) e = hipStreamSynchronize(s);   // pageable host vectors are released below
   c->pool.release(scr); c->pool.release(dw);
   if (e != hipSuccess) { ics_img_destroy(*out); *out = nullptr; return fail(e == hipErrorOutOfMemory ? ICS_ENOMEM : ICS_EHIP, "img_resize: %s", hipGetErrorString(e)); }
+  return ICS_OK;
+}
+
+// ---- lib/utils.py filters on device images (csrc/ics_img_filters.hip) ----------------------------------------------------------
+// A small host table (kernel factors, spatial weights) -> device, queued.  It goes through the context's pinned staging area:
+// the copy reads memory the context owns, `pin_ev` marks it and the next writer of the area waits for that event, so the
+// caller's vector may die at once and the stream is not synchronised.  Only a table larger than the area (64 KB) is copied
+// from pageable memory, and then that copy alone is waited for before the vector goes out of scope.
+static hipError_t put_table(ics_ctx* c, float* dev, const std::vector<float>& t) {
+  const size_t bytes = t.size() * sizeof(float);
+  hipStream_t s = c->stream;
+  hipError_t e = hipSuccess;
+  if (bytes > ics_ctx::PIN_DOUBLES * 8) {
+    e = hipMemcpyAsync(dev, t.data(), bytes, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    return e;
+  }
+  if (!c->pin) { e = hipHostMalloc((void**)&c->pin, ics_ctx::PIN_DOUBLES * 8, hipHostMallocDefault); if (e == hipSuccess) e = hipEventCreateWithFlags(&c->pin_ev, hipEventDisableTiming); }
+  if (e == hipSuccess && c->pin_used) e = hipEventSynchronize(c->pin_ev);
+  if (e != hipSuccess) return e;
+  memcpy(c->pin, t.data(), bytes);
+  e = hipMemcpyAsync(dev, c->pin, bytes, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) e = hipEventRecord(c->pin_ev, s);
+  c->pin_used = true;
+  return e;
+}
+
+// convolve2d(mode="same", boundary="symm") per channel [+ USM epilogue]; the kernels take the taps reversed (ics_img_filters.hip)
+static int img_conv_common(const ics_img* src, const float* kern, int KH, int KW, int usm, float amount, ics_img** out) {
+  if (!src || !kern || !out) return fail(ICS_EINVAL, "NULL argument");
+  if (KH < 1 || KW < 1) return fail(ICS_EINVAL, "bad kernel size %d x %d", KH, KW);
+  ics_ctx* c = src->ctx;
+  const int H = src->H, W = src->W;
+  // rank-1 test on the float32 taps: an outer product rounded to float32 entry by entry is one to 4 x 2^-24 of its largest product
+  std::vector<double> kd(kern, kern + (size_t)KH * KW), col, row;
+  const bool sep = rank1_factors(kd.data(), KH, KW, col, row, 0x1p-21);
+  const bool cols_only = !sep && KW == 1 && KH > 1;
+  if (sep ? (ics_img_conv_rows_lds(1, KW) > 160 * 1024 || ics_img_conv_cols_lds(KH) > 160 * 1024)
+          : (cols_only ? ics_img_conv_cols_lds(KH) > 160 * 1024 : ics_img_conv_rows_lds(KH, KW) > 160 * 1024))
+    return fail(ICS_ENOSUP, "kernel %d x %d (%s) too large for the LDS tile (rank 1: up to 129 x 764; otherwise (15 + KH) * (260 + 12 * ceil(KW / 4)) floats within 160 KB)",
+                KH, KW, sep ? "rank 1" : "not rank 1");
+  std::vector<float> t;
+  if (sep) {   // [KW row taps][KH column taps], both reversed
+    for (int u = 0; u < KW; ++u) t.push_back((float)row[KW - 1 - u]);
+    for (int v = 0; v < KH; ++v) t.push_back((float)col[KH - 1 - v]);
+  } else {
+    for (int v = 0; v < KH; ++v) for (int u = 0; u < KW; ++u) t.push_back(kern[(size_t)(KH - 1 - v) * KW + (KW - 1 - u)]);
+  }
+  RC(img_new(c, H, W, out));
+  hipStream_t s = c->stream;
+  float *dk = nullptr, *tmp = nullptr;
+  hipError_t e = c->pool.alloc((void**)&dk, t.size() * 4);
+  if (e == hipSuccess && sep) e = c->pool.alloc((void**)&tmp, (size_t)H * W * 12);
+  if (e == hipSuccess) e = put_table(c, dk, t);
+  if (e == hipSuccess) e = hipEventRecord(c->ev0, s);
+  if (e == hipSuccess) {
+    if (sep) {   // rows (1 x KW), then columns (KH x 1) with the USM epilogue against the original frame
+      e = ics_launch_img_conv_rows(src->d, H, W, dk, 1, KW, tmp, src->d, 0, 0.f, s);
+      if (e == hipSuccess) e = ics_launch_img_conv_cols(tmp, H, W, dk + KW, KH, (*out)->d, src->d, usm, amount, s);
+    } else if (cols_only) {
+      e = ics_launch_img_conv_cols(src->d, H, W, dk, KH, (*out)->d, src->d, usm, amount, s);
+    } else {
+      e = ics_launch_img_conv_rows(src->d, H, W, dk, KH, KW, (*out)->d, src->d, usm, amount, s);
+    }
+  }
+  if (e == hipSuccess) e = hipEventRecord(c->ev1, s);
+  if (e == hipSuccess) c->ev_pending = true;
+  c->pool.release(dk); c->pool.release(tmp);   // (queued work of this context runs on its one stream: so does whatever reuses the blocks)
+  if (e != hipSuccess) { ics_img_destroy(*out); *out = nullptr; return fail(e == hipErrorOutOfMemory ? ICS_ENOMEM : ICS_EHIP, "img_convolve: %s", hipGetErrorString(e)); }
+  return ICS_OK;
+}
+extern "C" int ics_img_convolve(const ics_img* src, const float* kern, int KH, int KW, ics_img** out) {
+  return img_conv_common(src, kern, KH, KW, 0, 0.f, out);
+}
+extern "C" int ics_img_usm(const ics_img* src, const float* kern, int KH, int KW, float amount, ics_img** out) {
+  return img_conv_common(src, kern, KH, KW, 1, amount, out);
+}
+
+extern "C" int ics_img_bilateral(const ics_img* src, int radius, float std_i, float std_s, ics_img** out) {
+  if (!src || !out) return fail(ICS_EINVAL, "NULL argument");
+  if (radius < 0) return fail(ICS_EINVAL, "radius %d", radius);
+  if (!(std_i > 0.f) || !(std_s > 0.f)) return fail(ICS_EINVAL, "std_i = %g, std_s = %g (both must be positive)", (double)std_i, (double)std_s);
+  if (radius > 4096 || ics_img_bilateral_lds(radius) > 160 * 1024) return fail(ICS_ENOSUP, "radius %d too large for the LDS tile (up to 34)", radius);
+  ics_ctx* c = src->ctx;
+  const int H = src->H, W = src->W, D = 2 * radius + 1;
+  std::vector<float> ws((size_t)D * D);   // x offset j slow, y offset i fast: the reference's offset order
+  for (int j = -radius; j <= radius; ++j)
+    for (int i = -radius; i <= radius; ++i) ws[(size_t)(j + radius) * D + (i + radius)] = (float)exp((double)(i * i + j * j) * (-1.0 / (2.0 * (double)std_s * (double)std_s)));
+  RC(img_new(c, H, W, out));
+  hipStream_t s = c->stream;
+  float* dws = nullptr;
+  hipError_t e = c->pool.alloc((void**)&dws, ws.size() * 4);
+  if (e == hipSuccess) e = put_table(c, dws, ws);
+  if (e == hipSuccess) e = hipEventRecord(c->ev0, s);
+  if (e == hipSuccess) e = ics_launch_img_bilateral(src->d, H, W, radius, (float)(-1.0 / (2.0 * (double)std_i * (double)std_i)), dws, (*out)->d, s);
+  if (e == hipSuccess) e = hipEventRecord(c->ev1, s);
+  if (e == hipSuccess) c->ev_pending = true;
+  c->pool.release(dws);
+  if (e != hipSuccess) { ics_img_destroy(*out); *out = nullptr; return fail(e == hipErrorOutOfMemory ? ICS_ENOMEM : ICS_EHIP, "img_bilateral: %s", hipGetErrorString(e)); }
   return ICS_OK;
 }
 

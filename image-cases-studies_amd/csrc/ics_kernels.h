@@ -251,3 +251,17 @@ hipError_t ics_launch_img_gamma(float* a, long n, float div, float exponent, flo
 hipError_t ics_launch_f32_to_f64(const float* in, double* out, long n, hipStream_t s);
 hipError_t ics_launch_int_to_f32(const void* in, int bytes_per_value, float* out, long n, hipStream_t s);   // uint8 / uint16 -> float32
 hipError_t ics_launch_f64_to_f32(const double* in, float* out, long n, hipStream_t s);
+
+// ---- lib/utils.py filters on device-resident images (ics_img_filters.hip): H x W x 3 float32, channels independent --------
+// `wr`: the kernel reversed on both axes.  rows: KH x KW taps on a 16-row tile (KH = 1: row pass of a rank-1 kernel; KH > 1: the
+// non-separable fallback); cols: KH x 1 taps on a 32-row tile.  usm: out = src0 + (src0 - conv) * amount.  *_lds: dynamic LDS
+// bytes of one workgroup (the launch fails above 160 KB).
+size_t ics_img_conv_rows_lds(int KH, int KW);
+size_t ics_img_conv_cols_lds(int KH);
+size_t ics_img_bilateral_lds(int radius);
+hipError_t ics_launch_img_conv_rows(const float* src, int H, int W, const float* wr, int KH, int KW, float* out, const float* src0, int usm,
+                                    float amount, hipStream_t s);
+hipError_t ics_launch_img_conv_cols(const float* src, int H, int W, const float* wr, int KH, float* out, const float* src0, int usm, float amount,
+                                    hipStream_t s);
+// ki = -1 / (2 std_i^2); ws: (2 radius + 1)^2 float32 spatial weights, x offset slow
+hipError_t ics_launch_img_bilateral(const float* src, int H, int W, int radius, float ki, const float* ws, float* out, hipStream_t s);

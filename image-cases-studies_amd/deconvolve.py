@@ -79,21 +79,25 @@ def mask_window(i, top, bottom, left, right):
 @utils.timeit
 def deblur_module(pic, filename, dest_path, blur_width, confidence=10, tolerance=1, quality="normal", bits=8,
                   mask=None, display=True, blur="static", preview=False, p=1, order=2, norm=1, priority=0, mask_size=255,
-                  iterations=200, refocus=False, pyramid=True, solver=None, save=True, device_resident=None):
+                  iterations=200, refocus=False, pyramid=True, solver=None, save=True, device_resident=None, sharpen=None):
     """deconvolve.py:65-368.  Extra keyword arguments (not in the reference): `pyramid=False` runs the
     single scale-1 level only, `solver` replaces `dc.richardson_lucy_MM` (tests record the calls),
     `save=False` returns the float image instead of writing the TIFF, `device_resident=True` keeps every frame in HBM
     from the first upload to the final download (`_deblur_device`; same arithmetic, same calls into the solver; the two
     paths differ by float32 `powf` of the gamma steps, numpy vs device: <= 2e-5 of the 16-bit range, tests/test_driver.py).
     Default (None): resident unless a `solver` is given or `display` asks for the matplotlib pop-up of the host frames --
-    2048^2, 15-px blur, 20 iterations: 0.085 s resident, 0.6-0.9 s with the frames on the host between the solver calls."""
+    2048^2, 15-px blur, 20 iterations: 0.085 s resident, 0.6-0.9 s with the frames on the host between the solver calls.
+    `sharpen=(radius, strength, amount)` or `(radius, strength, amount, method)`: `utils.USM` with these arguments on the
+    deblurred frame, in the gamma-encoded domain, immediately before the final clip to [0, 1] (the local contrast the
+    reference's README advises to add afterwards); on the resident path the frame is sharpened in HBM."""
+    sharpen = _sharpen_args(sharpen)
     if device_resident is None:
         device_resident = solver is None and not display
     if device_resident:
         if solver is not None:
             raise ValueError("device_resident=True runs the GPU solver; `solver` cannot be replaced")
         return _deblur_device(pic, filename, dest_path, blur_width, confidence, tolerance, quality, bits, mask, display, blur, preview, p,
-                              order, norm, priority, mask_size, iterations, refocus, pyramid, save)
+                              order, norm, priority, mask_size, iterations, refocus, pyramid, save, sharpen)
     rl = solver if solver is not None else dc.richardson_lucy_MM
     pic = np.ascontiguousarray(pic, dtype=np.float32)
     pic = pad_image(pic, (1, 1)).astype(np.float32)                       # :94
@@ -195,6 +199,8 @@ def deblur_module(pic, filename, dest_path, blur_width, confidence=10, tolerance
                     pass
     except KeyboardInterrupt:                                             # :338-342
         pass
+    if sharpen is not None:                                               # per channel, as a user of lib.utils would
+        deblured_image = np.dstack([utils.USM(deblured_image[..., c], *sharpen) for c in range(3)]).astype(np.float32)
     deblured_image = np.clip(deblured_image, 0., 1.)                      # :346
     deblured_image = deblured_image ** 2.2
     deblured_image = deblured_image * (2 ** 16 - 1)
@@ -212,6 +218,20 @@ def deblur_module(pic, filename, dest_path, blur_width, confidence=10, tolerance
     return deblured_image, psf
 
 
+def _sharpen_args(sharpen):
+    """`sharpen` of deblur_module -> None or (radius, strength, amount, method)"""
+    if sharpen is None:
+        return None
+    sharpen = tuple(sharpen)
+    if len(sharpen) == 3:
+        sharpen += ("bessel",)
+    if len(sharpen) != 4:
+        raise ValueError("sharpen takes (radius, strength, amount) or (radius, strength, amount, method), got %d values" % len(sharpen))
+    if sharpen[3] not in ("bessel", "gauss"):
+        raise ValueError("sharpen method %r (bessel or gauss)" % (sharpen[3],))
+    return sharpen
+
+
 def _level_shape(i, M, N):
     """deconvolve.py:232-243 -- odd size of pyramid level `i`"""
     temp_width, temp_height = int(np.floor(i * N)), int(np.floor(i * M))
@@ -223,7 +243,7 @@ def _level_shape(i, M, N):
 
 
 def _deblur_device(pic, filename, dest_path, blur_width, confidence, tolerance, quality, bits, mask, display, blur, preview, p, order, norm,
-                   priority, mask_size, iterations, refocus, pyramid, save):
+                   priority, mask_size, iterations, refocus, pyramid, save, sharpen=None):
     """`deblur_module` (deconvolve.py:65-368) with every frame resident in HBM: one upload of the picture,
     one download of the result; pad_image, gamma, the window views, the resize between pyramid levels and the solver all
     work on `lib._native.DeviceImage`s.  Line references as in `deblur_module` above."""
@@ -325,6 +345,9 @@ def _deblur_device(pic, filename, dest_path, blur_width, confidence, tolerance, 
             phases[case] = time.perf_counter() - t_case
     except KeyboardInterrupt:
         pass
+    if sharpen is not None:
+        deb, old = deb.usm(*sharpen), deb
+        old.close()
     deb.gamma(1.0, 2.2, 2 ** 16 - 1, clip01=True)                           # :346-352
     out = deb.to_host()
     deb.close()

@@ -154,6 +154,9 @@ def load():
     lib.ics_img_paste.argtypes = [vp, ci, ci, vp]
     lib.ics_img_gamma.argtypes = [vp, cf, cf, cf, ci]
     lib.ics_img_resize.argtypes = [vp, ci, ci, C.POINTER(vp)]
+    lib.ics_img_convolve.argtypes = [vp, vp, ci, ci, C.POINTER(vp)]
+    lib.ics_img_usm.argtypes = [vp, vp, ci, ci, cf, C.POINTER(vp)]
+    lib.ics_img_bilateral.argtypes = [vp, ci, cf, cf, C.POINTER(vp)]
     lib.ics_rl_upload_img.argtypes = [vp, vp, ci, ci, vp, ci, ci, vp]
     lib.ics_rl_download_img.argtypes = [vp, vp, ci, ci]
     lib.ics_group_create.argtypes = [ci, ci, ci, C.c_char_p, ci, C.POINTER(vp)]
@@ -175,6 +178,7 @@ def load():
                  "ics_rl_download", "ics_rl_run", "ics_rl_stage", "ics_rl_read", "ics_rl_write", "ics_rl_read_rows", "ics_rl_write_rows", "ics_rl_copy_rows", "ics_normalize_kernel",
                  "ics_tv", "ics_conv2d_symm", "ics_usm", "ics_bilateral", "ics_resize_bicubic", "ics_img_create", "ics_img_shape",
                  "ics_img_upload", "ics_img_upload_int", "ics_img_download", "ics_img_pad_edge", "ics_img_crop", "ics_img_paste", "ics_img_gamma", "ics_img_resize",
+                 "ics_img_convolve", "ics_img_usm", "ics_img_bilateral",
                  "ics_rl_upload_img", "ics_rl_download_img", "ics_group_create", "ics_group_info", "ics_group_barrier",
                  "ics_group_allreduce_max", "ics_group_allreduce_sum", "ics_group_describe", "ics_group_allgather"):
         getattr(lib, name).restype = ci
@@ -244,7 +248,8 @@ class Context:
         _check(load().ics_ctx_synchronize(self._h))
 
     def last_kernel_ms(self):
-        """device time of the kernels of the last blur / USM / bilateral call (transfers excluded)"""
+        """device time of the kernels of the last blur / USM / bilateral call (transfers excluded); after a DeviceImage filter,
+        which is only queued, this waits for its kernels"""
         ms = C.c_float(0)
         _check(load().ics_ctx_last_kernel_ms(self._h, C.byref(ms)))
         return ms.value
@@ -308,7 +313,8 @@ class Context:
 
 class DeviceImage:
     """ics_img: an H x W x 3 float32 image that lives in HBM (the frames `deconvolve.deblur_module` carries between two
-    richardson_lucy_MM calls).  Methods that return an image create a new one; `gamma` and `paste` work in place."""
+    richardson_lucy_MM calls).  Methods that return an image create a new one and leave this one untouched; `gamma` and `paste`
+    work in place."""
 
     def __init__(self, handle, ctx):
         self._h, self.ctx = handle, ctx
@@ -365,6 +371,36 @@ class DeviceImage:
 
     def gamma(self, div, exponent, mul=1.0, clip01=False):
         _check(load().ics_img_gamma(self._h, float(div), float(exponent), float(mul), int(bool(clip01))))
+
+    # ---- lib.utils filters, each channel on its own (csrc/ics_img_filters.hip); arguments as the lib.utils functions of the same name
+    @staticmethod
+    def _kern(kern):
+        kern = np.ascontiguousarray(kern, dtype=np.float32)
+        if kern.ndim != 2:
+            raise ValueError("expected a 2-D kernel, got shape %s" % (kern.shape,))
+        return kern
+
+    def convolve(self, kern):
+        """scipy.signal.convolve2d(channel, kern, mode="same", boundary="symm") on every channel"""
+        kern = self._kern(kern)
+        return self._new(load().ics_img_convolve, _ptr(kern), kern.shape[0], kern.shape[1])
+
+    def gaussian_blur(self, radius, amount):
+        from . import utils
+        return self.convolve(utils.gaussian_kernel(radius, amount))
+
+    def bessel_blur(self, radius, amount):
+        from . import utils
+        return self.convolve(utils.kaiser_kernel(radius, amount))
+
+    def usm(self, radius, strength, amount, method="bessel"):
+        """self + (self - blur(self, radius, strength)) * amount, the blur's last pass and the mask fused"""
+        from . import utils
+        kern = self._kern({"bessel": utils.kaiser_kernel, "gauss": utils.gaussian_kernel}[method](radius, strength))
+        return self._new(load().ics_img_usm, _ptr(kern), kern.shape[0], kern.shape[1], float(amount))
+
+    def bilateral(self, radius, std_i, std_s):
+        return self._new(load().ics_img_bilateral, int(radius), float(std_i), float(std_s))
 
     def close(self):
         if self._h:

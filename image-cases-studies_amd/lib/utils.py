@@ -14,7 +14,9 @@ Same names and argument meaning as the reference (file:line in /root/reference/l
     convolve(a, b, domain)                   :420-447   (FFT convolution; unused by the reference)
 
 The filters run on the GPU through libics_hip.so in float64 like the reference (scipy's
-convolve2d(mode="same", boundary="symm")); there is no CPU fallback for them.  The colour tools of
+convolve2d(mode="same", boundary="symm")); there is no CPU fallback for them.  Given a `lib._native.DeviceImage`
+(H x W x 3 float32 in HBM) instead of a 2-D array, the four filters work on it there, every channel on its own
+in float32, and return a new DeviceImage (csrc/ics_img_filters.hip): no transfer, no synchronisation.  The colour tools of
 the reference (Lagrange_interpolation, grey_point, auto_vibrance, overlay, blending) and its dead
 code (divTV, gradTVEM) are outside the deconvolution path and are not provided.
 
@@ -118,21 +120,29 @@ def _as2d(src):
 def bilateral_filter(source, radius, std_i, std_s, parallel=1):
     """lib/utils.py:194-234: symmetric padding by `radius`, all (2r+1)^2 offsets,
     w = gaussian(neighbour - source, std_i) * gaussian(distance, std_s), result = sum(neighbour*w)/sum(w)."""
+    if isinstance(source, _native.DeviceImage):
+        return source.bilateral(radius, std_i, std_s)
     return _native.Context.get().bilateral(_as2d(source), int(radius), float(std_i), float(std_s))
 
 
 def bessel_blur(src, radius, amount):
     """lib/utils.py:237-249: convolve2d(src, kaiser_kernel(radius, amount), mode="same", boundary="symm")"""
+    if isinstance(src, _native.DeviceImage):
+        return src.bessel_blur(radius, amount)
     return _native.Context.get().conv2d_symm(_as2d(src), kaiser_kernel(radius, amount))
 
 
 def gaussian_blur(src, radius, amount):
     """lib/utils.py:252-264: convolve2d(src, gaussian_kernel(radius, amount), mode="same", boundary="symm")"""
+    if isinstance(src, _native.DeviceImage):
+        return src.gaussian_blur(radius, amount)
     return _native.Context.get().conv2d_symm(_as2d(src), gaussian_kernel(radius, amount))
 
 
 def USM(src, radius, strength, amount, method="bessel"):
     """lib/utils.py:267-277: src + (src - blur(src, radius, strength)) * amount, fused on the device."""
+    if isinstance(src, _native.DeviceImage):
+        return src.usm(radius, strength, amount, method)
     kern = {"bessel": kaiser_kernel, "gauss": gaussian_kernel}[method](radius, strength)
     return _native.Context.get().usm(_as2d(src), kern, float(amount))
 

@@ -368,6 +368,19 @@ int ics_img_paste(ics_img *dst, int y0, int x0, const ics_img *src);
 int ics_img_gamma(ics_img *img, float div, float exponent, float mul, int clip01);
 /* deconvolve.py:245-249 on a device image (ics_resize_bicubic semantics, result rounded to float32) */
 int ics_img_resize(const ics_img *src, int OH, int OW, ics_img **out);
+/* The lib/utils.py filters on a device image, each channel on its own (the reference filters pic[..., i] one after the other):
+ * float32 arithmetic, FMA accumulation in a fixed order (two runs give identical bits).  Queued like the other ics_img_*
+ * operations: no synchronisation, the result comes from the context's pool; ics_ctx_last_kernel_ms afterwards waits for the
+ * kernels of the last one and returns their device time.
+ * convolve: scipy.signal.convolve2d(channel, kern, mode="same", boundary="symm") (lib/utils.py:237-264); kern: KH x KW float32,
+ *   row-major.  An outer product (every lib/utils.py window) runs as a row pass and a column pass, anything else as one
+ *   KH x KW pass; ICS_ENOSUP when tile + halo exceed the 160 KB of LDS (rank 1: KW > 764 or KH > 129; otherwise e.g. above 71 x 71).
+ * usm: src + (src - convolve(src, kern)) * amount (lib/utils.py:267-277), the epilogue of the last pass.
+ * bilateral: lib/utils.py:173-234, symmetric padding by `radius`, gaussian(x, s) = exp(-x^2 / (2 s^2)); ICS_ENOSUP when the
+ *   tile + halo exceed LDS (radius > 34). */
+int ics_img_convolve(const ics_img *src, const float *kern, int KH, int KW, ics_img **out);
+int ics_img_usm(const ics_img *src, const float *kern, int KH, int KW, float amount, ics_img **out);
+int ics_img_bilateral(const ics_img *src, int radius, float std_i, float std_s, ics_img **out);
 /* richardson_lucy_MM(image[iy:iy+M, ix:ix+N], u[uy:uy+uM, ux:ux+uN], psf, ...) with both windows taken from device
  * images (deconvolve.py:277-313 passes such views); psf is a host MK*MK*3 array as in ics_rl_upload. */
 int ics_rl_upload_img(ics_rl *job, const ics_img *image, int iy, int ix, const ics_img *u, int uy, int ux, const float *psf);

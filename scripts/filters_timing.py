@@ -1,19 +1,80 @@
-"""Timing of the lib/utils.py filters on one 4096 x 4096 float64 channel (GPU box): device time of the kernels (HIP events,
-ics_ctx_last_kernel_ms), wall time of the call including the two PCIe transfers of the 134 MB channel, and scipy's own
-convolve2d on the host for the blur."""
-import os, sys, time
+"""Timing of the lib/utils.py filters on one seeded SIZE x SIZE RGB float32 picture (GPU box), one JSON line:
+
+    python scripts/filters_timing.py [SIZE=4096]
+
+  resident   the filters on a DeviceImage in HBM (csrc/ics_img_filters.hip): device time of the kernels (HIP events around them,
+             ics_ctx_last_kernel_ms; warm, median of 25) and wall time of the queued call up to a stream synchronise
+  per_channel_f64   the path without DeviceImage: three utils.USM / utils.bilateral_filter calls on float64 channels taken from
+             the host -- their summed kernel time (Context.last_kernel_ms, transfers excluded) and their wall time including the
+             PCIe transfers (warm, median of 5)
+  separable  achieved bytes per second of the two-pass filters against their algorithmic bytes: 12 B/px per transit, 4 transits
+             for a blur (read src, write tmp, read tmp, write out), 5 for USM (the epilogue reads src again); also as a fraction
+             of the 8 TB/s HBM peak
+  checks     the resident USM must not take longer than the three float64 calls, in kernel time and in wall time (a guard against a
+             broken kernel, not a target); the exit status is 1 if one of them fails
+Starts no child process; a job script puts its own time limit around it."""
+import json
+import os
+import sys
+import time
+
 import numpy as np
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "image-cases-studies_amd"))
-from lib import _native, utils
-ctx = _native.Context.get()
-rng = np.random.default_rng(0)
-src = rng.random((4096, 4096))
-for name, fn in (("gaussian_blur(r=15, 2.5)", lambda: utils.gaussian_blur(src, 15, 2.5)), ("bessel_blur(r=31, 4.0)", lambda: utils.bessel_blur(src, 31, 4.0)),
-                 ("USM(r=15, bessel)", lambda: utils.USM(src, 15, 3.0, 0.7)), ("bilateral(r=5)", lambda: utils.bilateral_filter(src, 5, 0.1, 2.0)),
-                 ("bilateral(r=10)", lambda: utils.bilateral_filter(src, 10, 0.1, 4.0))):
-    fn()
-    t0 = time.perf_counter(); fn(); wall = time.perf_counter() - t0
-    print("%-28s device %.3f ms   call incl. transfers %.1f ms" % (name, ctx.last_kernel_ms(), wall * 1e3))
-from scipy.signal import convolve2d
-t0 = time.perf_counter(); convolve2d(src, utils.gaussian_kernel(15, 2.5), mode="same", boundary="symm"); print("scipy convolve2d 15x15 on the host: %.0f ms" % ((time.perf_counter() - t0) * 1e3))
+from lib import _native, utils  # noqa: E402
+
+HBM_PEAK = 8e12
+REPS_RESIDENT, REPS_F64 = 25, 5
+
+
+def main():
+    size = int(sys.argv[1]) if len(sys.argv) > 1 else 4096
+    ctx = _native.Context.get()
+    rng = np.random.default_rng(0)
+    pic = rng.random((size, size, 3), dtype=np.float32)
+    img = _native.DeviceImage.from_host(pic, ctx)
+    ops = {"usm_gauss15": lambda s: utils.USM(s, 15, 2.5, 0.7, method="gauss"),
+           "usm_bessel15": lambda s: utils.USM(s, 15, 3.0, 0.7, method="bessel"),
+           "bilateral_r5": lambda s: utils.bilateral_filter(s, 5, 0.1, 2.0),
+           "gaussian_blur15": lambda s: utils.gaussian_blur(s, 15, 2.5)}
+    res = {"size": size, "device": ctx.name, "resident": {}, "per_channel_f64": {}, "separable": {}}
+    for name, fn in ops.items():
+        fn(img).close()                                   # warm: code object, pool blocks
+        ctx.synchronize()
+        kernel, wall = [], []
+        for _ in range(REPS_RESIDENT):
+            t0 = time.perf_counter()
+            out = fn(img)
+            ctx.synchronize()
+            wall.append((time.perf_counter() - t0) * 1e3)
+            kernel.append(ctx.last_kernel_ms())
+            out.close()
+        res["resident"][name] = {"kernel_ms": round(float(np.median(kernel)), 4), "wall_ms": round(float(np.median(wall)), 4)}
+    chans = [np.ascontiguousarray(pic[..., c], dtype=np.float64) for c in range(3)]
+    for name, fn in ops.items():
+        if name == "gaussian_blur15":
+            continue
+        fn(chans[0])                                      # warm
+        kernel, wall = [], []
+        for _ in range(REPS_F64):
+            k = 0.0
+            t0 = time.perf_counter()
+            for ch in chans:
+                fn(ch)
+                k += ctx.last_kernel_ms()
+            wall.append((time.perf_counter() - t0) * 1e3)
+            kernel.append(k)
+        res["per_channel_f64"][name] = {"kernel_ms": round(float(np.median(kernel)), 4), "wall_ms": round(float(np.median(wall)), 4)}
+    for name, transits in (("gaussian_blur15", 4), ("usm_gauss15", 5), ("usm_bessel15", 5)):
+        nbytes = transits * 12 * size * size
+        rate = nbytes / (res["resident"][name]["kernel_ms"] * 1e-3)
+        res["separable"][name] = {"algorithmic_bytes": nbytes, "bytes_per_s": round(rate, -6), "fraction_of_8TBps": round(rate / HBM_PEAK, 4)}
+    res["checks"] = {"%s_%s" % (name, what): res["resident"][name][what] <= res["per_channel_f64"][name][what]
+                     for name in ("usm_gauss15", "usm_bessel15") for what in ("kernel_ms", "wall_ms")}
+    print(json.dumps(res))
+    return 0 if all(res["checks"].values()) else 1
+
+
+if __name__ == "__main__":
+    sys.exit(main())
