@@ -265,3 +265,12 @@ hipError_t ics_launch_img_conv_cols(const float* src, int H, int W, const float*
                                     hipStream_t s);
 // ki = -1 / (2 std_i^2); ws: (2 radius + 1)^2 float32 spatial weights, x offset slow
 hipError_t ics_launch_img_bilateral(const float* src, int H, int W, int radius, float ki, const float* ws, float* out, hipStream_t s);
+
+// ---- TV denoising of device-resident images (ics_img_tvdenoise.hip): Chambolle's dual iteration, tau = 1 / 8 ------------------
+// q: up to two frame pairs (qx, qy) of H x W x 3 floats each, q[0..1] and q[2..3], as many as ics_img_tv_pairs says; route 1: a
+// launch per iteration, 2: ICS_IMG_TV_BLOCK iterations per launch on an LDS tile; coupling 0: per channel, 1: one s per pixel.
+#define ICS_IMG_TV_BLOCK 4      // (== include/ics_hip.h)
+size_t ics_img_tv_block_lds();
+int ics_img_tv_pairs(int iterations, int route);
+hipError_t ics_launch_img_tv_denoise(const float* f, int H, int W, float weight, int iterations, int coupling, int route, float* const q[4],
+                                     float* out, hipStream_t s);

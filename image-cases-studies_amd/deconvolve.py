@@ -79,7 +79,7 @@ def mask_window(i, top, bottom, left, right):
 @utils.timeit
 def deblur_module(pic, filename, dest_path, blur_width, confidence=10, tolerance=1, quality="normal", bits=8,
                   mask=None, display=True, blur="static", preview=False, p=1, order=2, norm=1, priority=0, mask_size=255,
-                  iterations=200, refocus=False, pyramid=True, solver=None, save=True, device_resident=None, sharpen=None):
+                  iterations=200, refocus=False, pyramid=True, solver=None, save=True, device_resident=None, sharpen=None, denoise=None):
     """deconvolve.py:65-368.  Extra keyword arguments (not in the reference): `pyramid=False` runs the
     single scale-1 level only, `solver` replaces `dc.richardson_lucy_MM` (tests record the calls),
     `save=False` returns the float image instead of writing the TIFF, `device_resident=True` keeps every frame in HBM
@@ -89,15 +89,20 @@ def deblur_module(pic, filename, dest_path, blur_width, confidence=10, tolerance
     2048^2, 15-px blur, 20 iterations: 0.085 s resident, 0.6-0.9 s with the frames on the host between the solver calls.
     `sharpen=(radius, strength, amount)` or `(radius, strength, amount, method)`: `utils.USM` with these arguments on the
     deblurred frame, in the gamma-encoded domain, immediately before the final clip to [0, 1] (the local contrast the
-    reference's README advises to add afterwards); on the resident path the frame is sharpened in HBM."""
+    reference's README advises to add afterwards); on the resident path the frame is sharpened in HBM.
+    `denoise=(weight, iterations)` or `(weight, iterations, coupling)`: `utils.tv_denoise` with these arguments (coupling
+    "vector" unless given) on the deblurred frame, in the gamma-encoded domain, before `sharpen` and before the final clip:
+    Richardson-Lucy amplifies noise, and the total-variation denoiser removes it without blunting the restored edges; on the
+    resident path the frame stays in HBM."""
     sharpen = _sharpen_args(sharpen)
+    denoise = _denoise_args(denoise)
     if device_resident is None:
         device_resident = solver is None and not display
     if device_resident:
         if solver is not None:
             raise ValueError("device_resident=True runs the GPU solver; `solver` cannot be replaced")
         return _deblur_device(pic, filename, dest_path, blur_width, confidence, tolerance, quality, bits, mask, display, blur, preview, p,
-                              order, norm, priority, mask_size, iterations, refocus, pyramid, save, sharpen)
+                              order, norm, priority, mask_size, iterations, refocus, pyramid, save, sharpen, denoise)
     rl = solver if solver is not None else dc.richardson_lucy_MM
     pic = np.ascontiguousarray(pic, dtype=np.float32)
     pic = pad_image(pic, (1, 1)).astype(np.float32)                       # :94
@@ -199,6 +204,8 @@ def deblur_module(pic, filename, dest_path, blur_width, confidence=10, tolerance
                     pass
     except KeyboardInterrupt:                                             # :338-342
         pass
+    if denoise is not None:
+        deblured_image = utils.tv_denoise(np.ascontiguousarray(deblured_image, dtype=np.float32), *denoise)
     if sharpen is not None:                                               # per channel, as a user of lib.utils would
         deblured_image = np.dstack([utils.USM(deblured_image[..., c], *sharpen) for c in range(3)]).astype(np.float32)
     deblured_image = np.clip(deblured_image, 0., 1.)                      # :346
@@ -232,6 +239,25 @@ def _sharpen_args(sharpen):
     return sharpen
 
 
+def _denoise_args(denoise):
+    """`denoise` of deblur_module -> None or (weight, iterations, coupling)"""
+    if denoise is None:
+        return None
+    denoise = tuple(denoise)
+    if len(denoise) == 2:
+        denoise += ("vector",)
+    if len(denoise) != 3:
+        raise ValueError("denoise takes (weight, iterations) or (weight, iterations, coupling), got %d values" % len(denoise))
+    weight, iterations, coupling = denoise
+    if coupling not in ("channel", "vector"):
+        raise ValueError("denoise coupling %r (channel or vector)" % (coupling,))
+    if not (np.isfinite(weight) and weight > 0):
+        raise ValueError("denoise weight %r (must be positive and finite)" % (weight,))
+    if int(iterations) != iterations or iterations < 0:
+        raise ValueError("denoise iterations %r (a non-negative integer)" % (iterations,))
+    return float(weight), int(iterations), coupling
+
+
 def _level_shape(i, M, N):
     """deconvolve.py:232-243 -- odd size of pyramid level `i`"""
     temp_width, temp_height = int(np.floor(i * N)), int(np.floor(i * M))
@@ -243,7 +269,7 @@ def _level_shape(i, M, N):
 
 
 def _deblur_device(pic, filename, dest_path, blur_width, confidence, tolerance, quality, bits, mask, display, blur, preview, p, order, norm,
-                   priority, mask_size, iterations, refocus, pyramid, save, sharpen=None):
+                   priority, mask_size, iterations, refocus, pyramid, save, sharpen=None, denoise=None):
     """`deblur_module` (deconvolve.py:65-368) with every frame resident in HBM: one upload of the picture,
     one download of the result; pad_image, gamma, the window views, the resize between pyramid levels and the solver all
     work on `lib._native.DeviceImage`s.  Line references as in `deblur_module` above."""
@@ -345,6 +371,9 @@ def _deblur_device(pic, filename, dest_path, blur_width, confidence, tolerance, 
             phases[case] = time.perf_counter() - t_case
     except KeyboardInterrupt:
         pass
+    if denoise is not None:
+        deb, old = deb.tv_denoise(*denoise), deb
+        old.close()
     if sharpen is not None:
         deb, old = deb.usm(*sharpen), deb
         old.close()

@@ -85,6 +85,7 @@ def describe(M, N, MK, params):
 
 
 FRAME_LIMIT_BYTES = 1 << 31      # include/ics_hip.h ICS_FRAME_LIMIT_BYTES
+IMG_TV_BLOCK = 4                 # include/ics_hip.h ICS_IMG_TV_BLOCK: iterations per launch of the blocked TV denoise route
 
 
 def frame_bytes(M, N, MK):
@@ -157,6 +158,7 @@ def load():
     lib.ics_img_convolve.argtypes = [vp, vp, ci, ci, C.POINTER(vp)]
     lib.ics_img_usm.argtypes = [vp, vp, ci, ci, cf, C.POINTER(vp)]
     lib.ics_img_bilateral.argtypes = [vp, ci, cf, cf, C.POINTER(vp)]
+    lib.ics_img_tv_denoise.argtypes = [vp, cf, ci, ci, ci, C.POINTER(vp)]
     lib.ics_rl_upload_img.argtypes = [vp, vp, ci, ci, vp, ci, ci, vp]
     lib.ics_rl_download_img.argtypes = [vp, vp, ci, ci]
     lib.ics_group_create.argtypes = [ci, ci, ci, C.c_char_p, ci, C.POINTER(vp)]
@@ -178,7 +180,7 @@ def load():
                  "ics_rl_download", "ics_rl_run", "ics_rl_stage", "ics_rl_read", "ics_rl_write", "ics_rl_read_rows", "ics_rl_write_rows", "ics_rl_copy_rows", "ics_normalize_kernel",
                  "ics_tv", "ics_conv2d_symm", "ics_usm", "ics_bilateral", "ics_resize_bicubic", "ics_img_create", "ics_img_shape",
                  "ics_img_upload", "ics_img_upload_int", "ics_img_download", "ics_img_pad_edge", "ics_img_crop", "ics_img_paste", "ics_img_gamma", "ics_img_resize",
-                 "ics_img_convolve", "ics_img_usm", "ics_img_bilateral",
+                 "ics_img_convolve", "ics_img_usm", "ics_img_bilateral", "ics_img_tv_denoise",
                  "ics_rl_upload_img", "ics_rl_download_img", "ics_group_create", "ics_group_info", "ics_group_barrier",
                  "ics_group_allreduce_max", "ics_group_allreduce_sum", "ics_group_describe", "ics_group_allgather"):
         getattr(lib, name).restype = ci
@@ -401,6 +403,17 @@ class DeviceImage:
 
     def bilateral(self, radius, std_i, std_s):
         return self._new(load().ics_img_bilateral, int(radius), float(std_i), float(std_s))
+
+    def tv_denoise(self, weight=0.1, iterations=50, coupling="vector", route=0):
+        """TV (Rudin-Osher-Fatemi) denoising, min_u 1/2 |u - self|^2 + weight * TV(u): `iterations` steps of Chambolle's dual
+        projection with tau = 1/8, no early stop (csrc/ics_img_tvdenoise.hip; the algorithm is restated in tests/tv_denoise_ref.py).
+        coupling "channel": every channel on its own; "vector": one gradient magnitude per pixel, summed over the channels, so
+        the channels share their edges and chromatic noise is smoothed away.  route 0: the library's choice, 1: a launch per
+        iteration, 2: IMG_TV_BLOCK iterations per launch on LDS tiles; all give identical bits.  skimage's denoise_tv_chambolle
+        steps with tau = 1/4 and stops on an energy criterion; parity with it is unpinned (skimage is no dependency)."""
+        if coupling not in ("channel", "vector"):
+            raise ValueError("coupling %r (channel or vector)" % (coupling,))
+        return self._new(load().ics_img_tv_denoise, float(weight), int(iterations), int(coupling == "vector"), int(route))
 
     def close(self):
         if self._h:

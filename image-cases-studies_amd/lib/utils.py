@@ -16,7 +16,8 @@ Same names and argument meaning as the reference (file:line in /root/reference/l
 The filters run on the GPU through libics_hip.so in float64 like the reference (scipy's
 convolve2d(mode="same", boundary="symm")); there is no CPU fallback for them.  Given a `lib._native.DeviceImage`
 (H x W x 3 float32 in HBM) instead of a 2-D array, the four filters work on it there, every channel on its own
-in float32, and return a new DeviceImage (csrc/ics_img_filters.hip): no transfer, no synchronisation.  The colour tools of
+in float32, and return a new DeviceImage (csrc/ics_img_filters.hip): no transfer, no synchronisation; `tv_denoise` (not in the
+reference, csrc/ics_img_tvdenoise.hip) works on such an image or on an H x W x 3 array.  The colour tools of
 the reference (Lagrange_interpolation, grey_point, auto_vibrance, overlay, blending) and its dead
 code (divTV, gradTVEM) are outside the deconvolution path and are not provided.
 
@@ -123,6 +124,28 @@ def bilateral_filter(source, radius, std_i, std_s, parallel=1):
     if isinstance(source, _native.DeviceImage):
         return source.bilateral(radius, std_i, std_s)
     return _native.Context.get().bilateral(_as2d(source), int(radius), float(std_i), float(std_s))
+
+
+def tv_denoise(src, weight=0.1, iterations=50, coupling="vector"):
+    """Not in the reference's lib/utils.py (its README lists "TV denoise" among what may come): Rudin-Osher-Fatemi denoising
+    min_u 1/2 |u - src|^2 + weight * TV(u) by `iterations` steps of Chambolle's dual projection (tau = 1/8, no early stop) on the
+    device, float32.  coupling "vector" ties the three channels to one edge set, "channel" treats each on its own.  A
+    `lib._native.DeviceImage` gives a new DeviceImage (nothing crosses PCIe); an H x W x 3 array is uploaded once and the float32
+    result downloaded once.  Parity with skimage.restoration.denoise_tv_chambolle (tau = 1/4, energy stop) is unpinned."""
+    if isinstance(src, _native.DeviceImage):
+        return src.tv_denoise(weight, iterations, coupling)
+    arr = np.asarray(src)
+    if arr.ndim != 3 or arr.shape[2] != 3:
+        raise ValueError("expected a DeviceImage or an H x W x 3 array, got shape %s" % (arr.shape,))
+    img = _native.DeviceImage.from_host(np.ascontiguousarray(arr, dtype=np.float32))
+    try:
+        res = img.tv_denoise(weight, iterations, coupling)
+    finally:
+        img.close()
+    try:
+        return res.to_host()
+    finally:
+        res.close()
 
 
 def bessel_blur(src, radius, amount):

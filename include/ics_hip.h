@@ -381,6 +381,21 @@ int ics_img_resize(const ics_img *src, int OH, int OW, ics_img **out);
 int ics_img_convolve(const ics_img *src, const float *kern, int KH, int KW, ics_img **out);
 int ics_img_usm(const ics_img *src, const float *kern, int KH, int KW, float amount, ics_img **out);
 int ics_img_bilateral(const ics_img *src, int radius, float std_i, float std_s, ics_img **out);
+/* TV (Rudin-Osher-Fatemi) denoising of a device image: Chambolle's dual projection iteration for
+ * min_u 1/2 |u - src|^2 + weight * TV(u), a fixed number of iterations (no early stop), tau = 1/8 (the step Chambolle's proof
+ * covers; float32 rounding then does not grow with the iteration count).  q = (qx, qy) starts at 0 and per iteration
+ *   u = src + div q,  (div q)[y,x] = qx[y,x] - qx[y,x-1] + qy[y,x] - qy[y-1,x]  (terms with index -1 are 0)
+ *   gx = u[y,x+1] - u[y,x], gy = u[y+1,x] - u[y,x]  (0 in the last column / row),  s = gx^2 + gy^2
+ *   q = (q + tau g) / (1 + (tau / weight) sqrt(s))
+ * the result is src + div q; iterations = 0 copies src.  coupling 0 (channel): every channel on its own; 1 (vector): s is summed
+ * over the three channels and shared by them (one edge set for all channels: chromatic noise is not kept as colour edges).
+ * route 1: one launch per iteration; 2: ICS_IMG_TV_BLOCK iterations per launch on a tile in LDS; 0: the library's choice (see
+ * DESIGN.md).  The routes give identical bits, and so do two runs.  Queued like the other image filters (no synchronisation;
+ * ics_ctx_last_kernel_ms afterwards returns the device time of its kernels); src is not written.  ICS_EINVAL: weight <= 0 or
+ * not finite, iterations < 0, unknown coupling or route.  Not pinned against skimage.restoration.denoise_tv_chambolle (which
+ * steps with tau = 1/4). */
+#define ICS_IMG_TV_BLOCK 4
+int ics_img_tv_denoise(const ics_img *src, float weight, int iterations, int coupling, int route, ics_img **out);
 /* richardson_lucy_MM(image[iy:iy+M, ix:ix+N], u[uy:uy+uM, ux:ux+uN], psf, ...) with both windows taken from device
  * images (deconvolve.py:277-313 passes such views); psf is a host MK*MK*3 array as in ics_rl_upload. */
 int ics_rl_upload_img(ics_rl *job, const ics_img *image, int iy, int ix, const ics_img *u, int uy, int ux, const float *psf);

@@ -10,6 +10,10 @@
   separable  achieved bytes per second of the two-pass filters against their algorithmic bytes: 12 B/px per transit, 4 transits
              for a blur (read src, write tmp, read tmp, write out), 5 for USM (the epilogue reads src again); also as a fraction
              of the 8 TB/s HBM peak
+  tv_denoise DeviceImage.tv_denoise (csrc/ics_img_tvdenoise.hip), weight 0.1, 50 iterations, both couplings, route 1 (a launch per
+             iteration) and route 2 (4 iterations per launch on LDS tiles): kernel ms (median of 9) and GB/s on the model of
+             60 B/px per iteration (read q 24 + read f 12 + write q 24; 8 TB/s would be 0.126 ms per iteration at 4096^2);
+             "auto" names the route that route=0 takes at this size
   checks     the resident USM must not take longer than the three float64 calls, in kernel time and in wall time (a guard against a
              broken kernel, not a target); the exit status is 1 if one of them fails
 Starts no child process; a job script puts its own time limit around it."""
@@ -25,7 +29,8 @@ sys.path.insert(0, os.path.join(ROOT, "image-cases-studies_amd"))
 from lib import _native, utils  # noqa: E402
 
 HBM_PEAK = 8e12
-REPS_RESIDENT, REPS_F64 = 25, 5
+REPS_RESIDENT, REPS_F64, REPS_TV = 25, 5, 9
+TV_WEIGHT, TV_ITERATIONS = 0.1, 50
 
 
 def main():
@@ -70,6 +75,20 @@ def main():
         nbytes = transits * 12 * size * size
         rate = nbytes / (res["resident"][name]["kernel_ms"] * 1e-3)
         res["separable"][name] = {"algorithmic_bytes": nbytes, "bytes_per_s": round(rate, -6), "fraction_of_8TBps": round(rate / HBM_PEAK, 4)}
+    res["tv_denoise"] = {"weight": TV_WEIGHT, "iterations": TV_ITERATIONS, "model_bytes": 60 * size * size * TV_ITERATIONS}
+    for coupling in ("channel", "vector"):
+        for route in (1, 2, 0):
+            img.tv_denoise(TV_WEIGHT, TV_ITERATIONS, coupling, route=route).close()        # warm
+            ctx.synchronize()
+            kernel = []
+            for _ in range(REPS_TV):
+                out = img.tv_denoise(TV_WEIGHT, TV_ITERATIONS, coupling, route=route)
+                kernel.append(ctx.last_kernel_ms())
+                out.close()
+            ms = float(np.median(kernel))
+            res["tv_denoise"]["%s_%s" % (coupling, {1: "route1", 2: "route2", 0: "auto"}[route])] = {
+                "kernel_ms": round(ms, 4), "ms_per_iteration": round(ms / TV_ITERATIONS, 5),
+                "GBps_on_60B_model": round(res["tv_denoise"]["model_bytes"] / (ms * 1e-3) / 1e9, 1)}
     res["checks"] = {"%s_%s" % (name, what): res["resident"][name][what] <= res["per_channel_f64"][name][what]
                      for name in ("usm_gauss15", "usm_bessel15") for what in ("kernel_ms", "wall_ms")}
     print(json.dumps(res))
