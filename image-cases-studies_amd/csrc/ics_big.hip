@@ -4,7 +4,7 @@
 // are FFTs).  The tuned kernels of this library are compiled per size (matrix cores to 37, packed fp32 to 63); beyond that these
 // two kernels take the size at run time.  Plain fp32 FMA streams out of LDS -- built to be correct and to keep the arithmetic units
 // busy, not tuned per size: at 4096^2 a 65x65 convolution is 4.2e11 flop per pass.  Under ICS_CONV_AUTO they also serve the upper part
-// of the compiled range where they are the faster ones (ics_api.hip, resolve_route).
+// of the compiled range where they are the faster ones (ics_route.hip, resolve_route).
 //
 //   k_conv_big  : out[y, x, c] = sum_{a,b<K} W[a, b, c] * in[y + a - pad, x + b - pad, c]   (u-frame coordinates, as ics_conv.hip)
 //                 W = rot180(psf), out = error - image on the M x N interior (mode 0: pyx:477-488)
@@ -234,7 +234,7 @@ __global__ __launch_bounds__(256) void k_gradk_big(IcsGradkArgs a, GradkBig cfg)
 // ---- tap blocks on the matrix cores (PSF sizes 51 ... 127) ---------------------------------------------------------------------
 // A convolution is linear in its taps: the K x K PSF is cut into nblk x nblk blocks of Kb x Kb taps (Kb odd, 23 ... 33: sizes the
 // matrix-core convolution is built for), block (qa, qb) is convolved by k_conv_mfma<Kb> with the input pointer shifted by
-// (qa Kb + Kb/2 - pad, qb Kb + Kb/2 - pad), and the block results are added (ics_api.hip, do_conv_blocks).  This kernel packs the
+// (qa Kb + Kb/2 - pad, qb Kb + Kb/2 - pad), and the block results are added (ics_run.hip, do_conv_blocks).  This kernel packs the
 // block weight tables in the format k_psf packs the whole-PSF tables in (ics_common.h): one workgroup per block, both orientations.
 __global__ __launch_bounds__(256) void k_pack_blocks(const float* __restrict__ psf, int K, int Kb, int nblk, void* tconv, void* tcorr, size_t table_floats) {
   __shared__ uint32_t smax;
@@ -251,7 +251,7 @@ __global__ __launch_bounds__(256) void k_pack_blocks(const float* __restrict__ p
   uint32_t sb = 127u;
   if (m > 0.f && e != 255u) { sb = 268u - e; sb = sb > 240u ? 240u : sb; }
   const float s_w = __uint_as_float(sb << 23), inv_w = __uint_as_float((254u - sb) << 23);
-  // the residual's blocks are chained with alternating signs, the last one positive (ics_api.hip, do_conv_blocks)
+  // the residual's blocks are chained with alternating signs, the last one positive (ics_run.hip, do_conv_blocks)
   const float s_wc = ((nblk * nblk - 1 - (int)blockIdx.x) & 1) ? -s_w : s_w;
   _Float16* tc = reinterpret_cast<_Float16*>(reinterpret_cast<float*>(tconv) + (size_t)blockIdx.x * table_floats);
   _Float16* tr = reinterpret_cast<_Float16*>(reinterpret_cast<float*>(tcorr) + (size_t)blockIdx.x * table_floats);

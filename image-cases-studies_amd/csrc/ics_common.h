@@ -109,7 +109,7 @@ struct IcsDebug {
   std::atomic<int> pam_exact;         // ICS_PAM_EXACT         1 = the TV term of ALL three extended kinds (tv_mode 1, 2, 3) with IEEE sqrt / division per value
   std::atomic<int> fail_window_alloc; // (test hook)           n = the n-th allocation of the next ensure_window() fails once with ICS_ENOMEM
   std::atomic<int> pool_limit_mb;     // ICS_POOL_LIMIT_MB     cap of a context's cache of freed device blocks in MiB (-1: a quarter of the device memory; 0: no caching)
-  std::atomic<int> overlap;           // ICS_OVERLAP           0 = drain at every outer boundary, 1 (default) = statistics on a second stream where that measured ahead (resolve_route, ics_api.hip), 2 = second stream always
+  std::atomic<int> overlap;           // ICS_OVERLAP           0 = drain at every outer boundary, 1 (default) = statistics on a second stream where that measured ahead (resolve_route, ics_route.hip), 2 = second stream always
   std::atomic<int> fft_gradk;         // ICS_FFT_GRADK         0 = the FFT-tile pipeline takes its PSF gradient on the matrix cores (k_gradk_mfma on the mirrors) instead of on the tiles
   std::atomic<int> fft_fused;         // ICS_FFT_FUSED         0 = the FFT-tile pipeline runs A11 and A13 as two kernels (k_conv_fft<0> + k_gradk_fft) instead of the fused three-transform unit
   std::atomic<int> fft_conv2;         // ICS_FFT_CONV2         0 = the FFT-tile pipeline runs A1 and A3 as two kernels; 1 (default) = as one unit per tile pair (k_conv_fft<2>) for the PSF sizes it pays for; 2 = wherever it is built

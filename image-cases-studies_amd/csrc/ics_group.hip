@@ -12,7 +12,7 @@
 
 #include <hip/hip_runtime.h>
 
-#include "../../include/ics_hip.h"
+#include "ics_host.h"
 
 // the slice of rccl.h this file needs (ROCm 7.2 /opt/rocm/include/rccl/rccl.h: the NCCL 2.x ABI)
 namespace {
@@ -36,8 +36,6 @@ struct Rccl {
 };
 Rccl g_rccl = {};
 }  // namespace
-
-int ics_set_error(int code, const char* fmt, ...);   // ics_api.hip
 
 struct ics_group {
   int rank, world, device;
@@ -217,7 +215,7 @@ extern "C" int ics_group_describe(const ics_group* g, int* backend, int* nranks,
 // Point-to-point rows between the frames of two band jobs on different ranks (lib/banded.py, rank mode): `count` floats from
 // device pointer `send` to rank send_peer and / or into `recv` from rank recv_peer (peer < 0: that side is absent), one
 // ncclGroup so that neighbours exchanging both ways cannot deadlock.  The caller has drained the stream that produced `send`;
-// the call returns when the transfer is complete.  (ics_rl_exchange_rows in ics_api.hip resolves frame rows to pointers.)
+// the call returns when the transfer is complete.  (ics_rl_exchange_rows in ics_job.hip resolves frame rows to pointers.)
 int ics_group_sendrecv_device(ics_group* g, const float* send, size_t send_count, int send_peer, float* recv, size_t recv_count, int recv_peer) {
   if (!g) return ics_set_error(ICS_EINVAL, "group is NULL");
   if (g->local) return ics_set_error(ICS_ESTATE, "a one-rank local group has no peers");
@@ -235,7 +233,7 @@ int ics_group_sendrecv_device(ics_group* g, const float* send, size_t send_count
 }
 
 // In-place all-reduce of a DEVICE buffer on the caller's stream (no staging, no host synchronisation): the step-size keys and the
-// PSF-gradient sums of the row-band split (ics_rl_allreduce_keys / ics_rl_allreduce_gradk in ics_api.hip).  kind: 0 = uint32 max,
+// PSF-gradient sums of the row-band split (ics_rl_allreduce_keys / ics_rl_allreduce_gradk in ics_job.hip).  kind: 0 = uint32 max,
 // 1 = float64 sum.  A local one-rank group has nothing to do.
 int ics_group_allreduce_device(ics_group* g, void* buf, size_t count, int kind, hipStream_t stream) {
   if (!g || !buf) return ics_set_error(ICS_EINVAL, "NULL argument");

@@ -11,7 +11,7 @@
 //     acc[ ((((tile * 4 + cb) * 3 + ch) * RS + t) * 64 + lane) * 4 + r ]
 // i.e. one aligned float4 per lane, 1 KiB contiguous per wave instruction, 3 RS loads per tile instead of 4 RS (dwordx3) or 8 RS.
 // `image` is constant during a run in the shipped loop (pyx:545-549 subtract exactly 0; only tv_mode 1 writes it): the copy is
-// made once per upload (ics_api.hip, ensure_image_acc) and costs one frame read + one frame write.
+// made once per upload (ics_job.hip, ensure_image_acc) and costs one frame read + one frame write.
 #pragma once
 #include "ics_common.h"
 

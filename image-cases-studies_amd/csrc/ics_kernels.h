@@ -231,6 +231,7 @@ hipError_t ics_launch_stats(const IcsStatsArgs& a, hipStream_t s);
 hipError_t ics_launch_hasnan(const float* u, const IcsGeom& g, int* flag, hipStream_t s);
 
 // ---- standalone operators ----------------------------------------------------------------------
+hipError_t ics_launch_normalize(float* kern, int K, hipStream_t s);   // [K][K][3] in place: negatives clamped, each channel divided by its sum
 hipError_t ics_launch_tv(const float* u, int M, int N, float eps, int order, int norm, float* out, float* div, hipStream_t s);
 // one LDS-tiled pass: out = conv2d_symm(src, kern); usm: out = src0 + (src0 - conv) * amount (lib/utils.py:275)
 hipError_t ics_launch_conv2d_symm(const double* src, int H, int W, const double* kern, int KH, int KW, double* out,

@@ -625,7 +625,7 @@ __global__ __launch_bounds__(64 * NW) void k_gradk(IcsGradkArgs a) {
 // partial block (two cache lines per instruction, eight in flight); the 16 waves of the workgroup take the blocks 16 apart and
 // their sums meet in LDS in wave order.  (Round 3: 8.1 -> ~4 us; 32 lanes per output at a 3 KB stride fetched a line per lane.)
 // (La x Lb valid taps of the block land at (a0, b0) of the Kf x Kf gradient: the whole gradient is La = Lb = Kf, a0 = b0 = 0; the
-//  split gradient of PSF sizes 33 ... 49 reduces four tap blocks, ics_api.hip)
+//  split gradient of PSF sizes 33 ... 49 reduces four tap blocks, ics_run.hip)
 __global__ __launch_bounds__(1024) void k_gradk_reduce(const float* __restrict__ partial, int nblocks, float* __restrict__ gradk, int NT, int La, int Lb,
                                                       int Kf, int a0, int b0) {
   __shared__ double sh[16][64];
@@ -1157,5 +1157,27 @@ hipError_t ics_launch_psf(const IcsPsfArgs& a, hipStream_t s) {
   } else {
     hipLaunchKernelGGL(k_psf<false>, dim3(1), dim3(ICS_PSF_THREADS), (size_t)3 * a.K * a.K * sizeof(float), s, a);
   }
+  return hipGetLastError();
+}
+
+// ---- standalone operator: PSF normalisation (ics_normalize_kernel, ics_ops.hip) -----------------------------------------------
+namespace {
+// lib/deconvolution.pyx:47-70: clamp negatives, divide each channel by its sequential float32 sum
+__global__ __launch_bounds__(256) void k_normalize(float* kern, int K) {
+  __shared__ float ssum[4];
+  const int n = 3 * K * K, tid = threadIdx.x;
+  for (int i = tid; i < n; i += 256) if (kern[i] < 0.f) kern[i] = 0.f;
+  __syncthreads();
+  if (tid < 3) {
+    float s = 0.f;
+    for (int i = 0; i < K * K; ++i) s = __fadd_rn(s, kern[3 * i + tid]);
+    ssum[tid] = s;
+  }
+  __syncthreads();
+  for (int i = tid; i < n; i += 256) kern[i] = __fdiv_rn(kern[i], ssum[i % 3]);
+}
+}  // namespace
+hipError_t ics_launch_normalize(float* kern, int K, hipStream_t s) {
+  hipLaunchKernelGGL(k_normalize, dim3(1), dim3(256), 0, s, kern, K);
   return hipGetLastError();
 }

@@ -1,5 +1,5 @@
 // ics_planar.hip -- channel-planar mirrors of the job's frames (ics_common.h: ics_ppitch, ics_plane_floats) for the FFT-tile pipeline
-// (ics_conv_fft.hip; ics_api.hip "planar pipeline").
+// (ics_conv_fft.hip; ics_job.hip "FFT-tile pipeline: mirrors").
 //
 // The overlap-save FFT convolution works on one channel of a tile pair at a time; from HWC frames every access touches 4 of each 12 bytes
 // and a work unit pulls three times its useful cache lines through the CU's miss path (measured: 30 k of a unit's 70 k shader clocks in the

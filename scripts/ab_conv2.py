@@ -1,5 +1,5 @@
 """A/B of mode 2 of the transform tiles (A1 + A3 as one unit per tile pair, k_conv_fft<2>) against the two kernels, per (frame size, PSF size):
-ms per inner iteration with conv = ICS_CONV_FFT, debug switch fft_conv2 = 0 / 2 -- what ICS_CONV2_MAX_K (csrc/ics_api.hip) is set from.
+ms per inner iteration with conv = ICS_CONV_FFT, debug switch fft_conv2 = 0 / 2 -- what ICS_CONV2_MAX_K (csrc/ics_route.hip) is set from.
 Run on the GPU box:    python scripts/ab_conv2.py [size,psf ...]"""
 import os
 import sys

@@ -1,5 +1,5 @@
 """A/B of the convolution paths per (frame size, PSF size): ms per inner iteration with the matrix-core kernels (conv = 2) and with the
-transform tiles (conv = 3), blind and non-blind -- what `fft_preferred` (csrc/ics_api.hip) is set from.  Run on the GPU box:
+transform tiles (conv = 3), blind and non-blind -- what `fft_preferred` (csrc/ics_route.hip) is set from.  Run on the GPU box:
     python scripts/ab_fft.py [size,psf ...]"""
 import os
 import sys

@@ -1,6 +1,6 @@
 """Whole-call cases keyed by the kernel route they run on (no device needed to build the list or to route it).
 
-resolve_route (csrc/ics_api.hip) picks, per run, the convolution family, the PSF-gradient family, the fp16 split and the accumulator-order
+resolve_route (csrc/ics_route.hip) picks, per run, the convolution family, the PSF-gradient family, the fp16 split and the accumulator-order
 image copy; tests/golden/route_table.json names every route it can return.  This module builds a seeded, deterministic list of whole
 richardson_lucy_MM calls, each with the debug switches it sets, and records the route `lib._native.describe` returns for it.
 tests/test_route_coverage.py checks that every route of the table has a case; tests/test_gpu_route_matrix.py runs every case against the
@@ -21,7 +21,7 @@ SWITCH_DEFAULTS = {"conv_path": 0, "small_iter": 1, "fused_gradk": 1, "fft_gradk
                    "planar_image": 1, "fused_rs": 0, "max_wgs": 0, "overlap": 1}
 VARIANTS = ("plain", "black_top", "black_left", "black_bottom", "scaled", "flat")     # scripts/dbg/fuzz_runs.py's data variants
 FFT_P = 128            # transform tile edge (csrc/ics_conv_fft.hip ICS_FFT_P)
-CONV2_MAX_K = 25       # csrc/ics_api.hip ICS_CONV2_MAX_K: A1 + A3 as one unit up to this PSF size
+CONV2_MAX_K = 25       # csrc/ics_route.hip ICS_CONV2_MAX_K: A1 + A3 as one unit up to this PSF size
 FFT_MAX_K = 85         # csrc/ics_conv_fft.hip ICS_FFT_MAX_K: one tile per PSF up to here, tap blocks above
 TILE = 64              # csrc/ics_common.h ICS_TILE
 FLAG_NO_FUSED_GRADK = 1

@@ -184,7 +184,7 @@ def test_blind_bands_match_one_job(bands, conv):
 @pytest.mark.gpu
 @pytest.mark.parametrize("MK,M,N", [(65, 330, 150), (99, 420, 140), (129, 500, 150)])
 def test_blind_bands_with_tap_block_psf_sizes_match_one_job(MK, M, N):
-    """PSF sizes that run as tap blocks (csrc/ics_api.hip do_conv_blocks: 4, 9 and 16 blocks -- the chain of the residual's blocks starts
+    """PSF sizes that run as tap blocks (csrc/ics_run.hip do_conv_blocks: 4, 9 and 16 blocks -- the chain of the residual's blocks starts
     from the negated image of EACH band job for the even counts), two bands against the single job."""
     case = orc.synth_case(M, N, MK, seed=MK, blind=True)
     win = (M // 2 - 40, M // 2 + 41, 20, N - 20)

@@ -48,7 +48,7 @@ def test_labels_follow_the_library_routing(MK, blind):
 
 def test_route_switches():
     from lib import _native as nv
-    # transform tiles under AUTO (csrc/ics_api.hip fft_preferred, measured with scripts/ab_fft.py; round 6, with A11 + A13 and A1 + A3 fused on the tiles):
+    # transform tiles under AUTO (csrc/ics_route.hip fft_preferred, measured with scripts/ab_fft.py; round 6, with A11 + A13 and A1 + A3 fused on the tiles):
     # 19 x 19 ... 65 x 65 from 1.5 Mpx (blind: 1 Mpx), 17 x 17 from 4 Mpx (blind: 2 Mpx), 15 x 15 from 4 Mpx (blind: 6 Mpx), 9 x 9 ... 13 x 13 from 6 Mpx, smaller from 12 Mpx
     assert _route(4096, 17, True).conv_family == 5 and _route(4096, 17, False).conv_family == 5
     assert _route(2048, 17, True).conv_family == 5 and _route(2048, 17, False).conv_family == 5 and _route(1024, 17, True).conv_family == 1

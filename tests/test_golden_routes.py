@@ -1,6 +1,6 @@
 """Which kernel families the whole-loop reference fixtures reach under ICS_CONV_AUTO (CPU only: ics_describe needs no device).
 
-AUTO's thresholds (csrc/ics_api.hip: the small-frame kernel, fft_preferred) decide which family a fixture exercises when a GPU
+AUTO's thresholds (csrc/ics_route.hip: the small-frame kernel, fft_preferred) decide which family a fixture exercises when a GPU
 test runs it with conv=0.  When they moved in round 6 the fp16-split matrix cores (conv family 1) silently lost most of their
 whole-loop coverage.  This pins it: if a threshold moves and a family or a PSF size drops out, the fix is a forced `conv`
 parametrisation or a new fixture (oracle/make_golden_levels.py), not lost coverage."""

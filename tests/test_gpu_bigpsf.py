@@ -91,7 +91,7 @@ def _fft64(a, b, mode):
 @pytest.mark.parametrize("conv", [0, 2, 3])
 @pytest.mark.parametrize("MK,M,N", [(129, 140, 150), (133, 64, 200), (191, 33, 300), (255, 90, 70), (255, 300, 280)])
 def test_psf_129_to_255_stages_against_float64(MK, M, N, conv):
-    """PSF sizes above 127 (csrc/ics_api.hip psf_blocks_only): convolutions as up to 8 x 8 blocks of <= 33 x 33 taps, the gradient as up
+    """PSF sizes above 127 (csrc/ics_route.hip psf_blocks_only): convolutions as up to 8 x 8 blocks of <= 33 x 33 taps, the gradient as up
     to 9 x 9 blocks of <= 31 x 31, nothing else behind them.  Against float64 FFT products (direct float64 sums of 65 025 taps per
     output value take minutes in numpy; a float64 FFT is exact to ~1e-15 of the largest value), same gates as the sizes below."""
     from lib import _native as nv
@@ -182,7 +182,7 @@ def test_big_psf_refusals():
 
 @pytest.mark.parametrize("MK", [45, 51, 59, 63])
 def test_auto_path_above_37_against_the_kernels_compiled_per_size(MK):
-    """ICS_CONV_AUTO (csrc/ics_api.hip): matrix-core kernels to 49 x 49, ics_big.hip (resolve_route) above; ICS_CONV_VECTOR keeps the
+    """ICS_CONV_AUTO (csrc/ics_route.hip): matrix-core kernels to 49 x 49, ics_big.hip (resolve_route) above; ICS_CONV_VECTOR keeps the
     packed-fp32 kernels compiled per size.  Both against float64 direct sums with the same gate, and against each other."""
     from lib import _native as nv
     M, N = 70 + MK, 131
@@ -214,7 +214,7 @@ def test_auto_path_above_37_against_the_kernels_compiled_per_size(MK):
 
 @pytest.mark.parametrize("MK,M,N", [(33, 97, 140), (39, 150, 131), (45, 70, 200), (47, 129, 129), (49, 160, 90)])
 def test_split_matrix_core_gradient_33_to_49(MK, M, N):
-    """csrc/ics_api.hip do_gradk_split: the K x K taps as four blocks (rows / columns [0, 31) and [31, K)) on the 31 x 31 / 15 x 15
+    """csrc/ics_run.hip do_gradk_split: the K x K taps as four blocks (rows / columns [0, 31) and [31, K)) on the 31 x 31 / 15 x 15
     fp16-split kernel with shifted frame pointers.  Against float64 direct sums (the gate of every gradient kernel) and against the
     fp32-MFMA kernel (conv = ICS_CONV_VECTOR) on the same inputs."""
     from lib import _native as nv

@@ -1,4 +1,4 @@
-"""Host runtime of ics_rl_run (csrc/ics_api.hip), round 4: the abort channel of the progress callback (ABI 4), one hipGraph
+"""Host runtime of ics_rl_run (csrc/ics_run.hip), round 4: the abort channel of the progress callback (ABI 4), one hipGraph
 submission per outer iteration on small frames, recovery from a failed stats-window allocation, ics_rl_describe."""
 import contextlib
 import io

@@ -1,6 +1,6 @@
 """The routing table of ics_describe, pinned field by field (CPU only: ics_describe needs no device).
 
-Every kernel family a run launches is decided by one function of csrc/ics_api.hip (resolve_route).  This sweep covers the regimes
+Every kernel family a run launches is decided by one function of csrc/ics_route.hip (resolve_route).  This sweep covers the regimes
 that function separates -- the small-frame kernel, the matrix cores, the transform tiles, tap blocks, the run-time-sized kernels and
 the edge where the planar mirrors stop fitting 2 GiB (18784 x 9256 / 33) -- over blind / non-blind, params.conv 0-3, tv_mode 0-3, fuse,
 ICS_FLAG_NO_FUSED_GRADK and the routing switches, and compares every field of ics_rl_route (or the error code, where describe refuses
