@@ -3,7 +3,10 @@
 //   mode 0 (A1+A2 / A11, lib/deconvolution.pyx:477-488, 555-565):  error = convolve(u, psf, "valid") - image
 //   mode 1 (A3, pyx:490-491):  gradu = convolve(error, rot180(psf), "full")  (+ the reductions of A7, pyx:523-524)
 //   mode 2 (A1+A2+A3 in one unit, round 6):  gradu straight from u and the image -- interior tiles never leave the frequency domain,
-//                                             G = S1 (16384 S0 T - F) with F = the image windows' spectra (k_fft_image_spectrum); see tile_is_border
+//                                             G = S1 (16384 S0 T - F) with F = the image windows' spectra (k_fft_image_spectrum); see tile_is_border.
+//                                             Its tiles are 128 - 2 K + 2 pixels a side and cover the whole u-frame; the last tile of an axis also stores
+//                                             the up to 2 pad rows / columns of the pad ring behind it where that saves a tile row / column (tile_rows;
+//                                             4096^2 / 15: 41 x 41 tiles instead of 42 x 42, 2523 units = ten rounds on 256 workgroups instead of eleven)
 //   k_synth_gradk_fft (A11+A12+A13 in one unit, round 6), k_gradk_fft (A12+A13), k_fft_spectrum (the weight spectra): further down
 //
 // The reference computes both with scipy's complex64 FFT over the whole frame (pyx:478,491 -> scipy.signal.fftconvolve); here the frame is
@@ -42,6 +45,7 @@
 #include "ics_kernels.h"
 #include "ics_tw128.h"
 #include <algorithm>
+#include <cassert>
 #include <mutex>
 #include <vector>
 
@@ -257,6 +261,8 @@ struct IcsFftArgs {
   int Vy;               // valid output ROWS per tile = 128 - K + 1: rows need no rounding to quads, and two more rows per tile save a whole round of
                         // units at some sizes (6144^2 / 31 x 31 back-projection: 65 x 65 tiles -> 63 x 65 = exactly 24 units per CU instead of 24.8)
   int tiles_x, ntiles, nunits;
+  int ext_y, ext_x;     // mode 2: the LAST tile row / column stores this many output rows / columns beyond its Vy / V, up to 2 pad -- the strip of the
+                        // pad ring that would otherwise take a tile row / column of its own (tile_rows).  0 everywhere else
   unsigned long long tiles_x_magic;   // floor(2^32 / tiles_x) + 1 (33 bits for tiles_x = 1): the unit decode divides by a multiply
   int oy0, ox0, oy1, ox1;   // output region in u-frame coordinates (mode 0: the M x N interior; mode 1: the whole u-frame)
   int gx0;                  // first column of the tile grid: ox0 rounded down to a multiple of 4, so that every 16-byte access of a plane row
@@ -294,6 +300,27 @@ ICS_FFT_HD Unit decode_unit(const IcsFftArgs& a, int n) {
     u.oy[t] = a.oy0 + ty * a.Vy; u.ox[t] = a.gx0 + tx * a.V;
   }
   return u;
+}
+
+// Output rows / columns tile (oy, ox) stores: Vy x V, cut at the region's far edge -- and, mode 2, the last tile of an axis goes on for
+// ext more.  Such a tile is one of the outer ring (oy + Vy >= M: fill_args), it takes both transform pairs with residual_window between
+// them, and then the second pair's outputs Vy .. Vy + ext - 1 are as good as the first Vy: they read the residual at buffer rows up to
+// Vy + ext - 1 + 2 pad <= 127 -- no wrap-around -- and what they read beyond row Vy + 2 pad, where the first pair's wrap-around begins, lies
+// at u-frame rows >= oy + Vy + pad >= pad + M, outside the interior, where residual_window has written the zeros that belong there.
+ICS_FFT_HD int tile_rows(const IcsFftArgs& a, int oy) {
+  const int rem = a.oy1 - oy;
+  return rem <= a.Vy + a.ext_y ? rem : a.Vy;
+}
+ICS_FFT_HD int tile_cols(const IcsFftArgs& a, int ox) {
+  const int rem = a.ox1 - ox;
+  return rem <= a.V + a.ext_x ? rem : a.V;
+}
+// (wave-uniform) a tile of the unit reaches beyond the output region's columns, or stops short of a quad's end: per-pixel column tests.
+// (EXT = false, here and in quad_lane: the kernels whose geometry never has an extension keep the plain Vy x V forms and do not read ext --
+//  they are at the end of their registers as it is)
+template <bool EXT> ICS_FFT_HD bool unit_is_edge(const IcsFftArgs& a, const Unit& u) {
+  if (EXT) return u.ox[0] < a.ox0 || tile_cols(a, u.ox[0]) != a.V || u.ox[1] < a.ox0 || tile_cols(a, u.ox[1]) != a.V;
+  return u.ox[0] < a.ox0 || u.ox[0] + a.V > a.ox1 || u.ox[1] < a.ox0 || u.ox[1] + a.V > a.ox1;
 }
 
 // walk position k -> unit (positions beyond the list stay beyond it: their accesses are dropped)
@@ -683,11 +710,12 @@ ICS_FFT_HD void maxima_keys(const Maxima& mx, uint32_t& kg, uint32_t& ku) {
 }
 
 // lane address of row group 0 of tile t in frame layout L, or ICS_FFT_NONE; `rows` = number of this lane's row groups inside the tile (0..4)
+template <bool EXT = false>
 ICS_FFT_HD int quad_lane(const IcsFftArgs& a, const Unit& u, const Lay& L, int tid, int t, int& rows, int& X) {
   const int r0 = tid >> 5, xq = tid & 31;
-  const int lim = a.oy1 - u.oy[t] < a.Vy ? a.oy1 - u.oy[t] : a.Vy;      // output rows of this tile
+  const int lim = EXT ? tile_rows(a, u.oy[t]) : (a.oy1 - u.oy[t] < a.Vy ? a.oy1 - u.oy[t] : a.Vy);      // output rows of this tile
   X = u.ox[t] + 4 * xq;
-  const bool ok = u.has[t] && 4 * xq < a.V && X < a.ox1 && r0 < lim;
+  const bool ok = EXT ? (u.has[t] && 4 * xq < tile_cols(a, u.ox[t]) && r0 < lim) : (u.has[t] && 4 * xq < a.V && X < a.ox1 && r0 < lim);
   rows = ok ? (lim - r0 + 31) >> 5 : 0;                                // row groups i with r0 + 32 i < lim
   return ok ? L.org + (u.oy[t] + r0) * L.pitch + X + L.cmul * u.c : ICS_FFT_NONE;
 }
@@ -713,10 +741,10 @@ ICS_FFT_HD void load_image_rows(const IcsFftArgs& a, const Mem& mem, const Unit&
 }
 // mode 1: the operands under tile t.  The PAM kinds (build-defined tv_mode 2 / 3; ics_conv.hip's epilogue for them) need u and the TV
 // term T = -div(p) instead of u and ut: two operand frames either way (a third does not fit 128 registers).
-template <bool TV>
+template <bool TV, bool EXT = false>
 ICS_FFT_HD void load_ops(const IcsFftArgs& a, const Mem& mem, const Unit& u, int tid, int t, Ops& o, int i0 = 0, int i1 = 4) {
   int rows, X;
-  const int va = quad_lane(a, u, mem.lu, tid, t, rows, X);   // (the same geometry: all frames of a job are)
+  const int va = quad_lane<EXT>(a, u, mem.lu, tid, t, rows, X);   // (the same geometry: all frames of a job are)
   const bool pam = TV && a.c.tv_kind >= 2;
 #pragma unroll
   for (int i = i0; i < i1; ++i) {
@@ -781,7 +809,7 @@ ICS_FFT_HD void residual_quads(const IcsFftArgs& a, const Mem& mem, const QuadOu
 // tiles of the outer ring take both transforms pairs, with the mask in between (`border`).  u-frame coordinates.
 ICS_FFT_HD bool tile_is_border(const IcsFftArgs& a, int oy, int ox) {
   const IcsGeom& g = a.c.g;
-  return oy - g.pad < g.pad || oy + a.Vy + g.pad > g.pad + g.M || ox - g.pad < g.pad || ox + a.V + g.pad > g.pad + g.N;
+  return oy - g.pad < g.pad || oy + tile_rows(a, oy) + g.pad > g.pad + g.M || ox - g.pad < g.pad || ox + tile_cols(a, ox) + g.pad > g.pad + g.N;
 }
 ICS_FFT_HD bool unit_is_border(const IcsFftArgs& a, const Unit& u) {
   return tile_is_border(a, u.oy[0], u.ox[0]) || (u.has[1] && tile_is_border(a, u.oy[1], u.ox[1]));
@@ -969,8 +997,8 @@ __global__ __launch_bounds__(ICS_FFT_THREADS) void k_conv_fft(IcsFftArgs a) {
     Ops ops;
     if (MODE == 0) load_image(a, mem, u, opaque(tid), fimg);
     else {
-      load_ops<TV>(a, mem, u, opaque(tid), 0, ops);
-      load_ops<TV>(a, mem, u, opaque(tid), 1, ops, 0, 1);   // (stages F and G leave registers for the first row group of tile 1's operands)
+      load_ops<TV, MODE == 2>(a, mem, u, opaque(tid), 0, ops);
+      load_ops<TV, MODE == 2>(a, mem, u, opaque(tid), 1, ops, 0, 1);   // (stages F and G leave registers for the first row group of tile 1's operands)
     }
     lds_barrier();
     stage_b<-1>(lds, opaque(tid));
@@ -980,7 +1008,7 @@ __global__ __launch_bounds__(ICS_FFT_THREADS) void k_conv_fft(IcsFftArgs a) {
     // row-quad epilogue, row group by row group (at most one group's raw values alive beside the operands).  Mode 1 has two operand
     // frames: it requests those of the second tile here and takes its maxima in a second pass, and the second tile of the next unit's
     // window goes out between the passes (registers: 128 per thread with 1024 of them).
-    if (MODE >= 1) load_ops<TV>(a, mem, u, opaque(tid), 1, ops, 1, 4);
+    if (MODE >= 1) load_ops<TV, MODE == 2>(a, mem, u, opaque(tid), 1, ops, 1, 4);
     Maxima mx; maxima_init(mx);
     v4f res[4][2];
     // lane address and row-group count of the two tiles ONCE per unit (as eight store_quad calls the address arithmetic of the epilogue
@@ -989,8 +1017,8 @@ __global__ __launch_bounds__(ICS_FFT_THREADS) void k_conv_fft(IcsFftArgs a) {
     QuadOut qo[2];
     const int te = opaque(tid);
 #pragma unroll
-    for (int t = 0; t < 2; ++t) qo[t].vo = quad_lane(a, u, mem.lout, te, t, qo[t].rows, qo[t].X);
-    const bool edge = u.ox[0] < a.ox0 || u.ox[0] + a.V > a.ox1 || u.ox[1] < a.ox0 || u.ox[1] + a.V > a.ox1;
+    for (int t = 0; t < 2; ++t) qo[t].vo = quad_lane<MODE == 2>(a, u, mem.lout, te, t, qo[t].rows, qo[t].X);
+    const bool edge = unit_is_edge<MODE == 2>(a, u);
     if (MODE == 0) {
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
@@ -1501,7 +1529,21 @@ void ics_conv_fft_fill_args(int mode, const IcsConvArgs& c, const float* spec, I
   else { a->oy0 = 0; a->ox0 = 0; a->oy1 = g.uM; a->ox1 = g.uN; }
   a->gx0 = a->ox0 & ~3;
   a->tiles_x = (a->ox1 - a->gx0 + a->V - 1) / a->V;
-  const int tiles_y = (a->oy1 - a->oy0 + a->Vy - 1) / a->Vy;
+  int tiles_y = (a->oy1 - a->oy0 + a->Vy - 1) / a->Vy;
+  a->ext_y = a->ext_x = 0;
+  if (mode == 2) {
+    // The far edge (tile_rows): where the tiles that cover the M interior rows end within 2 pad of the u-frame's last row, the last of them
+    // stores the rest of the pad ring as well and the tile row behind it is not run -- 42 -> 41 tile rows and columns at 4096 / 15, 2646 ->
+    // 2523 units = ten rounds on 256 workgroups instead of eleven.  An axis that loses no tile this way keeps ext = 0.
+    const int ny = (g.M + a->Vy - 1) / a->Vy, nx = (g.N + a->V - 1) / a->V;
+    if (ny < tiles_y) { a->ext_y = g.uM - ny * a->Vy; tiles_y = ny; }
+    if (nx < a->tiles_x) { a->ext_x = g.uN - nx * a->V; a->tiles_x = nx; }
+    // (0 < ext <= 2 pad follows from n V >= M and n < ceil(uM / V); an extended tile ends at or behind the interior's last row / column
+    //  -- what tile_rows' derivation rests on -- and is one of the outer ring)
+    assert(a->ext_y >= 0 && a->ext_y <= 2 * g.pad && a->ext_x >= 0 && a->ext_x <= 2 * g.pad);
+    assert(!a->ext_y || (ny * a->Vy >= g.M && (ny - 1) * a->Vy + icsfft::tile_rows(*a, (ny - 1) * a->Vy) == g.uM));      // (> M: tile_is_border's row test)
+    assert(!a->ext_x || (nx * a->V >= g.N && (nx - 1) * a->V + icsfft::tile_cols(*a, (nx - 1) * a->V) == g.uN));
+  }
   a->ntiles = a->tiles_x * tiles_y;
   a->tiles_x_magic = 0x100000000ull / (unsigned)a->tiles_x + 1ull;
   a->nunits = 3 * ((a->ntiles + 1) / 2);

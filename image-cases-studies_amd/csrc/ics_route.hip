@@ -200,6 +200,15 @@ extern "C" unsigned long long ics_rl_frame_bytes(int M, int N, int MK) {
   return (unsigned long long)ics_frame_floats(ics_make_geom(M, N, MK)) * 4ull;
 }
 
+// for the tests, beside ics_debug_set and like it outside the public header: the work units of mode 2 of the tiles (A1 + A3 in one unit per tile
+// pair) on such a frame = the blocks of its image spectra; 0 where mode 2 is not built.  No device needed.
+extern "C" int ics_debug_conv2_units(int M, int N, int MK) {
+  if (M < 1 || N < 1 || MK < 3 || !(MK & 1) || !psf_supported(MK)) return 0;
+  const IcsGeom g = ics_make_geom(M, N, MK);
+  if (!ics_conv_fft_supported(MK) || !ics_conv2_fft_supported(g)) return 0;
+  return (int)(ics_conv2_fft_fspec_floats(g) / ((size_t)8 * 1024 * 4));
+}
+
 extern "C" int ics_describe(int M, int N, int MK, const ics_rl_params* p, ics_rl_route* r) {
   if (M < 1 || N < 1 || MK < 3 || !(MK & 1)) return ics_set_error(ICS_EINVAL, "bad shape: M=%d N=%d MK=%d (MK odd >= 3)", M, N, MK);
   if (!psf_supported(MK)) return ics_set_error(ICS_ENOSUP, "PSF size %d not supported (odd sizes 3..%d)", MK, ICS_PSF_MAX);

@@ -212,6 +212,14 @@ def debug_set(name, value):
     return old.value
 
 
+def conv2_units(M, N, MK):
+    """work units (tile pair x channel) of the one-unit form of A1 + A3 on the transform tiles for such a frame, 0 where it is not built
+    (no device needed; for the tests, like debug_set)"""
+    fn = load().ics_debug_conv2_units
+    fn.argtypes, fn.restype = [C.c_int, C.c_int, C.c_int], C.c_int
+    return int(fn(int(M), int(N), int(MK)))
+
+
 def device_count():
     n = C.c_int(0)
     rc = load().ics_device_count(C.byref(n))
