@@ -1,5 +1,5 @@
 // ics_images.hip -- the ics_img_* entries of the C ABI (include/ics_hip.h).  Host side only; kernels live in ics_img.hip / ics_img_filters.hip /
-// ics_img_tvdenoise.hip / ics_resize.hip.
+// ics_img_tvdenoise.hip / ics_img_wavelet.hip / ics_resize.hip.
 #include "ics_host.h"
 
 using namespace ics_host;
@@ -251,5 +251,40 @@ extern "C" int ics_img_tv_denoise(const ics_img* src, float weight, int iteratio
   if (e == hipSuccess) c->ev_pending = true;
   for (int i = 0; i < 4; ++i) c->pool.release(q[i]);   // (reused on the context's one stream, behind these kernels)
   if (e != hipSuccess) { ics_img_destroy(*out); *out = nullptr; return ics_set_error(e == hipErrorOutOfMemory ? ICS_ENOMEM : ICS_EHIP, "img_tv_denoise: %s", hipGetErrorString(e)); }
+  return ICS_OK;
+}
+
+// ---- wavelet equaliser of a device image (csrc/ics_img_wavelet.hip) -------------------------------------------------------------
+// route 0: the per-scale route at every size.  The fused route moves 10 frame transits instead of 18 at J = 5 ("Wavelet
+// equaliser"), but no kernel times of the two routes exist yet, and a crossover is not to be guessed: scripts/filters_timing.py prints
+// the table (routes alternating) from which a size rule is to be set here.  Both routes are callable through `route`.
+extern "C" int ics_img_wavelet_equalize(const ics_img* src, int scales, const float* gains, const float* thresholds, float residual, int coupling,
+                                        int route, ics_img** out) {
+  if (!src || !out) return ics_set_error(ICS_EINVAL, "NULL argument");
+  if (scales < 1 || scales > ICS_IMG_WAVELET_MAX_SCALES) return ics_set_error(ICS_EINVAL, "scales = %d (1 .. %d)", scales, ICS_IMG_WAVELET_MAX_SCALES);
+  if (!gains) return ics_set_error(ICS_EINVAL, "gains is NULL");
+  for (int j = 0; j < scales; ++j) {
+    if (!std::isfinite(gains[j])) return ics_set_error(ICS_EINVAL, "gains[%d] = %g (must be finite)", j, (double)gains[j]);
+    if (thresholds && (!std::isfinite(thresholds[j]) || thresholds[j] < 0.f))
+      return ics_set_error(ICS_EINVAL, "thresholds[%d] = %g (must be finite and >= 0)", j, (double)thresholds[j]);
+  }
+  if (!std::isfinite(residual)) return ics_set_error(ICS_EINVAL, "residual = %g (must be finite)", (double)residual);
+  if (coupling != 0 && coupling != 1) return ics_set_error(ICS_EINVAL, "coupling %d (0 = channel, 1 = vector)", coupling);
+  if (route < 0 || route > 2) return ics_set_error(ICS_EINVAL, "route %d (0 = auto, 1 = per scale, 2 = first scales fused)", route);
+  ics_ctx* c = src->ctx;
+  const int H = src->H, W = src->W;
+  if (route == 0) route = 1;
+  RC(img_new(c, H, W, out));
+  hipStream_t s = c->stream;
+  float* tmp[2] = {nullptr, nullptr};
+  hipError_t e = hipSuccess;
+  const int frames = ics_img_wavelet_frames(scales, route);
+  for (int i = 0; i < frames && e == hipSuccess; ++i) e = c->pool.alloc((void**)&tmp[i], (size_t)H * W * 12);
+  if (e == hipSuccess) e = hipEventRecord(c->ev0, s);
+  if (e == hipSuccess) e = ics_launch_img_wavelet(src->d, H, W, scales, gains, thresholds, residual, coupling, route, tmp, (*out)->d, s);
+  if (e == hipSuccess) e = hipEventRecord(c->ev1, s);
+  if (e == hipSuccess) c->ev_pending = true;
+  for (int i = 0; i < 2; ++i) c->pool.release(tmp[i]);   // (reused on the context's one stream, behind these kernels)
+  if (e != hipSuccess) { ics_img_destroy(*out); *out = nullptr; return ics_set_error(e == hipErrorOutOfMemory ? ICS_ENOMEM : ICS_EHIP, "img_wavelet_equalize: %s", hipGetErrorString(e)); }
   return ICS_OK;
 }

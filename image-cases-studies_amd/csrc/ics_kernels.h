@@ -275,3 +275,14 @@ size_t ics_img_tv_block_lds();
 int ics_img_tv_pairs(int iterations, int route);
 hipError_t ics_launch_img_tv_denoise(const float* f, int H, int W, float weight, int iterations, int coupling, int route, float* const q[4],
                                      float* out, hipStream_t s);
+
+// ---- wavelet equaliser of device-resident images (ics_img_wavelet.hip): B3-spline a-trous scales, shrunk, weighted, summed --------
+// route 1: a launch per scale; 2: the first ICS_IMG_WAVELET_FUSED scales in one launch on an LDS tile, the rest as in route 1.
+// tmp: as many H x W x 3 frames as ics_img_wavelet_frames says (c_j ping-pong); the accumulator lives in `out`.  thresholds may be
+// nullptr (all 0); coupling 0: per channel, 1: one magnitude per pixel.
+#define ICS_IMG_WAVELET_MAX_SCALES 8      // (== include/ics_hip.h)
+#define ICS_IMG_WAVELET_FUSED 3           // (== include/ics_hip.h)
+size_t ics_img_wavelet_fused_lds();
+int ics_img_wavelet_frames(int scales, int route);
+hipError_t ics_launch_img_wavelet(const float* f, int H, int W, int scales, const float* gains, const float* thresholds, float residual,
+                                  int coupling, int route, float* const tmp[2], float* out, hipStream_t s);

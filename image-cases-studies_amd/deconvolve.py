@@ -79,7 +79,8 @@ def mask_window(i, top, bottom, left, right):
 @utils.timeit
 def deblur_module(pic, filename, dest_path, blur_width, confidence=10, tolerance=1, quality="normal", bits=8,
                   mask=None, display=True, blur="static", preview=False, p=1, order=2, norm=1, priority=0, mask_size=255,
-                  iterations=200, refocus=False, pyramid=True, solver=None, save=True, device_resident=None, sharpen=None, denoise=None):
+                  iterations=200, refocus=False, pyramid=True, solver=None, save=True, device_resident=None, sharpen=None, denoise=None,
+                  local_contrast=None):
     """deconvolve.py:65-368.  Extra keyword arguments (not in the reference): `pyramid=False` runs the
     single scale-1 level only, `solver` replaces `dc.richardson_lucy_MM` (tests record the calls),
     `save=False` returns the float image instead of writing the TIFF, `device_resident=True` keeps every frame in HBM
@@ -93,16 +94,22 @@ def deblur_module(pic, filename, dest_path, blur_width, confidence=10, tolerance
     `denoise=(weight, iterations)` or `(weight, iterations, coupling)`: `utils.tv_denoise` with these arguments (coupling
     "vector" unless given) on the deblurred frame, in the gamma-encoded domain, before `sharpen` and before the final clip:
     Richardson-Lucy amplifies noise, and the total-variation denoiser removes it without blunting the restored edges; on the
-    resident path the frame stays in HBM."""
+    resident path the frame stays in HBM.
+    `local_contrast=(gains,)`, `(gains, thresholds)` or `(gains, thresholds, coupling)`: `utils.wavelet_equalizer` with these
+    arguments (residual 1, coupling "vector" unless given) on the deblurred frame, in the gamma-encoded domain, after `denoise`,
+    before `sharpen` and before the final clip: the scale-by-scale form of the README's advice -- the 4 to 16 px detail that
+    Richardson-Lucy leaves flat is lifted by the gains of scales 2 to 4 while the 1 px noise it amplified keeps gain 1 or is
+    thresholded away; on the resident path the frame stays in HBM."""
     sharpen = _sharpen_args(sharpen)
     denoise = _denoise_args(denoise)
+    local_contrast = _local_contrast_args(local_contrast)
     if device_resident is None:
         device_resident = solver is None and not display
     if device_resident:
         if solver is not None:
             raise ValueError("device_resident=True runs the GPU solver; `solver` cannot be replaced")
         return _deblur_device(pic, filename, dest_path, blur_width, confidence, tolerance, quality, bits, mask, display, blur, preview, p,
-                              order, norm, priority, mask_size, iterations, refocus, pyramid, save, sharpen, denoise)
+                              order, norm, priority, mask_size, iterations, refocus, pyramid, save, sharpen, denoise, local_contrast)
     rl = solver if solver is not None else dc.richardson_lucy_MM
     pic = np.ascontiguousarray(pic, dtype=np.float32)
     pic = pad_image(pic, (1, 1)).astype(np.float32)                       # :94
@@ -206,6 +213,9 @@ def deblur_module(pic, filename, dest_path, blur_width, confidence=10, tolerance
         pass
     if denoise is not None:
         deblured_image = utils.tv_denoise(np.ascontiguousarray(deblured_image, dtype=np.float32), *denoise)
+    if local_contrast is not None:
+        gains, thresholds, coupling = local_contrast
+        deblured_image = utils.wavelet_equalizer(np.ascontiguousarray(deblured_image, dtype=np.float32), gains, thresholds, 1.0, coupling)
     if sharpen is not None:                                               # per channel, as a user of lib.utils would
         deblured_image = np.dstack([utils.USM(deblured_image[..., c], *sharpen) for c in range(3)]).astype(np.float32)
     deblured_image = np.clip(deblured_image, 0., 1.)                      # :346
@@ -258,6 +268,26 @@ def _denoise_args(denoise):
     return float(weight), int(iterations), coupling
 
 
+def _local_contrast_args(local_contrast):
+    """`local_contrast` of deblur_module -> None or (gains, thresholds or None, coupling), gains and thresholds as tuples of floats"""
+    if local_contrast is None:
+        return None
+    try:
+        local_contrast = tuple(local_contrast)
+    except TypeError:
+        raise ValueError("local_contrast takes (gains,), (gains, thresholds) or (gains, thresholds, coupling), got %r" % (local_contrast,))
+    if not 1 <= len(local_contrast) <= 3:
+        raise ValueError("local_contrast takes (gains,), (gains, thresholds) or (gains, thresholds, coupling), got %d values" % len(local_contrast))
+    gains, thresholds, coupling = (local_contrast + (None, "vector")[len(local_contrast) - 1:])[:3]
+    from lib._native import wavelet_args
+    try:
+        wavelet_args(gains, thresholds, 1.0, coupling)
+    except (ValueError, TypeError) as exc:
+        raise ValueError("local_contrast: %s" % exc)
+    as_floats = lambda v: tuple(float(x) for x in np.atleast_1d(np.asarray(v, dtype=np.float64)))     # noqa: E731
+    return as_floats(gains), None if thresholds is None else as_floats(thresholds), coupling
+
+
 def _level_shape(i, M, N):
     """deconvolve.py:232-243 -- odd size of pyramid level `i`"""
     temp_width, temp_height = int(np.floor(i * N)), int(np.floor(i * M))
@@ -269,7 +299,7 @@ def _level_shape(i, M, N):
 
 
 def _deblur_device(pic, filename, dest_path, blur_width, confidence, tolerance, quality, bits, mask, display, blur, preview, p, order, norm,
-                   priority, mask_size, iterations, refocus, pyramid, save, sharpen=None, denoise=None):
+                   priority, mask_size, iterations, refocus, pyramid, save, sharpen=None, denoise=None, local_contrast=None):
     """`deblur_module` (deconvolve.py:65-368) with every frame resident in HBM: one upload of the picture,
     one download of the result; pad_image, gamma, the window views, the resize between pyramid levels and the solver all
     work on `lib._native.DeviceImage`s.  Line references as in `deblur_module` above."""
@@ -373,6 +403,10 @@ def _deblur_device(pic, filename, dest_path, blur_width, confidence, tolerance, 
         pass
     if denoise is not None:
         deb, old = deb.tv_denoise(*denoise), deb
+        old.close()
+    if local_contrast is not None:
+        gains, thresholds, coupling = local_contrast
+        deb, old = deb.wavelet_equalize(gains, thresholds, 1.0, coupling), deb
         old.close()
     if sharpen is not None:
         deb, old = deb.usm(*sharpen), deb

@@ -86,6 +86,8 @@ def describe(M, N, MK, params):
 
 FRAME_LIMIT_BYTES = 1 << 31      # include/ics_hip.h ICS_FRAME_LIMIT_BYTES
 IMG_TV_BLOCK = 4                 # include/ics_hip.h ICS_IMG_TV_BLOCK: iterations per launch of the blocked TV denoise route
+IMG_WAVELET_MAX_SCALES = 8       # include/ics_hip.h ICS_IMG_WAVELET_MAX_SCALES: detail scales of the wavelet equaliser
+IMG_WAVELET_FUSED = 3            # include/ics_hip.h ICS_IMG_WAVELET_FUSED: scales the fused route runs in one launch on LDS tiles
 
 
 def frame_bytes(M, N, MK):
@@ -159,6 +161,7 @@ def load():
     lib.ics_img_usm.argtypes = [vp, vp, ci, ci, cf, C.POINTER(vp)]
     lib.ics_img_bilateral.argtypes = [vp, ci, cf, cf, C.POINTER(vp)]
     lib.ics_img_tv_denoise.argtypes = [vp, cf, ci, ci, ci, C.POINTER(vp)]
+    lib.ics_img_wavelet_equalize.argtypes = [vp, ci, vp, vp, cf, ci, ci, C.POINTER(vp)]
     lib.ics_rl_upload_img.argtypes = [vp, vp, ci, ci, vp, ci, ci, vp]
     lib.ics_rl_download_img.argtypes = [vp, vp, ci, ci]
     lib.ics_group_create.argtypes = [ci, ci, ci, C.c_char_p, ci, C.POINTER(vp)]
@@ -180,7 +183,7 @@ def load():
                  "ics_rl_download", "ics_rl_run", "ics_rl_stage", "ics_rl_read", "ics_rl_write", "ics_rl_read_rows", "ics_rl_write_rows", "ics_rl_copy_rows", "ics_normalize_kernel",
                  "ics_tv", "ics_conv2d_symm", "ics_usm", "ics_bilateral", "ics_resize_bicubic", "ics_img_create", "ics_img_shape",
                  "ics_img_upload", "ics_img_upload_int", "ics_img_download", "ics_img_pad_edge", "ics_img_crop", "ics_img_paste", "ics_img_gamma", "ics_img_resize",
-                 "ics_img_convolve", "ics_img_usm", "ics_img_bilateral", "ics_img_tv_denoise",
+                 "ics_img_convolve", "ics_img_usm", "ics_img_bilateral", "ics_img_tv_denoise", "ics_img_wavelet_equalize",
                  "ics_rl_upload_img", "ics_rl_download_img", "ics_group_create", "ics_group_info", "ics_group_barrier",
                  "ics_group_allreduce_max", "ics_group_allreduce_sum", "ics_group_describe", "ics_group_allgather"):
         getattr(lib, name).restype = ci
@@ -229,6 +232,34 @@ def device_count():
 def default_device():
     """One process per GPU: LOCAL_RANK picks the device (torchrun / bench.py), ICS_DEVICE overrides."""
     return int(os.environ.get("ICS_DEVICE", os.environ.get("LOCAL_RANK", "0")))
+
+
+def wavelet_args(gains, thresholds=None, residual=1.0, coupling="vector", route=0):
+    """the arguments of DeviceImage.wavelet_equalize checked (ValueError) and as (gains, thresholds or None, residual, coupling,
+    route): float32 arrays, a float, a string, an int"""
+    def finite(a):                                  # as float32, which is what the library takes
+        a = np.asarray(a, dtype=np.float64)
+        return bool(np.all(np.isfinite(a)) and np.all(np.abs(a) <= np.finfo(np.float32).max))
+    g = np.atleast_1d(np.asarray(gains, dtype=np.float64))
+    if g.ndim != 1 or not 1 <= g.size <= IMG_WAVELET_MAX_SCALES:
+        raise ValueError("gains: one value per scale, 1 to %d scales, got shape %s" % (IMG_WAVELET_MAX_SCALES, g.shape))
+    if not finite(g):
+        raise ValueError("gains %r (must be finite)" % (gains,))
+    t = None
+    if thresholds is not None:
+        t = np.atleast_1d(np.asarray(thresholds, dtype=np.float64))
+        if t.shape != g.shape:
+            raise ValueError("thresholds: %s values for %d gains (one per scale, or None)" % (t.shape, g.size))
+        if not finite(t) or np.any(t < 0):
+            raise ValueError("thresholds %r (must be finite and >= 0)" % (thresholds,))
+        t = np.ascontiguousarray(t, dtype=np.float32)
+    if not finite(residual):
+        raise ValueError("residual %r (must be finite)" % (residual,))
+    if coupling not in ("channel", "vector"):
+        raise ValueError("coupling %r (channel or vector)" % (coupling,))
+    if route not in (0, 1, 2):
+        raise ValueError("route %r (0: the library's choice, 1: a launch per scale, 2: the first scales fused)" % (route,))
+    return np.ascontiguousarray(g, dtype=np.float32), t, float(residual), coupling, int(route)
 
 
 class Context:
@@ -422,6 +453,21 @@ class DeviceImage:
         if coupling not in ("channel", "vector"):
             raise ValueError("coupling %r (channel or vector)" % (coupling,))
         return self._new(load().ics_img_tv_denoise, float(weight), int(iterations), int(coupling == "vector"), int(route))
+
+    def wavelet_equalize(self, gains, thresholds=None, residual=1.0, coupling="vector", route=0):
+        """Wavelet equaliser: an undecimated B3-spline ("a trous") decomposition into len(gains) <= IMG_WAVELET_MAX_SCALES detail
+        scales (scale j holds the detail of about 2^j pixels: taps [1 4 6 4 1] / 16 dilated by 2^j along x, then y, symmetric
+        boundary); every detail is soft-thresholded by thresholds[j] (None: 0), multiplied by gains[j], and the result is
+        residual * coarsest approximation + the sum of the scales (csrc/ics_img_wavelet.hip; restated in tests/wavelet_ref.py).
+        gains 1, thresholds 0, residual 1 returns the picture; a gain above 1 lifts the local contrast of its scale, a threshold on
+        the finest scales removes noise there and nowhere else.  coupling "channel": every value is shrunk on its own; "vector":
+        the three channels of a pixel are shrunk together by their magnitude, so the hue of a detail is kept.  route 0: the
+        library's choice, 1: a launch per scale, 2: the first IMG_WAVELET_FUSED scales in one launch on LDS tiles; all give
+        identical bits.  ValueError (before any native call): no or more than 8 gains, thresholds of another length, a value that
+        is not finite, a negative threshold, unknown coupling or route."""
+        g, t, residual, coupling, route = wavelet_args(gains, thresholds, residual, coupling, route)
+        return self._new(load().ics_img_wavelet_equalize, int(g.size), _ptr(g), None if t is None else _ptr(t), residual,
+                         int(coupling == "vector"), route)
 
     def close(self):
         if self._h:

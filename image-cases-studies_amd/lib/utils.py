@@ -16,8 +16,9 @@ Same names and argument meaning as the reference (file:line in /root/reference/l
 The filters run on the GPU through libics_hip.so in float64 like the reference (scipy's
 convolve2d(mode="same", boundary="symm")); there is no CPU fallback for them.  Given a `lib._native.DeviceImage`
 (H x W x 3 float32 in HBM) instead of a 2-D array, the four filters work on it there, every channel on its own
-in float32, and return a new DeviceImage (csrc/ics_img_filters.hip): no transfer, no synchronisation; `tv_denoise` (not in the
-reference, csrc/ics_img_tvdenoise.hip) works on such an image or on an H x W x 3 array.  The colour tools of
+in float32, and return a new DeviceImage (csrc/ics_img_filters.hip): no transfer, no synchronisation; `tv_denoise` and
+`wavelet_equalizer` (not in the reference; csrc/ics_img_tvdenoise.hip, csrc/ics_img_wavelet.hip) work on such an image or on an
+H x W x 3 array.  The colour tools of
 the reference (Lagrange_interpolation, grey_point, auto_vibrance, overlay, blending) and its dead
 code (divTV, gradTVEM) are outside the deconvolution path and are not provided.
 
@@ -140,6 +141,33 @@ def tv_denoise(src, weight=0.1, iterations=50, coupling="vector"):
     img = _native.DeviceImage.from_host(np.ascontiguousarray(arr, dtype=np.float32))
     try:
         res = img.tv_denoise(weight, iterations, coupling)
+    finally:
+        img.close()
+    try:
+        return res.to_host()
+    finally:
+        res.close()
+
+
+def wavelet_equalizer(src, gains, thresholds=None, residual=1.0, coupling="vector"):
+    """Not in the reference's lib/utils.py (its README advises to add local contrast "through wavelets high-pass filter" after the
+    deconvolution, and lists wavelet denoising among what may come): the picture is split into len(gains) <= 8 detail scales by the
+    undecimated B3-spline ("a trous") transform, scale j holding the detail of about 2^j pixels; every scale is soft-thresholded by
+    thresholds[j] (None: 0) and multiplied by gains[j], and the scales are summed back onto residual * the coarsest approximation.
+    gains=[1, 1.6, 1.8, 1.4, 1] lifts the 2 - 8 px contrast and leaves the 1 px noise alone; gains=[1] * 5 with
+    thresholds=[0.03, 0.015, 0, 0, 0] removes noise from the two finest scales only.  coupling "vector" shrinks the three channels
+    of a pixel together (no hue shift), "channel" each on its own.  A `lib._native.DeviceImage` gives a new DeviceImage (nothing
+    crosses PCIe); an H x W x 3 array is uploaded once and the float32 result downloaded once (`DeviceImage.wavelet_equalize`,
+    csrc/ics_img_wavelet.hip)."""
+    if isinstance(src, _native.DeviceImage):
+        return src.wavelet_equalize(gains, thresholds, residual, coupling)
+    arr = np.asarray(src)
+    if arr.ndim != 3 or arr.shape[2] != 3:
+        raise ValueError("expected a DeviceImage or an H x W x 3 array, got shape %s" % (arr.shape,))
+    _native.wavelet_args(gains, thresholds, residual, coupling)        # refused before anything is uploaded
+    img = _native.DeviceImage.from_host(np.ascontiguousarray(arr, dtype=np.float32))
+    try:
+        res = img.wavelet_equalize(gains, thresholds, residual, coupling)
     finally:
         img.close()
     try:

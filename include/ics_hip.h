@@ -396,6 +396,24 @@ int ics_img_bilateral(const ics_img *src, int radius, float std_i, float std_s, 
  * steps with tau = 1/4). */
 #define ICS_IMG_TV_BLOCK 4
 int ics_img_tv_denoise(const ics_img *src, float weight, int iterations, int coupling, int route, ics_img **out);
+/* Wavelet equaliser of a device image: an undecimated B3-spline ("a trous", starlet) decomposition into `scales` detail scales
+ * (1 .. ICS_IMG_WAVELET_MAX_SCALES) whose details are soft-thresholded, multiplied by a gain and summed back.  c_0 = src and
+ *   c_{j+1} = V_j(H_j(c_j)):  taps [1 4 6 4 1] / 16 at offsets {-2 .. 2} * 2^j along x (H_j), then along y (V_j); an index outside
+ *     the picture folds as numpy.pad(mode="symmetric") (i mod 2n, then 2n - 1 - i if >= n: repeatedly on narrow frames); one axis
+ *     pass is ((a[-2] + a[+2]) / 16 + (a[-1] + a[+1]) * 4 / 16) + a[0] * 6 / 16, without FMA
+ *   w_j = c_j - c_{j+1},  s_j = shrink(w_j, thresholds[j])  (thresholds == NULL: all 0)
+ *     coupling 0 (channel): sign(w) max(|w| - t, 0) per value;  1 (vector): w_c * (max(m - t, 0) / m) with
+ *     m = sqrt(w_r^2 + w_g^2 + w_b^2), the squares added smallest first, 0 where m = 0 (IEEE square root and division)
+ *   out = residual * c_J + (((gains[0] s_0) + gains[1] s_1) + ... ), accumulated in that order from zero.
+ * gains all 1, thresholds 0, residual 1 gives src back up to rounding; gains above 1 lift the local contrast of their scale;
+ * thresholds on the finest scales remove noise and leave the coarser scales alone.  route 1: one launch per scale; 2: the first
+ * ICS_IMG_WAVELET_FUSED scales in one launch on a tile in LDS, the others as in route 1; 0: the library's choice.  The
+ * routes give identical bits, and so do two runs.  Queued like the other image filters; src is not written.  ICS_EINVAL: scales
+ * outside 1 .. 8, gains NULL, a gain / threshold / residual that is not finite, a negative threshold, unknown coupling or route. */
+#define ICS_IMG_WAVELET_MAX_SCALES 8
+#define ICS_IMG_WAVELET_FUSED 3
+int ics_img_wavelet_equalize(const ics_img *src, int scales, const float *gains, const float *thresholds /* may be NULL */,
+                             float residual, int coupling, int route, ics_img **out);
 /* richardson_lucy_MM(image[iy:iy+M, ix:ix+N], u[uy:uy+uM, ux:ux+uN], psf, ...) with both windows taken from device
  * images (deconvolve.py:277-313 passes such views); psf is a host MK*MK*3 array as in ics_rl_upload. */
 int ics_rl_upload_img(ics_rl *job, const ics_img *image, int iy, int ix, const ics_img *u, int uy, int ux, const float *psf);

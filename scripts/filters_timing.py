@@ -14,6 +14,11 @@
              iteration) and route 2 (4 iterations per launch on LDS tiles): kernel ms (median of 9) and GB/s on the model of
              60 B/px per iteration (read q 24 + read f 12 + write q 24; 8 TB/s would be 0.126 ms per iteration at 4096^2);
              "auto" names the route that route=0 takes at this size
+  wavelet_equalizer   DeviceImage.wavelet_equalize (csrc/ics_img_wavelet.hip), J = 5 scales, the contrast-lift gains with thresholds on
+             the two finest scales, both couplings, route 1 (a launch per scale: 3 + 4 + 4 + 4 + 3 = 18 frame transits of 12 B/px)
+             and route 2 (the first 3 scales fused on LDS tiles: 3 + 4 + 3 = 10 transits): kernel ms, median and minimum of 9 rounds
+             in which the routes alternate, and the bytes per second each achieves on its own transit count; "auto" names the route
+             that route=0 takes at this size
   checks     the resident USM must not take longer than the three float64 calls, in kernel time and in wall time (a guard against a
              broken kernel, not a target); the exit status is 1 if one of them fails
 Starts no child process; a job script puts its own time limit around it."""
@@ -29,8 +34,10 @@ sys.path.insert(0, os.path.join(ROOT, "image-cases-studies_amd"))
 from lib import _native, utils  # noqa: E402
 
 HBM_PEAK = 8e12
-REPS_RESIDENT, REPS_F64, REPS_TV = 25, 5, 9
+REPS_RESIDENT, REPS_F64, REPS_TV, REPS_WAVELET = 25, 5, 9, 9
 TV_WEIGHT, TV_ITERATIONS = 0.1, 50
+WAVELET_GAINS, WAVELET_THRESHOLDS = (1.0, 1.6, 1.8, 1.4, 1.0), (0.03, 0.015, 0.0, 0.0, 0.0)
+WAVELET_TRANSITS = {1: 18, 2: 10}
 
 
 def main():
@@ -89,6 +96,23 @@ def main():
             res["tv_denoise"]["%s_%s" % (coupling, {1: "route1", 2: "route2", 0: "auto"}[route])] = {
                 "kernel_ms": round(ms, 4), "ms_per_iteration": round(ms / TV_ITERATIONS, 5),
                 "GBps_on_60B_model": round(res["tv_denoise"]["model_bytes"] / (ms * 1e-3) / 1e9, 1)}
+    res["wavelet_equalizer"] = {"gains": WAVELET_GAINS, "thresholds": WAVELET_THRESHOLDS, "transits": {"route1": 18, "route2": 10}}
+    for coupling in ("channel", "vector"):
+        times = {1: [], 2: [], 0: []}
+        for route in times:
+            img.wavelet_equalize(WAVELET_GAINS, WAVELET_THRESHOLDS, 1.0, coupling, route=route).close()     # warm
+        ctx.synchronize()
+        for _ in range(REPS_WAVELET):                      # the routes alternate within a round
+            for route in times:
+                out = img.wavelet_equalize(WAVELET_GAINS, WAVELET_THRESHOLDS, 1.0, coupling, route=route)
+                times[route].append(ctx.last_kernel_ms())
+                out.close()
+        for route, ms in times.items():
+            med = float(np.median(ms))
+            row = {"kernel_ms": round(med, 4), "min_ms": round(float(np.min(ms)), 4)}
+            if route:
+                row["TBps_on_its_transits"] = round(WAVELET_TRANSITS[route] * 12 * size * size / (med * 1e-3) / 1e12, 3)
+            res["wavelet_equalizer"]["%s_%s" % (coupling, {1: "route1", 2: "route2", 0: "auto"}[route])] = row
     res["checks"] = {"%s_%s" % (name, what): res["resident"][name][what] <= res["per_channel_f64"][name][what]
                      for name in ("usm_gauss15", "usm_bessel15") for what in ("kernel_ms", "wall_ms")}
     print(json.dumps(res))
