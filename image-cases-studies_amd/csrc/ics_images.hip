@@ -1,5 +1,5 @@
 // ics_images.hip -- the ics_img_* entries of the C ABI (include/ics_hip.h).  Host side only; kernels live in ics_img.hip / ics_img_filters.hip /
-// ics_img_tvdenoise.hip / ics_img_wavelet.hip / ics_resize.hip.
+// ics_img_tvdenoise.hip / ics_img_wavelet.hip / ics_img_guided.hip / ics_resize.hip.
 #include "ics_host.h"
 
 using namespace ics_host;
@@ -286,5 +286,35 @@ extern "C" int ics_img_wavelet_equalize(const ics_img* src, int scales, const fl
   if (e == hipSuccess) c->ev_pending = true;
   for (int i = 0; i < 2; ++i) c->pool.release(tmp[i]);   // (reused on the context's one stream, behind these kernels)
   if (e != hipSuccess) { ics_img_destroy(*out); *out = nullptr; return ics_set_error(e == hipErrorOutOfMemory ? ICS_ENOMEM : ICS_EHIP, "img_wavelet_equalize: %s", hipGetErrorString(e)); }
+  return ICS_OK;
+}
+
+// ---- guided filter of a device image (csrc/ics_img_guided.hip) ------------------------------------------------------------------
+// route 0: the two-launch route at every radius and size ("Guided filter": the measured table).
+extern "C" int ics_img_guided(const ics_img* src, int radius, float eps, float detail, int coupling, int route, ics_img** out) {
+  if (out) *out = nullptr;
+  if (!src || !out) return ics_set_error(ICS_EINVAL, "NULL argument");
+  if (radius < 1 || radius > ICS_IMG_GUIDED_MAX_RADIUS) return ics_set_error(ICS_EINVAL, "radius = %d (1 .. %d)", radius, ICS_IMG_GUIDED_MAX_RADIUS);
+  if (!std::isfinite(eps) || !(eps > 0.f)) return ics_set_error(ICS_EINVAL, "eps = %g (must be finite and > 0)", (double)eps);
+  if (!std::isfinite(detail)) return ics_set_error(ICS_EINVAL, "detail = %g (must be finite)", (double)detail);
+  if (coupling != 0 && coupling != 1) return ics_set_error(ICS_EINVAL, "coupling %d (0 = channel, 1 = vector)", coupling);
+  if (route < 0 || route > 2) return ics_set_error(ICS_EINVAL, "route %d (0 = auto, 1 = two launches, 2 = one launch)", route);
+  if (route == 2 && radius > ICS_IMG_GUIDED_FUSED_RADIUS)
+    return ics_set_error(ICS_EINVAL, "route 2 takes a radius up to %d, got %d", ICS_IMG_GUIDED_FUSED_RADIUS, radius);
+  ics_ctx* c = src->ctx;
+  const int H = src->H, W = src->W;
+  if (route == 0) route = 1;
+  RC(img_new(c, H, W, out));
+  hipStream_t s = c->stream;
+  float* coef = nullptr;
+  hipError_t e = hipSuccess;
+  const size_t floats = ics_img_guided_coef_floats(H, W, coupling, route);
+  if (floats) e = c->pool.alloc((void**)&coef, floats * sizeof(float));
+  if (e == hipSuccess) e = hipEventRecord(c->ev0, s);
+  if (e == hipSuccess) e = ics_launch_img_guided(src->d, H, W, radius, eps, detail, coupling, route, coef, (*out)->d, s);
+  if (e == hipSuccess) e = hipEventRecord(c->ev1, s);
+  if (e == hipSuccess) c->ev_pending = true;
+  c->pool.release(coef);   // (reused on the context's one stream, behind these kernels)
+  if (e != hipSuccess) { ics_img_destroy(*out); *out = nullptr; return ics_set_error(e == hipErrorOutOfMemory ? ICS_ENOMEM : ICS_EHIP, "img_guided: %s", hipGetErrorString(e)); }
   return ICS_OK;
 }

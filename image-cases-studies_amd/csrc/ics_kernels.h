@@ -286,3 +286,12 @@ size_t ics_img_wavelet_fused_lds();
 int ics_img_wavelet_frames(int scales, int route);
 hipError_t ics_launch_img_wavelet(const float* f, int H, int W, int scales, const float* gains, const float* thresholds, float residual,
                                   int coupling, int route, float* const tmp[2], float* out, hipStream_t s);
+
+// ---- guided filter of device-resident images (ics_img_guided.hip): box means, a solve per pixel, base layer + detail * (src - base) --
+// route 1: coefficients to the planar frame `coef` (ics_img_guided_coef_floats floats), then the output; 2: one launch, coefficients
+// in LDS, radius <= ICS_IMG_GUIDED_FUSED_RADIUS, coef unused.  coupling 0: per channel, 1: the RGB pixel as the guide.
+#define ICS_IMG_GUIDED_MAX_RADIUS 32      // (== include/ics_hip.h)
+#define ICS_IMG_GUIDED_FUSED_RADIUS 8     // (== include/ics_hip.h)
+size_t ics_img_guided_coef_floats(int H, int W, int coupling, int route);
+hipError_t ics_launch_img_guided(const float* src, int H, int W, int radius, float eps, float detail, int coupling, int route, float* coef, float* out,
+                                 hipStream_t s);

@@ -80,7 +80,7 @@ def mask_window(i, top, bottom, left, right):
 def deblur_module(pic, filename, dest_path, blur_width, confidence=10, tolerance=1, quality="normal", bits=8,
                   mask=None, display=True, blur="static", preview=False, p=1, order=2, norm=1, priority=0, mask_size=255,
                   iterations=200, refocus=False, pyramid=True, solver=None, save=True, device_resident=None, sharpen=None, denoise=None,
-                  local_contrast=None):
+                  local_contrast=None, detail=None):
     """deconvolve.py:65-368.  Extra keyword arguments (not in the reference): `pyramid=False` runs the
     single scale-1 level only, `solver` replaces `dc.richardson_lucy_MM` (tests record the calls),
     `save=False` returns the float image instead of writing the TIFF, `device_resident=True` keeps every frame in HBM
@@ -99,17 +99,23 @@ def deblur_module(pic, filename, dest_path, blur_width, confidence=10, tolerance
     arguments (residual 1, coupling "vector" unless given) on the deblurred frame, in the gamma-encoded domain, after `denoise`,
     before `sharpen` and before the final clip: the scale-by-scale form of the README's advice -- the 4 to 16 px detail that
     Richardson-Lucy leaves flat is lifted by the gains of scales 2 to 4 while the 1 px noise it amplified keeps gain 1 or is
-    thresholded away; on the resident path the frame stays in HBM."""
+    thresholded away; on the resident path the frame stays in HBM.
+    `detail=(radius, eps, gain)` or `(radius, eps, gain, coupling)`: `utils.guided_filter` with these arguments (coupling
+    "vector" unless given) on the deblurred frame, in the gamma-encoded domain, after `local_contrast`, before `sharpen` and before
+    the final clip: the frame's guided-filter base layer plus `gain` times its detail -- a gain above 1 sharpens at radii of 8 to
+    32 px without the halos a Gaussian mask of that size puts around the edges Richardson-Lucy has just restored, a gain below 1
+    smooths texture and keeps them; on the resident path the frame stays in HBM."""
     sharpen = _sharpen_args(sharpen)
     denoise = _denoise_args(denoise)
     local_contrast = _local_contrast_args(local_contrast)
+    detail = _detail_args(detail)
     if device_resident is None:
         device_resident = solver is None and not display
     if device_resident:
         if solver is not None:
             raise ValueError("device_resident=True runs the GPU solver; `solver` cannot be replaced")
         return _deblur_device(pic, filename, dest_path, blur_width, confidence, tolerance, quality, bits, mask, display, blur, preview, p,
-                              order, norm, priority, mask_size, iterations, refocus, pyramid, save, sharpen, denoise, local_contrast)
+                              order, norm, priority, mask_size, iterations, refocus, pyramid, save, sharpen, denoise, local_contrast, detail)
     rl = solver if solver is not None else dc.richardson_lucy_MM
     pic = np.ascontiguousarray(pic, dtype=np.float32)
     pic = pad_image(pic, (1, 1)).astype(np.float32)                       # :94
@@ -216,6 +222,8 @@ def deblur_module(pic, filename, dest_path, blur_width, confidence=10, tolerance
     if local_contrast is not None:
         gains, thresholds, coupling = local_contrast
         deblured_image = utils.wavelet_equalizer(np.ascontiguousarray(deblured_image, dtype=np.float32), gains, thresholds, 1.0, coupling)
+    if detail is not None:
+        deblured_image = utils.guided_filter(np.ascontiguousarray(deblured_image, dtype=np.float32), *detail)
     if sharpen is not None:                                               # per channel, as a user of lib.utils would
         deblured_image = np.dstack([utils.USM(deblured_image[..., c], *sharpen) for c in range(3)]).astype(np.float32)
     deblured_image = np.clip(deblured_image, 0., 1.)                      # :346
@@ -288,6 +296,25 @@ def _local_contrast_args(local_contrast):
     return as_floats(gains), None if thresholds is None else as_floats(thresholds), coupling
 
 
+def _detail_args(detail):
+    """`detail` of deblur_module -> None or (radius, eps, gain, coupling)"""
+    if detail is None:
+        return None
+    try:
+        detail = tuple(detail)
+    except TypeError:
+        raise ValueError("detail takes (radius, eps, gain) or (radius, eps, gain, coupling), got %r" % (detail,))
+    if len(detail) not in (3, 4):
+        raise ValueError("detail takes (radius, eps, gain) or (radius, eps, gain, coupling), got %d values" % len(detail))
+    radius, eps, gain, coupling = (detail + ("vector",))[:4]
+    from lib._native import guided_args
+    try:
+        radius, eps, gain, coupling, _ = guided_args(radius, eps, gain, coupling)
+    except ValueError as exc:
+        raise ValueError("detail: %s" % exc)
+    return radius, eps, gain, coupling
+
+
 def _level_shape(i, M, N):
     """deconvolve.py:232-243 -- odd size of pyramid level `i`"""
     temp_width, temp_height = int(np.floor(i * N)), int(np.floor(i * M))
@@ -299,7 +326,7 @@ def _level_shape(i, M, N):
 
 
 def _deblur_device(pic, filename, dest_path, blur_width, confidence, tolerance, quality, bits, mask, display, blur, preview, p, order, norm,
-                   priority, mask_size, iterations, refocus, pyramid, save, sharpen=None, denoise=None, local_contrast=None):
+                   priority, mask_size, iterations, refocus, pyramid, save, sharpen=None, denoise=None, local_contrast=None, detail=None):
     """`deblur_module` (deconvolve.py:65-368) with every frame resident in HBM: one upload of the picture,
     one download of the result; pad_image, gamma, the window views, the resize between pyramid levels and the solver all
     work on `lib._native.DeviceImage`s.  Line references as in `deblur_module` above."""
@@ -407,6 +434,9 @@ def _deblur_device(pic, filename, dest_path, blur_width, confidence, tolerance, 
     if local_contrast is not None:
         gains, thresholds, coupling = local_contrast
         deb, old = deb.wavelet_equalize(gains, thresholds, 1.0, coupling), deb
+        old.close()
+    if detail is not None:
+        deb, old = deb.guided_filter(*detail), deb
         old.close()
     if sharpen is not None:
         deb, old = deb.usm(*sharpen), deb

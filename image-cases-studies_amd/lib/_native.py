@@ -88,6 +88,8 @@ FRAME_LIMIT_BYTES = 1 << 31      # include/ics_hip.h ICS_FRAME_LIMIT_BYTES
 IMG_TV_BLOCK = 4                 # include/ics_hip.h ICS_IMG_TV_BLOCK: iterations per launch of the blocked TV denoise route
 IMG_WAVELET_MAX_SCALES = 8       # include/ics_hip.h ICS_IMG_WAVELET_MAX_SCALES: detail scales of the wavelet equaliser
 IMG_WAVELET_FUSED = 3            # include/ics_hip.h ICS_IMG_WAVELET_FUSED: scales the fused route runs in one launch on LDS tiles
+IMG_GUIDED_MAX_RADIUS = 32       # include/ics_hip.h ICS_IMG_GUIDED_MAX_RADIUS: largest window radius of the guided filter
+IMG_GUIDED_FUSED_RADIUS = 8      # include/ics_hip.h ICS_IMG_GUIDED_FUSED_RADIUS: largest radius of its one-launch route
 
 
 def frame_bytes(M, N, MK):
@@ -162,6 +164,7 @@ def load():
     lib.ics_img_bilateral.argtypes = [vp, ci, cf, cf, C.POINTER(vp)]
     lib.ics_img_tv_denoise.argtypes = [vp, cf, ci, ci, ci, C.POINTER(vp)]
     lib.ics_img_wavelet_equalize.argtypes = [vp, ci, vp, vp, cf, ci, ci, C.POINTER(vp)]
+    lib.ics_img_guided.argtypes = [vp, ci, cf, cf, ci, ci, C.POINTER(vp)]
     lib.ics_rl_upload_img.argtypes = [vp, vp, ci, ci, vp, ci, ci, vp]
     lib.ics_rl_download_img.argtypes = [vp, vp, ci, ci]
     lib.ics_group_create.argtypes = [ci, ci, ci, C.c_char_p, ci, C.POINTER(vp)]
@@ -183,7 +186,7 @@ def load():
                  "ics_rl_download", "ics_rl_run", "ics_rl_stage", "ics_rl_read", "ics_rl_write", "ics_rl_read_rows", "ics_rl_write_rows", "ics_rl_copy_rows", "ics_normalize_kernel",
                  "ics_tv", "ics_conv2d_symm", "ics_usm", "ics_bilateral", "ics_resize_bicubic", "ics_img_create", "ics_img_shape",
                  "ics_img_upload", "ics_img_upload_int", "ics_img_download", "ics_img_pad_edge", "ics_img_crop", "ics_img_paste", "ics_img_gamma", "ics_img_resize",
-                 "ics_img_convolve", "ics_img_usm", "ics_img_bilateral", "ics_img_tv_denoise", "ics_img_wavelet_equalize",
+                 "ics_img_convolve", "ics_img_usm", "ics_img_bilateral", "ics_img_tv_denoise", "ics_img_wavelet_equalize", "ics_img_guided",
                  "ics_rl_upload_img", "ics_rl_download_img", "ics_group_create", "ics_group_info", "ics_group_barrier",
                  "ics_group_allreduce_max", "ics_group_allreduce_sum", "ics_group_describe", "ics_group_allgather"):
         getattr(lib, name).restype = ci
@@ -260,6 +263,34 @@ def wavelet_args(gains, thresholds=None, residual=1.0, coupling="vector", route=
     if route not in (0, 1, 2):
         raise ValueError("route %r (0: the library's choice, 1: a launch per scale, 2: the first scales fused)" % (route,))
     return np.ascontiguousarray(g, dtype=np.float32), t, float(residual), coupling, int(route)
+
+
+def guided_args(radius, eps, detail=0.0, coupling="vector", route=0):
+    """the arguments of DeviceImage.guided_filter checked (ValueError) and as (radius, eps, detail, coupling, route): an int, two
+    floats, a string, an int"""
+    def finite(v):                                  # as float32, which is what the library takes
+        try:
+            v = float(v)
+        except (TypeError, ValueError):
+            return False
+        return bool(np.isfinite(v) and abs(v) <= float(np.finfo(np.float32).max))
+    try:
+        whole = int(radius) == radius and not isinstance(radius, bool)
+    except (TypeError, ValueError, OverflowError):
+        whole = False
+    if not whole or not 1 <= int(radius) <= IMG_GUIDED_MAX_RADIUS:
+        raise ValueError("radius %r (an integer, 1 to %d)" % (radius, IMG_GUIDED_MAX_RADIUS))
+    if not finite(eps) or not np.float32(eps) > 0:
+        raise ValueError("eps %r (must be finite and > 0)" % (eps,))
+    if not finite(detail):
+        raise ValueError("detail %r (must be finite)" % (detail,))
+    if coupling not in ("channel", "vector"):
+        raise ValueError("coupling %r (channel or vector)" % (coupling,))
+    if route not in (0, 1, 2):
+        raise ValueError("route %r (0: the library's choice, 1: two launches, 2: one launch on LDS tiles)" % (route,))
+    if route == 2 and int(radius) > IMG_GUIDED_FUSED_RADIUS:
+        raise ValueError("route 2 takes a radius up to %d, got %d" % (IMG_GUIDED_FUSED_RADIUS, int(radius)))
+    return int(radius), float(eps), float(detail), coupling, int(route)
 
 
 class Context:
@@ -468,6 +499,19 @@ class DeviceImage:
         g, t, residual, coupling, route = wavelet_args(gains, thresholds, residual, coupling, route)
         return self._new(load().ics_img_wavelet_equalize, int(g.size), _ptr(g), None if t is None else _ptr(t), residual,
                          int(coupling == "vector"), route)
+
+    def guided_filter(self, radius, eps, detail=0.0, coupling="vector", route=0):
+        """Guided filter with the picture as its own guide (He, Sun, Tang): the edge-preserving base layer q of the
+        (2 radius + 1)^2 box windows (radius 1 .. IMG_GUIDED_MAX_RADIUS), and q + detail * (picture - q): detail 0 returns q (a
+        smoothing that keeps edges), 0 < detail < 1 smooths texture, detail > 1 lifts it without halos around edges.  eps is the
+        variance (pixel values in [0, 1]) below which a window counts as flat and is averaged: 1e-2 smooths all but strong edges,
+        1e-4 keeps fine texture.  coupling "channel": every channel is its own guide; "vector": the RGB pixel is the guide, one set
+        of edges for the three channels (csrc/ics_img_guided.hip; restated in tests/guided_ref.py).  route 0: the library's choice,
+        1: two launches, 2: one launch with the coefficients in LDS (radius <= IMG_GUIDED_FUSED_RADIUS); all give identical bits.
+        ValueError (before any native call): a radius that is no integer in 1 .. 32, eps not finite or <= 0, detail not finite,
+        unknown coupling or route."""
+        radius, eps, detail, coupling, route = guided_args(radius, eps, detail, coupling, route)
+        return self._new(load().ics_img_guided, radius, eps, detail, int(coupling == "vector"), route)
 
     def close(self):
         if self._h:

@@ -16,8 +16,9 @@ Same names and argument meaning as the reference (file:line in /root/reference/l
 The filters run on the GPU through libics_hip.so in float64 like the reference (scipy's
 convolve2d(mode="same", boundary="symm")); there is no CPU fallback for them.  Given a `lib._native.DeviceImage`
 (H x W x 3 float32 in HBM) instead of a 2-D array, the four filters work on it there, every channel on its own
-in float32, and return a new DeviceImage (csrc/ics_img_filters.hip): no transfer, no synchronisation; `tv_denoise` and
-`wavelet_equalizer` (not in the reference; csrc/ics_img_tvdenoise.hip, csrc/ics_img_wavelet.hip) work on such an image or on an
+in float32, and return a new DeviceImage (csrc/ics_img_filters.hip): no transfer, no synchronisation; `tv_denoise`,
+`wavelet_equalizer` and `guided_filter` (not in the reference; csrc/ics_img_tvdenoise.hip, csrc/ics_img_wavelet.hip,
+csrc/ics_img_guided.hip) work on such an image or on an
 H x W x 3 array.  The colour tools of
 the reference (Lagrange_interpolation, grey_point, auto_vibrance, overlay, blending) and its dead
 code (divTV, gradTVEM) are outside the deconvolution path and are not provided.
@@ -168,6 +169,32 @@ def wavelet_equalizer(src, gains, thresholds=None, residual=1.0, coupling="vecto
     img = _native.DeviceImage.from_host(np.ascontiguousarray(arr, dtype=np.float32))
     try:
         res = img.wavelet_equalize(gains, thresholds, residual, coupling)
+    finally:
+        img.close()
+    try:
+        return res.to_host()
+    finally:
+        res.close()
+
+
+def guided_filter(src, radius, eps, detail=0.0, coupling="vector"):
+    """Not in the reference's lib/utils.py (its bilateral_filter serves img/bilateral-unsharp-mask/ as the edge-aware base of a
+    sharpening, at (2 radius + 1)^2 exponentials per pixel): He, Sun and Tang's guided filter with the picture as its own guide.
+    q is the edge-preserving base layer of the (2 radius + 1)^2 box windows, radius 1 .. 32; the result is q + detail * (src - q):
+    detail 0 the base layer itself, detail 1.5 with radius 16 and eps 1e-3 a halo-free sharpening of a deblurred frame, detail 0.5
+    with radius 8 and eps 1e-2 a smoothing that leaves edges alone.  eps is the variance below which a window counts as flat.
+    coupling "vector" guides with the RGB pixel (one set of edges for all channels), "channel" every channel by itself.  A
+    `lib._native.DeviceImage` gives a new DeviceImage (nothing crosses PCIe); an H x W x 3 array is uploaded once and the float32
+    result downloaded once (`DeviceImage.guided_filter`, csrc/ics_img_guided.hip)."""
+    if isinstance(src, _native.DeviceImage):
+        return src.guided_filter(radius, eps, detail, coupling)
+    arr = np.asarray(src)
+    if arr.ndim != 3 or arr.shape[2] != 3:
+        raise ValueError("expected a DeviceImage or an H x W x 3 array, got shape %s" % (arr.shape,))
+    _native.guided_args(radius, eps, detail, coupling)                  # refused before anything is uploaded
+    img = _native.DeviceImage.from_host(np.ascontiguousarray(arr, dtype=np.float32))
+    try:
+        res = img.guided_filter(radius, eps, detail, coupling)
     finally:
         img.close()
     try:

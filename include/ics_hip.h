@@ -414,6 +414,24 @@ int ics_img_tv_denoise(const ics_img *src, float weight, int iterations, int cou
 #define ICS_IMG_WAVELET_FUSED 3
 int ics_img_wavelet_equalize(const ics_img *src, int scales, const float *gains, const float *thresholds /* may be NULL */,
                              float residual, int coupling, int route, ics_img **out);
+/* Guided filter of a device image with the picture as its own guide (He, Sun, Tang): an edge-preserving base layer q from box means
+ * and one closed-form solve per pixel, and the detail src - q scaled back onto it.  I' = src - 0.5;
+ *   mean(x) = the sum of x over the (2 radius + 1)^2 window clipped to the picture / its pixel count; a sum runs along x first, then
+ *     along y, the taps added from zero in ascending offset order, without running sums
+ *   coupling 0 (channel), per channel: mu = mean(I'), v = mean(I'^2) - mu mu, a = v / (v + eps), b = mu - a mu
+ *   coupling 1 (vector): mu_i = mean(I'_i), S_ij = mean(I'_i I'_j) - mu_i mu_j, M = S + eps E, c_ij its six cofactors,
+ *     det = (M00 c00 + M01 c01) + M02 c02, A_ij = [i = j] - eps (c_ij / det) (= M^-1 S, symmetric), b_i = mu_i - sum_j A_ij mu_j:
+ *     one set of edges for the three channels
+ *   q = mean(a) I' + mean(b) + 0.5 (vector: mean(A) I' + mean(b) + 0.5);  out = q when detail == 0, else q + detail (src - q).
+ * detail above 1 lifts texture without halos at the edges, between 0 and 1 smooths it; eps is the variance (of values in [0, 1])
+ * below which a window counts as flat.  No FMA, IEEE division (restated in tests/guided_ref.py).  route 1: two launches, any radius
+ * up to ICS_IMG_GUIDED_MAX_RADIUS; 2: one launch with the coefficients kept in LDS, radius <= ICS_IMG_GUIDED_FUSED_RADIUS; 0: the
+ * library's choice.  The routes give identical bits, and so do two runs.  Queued like the other image filters; src is
+ * not written.  ICS_EINVAL: radius outside 1 .. 32, eps not finite or <= 0, detail not finite, unknown coupling or route, route 2
+ * with a radius above ICS_IMG_GUIDED_FUSED_RADIUS. */
+#define ICS_IMG_GUIDED_MAX_RADIUS 32
+#define ICS_IMG_GUIDED_FUSED_RADIUS 8
+int ics_img_guided(const ics_img *src, int radius, float eps, float detail, int coupling, int route, ics_img **out);
 /* richardson_lucy_MM(image[iy:iy+M, ix:ix+N], u[uy:uy+uM, ux:ux+uN], psf, ...) with both windows taken from device
  * images (deconvolve.py:277-313 passes such views); psf is a host MK*MK*3 array as in ics_rl_upload. */
 int ics_rl_upload_img(ics_rl *job, const ics_img *image, int iy, int ix, const ics_img *u, int uy, int ux, const float *psf);

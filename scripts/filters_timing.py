@@ -1,6 +1,6 @@
 """Timing of the lib/utils.py filters on one seeded SIZE x SIZE RGB float32 picture (GPU box), one JSON line:
 
-    python scripts/filters_timing.py [SIZE=4096]
+    python scripts/filters_timing.py [SIZE=4096] [guided]       ("guided": that section alone)
 
   resident   the filters on a DeviceImage in HBM (csrc/ics_img_filters.hip): device time of the kernels (HIP events around them,
              ics_ctx_last_kernel_ms; warm, median of 25) and wall time of the queued call up to a stream synchronise
@@ -19,6 +19,11 @@
              and route 2 (the first 3 scales fused on LDS tiles: 3 + 4 + 3 = 10 transits): kernel ms, median and minimum of 9 rounds
              in which the routes alternate, and the bytes per second each achieves on its own transit count; "auto" names the route
              that route=0 takes at this size
+  guided     DeviceImage.guided_filter (csrc/ics_img_guided.hip), eps 1e-3, detail 1.5, radius 4, 8, 16, 32, both couplings, route 1
+             (two launches: 84 B/px "channel", 108 B/px "vector") and route 2 (one launch, coefficients in LDS, radius <= 8: 24 B/px):
+             kernel ms, median and minimum of 9 rounds in which the routes alternate, and TB/s on the 84 / 108 B/px model; "auto" is
+             what route=0 takes.  For context the bilateral filter at the same radius (std_i 0.1, std_s radius / 2), or "refused"
+             where its tile does not fit
   checks     the resident USM must not take longer than the three float64 calls, in kernel time and in wall time (a guard against a
              broken kernel, not a target); the exit status is 1 if one of them fails
 Starts no child process; a job script puts its own time limit around it."""
@@ -34,10 +39,45 @@ sys.path.insert(0, os.path.join(ROOT, "image-cases-studies_amd"))
 from lib import _native, utils  # noqa: E402
 
 HBM_PEAK = 8e12
-REPS_RESIDENT, REPS_F64, REPS_TV, REPS_WAVELET = 25, 5, 9, 9
+REPS_RESIDENT, REPS_F64, REPS_TV, REPS_WAVELET, REPS_GUIDED = 25, 5, 9, 9, 9
 TV_WEIGHT, TV_ITERATIONS = 0.1, 50
 WAVELET_GAINS, WAVELET_THRESHOLDS = (1.0, 1.6, 1.8, 1.4, 1.0), (0.03, 0.015, 0.0, 0.0, 0.0)
 WAVELET_TRANSITS = {1: 18, 2: 10}
+
+
+GUIDED_RADII, GUIDED_EPS, GUIDED_DETAIL = (4, 8, 16, 32), 1e-3, 1.5
+GUIDED_BYTES = {"channel": 84, "vector": 108}
+
+
+def guided_section(img, ctx, size):
+    res = {"eps": GUIDED_EPS, "detail": GUIDED_DETAIL, "model_bytes_per_px": GUIDED_BYTES}
+    for r in GUIDED_RADII:
+        for coupling in ("channel", "vector"):
+            times = {route: [] for route in ((1, 2, 0) if r <= _native.IMG_GUIDED_FUSED_RADIUS else (1, 0))}
+            for route in times:
+                img.guided_filter(r, GUIDED_EPS, GUIDED_DETAIL, coupling, route=route).close()     # warm
+            ctx.synchronize()
+            for _ in range(REPS_GUIDED):                   # the routes alternate within a round
+                for route in times:
+                    out = img.guided_filter(r, GUIDED_EPS, GUIDED_DETAIL, coupling, route=route)
+                    times[route].append(ctx.last_kernel_ms())
+                    out.close()
+            for route, ms in times.items():
+                med = float(np.median(ms))
+                res["r%d_%s_%s" % (r, coupling, {1: "route1", 2: "route2", 0: "auto"}[route])] = {
+                    "kernel_ms": round(med, 4), "min_ms": round(float(np.min(ms)), 4),
+                    "TBps_on_model": round(GUIDED_BYTES[coupling] * size * size / (med * 1e-3) / 1e12, 3)}
+        try:
+            img.bilateral(r, 0.1, r / 2.0).close()         # warm
+            ms = []
+            for _ in range(REPS_GUIDED):
+                out = img.bilateral(r, 0.1, r / 2.0)
+                ms.append(ctx.last_kernel_ms())
+                out.close()
+            res["r%d_bilateral" % r] = {"kernel_ms": round(float(np.median(ms)), 4), "min_ms": round(float(np.min(ms)), 4)}
+        except (ValueError, RuntimeError) as exc:
+            res["r%d_bilateral" % r] = "refused: %s" % exc
+    return res
 
 
 def main():
@@ -46,6 +86,9 @@ def main():
     rng = np.random.default_rng(0)
     pic = rng.random((size, size, 3), dtype=np.float32)
     img = _native.DeviceImage.from_host(pic, ctx)
+    if sys.argv[2:] == ["guided"]:
+        print(json.dumps({"size": size, "device": ctx.name, "guided": guided_section(img, ctx, size)}))
+        return 0
     ops = {"usm_gauss15": lambda s: utils.USM(s, 15, 2.5, 0.7, method="gauss"),
            "usm_bessel15": lambda s: utils.USM(s, 15, 3.0, 0.7, method="bessel"),
            "bilateral_r5": lambda s: utils.bilateral_filter(s, 5, 0.1, 2.0),
@@ -113,6 +156,7 @@ def main():
             if route:
                 row["TBps_on_its_transits"] = round(WAVELET_TRANSITS[route] * 12 * size * size / (med * 1e-3) / 1e12, 3)
             res["wavelet_equalizer"]["%s_%s" % (coupling, {1: "route1", 2: "route2", 0: "auto"}[route])] = row
+    res["guided"] = guided_section(img, ctx, size)
     res["checks"] = {"%s_%s" % (name, what): res["resident"][name][what] <= res["per_channel_f64"][name][what]
                      for name in ("usm_gauss15", "usm_bessel15") for what in ("kernel_ms", "wall_ms")}
     print(json.dumps(res))
