@@ -1,7 +1,7 @@
 // ics_host.h -- what the host translation units of libics_hip.so share (ics_context.hip, ics_job.hip, ics_route.hip, ics_run.hip,
 // ics_ops.hip, ics_images.hip, ics_group.hip): the error channel, the context with its block pool, the device-resident job, device
 // images, the event-bracket profiler, the route of a run, and the helpers that cross a unit boundary (namespace ics_host).
-// Host side only: kernel units include ics_kernels.h / ics_common.h, not this.
+// Host side only: kernel units include ics_kernels.h / ics_common.h (the device-image filter units through ics_img_px.h), not this.
 #pragma once
 #include <math.h>
 #include <stdarg.h>

@@ -1,5 +1,5 @@
 // ics_images.hip -- the ics_img_* entries of the C ABI (include/ics_hip.h).  Host side only; kernels live in ics_img.hip / ics_img_filters.hip /
-// ics_img_tvdenoise.hip / ics_img_wavelet.hip / ics_img_guided.hip / ics_resize.hip.
+// ics_img_tvdenoise.hip / ics_img_wavelet.hip / ics_img_guided.hip (what these four share: ics_img_px.h) / ics_resize.hip.
 #include "ics_host.h"
 
 using namespace ics_host;
@@ -26,6 +26,47 @@ extern "C" void ics_img_destroy(ics_img* m) {
   m->ctx->pool.release(m->d);   // (operations on the image are queued on the context's stream; so is whatever reuses the block)
   delete m;
 }
+
+namespace {
+// An entry that makes a new image: *out, up to four pool temporaries and the ev0 / ev1 bracket around its kernels.  *out is NULL from
+// the start and stays NULL unless finish() returns ICS_OK; whatever is still held when the scope ends, on any return, goes back to
+// the pool (queued work of a context runs on its one stream: so does whatever reuses the blocks).
+struct ImgOp {
+  ics_ctx* c; ics_img** out; const char* name;
+  void* tmp[4] = {nullptr, nullptr, nullptr, nullptr};
+  int ntmp = 0;
+  bool bracket = false, ok = false;
+  ImgOp(ics_ctx* ctx, ics_img** o, const char* entry) : c(ctx), out(o), name(entry) {}   // (*out: cleared by check_new)
+  ImgOp(const ImgOp&) = delete;
+  ~ImgOp() { release(); if (!ok) { ics_img_destroy(*out); *out = nullptr; } }
+  void release() { for (int i = 0; i < ntmp; ++i) c->pool.release(tmp[i]); ntmp = 0; }
+  hipError_t alloc(void** p, size_t bytes) {
+    if (ntmp == 4) return hipErrorInvalidValue;
+    hipError_t e = c->pool.alloc(p, bytes);
+    if (e == hipSuccess) tmp[ntmp++] = *p;
+    return e;
+  }
+  hipError_t begin() { bracket = true; return hipEventRecord(c->ev0, c->stream); }
+  int finish(hipError_t e) {
+    if (bracket && e == hipSuccess) e = hipEventRecord(c->ev1, c->stream);
+    if (bracket && e == hipSuccess) c->ev_pending = true;
+    release();
+    ok = e == hipSuccess;   // (otherwise the destructor destroys *out)
+    return ok ? ICS_OK : ics_set_error(e == hipErrorOutOfMemory ? ICS_ENOMEM : ICS_EHIP, "%s: %s", name, hipGetErrorString(e));
+  }
+};
+int check_new(const void* src, ics_img** out) {   // the arguments every such entry has; *out is NULL from here on unless the entry succeeds
+  if (out) *out = nullptr;
+  return src && out ? ICS_OK : ics_set_error(ICS_EINVAL, "NULL argument");
+}
+int check_coupling(int coupling) {
+  return coupling == 0 || coupling == 1 ? ICS_OK : ics_set_error(ICS_EINVAL, "coupling %d (0 = channel, 1 = vector)", coupling);
+}
+int check_route(int route, const char* one, const char* two) {
+  return route >= 0 && route <= 2 ? ICS_OK : ics_set_error(ICS_EINVAL, "route %d (0 = auto, 1 = %s, 2 = %s)", route, one, two);
+}
+}  // namespace
+
 extern "C" int ics_img_shape(const ics_img* m, int* H, int* W) {
   if (!m) return ics_set_error(ICS_EINVAL, "image is NULL");
   if (H) *H = m->H;
@@ -62,22 +103,20 @@ extern "C" int ics_img_download(const ics_img* m, float* host) {
   return ICS_OK;
 }
 extern "C" int ics_img_pad_edge(const ics_img* src, int top, int bottom, int left, int right, ics_img** out) {
-  if (!src || !out) return ics_set_error(ICS_EINVAL, "NULL argument");
+  RC(check_new(src, out));
   if (top < 0 || bottom < 0 || left < 0 || right < 0) return ics_set_error(ICS_EINVAL, "negative padding");
+  ImgOp op(src->ctx, out, "img_pad_edge");
   RC(img_new(src->ctx, src->H + top + bottom, src->W + left + right, out));
-  hipError_t e = ics_launch_img_pad_edge(src->d, src->H, src->W, (*out)->d, top, bottom, left, right, src->ctx->stream);
-  if (e != hipSuccess) { ics_img_destroy(*out); *out = nullptr; return ics_set_error(ICS_EHIP, "img_pad_edge: %s", hipGetErrorString(e)); }
-  return ICS_OK;
+  return op.finish(ics_launch_img_pad_edge(src->d, src->H, src->W, (*out)->d, top, bottom, left, right, src->ctx->stream));
 }
 
 extern "C" int ics_img_crop(const ics_img* src, int y0, int x0, int H, int W, ics_img** out) {
-  if (!src || !out) return ics_set_error(ICS_EINVAL, "NULL argument");
+  RC(check_new(src, out));
   if (!rect_ok(src, y0, x0, H, W)) return ics_set_error(ICS_EINVAL, "crop [%d:%d, %d:%d] outside a %d x %d image", y0, y0 + H, x0, x0 + W, src->H, src->W);
+  ImgOp op(src->ctx, out, "img_crop");
   RC(img_new(src->ctx, H, W, out));
-  hipError_t e = hipMemcpy2DAsync((*out)->d, (size_t)W * 12, src->d + ((size_t)y0 * src->W + x0) * 3, (size_t)src->W * 12, (size_t)W * 12, H,
-                                  hipMemcpyDeviceToDevice, src->ctx->stream);
-  if (e != hipSuccess) { ics_img_destroy(*out); *out = nullptr; return ics_set_error(ICS_EHIP, "img_crop: %s", hipGetErrorString(e)); }
-  return ICS_OK;
+  return op.finish(hipMemcpy2DAsync((*out)->d, (size_t)W * 12, src->d + ((size_t)y0 * src->W + x0) * 3, (size_t)src->W * 12, (size_t)W * 12, H,
+                                    hipMemcpyDeviceToDevice, src->ctx->stream));
 }
 extern "C" int ics_img_paste(ics_img* dst, int y0, int x0, const ics_img* src) {
   if (!src || !dst) return ics_set_error(ICS_EINVAL, "NULL argument");
@@ -97,13 +136,14 @@ extern "C" int ics_img_gamma(ics_img* m, float div, float exponent, float mul, i
 // deconvolve.py:245-249 on a device image: float64 inside (as skimage / scipy compute), rounded to float32 like the
 // reference's `.astype(np.float32)`
 extern "C" int ics_img_resize(const ics_img* src, int OH, int OW, ics_img** out) {
-  if (!src || !out) return ics_set_error(ICS_EINVAL, "NULL argument");
+  RC(check_new(src, out));
   if (OH < 1 || OW < 1 || src->H < 2 || src->W < 2) return ics_set_error(ICS_EINVAL, "bad sizes");
   ics_ctx* c = src->ctx;
   HIPCHK(hipSetDevice(c->device));
   hipStream_t s = c->stream;
   const int H = src->H, W = src->W;
   if (H == OH && W == OW) return ics_img_crop(src, 0, 0, H, W, out);
+  ImgOp op(c, out, "img_resize");
   RC(img_new(c, OH, OW, out));
   auto weights = [](double sigma, std::vector<double>& w) {
     const int r = (int)(4.0 * sigma + 0.5);
@@ -119,8 +159,8 @@ extern "C" int ics_img_resize(const ics_img* src, int OH, int OW, ics_img** out)
   if (sy > 1e-15) ry = weights(sy, hwy);
   if (sx > 1e-15) rx = weights(sx, hwx);
   double *scr = nullptr, *dw = nullptr;          // (the float32 frames are read and written by the float64 pipeline's first and last pass)
-  hipError_t e = c->pool.alloc((void**)&scr, ics_resize_scratch_doubles(H, W, 3) * 8);
-  if (e == hipSuccess) e = c->pool.alloc((void**)&dw, (hwy.size() + hwx.size() + 1) * 8);
+  hipError_t e = op.alloc((void**)&scr, ics_resize_scratch_doubles(H, W, 3) * 8);
+  if (e == hipSuccess) e = op.alloc((void**)&dw, (hwy.size() + hwx.size() + 1) * 8);
   const size_t nw = hwy.size() + hwx.size();
   bool staged = false;
   if (e == hipSuccess && nw) {
@@ -141,15 +181,14 @@ extern "C" int ics_img_resize(const ics_img* src, int OH, int OW, ics_img** out)
   }
   if (e == hipSuccess) e = ics_launch_resize_f32(src->d, H, W, 3, hwy.empty() ? nullptr : dw, ry, hwx.empty() ? nullptr : dw + hwy.size(), rx, scr, (*out)->d, OH, OW, s);
   if (e == hipSuccess && nw && !staged) e = hipStreamSynchronize(s);   // pageable host vectors are released below
-  c->pool.release(scr); c->pool.release(dw);
-  if (e != hipSuccess) { ics_img_destroy(*out); *out = nullptr; return ics_set_error(e == hipErrorOutOfMemory ? ICS_ENOMEM : ICS_EHIP, "img_resize: %s", hipGetErrorString(e)); }
-  return ICS_OK;
+  return op.finish(e);
 }
 
 // ---- lib/utils.py filters on device images (csrc/ics_img_filters.hip) ----------------------------------------------------------
 // convolve2d(mode="same", boundary="symm") per channel [+ USM epilogue]; the kernels take the taps reversed (ics_img_filters.hip)
 static int img_conv_common(const ics_img* src, const float* kern, int KH, int KW, int usm, float amount, ics_img** out) {
-  if (!src || !kern || !out) return ics_set_error(ICS_EINVAL, "NULL argument");
+  RC(check_new(src, out));
+  if (!kern) return ics_set_error(ICS_EINVAL, "NULL argument");
   if (KH < 1 || KW < 1) return ics_set_error(ICS_EINVAL, "bad kernel size %d x %d", KH, KW);
   ics_ctx* c = src->ctx;
   const int H = src->H, W = src->W;
@@ -168,13 +207,14 @@ static int img_conv_common(const ics_img* src, const float* kern, int KH, int KW
   } else {
     for (int v = 0; v < KH; ++v) for (int u = 0; u < KW; ++u) t.push_back(kern[(size_t)(KH - 1 - v) * KW + (KW - 1 - u)]);
   }
+  ImgOp op(c, out, "img_convolve");
   RC(img_new(c, H, W, out));
   hipStream_t s = c->stream;
   float *dk = nullptr, *tmp = nullptr;
-  hipError_t e = c->pool.alloc((void**)&dk, t.size() * 4);
-  if (e == hipSuccess && sep) e = c->pool.alloc((void**)&tmp, (size_t)H * W * 12);
+  hipError_t e = op.alloc((void**)&dk, t.size() * 4);
+  if (e == hipSuccess && sep) e = op.alloc((void**)&tmp, (size_t)H * W * 12);
   if (e == hipSuccess) e = put_table(c, dk, t);
-  if (e == hipSuccess) e = hipEventRecord(c->ev0, s);
+  if (e == hipSuccess) e = op.begin();
   if (e == hipSuccess) {
     if (sep) {   // rows (1 x KW), then columns (KH x 1) with the USM epilogue against the original frame
       e = ics_launch_img_conv_rows(src->d, H, W, dk, 1, KW, tmp, src->d, 0, 0.f, s);
@@ -185,11 +225,7 @@ static int img_conv_common(const ics_img* src, const float* kern, int KH, int KW
       e = ics_launch_img_conv_rows(src->d, H, W, dk, KH, KW, (*out)->d, src->d, usm, amount, s);
     }
   }
-  if (e == hipSuccess) e = hipEventRecord(c->ev1, s);
-  if (e == hipSuccess) c->ev_pending = true;
-  c->pool.release(dk); c->pool.release(tmp);   // (queued work of this context runs on its one stream: so does whatever reuses the blocks)
-  if (e != hipSuccess) { ics_img_destroy(*out); *out = nullptr; return ics_set_error(e == hipErrorOutOfMemory ? ICS_ENOMEM : ICS_EHIP, "img_convolve: %s", hipGetErrorString(e)); }
-  return ICS_OK;
+  return op.finish(e);
 }
 extern "C" int ics_img_convolve(const ics_img* src, const float* kern, int KH, int KW, ics_img** out) {
   return img_conv_common(src, kern, KH, KW, 0, 0.f, out);
@@ -199,7 +235,7 @@ extern "C" int ics_img_usm(const ics_img* src, const float* kern, int KH, int KW
 }
 
 extern "C" int ics_img_bilateral(const ics_img* src, int radius, float std_i, float std_s, ics_img** out) {
-  if (!src || !out) return ics_set_error(ICS_EINVAL, "NULL argument");
+  RC(check_new(src, out));
   if (radius < 0) return ics_set_error(ICS_EINVAL, "radius %d", radius);
   if (!(std_i > 0.f) || !(std_s > 0.f)) return ics_set_error(ICS_EINVAL, "std_i = %g, std_s = %g (both must be positive)", (double)std_i, (double)std_s);
   if (radius > 4096 || ics_img_bilateral_lds(radius) > 160 * 1024) return ics_set_error(ICS_ENOSUP, "radius %d too large for the LDS tile (up to 34)", radius);
@@ -208,18 +244,14 @@ extern "C" int ics_img_bilateral(const ics_img* src, int radius, float std_i, fl
   std::vector<float> ws((size_t)D * D);   // x offset j slow, y offset i fast: the reference's offset order
   for (int j = -radius; j <= radius; ++j)
     for (int i = -radius; i <= radius; ++i) ws[(size_t)(j + radius) * D + (i + radius)] = (float)exp((double)(i * i + j * j) * (-1.0 / (2.0 * (double)std_s * (double)std_s)));
+  ImgOp op(c, out, "img_bilateral");
   RC(img_new(c, H, W, out));
-  hipStream_t s = c->stream;
   float* dws = nullptr;
-  hipError_t e = c->pool.alloc((void**)&dws, ws.size() * 4);
+  hipError_t e = op.alloc((void**)&dws, ws.size() * 4);
   if (e == hipSuccess) e = put_table(c, dws, ws);
-  if (e == hipSuccess) e = hipEventRecord(c->ev0, s);
-  if (e == hipSuccess) e = ics_launch_img_bilateral(src->d, H, W, radius, (float)(-1.0 / (2.0 * (double)std_i * (double)std_i)), dws, (*out)->d, s);
-  if (e == hipSuccess) e = hipEventRecord(c->ev1, s);
-  if (e == hipSuccess) c->ev_pending = true;
-  c->pool.release(dws);
-  if (e != hipSuccess) { ics_img_destroy(*out); *out = nullptr; return ics_set_error(e == hipErrorOutOfMemory ? ICS_ENOMEM : ICS_EHIP, "img_bilateral: %s", hipGetErrorString(e)); }
-  return ICS_OK;
+  if (e == hipSuccess) e = op.begin();
+  if (e == hipSuccess) e = ics_launch_img_bilateral(src->d, H, W, radius, (float)(-1.0 / (2.0 * (double)std_i * (double)std_i)), dws, (*out)->d, c->stream);
+  return op.finish(e);
 }
 
 // ---- TV denoising of a device image (csrc/ics_img_tvdenoise.hip) ---------------------------------------------------------------
@@ -228,30 +260,27 @@ extern "C" int ics_img_bilateral(const ics_img* src, int radius, float std_i, fl
 // one 32 x 32 tile per workgroup leaves three quarters of the compute units idle there.
 static const long TV_BLOCK_MIN_PIXELS = 512L * 512L;
 extern "C" int ics_img_tv_denoise(const ics_img* src, float weight, int iterations, int coupling, int route, ics_img** out) {
-  if (!src || !out) return ics_set_error(ICS_EINVAL, "NULL argument");
+  RC(check_new(src, out));
   if (!(weight > 0.f) || !std::isfinite(weight)) return ics_set_error(ICS_EINVAL, "weight = %g (must be positive and finite)", (double)weight);
   if (iterations < 0) return ics_set_error(ICS_EINVAL, "iterations = %d", iterations);
-  if (coupling != 0 && coupling != 1) return ics_set_error(ICS_EINVAL, "coupling %d (0 = channel, 1 = vector)", coupling);
-  if (route < 0 || route > 2) return ics_set_error(ICS_EINVAL, "route %d (0 = auto, 1 = per iteration, 2 = blocked)", route);
+  RC(check_coupling(coupling));
+  RC(check_route(route, "per iteration", "blocked"));
   ics_ctx* c = src->ctx;
   const int H = src->H, W = src->W;
   if (route == 0) route = (long)H * W >= TV_BLOCK_MIN_PIXELS ? 2 : 1;
+  ImgOp op(c, out, "img_tv_denoise");
   RC(img_new(c, H, W, out));
   hipStream_t s = c->stream;
   float* q[4] = {nullptr, nullptr, nullptr, nullptr};
   hipError_t e = hipSuccess;
   const int frames = iterations ? 2 * ics_img_tv_pairs(iterations, route) : 0;
-  for (int i = 0; i < frames && e == hipSuccess; ++i) e = c->pool.alloc((void**)&q[i], (size_t)H * W * 12);
-  if (e == hipSuccess) e = hipEventRecord(c->ev0, s);
+  for (int i = 0; i < frames && e == hipSuccess; ++i) e = op.alloc((void**)&q[i], (size_t)H * W * 12);
+  if (e == hipSuccess) e = op.begin();
   if (e == hipSuccess) {
     if (iterations == 0) e = hipMemcpyAsync((*out)->d, src->d, (size_t)H * W * 12, hipMemcpyDeviceToDevice, s);
     else e = ics_launch_img_tv_denoise(src->d, H, W, weight, iterations, coupling, route, q, (*out)->d, s);
   }
-  if (e == hipSuccess) e = hipEventRecord(c->ev1, s);
-  if (e == hipSuccess) c->ev_pending = true;
-  for (int i = 0; i < 4; ++i) c->pool.release(q[i]);   // (reused on the context's one stream, behind these kernels)
-  if (e != hipSuccess) { ics_img_destroy(*out); *out = nullptr; return ics_set_error(e == hipErrorOutOfMemory ? ICS_ENOMEM : ICS_EHIP, "img_tv_denoise: %s", hipGetErrorString(e)); }
-  return ICS_OK;
+  return op.finish(e);
 }
 
 // ---- wavelet equaliser of a device image (csrc/ics_img_wavelet.hip) -------------------------------------------------------------
@@ -260,7 +289,7 @@ extern "C" int ics_img_tv_denoise(const ics_img* src, float weight, int iteratio
 // the table (routes alternating) from which a size rule is to be set here.  Both routes are callable through `route`.
 extern "C" int ics_img_wavelet_equalize(const ics_img* src, int scales, const float* gains, const float* thresholds, float residual, int coupling,
                                         int route, ics_img** out) {
-  if (!src || !out) return ics_set_error(ICS_EINVAL, "NULL argument");
+  RC(check_new(src, out));
   if (scales < 1 || scales > ICS_IMG_WAVELET_MAX_SCALES) return ics_set_error(ICS_EINVAL, "scales = %d (1 .. %d)", scales, ICS_IMG_WAVELET_MAX_SCALES);
   if (!gains) return ics_set_error(ICS_EINVAL, "gains is NULL");
   for (int j = 0; j < scales; ++j) {
@@ -269,52 +298,43 @@ extern "C" int ics_img_wavelet_equalize(const ics_img* src, int scales, const fl
       return ics_set_error(ICS_EINVAL, "thresholds[%d] = %g (must be finite and >= 0)", j, (double)thresholds[j]);
   }
   if (!std::isfinite(residual)) return ics_set_error(ICS_EINVAL, "residual = %g (must be finite)", (double)residual);
-  if (coupling != 0 && coupling != 1) return ics_set_error(ICS_EINVAL, "coupling %d (0 = channel, 1 = vector)", coupling);
-  if (route < 0 || route > 2) return ics_set_error(ICS_EINVAL, "route %d (0 = auto, 1 = per scale, 2 = first scales fused)", route);
+  RC(check_coupling(coupling));
+  RC(check_route(route, "per scale", "first scales fused"));
   ics_ctx* c = src->ctx;
   const int H = src->H, W = src->W;
   if (route == 0) route = 1;
+  ImgOp op(c, out, "img_wavelet_equalize");
   RC(img_new(c, H, W, out));
-  hipStream_t s = c->stream;
   float* tmp[2] = {nullptr, nullptr};
   hipError_t e = hipSuccess;
   const int frames = ics_img_wavelet_frames(scales, route);
-  for (int i = 0; i < frames && e == hipSuccess; ++i) e = c->pool.alloc((void**)&tmp[i], (size_t)H * W * 12);
-  if (e == hipSuccess) e = hipEventRecord(c->ev0, s);
-  if (e == hipSuccess) e = ics_launch_img_wavelet(src->d, H, W, scales, gains, thresholds, residual, coupling, route, tmp, (*out)->d, s);
-  if (e == hipSuccess) e = hipEventRecord(c->ev1, s);
-  if (e == hipSuccess) c->ev_pending = true;
-  for (int i = 0; i < 2; ++i) c->pool.release(tmp[i]);   // (reused on the context's one stream, behind these kernels)
-  if (e != hipSuccess) { ics_img_destroy(*out); *out = nullptr; return ics_set_error(e == hipErrorOutOfMemory ? ICS_ENOMEM : ICS_EHIP, "img_wavelet_equalize: %s", hipGetErrorString(e)); }
-  return ICS_OK;
+  for (int i = 0; i < frames && e == hipSuccess; ++i) e = op.alloc((void**)&tmp[i], (size_t)H * W * 12);
+  if (e == hipSuccess) e = op.begin();
+  if (e == hipSuccess) e = ics_launch_img_wavelet(src->d, H, W, scales, gains, thresholds, residual, coupling, route, tmp, (*out)->d, c->stream);
+  return op.finish(e);
 }
 
 // ---- guided filter of a device image (csrc/ics_img_guided.hip) ------------------------------------------------------------------
 // route 0: the two-launch route at every radius and size ("Guided filter": the measured table).
 extern "C" int ics_img_guided(const ics_img* src, int radius, float eps, float detail, int coupling, int route, ics_img** out) {
-  if (out) *out = nullptr;
-  if (!src || !out) return ics_set_error(ICS_EINVAL, "NULL argument");
+  RC(check_new(src, out));
   if (radius < 1 || radius > ICS_IMG_GUIDED_MAX_RADIUS) return ics_set_error(ICS_EINVAL, "radius = %d (1 .. %d)", radius, ICS_IMG_GUIDED_MAX_RADIUS);
   if (!std::isfinite(eps) || !(eps > 0.f)) return ics_set_error(ICS_EINVAL, "eps = %g (must be finite and > 0)", (double)eps);
   if (!std::isfinite(detail)) return ics_set_error(ICS_EINVAL, "detail = %g (must be finite)", (double)detail);
-  if (coupling != 0 && coupling != 1) return ics_set_error(ICS_EINVAL, "coupling %d (0 = channel, 1 = vector)", coupling);
-  if (route < 0 || route > 2) return ics_set_error(ICS_EINVAL, "route %d (0 = auto, 1 = two launches, 2 = one launch)", route);
+  RC(check_coupling(coupling));
+  RC(check_route(route, "two launches", "one launch"));
   if (route == 2 && radius > ICS_IMG_GUIDED_FUSED_RADIUS)
     return ics_set_error(ICS_EINVAL, "route 2 takes a radius up to %d, got %d", ICS_IMG_GUIDED_FUSED_RADIUS, radius);
   ics_ctx* c = src->ctx;
   const int H = src->H, W = src->W;
   if (route == 0) route = 1;
+  ImgOp op(c, out, "img_guided");
   RC(img_new(c, H, W, out));
-  hipStream_t s = c->stream;
   float* coef = nullptr;
   hipError_t e = hipSuccess;
   const size_t floats = ics_img_guided_coef_floats(H, W, coupling, route);
-  if (floats) e = c->pool.alloc((void**)&coef, floats * sizeof(float));
-  if (e == hipSuccess) e = hipEventRecord(c->ev0, s);
-  if (e == hipSuccess) e = ics_launch_img_guided(src->d, H, W, radius, eps, detail, coupling, route, coef, (*out)->d, s);
-  if (e == hipSuccess) e = hipEventRecord(c->ev1, s);
-  if (e == hipSuccess) c->ev_pending = true;
-  c->pool.release(coef);   // (reused on the context's one stream, behind these kernels)
-  if (e != hipSuccess) { ics_img_destroy(*out); *out = nullptr; return ics_set_error(e == hipErrorOutOfMemory ? ICS_ENOMEM : ICS_EHIP, "img_guided: %s", hipGetErrorString(e)); }
-  return ICS_OK;
+  if (floats) e = op.alloc((void**)&coef, floats * sizeof(float));
+  if (e == hipSuccess) e = op.begin();
+  if (e == hipSuccess) e = ics_launch_img_guided(src->d, H, W, radius, eps, detail, coupling, route, coef, (*out)->d, c->stream);
+  return op.finish(e);
 }

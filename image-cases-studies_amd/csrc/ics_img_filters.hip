@@ -18,7 +18,7 @@
 //
 // Occupancy against LDS (160 KB per CU): 15 taps -> row pass 16 x 308 x 4 = 19 KB (8 workgroups = 32 waves per CU), column pass
 // 46 x 256 x 4 = 46 KB (3 workgroups); bilateral radius 5 -> 26 x 296 x 4 = 30 KB (5 workgroups).
-#include "ics_kernels.h"
+#include "ics_img_px.h"
 
 namespace {
 
@@ -28,11 +28,6 @@ namespace {
 
 struct __attribute__((packed, aligned(4))) f4u { float x, y, z, w; };   // 16-byte access at 4-byte alignment
 
-__device__ __forceinline__ int symm(int i, int n) {  // ... x1 x0 | x0 x1 ... x(n-1) | x(n-1) x(n-2) ... (any distance)
-  const int p = 2 * n;
-  i %= p; if (i < 0) i += p;
-  return i < n ? i : p - 1 - i;
-}
 // flat index 3 x + c of the symmetric extension of a W-pixel row
 __device__ __forceinline__ int symf(int g, int W) {
   const int px = g >= 0 ? g / 3 : -((2 - g) / 3);
@@ -193,11 +188,6 @@ __global__ __launch_bounds__(256) void k_img_bilateral(const float* __restrict__
   }
 }
 
-hipError_t set_lds(const void* kern, size_t bytes) {
-  if (bytes <= 64 * 1024) return hipSuccess;
-  return hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-}
-
 }  // namespace
 
 size_t ics_img_conv_rows_lds(int KH, int KW) { return (size_t)(RT + KH - 1) * (FT + 12 * ((KW + 3) / 4) + 4) * sizeof(float); }
@@ -211,7 +201,7 @@ hipError_t ics_launch_img_conv_rows(const float* src, int H, int W, const float*
                                     float amount, hipStream_t s) {
   const size_t lds = ics_img_conv_rows_lds(KH, KW);
   if (lds > 160 * 1024) return hipErrorInvalidValue;
-  hipError_t e = set_lds(reinterpret_cast<const void*>(k_img_conv_rows), lds);
+  hipError_t e = set_dynamic_lds(k_img_conv_rows, lds);
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(k_img_conv_rows, dim3((3 * W + FT - 1) / FT, (H + RT - 1) / RT), dim3(256), lds, s, src, H, W, wr, KH, KW, out, src0, usm, amount);
   return hipGetLastError();
@@ -221,7 +211,7 @@ hipError_t ics_launch_img_conv_cols(const float* src, int H, int W, const float*
                                     hipStream_t s) {
   const size_t lds = ics_img_conv_cols_lds(KH);
   if (lds > 160 * 1024) return hipErrorInvalidValue;
-  hipError_t e = set_lds(reinterpret_cast<const void*>(k_img_conv_cols), lds);
+  hipError_t e = set_dynamic_lds(k_img_conv_cols, lds);
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(k_img_conv_cols, dim3((3 * W + FT - 1) / FT, (H + VT - 1) / VT), dim3(256), lds, s, src, H, W, wr, KH, out, src0, usm, amount);
   return hipGetLastError();
@@ -230,7 +220,7 @@ hipError_t ics_launch_img_conv_cols(const float* src, int H, int W, const float*
 hipError_t ics_launch_img_bilateral(const float* src, int H, int W, int radius, float ki, const float* ws, float* out, hipStream_t s) {
   const size_t lds = ics_img_bilateral_lds(radius);
   if (lds > 160 * 1024) return hipErrorInvalidValue;
-  hipError_t e = set_lds(reinterpret_cast<const void*>(k_img_bilateral), lds);
+  hipError_t e = set_dynamic_lds(k_img_bilateral, lds);
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(k_img_bilateral, dim3((3 * W + FT - 1) / FT, (H + RT - 1) / RT), dim3(256), lds, s, src, H, W, radius, ki, ws, out);
   return hipGetLastError();

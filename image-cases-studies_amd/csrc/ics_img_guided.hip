@@ -30,24 +30,13 @@
 // Route 2 (k_img_gf_fused), r <= ICS_IMG_GUIDED_FUSED_RADIUS: the same two phases in one launch, the coefficients of the tile plus an
 // r halo kept in LDS.  The coefficient region is C x C, C = 32 + 2 r rounded up to a multiple of 4 (whole groups of GFP), I' is staged
 // on (C + 2 r)^2: 3 (C + 2 r)(C + 2 r + 1) + (C + 2 r)(C + 1) + K C (C + 1) floats, 147 136 B at r = 8 (vector), 173 696 B at r = 9.
-#include "ics_kernels.h"
+#include "ics_img_px.h"
 
 namespace {
 
 #define GFT 32                         // output tile edge
 #define GFP 4                          // neighbouring sums a lane forms from one stream of taps
 #define GFLANES 256                    // (GFT / GFP) * GFT: in the apply phase a lane owns GFP vertical neighbours
-
-struct __attribute__((packed, aligned(4))) f3u { float x, y, z; };   // one pixel: 12-byte access at 4-byte alignment
-
-__device__ __forceinline__ void ld3(const float* __restrict__ p, float v[3]) {
-  const f3u t = *reinterpret_cast<const f3u*>(p);
-  v[0] = t.x; v[1] = t.y; v[2] = t.z;
-}
-__device__ __forceinline__ void st3(float* __restrict__ p, const float v[3]) {
-  const f3u t = {v[0], v[1], v[2]};
-  *reinterpret_cast<f3u*>(p) = t;
-}
 
 // ---- the arithmetic every route shares ------------------------------------------------------------------------------------------
 // pixels of the window of (y, x) that lie in the picture
@@ -302,9 +291,6 @@ static_assert(gf_coef_lds(ICS_IMG_GUIDED_FUSED_RADIUS, gf_fused_c(ICS_IMG_GUIDED
               gf_coef_lds(ICS_IMG_GUIDED_FUSED_RADIUS + 1, gf_fused_c(ICS_IMG_GUIDED_FUSED_RADIUS + 1), 9) > 160 * 1024,
               "ICS_IMG_GUIDED_FUSED_RADIUS is not the largest radius whose fused tile fits the LDS");
 
-template <typename Kern>
-hipError_t gf_lds(Kern kern, size_t lds) { return hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); }
-
 }  // namespace
 
 // floats of the coefficient frame route 1 needs (route 2: none)
@@ -316,28 +302,19 @@ hipError_t ics_launch_img_guided(const float* src, int H, int W, int radius, flo
     return hipErrorInvalidValue;
   const int K = coupling ? 9 : 6, r = radius;
   const dim3 grid((W + GFT - 1) / GFT, (H + GFT - 1) / GFT), block(GFLANES);
-  hipError_t e;
   if (route == 2) {
     const size_t lds = gf_coef_lds(r, gf_fused_c(r), K);
-    if (coupling) {
-      if ((e = gf_lds(k_img_gf_fused<true>, lds)) != hipSuccess) return e;
-      hipLaunchKernelGGL(k_img_gf_fused<true>, grid, block, lds, s, src, out, H, W, r, eps, detail);
-    } else {
-      if ((e = gf_lds(k_img_gf_fused<false>, lds)) != hipSuccess) return e;
-      hipLaunchKernelGGL(k_img_gf_fused<false>, grid, block, lds, s, src, out, H, W, r, eps, detail);
-    }
+    hipError_t e = coupling ? set_dynamic_lds(k_img_gf_fused<true>, lds) : set_dynamic_lds(k_img_gf_fused<false>, lds);
+    if (e != hipSuccess) return e;
+    ICS_LAUNCH_VEC(coupling, k_img_gf_fused, grid, block, lds, s, src, out, H, W, r, eps, detail);
     return hipGetLastError();
   }
   if (!coef) return hipErrorInvalidValue;
   const size_t lds_a = gf_coef_lds(r, GFT, K), lds_b = sizeof(float) * (size_t)((GFT + 2 * r) * (GFT + 2 * r + 1) + (GFT + 2 * r) * (GFT + 1));
-  if (coupling) {
-    if ((e = gf_lds(k_img_gf_coef<true>, lds_a)) != hipSuccess || (e = gf_lds(k_img_gf_apply<true>, lds_b)) != hipSuccess) return e;
-    hipLaunchKernelGGL(k_img_gf_coef<true>, grid, block, lds_a, s, src, coef, H, W, r, eps);
-    hipLaunchKernelGGL(k_img_gf_apply<true>, grid, block, lds_b, s, src, (const float*)coef, out, H, W, r, detail);
-  } else {
-    if ((e = gf_lds(k_img_gf_coef<false>, lds_a)) != hipSuccess || (e = gf_lds(k_img_gf_apply<false>, lds_b)) != hipSuccess) return e;
-    hipLaunchKernelGGL(k_img_gf_coef<false>, grid, block, lds_a, s, src, coef, H, W, r, eps);
-    hipLaunchKernelGGL(k_img_gf_apply<false>, grid, block, lds_b, s, src, (const float*)coef, out, H, W, r, detail);
-  }
+  hipError_t e = coupling ? set_dynamic_lds(k_img_gf_coef<true>, lds_a) : set_dynamic_lds(k_img_gf_coef<false>, lds_a);
+  if (e == hipSuccess) e = coupling ? set_dynamic_lds(k_img_gf_apply<true>, lds_b) : set_dynamic_lds(k_img_gf_apply<false>, lds_b);
+  if (e != hipSuccess) return e;
+  ICS_LAUNCH_VEC(coupling, k_img_gf_coef, grid, block, lds_a, s, src, coef, H, W, r, eps);
+  ICS_LAUNCH_VEC(coupling, k_img_gf_apply, grid, block, lds_b, s, src, (const float*)coef, out, H, W, r, detail);
   return hipGetLastError();
 }

@@ -23,7 +23,7 @@
 // last row / column takes g = 0 (the boundary rule above, not a mirror).  A launch writes q of its tile to the other frame pair; the
 // last launch (also the one with the remainder iterations % TVT) writes f + div q instead.  Bytes per pixel and launch: read
 // 36 x (41 / 32)^2 = 59, write 24 (the last: 12), against 240 for four launches of route 1.
-#include "ics_kernels.h"
+#include "ics_img_px.h"
 
 namespace {
 
@@ -31,8 +31,6 @@ namespace {
 #define TVT ICS_IMG_TV_BLOCK           // iterations per launch
 #define TVS (TVB + 1 + 2 * TVT)        // staged tile edge
 #define TVN (TVS * TVS)
-
-struct __attribute__((packed, aligned(4))) f3u { float x, y, z; };   // one pixel: 12-byte access at 4-byte alignment
 
 __device__ __forceinline__ float tv_u(float f, float qx, float qxl, float qy, float qyu) {
   return __fadd_rn(f, __fadd_rn(__fsub_rn(qx, qxl), __fsub_rn(qy, qyu)));
@@ -61,14 +59,6 @@ __device__ __forceinline__ void tv_step(float qx[3], float qy[3], const float u[
   }
 }
 
-__device__ __forceinline__ void ld3(const float* __restrict__ p, float v[3]) {
-  const f3u t = *reinterpret_cast<const f3u*>(p);
-  v[0] = t.x; v[1] = t.y; v[2] = t.z;
-}
-__device__ __forceinline__ void st3(float* __restrict__ p, const float v[3]) {
-  const f3u t = {v[0], v[1], v[2]};
-  *reinterpret_cast<f3u*>(p) = t;
-}
 __device__ __forceinline__ void zero3(float v[3]) { v[0] = v[1] = v[2] = 0.f; }
 
 // ---- route 1: one iteration; qxi == nullptr: q = 0 (the first iteration) ----------------------------------------------------
@@ -210,16 +200,14 @@ hipError_t ics_launch_img_tv_denoise(const float* f, int H, int W, float weight,
     const dim3 grid((W + 63) / 64, (H + 3) / 4);
     for (int it = 0; it < iterations; ++it) {
       float *qxo = q[2 * (it & 1)], *qyo = q[2 * (it & 1) + 1];
-      if (coupling) hipLaunchKernelGGL(k_img_tv_iter<true>, grid, dim3(256), 0, s, f, qxi, qyi, qxo, qyo, H, W, tau, k);
-      else hipLaunchKernelGGL(k_img_tv_iter<false>, grid, dim3(256), 0, s, f, qxi, qyi, qxo, qyo, H, W, tau, k);
+      ICS_LAUNCH_VEC(coupling, k_img_tv_iter, grid, dim3(256), 0, s, f, qxi, qyi, qxo, qyo, H, W, tau, k);
       qxi = qxo; qyi = qyo;
     }
     hipLaunchKernelGGL(k_img_tv_final, grid, dim3(256), 0, s, f, qxi, qyi, out, H, W);
     return hipGetLastError();
   }
   const size_t lds = ics_img_tv_block_lds();
-  const void* kern = coupling ? reinterpret_cast<const void*>(k_img_tv_block<true>) : reinterpret_cast<const void*>(k_img_tv_block<false>);
-  hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  hipError_t e = coupling ? set_dynamic_lds(k_img_tv_block<true>, lds) : set_dynamic_lds(k_img_tv_block<false>, lds);
   if (e != hipSuccess) return e;
   const dim3 grid((W + TVB - 1) / TVB, (H + TVB - 1) / TVB);
   const int launches = (iterations + TVT - 1) / TVT;
@@ -227,8 +215,7 @@ hipError_t ics_launch_img_tv_denoise(const float* f, int H, int W, float weight,
     const bool last = j == launches - 1;
     const int n = iterations - done < TVT ? iterations - done : TVT;
     float *qxo = last ? nullptr : q[2 * (j & 1)], *qyo = last ? nullptr : q[2 * (j & 1) + 1], *o = last ? out : nullptr;
-    if (coupling) hipLaunchKernelGGL(k_img_tv_block<true>, grid, dim3(512), lds, s, f, qxi, qyi, qxo, qyo, o, H, W, n, tau, k);
-    else hipLaunchKernelGGL(k_img_tv_block<false>, grid, dim3(512), lds, s, f, qxi, qyi, qxo, qyo, o, H, W, n, tau, k);
+    ICS_LAUNCH_VEC(coupling, k_img_tv_block, grid, dim3(512), lds, s, f, qxi, qyi, qxo, qyo, o, H, W, n, tau, k);
     qxi = qxo; qyi = qyo; done += n;
   }
   return hipGetLastError();

@@ -3,7 +3,7 @@
 // soft-thresholded, multiplied by a gain, and the scales are summed back.
 //
 //   c_0      = f,  c_{j+1} = V_j(H_j(c_j)):  taps [1 4 6 4 1] / 16 at offsets {-2 .. 2} * 2^j along x, then along y
-//   index    outside the picture: folded as numpy.pad(mode="symmetric"), i mod 2n and then 2n - 1 - i if >= n (wv_fold)
+//   index    outside the picture: folded as numpy.pad(mode="symmetric"), i mod 2n and then 2n - 1 - i if >= n (wv_fold, ics_img_px.h)
 //   one pass ((a[-2] + a[+2]) / 16 + (a[-1] + a[+1]) * 4 / 16) + a[0] * 6 / 16   (wv_pass, no FMA)
 //   w_j      = c_j - c_{j+1};  s_j = sign(w) max(|w| - t_j, 0) ("channel") or w * (max(m - t_j, 0) / m), m = |w| over the three
 //              channels with the squares added smallest first ("vector"), 0 where m = 0
@@ -27,7 +27,7 @@
 // the row pass of the channel in work: 4 x 4560 floats = 72 960 B, two workgroups of 512 lanes = 16 waves per CU in 160 KB.  A lane
 // owns three output pixels and keeps their c_j and accumulator in registers.  It writes c_F and the accumulator once (or the result,
 // when J <= F); the remaining scales run as in route 1.
-#include "ics_kernels.h"
+#include "ics_img_px.h"
 
 namespace {
 
@@ -41,26 +41,7 @@ namespace {
 #define WVLANES 512
 #define WVPX (WVTW * WVTH / WVLANES)           // output pixels per lane: 3
 
-struct __attribute__((packed, aligned(4))) f3u { float x, y, z; };   // one pixel: 12-byte access at 4-byte alignment
 struct wv_prm { float g[WVF], t[WVF]; };
-
-__device__ __forceinline__ void ld3(const float* __restrict__ p, float v[3]) {
-  const f3u t = *reinterpret_cast<const f3u*>(p);
-  v[0] = t.x; v[1] = t.y; v[2] = t.z;
-}
-__device__ __forceinline__ void st3(float* __restrict__ p, const float v[3]) {
-  const f3u t = {v[0], v[1], v[2]};
-  *reinterpret_cast<f3u*>(p) = t;
-}
-
-// numpy.pad(mode="symmetric") index, folded as often as it takes
-__device__ __forceinline__ int wv_fold(int i, int n) {
-  if ((unsigned)i < (unsigned)n) return i;
-  const int p = 2 * n;
-  i %= p;
-  if (i < 0) i += p;
-  return i < n ? i : p - 1 - i;
-}
 
 // one axis pass of the B3 spline: am2 .. ap2 at offsets -2 d .. 2 d
 __device__ __forceinline__ float wv_pass(float am2, float am1, float a0, float ap1, float ap2) {
@@ -223,13 +204,11 @@ hipError_t ics_launch_img_wavelet(const float* f, int H, int W, int scales, cons
     wv_prm prm;
     for (int i = 0; i < WVF; ++i) { prm.g[i] = i < n ? gains[i] : 0.f; prm.t[i] = i < n && thresholds ? thresholds[i] : 0.f; }
     const size_t lds = ics_img_wavelet_fused_lds();
-    const void* kern = coupling ? reinterpret_cast<const void*>(k_img_wv_fused<true>) : reinterpret_cast<const void*>(k_img_wv_fused<false>);
-    hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipError_t e = coupling ? set_dynamic_lds(k_img_wv_fused<true>, lds) : set_dynamic_lds(k_img_wv_fused<false>, lds);
     if (e != hipSuccess) return e;
     const dim3 grid((W + WVTW - 1) / WVTW, (H + WVTH - 1) / WVTH);
     float* cout = last ? nullptr : tmp[0];
-    if (coupling) hipLaunchKernelGGL(k_img_wv_fused<true>, grid, dim3(WVLANES), lds, s, f, cout, out, H, W, n, prm, residual, last);
-    else hipLaunchKernelGGL(k_img_wv_fused<false>, grid, dim3(WVLANES), lds, s, f, cout, out, H, W, n, prm, residual, last);
+    ICS_LAUNCH_VEC(coupling, k_img_wv_fused, grid, dim3(WVLANES), lds, s, f, cout, out, H, W, n, prm, residual, last);
     cin = cout; j = n; w = 1;
   }
   const dim3 grid((W + 63) / 64, (H + 3) / 4);
@@ -237,8 +216,7 @@ hipError_t ics_launch_img_wavelet(const float* f, int H, int W, int scales, cons
     const int last = j == scales - 1;
     float* cout = last ? nullptr : tmp[w & 1];
     const float g = gains[j], t = thresholds ? thresholds[j] : 0.f;
-    if (coupling) hipLaunchKernelGGL(k_img_wv_scale<true>, grid, dim3(256), 0, s, cin, cout, out, H, W, 1 << j, g, t, residual, j == 0, last);
-    else hipLaunchKernelGGL(k_img_wv_scale<false>, grid, dim3(256), 0, s, cin, cout, out, H, W, 1 << j, g, t, residual, j == 0, last);
+    ICS_LAUNCH_VEC(coupling, k_img_wv_scale, grid, dim3(256), 0, s, cin, cout, out, H, W, 1 << j, g, t, residual, j == 0, last);
     cin = cout;
   }
   return hipGetLastError();

@@ -267,8 +267,8 @@ def _denoise_args(denoise):
     if len(denoise) != 3:
         raise ValueError("denoise takes (weight, iterations) or (weight, iterations, coupling), got %d values" % len(denoise))
     weight, iterations, coupling = denoise
-    if coupling not in ("channel", "vector"):
-        raise ValueError("denoise coupling %r (channel or vector)" % (coupling,))
+    from lib._native import _coupling
+    _coupling(coupling, "denoise coupling")
     if not (np.isfinite(weight) and weight > 0):
         raise ValueError("denoise weight %r (must be positive and finite)" % (weight,))
     if int(iterations) != iterations or iterations < 0:

@@ -90,6 +90,7 @@ IMG_WAVELET_MAX_SCALES = 8       # include/ics_hip.h ICS_IMG_WAVELET_MAX_SCALES:
 IMG_WAVELET_FUSED = 3            # include/ics_hip.h ICS_IMG_WAVELET_FUSED: scales the fused route runs in one launch on LDS tiles
 IMG_GUIDED_MAX_RADIUS = 32       # include/ics_hip.h ICS_IMG_GUIDED_MAX_RADIUS: largest window radius of the guided filter
 IMG_GUIDED_FUSED_RADIUS = 8      # include/ics_hip.h ICS_IMG_GUIDED_FUSED_RADIUS: largest radius of its one-launch route
+_F32_MAX = float(np.finfo(np.float32).max)   # what _finite32 compares against
 
 
 def frame_bytes(M, N, MK):
@@ -237,57 +238,66 @@ def default_device():
     return int(os.environ.get("ICS_DEVICE", os.environ.get("LOCAL_RANK", "0")))
 
 
+def _finite32(v, scalar=False):
+    """every value of `v` is finite as float32, which is what the library takes; scalar: and `v` is one number, no array"""
+    try:
+        a = float(v) if scalar else np.asarray(v, dtype=np.float64)
+    except (TypeError, ValueError):
+        return False
+    ok = abs(a) <= _F32_MAX                          # (nan and inf fail the comparison)
+    return bool(ok if scalar else ok.all())
+
+
+def _coupling(coupling, what="coupling"):
+    """"channel" / "vector" -> the library's 0 / 1"""
+    if coupling not in ("channel", "vector"):
+        raise ValueError("%s %r (channel or vector)" % (what, coupling))
+    return int(coupling == "vector")
+
+
+def _route(route, names):
+    if route not in (0, 1, 2):
+        raise ValueError("route %r (0: the library's choice, %s)" % (route, names))
+    return int(route)
+
+
 def wavelet_args(gains, thresholds=None, residual=1.0, coupling="vector", route=0):
     """the arguments of DeviceImage.wavelet_equalize checked (ValueError) and as (gains, thresholds or None, residual, coupling,
     route): float32 arrays, a float, a string, an int"""
-    def finite(a):                                  # as float32, which is what the library takes
-        a = np.asarray(a, dtype=np.float64)
-        return bool(np.all(np.isfinite(a)) and np.all(np.abs(a) <= np.finfo(np.float32).max))
     g = np.atleast_1d(np.asarray(gains, dtype=np.float64))
     if g.ndim != 1 or not 1 <= g.size <= IMG_WAVELET_MAX_SCALES:
         raise ValueError("gains: one value per scale, 1 to %d scales, got shape %s" % (IMG_WAVELET_MAX_SCALES, g.shape))
-    if not finite(g):
+    if not _finite32(g):
         raise ValueError("gains %r (must be finite)" % (gains,))
     t = None
     if thresholds is not None:
         t = np.atleast_1d(np.asarray(thresholds, dtype=np.float64))
         if t.shape != g.shape:
             raise ValueError("thresholds: %s values for %d gains (one per scale, or None)" % (t.shape, g.size))
-        if not finite(t) or np.any(t < 0):
+        if not _finite32(t) or np.any(t < 0):
             raise ValueError("thresholds %r (must be finite and >= 0)" % (thresholds,))
         t = np.ascontiguousarray(t, dtype=np.float32)
-    if not finite(residual):
+    if not _finite32(residual):
         raise ValueError("residual %r (must be finite)" % (residual,))
-    if coupling not in ("channel", "vector"):
-        raise ValueError("coupling %r (channel or vector)" % (coupling,))
-    if route not in (0, 1, 2):
-        raise ValueError("route %r (0: the library's choice, 1: a launch per scale, 2: the first scales fused)" % (route,))
-    return np.ascontiguousarray(g, dtype=np.float32), t, float(residual), coupling, int(route)
+    _coupling(coupling)
+    return np.ascontiguousarray(g, dtype=np.float32), t, float(residual), coupling, _route(route, "1: a launch per scale, 2: the first scales fused")
 
 
 def guided_args(radius, eps, detail=0.0, coupling="vector", route=0):
     """the arguments of DeviceImage.guided_filter checked (ValueError) and as (radius, eps, detail, coupling, route): an int, two
     floats, a string, an int"""
-    def finite(v):                                  # as float32, which is what the library takes
-        try:
-            v = float(v)
-        except (TypeError, ValueError):
-            return False
-        return bool(np.isfinite(v) and abs(v) <= float(np.finfo(np.float32).max))
     try:
         whole = int(radius) == radius and not isinstance(radius, bool)
     except (TypeError, ValueError, OverflowError):
         whole = False
     if not whole or not 1 <= int(radius) <= IMG_GUIDED_MAX_RADIUS:
         raise ValueError("radius %r (an integer, 1 to %d)" % (radius, IMG_GUIDED_MAX_RADIUS))
-    if not finite(eps) or not np.float32(eps) > 0:
+    if not _finite32(eps, scalar=True) or not np.float32(eps) > 0:
         raise ValueError("eps %r (must be finite and > 0)" % (eps,))
-    if not finite(detail):
+    if not _finite32(detail, scalar=True):
         raise ValueError("detail %r (must be finite)" % (detail,))
-    if coupling not in ("channel", "vector"):
-        raise ValueError("coupling %r (channel or vector)" % (coupling,))
-    if route not in (0, 1, 2):
-        raise ValueError("route %r (0: the library's choice, 1: two launches, 2: one launch on LDS tiles)" % (route,))
+    _coupling(coupling)
+    _route(route, "1: two launches, 2: one launch on LDS tiles")
     if route == 2 and int(radius) > IMG_GUIDED_FUSED_RADIUS:
         raise ValueError("route 2 takes a radius up to %d, got %d" % (IMG_GUIDED_FUSED_RADIUS, int(radius)))
     return int(radius), float(eps), float(detail), coupling, int(route)
@@ -481,9 +491,7 @@ class DeviceImage:
         the channels share their edges and chromatic noise is smoothed away.  route 0: the library's choice, 1: a launch per
         iteration, 2: IMG_TV_BLOCK iterations per launch on LDS tiles; all give identical bits.  skimage's denoise_tv_chambolle
         steps with tau = 1/4 and stops on an energy criterion; parity with it is unpinned (skimage is no dependency)."""
-        if coupling not in ("channel", "vector"):
-            raise ValueError("coupling %r (channel or vector)" % (coupling,))
-        return self._new(load().ics_img_tv_denoise, float(weight), int(iterations), int(coupling == "vector"), int(route))
+        return self._new(load().ics_img_tv_denoise, float(weight), int(iterations), _coupling(coupling), int(route))
 
     def wavelet_equalize(self, gains, thresholds=None, residual=1.0, coupling="vector", route=0):
         """Wavelet equaliser: an undecimated B3-spline ("a trous") decomposition into len(gains) <= IMG_WAVELET_MAX_SCALES detail
@@ -497,8 +505,7 @@ class DeviceImage:
         identical bits.  ValueError (before any native call): no or more than 8 gains, thresholds of another length, a value that
         is not finite, a negative threshold, unknown coupling or route."""
         g, t, residual, coupling, route = wavelet_args(gains, thresholds, residual, coupling, route)
-        return self._new(load().ics_img_wavelet_equalize, int(g.size), _ptr(g), None if t is None else _ptr(t), residual,
-                         int(coupling == "vector"), route)
+        return self._new(load().ics_img_wavelet_equalize, int(g.size), _ptr(g), None if t is None else _ptr(t), residual, _coupling(coupling), route)
 
     def guided_filter(self, radius, eps, detail=0.0, coupling="vector", route=0):
         """Guided filter with the picture as its own guide (He, Sun, Tang): the edge-preserving base layer q of the
@@ -511,7 +518,7 @@ class DeviceImage:
         ValueError (before any native call): a radius that is no integer in 1 .. 32, eps not finite or <= 0, detail not finite,
         unknown coupling or route."""
         radius, eps, detail, coupling, route = guided_args(radius, eps, detail, coupling, route)
-        return self._new(load().ics_img_guided, radius, eps, detail, int(coupling == "vector"), route)
+        return self._new(load().ics_img_guided, radius, eps, detail, _coupling(coupling), route)
 
     def close(self):
         if self._h:
