@@ -295,3 +295,14 @@ hipError_t ics_launch_img_wavelet(const float* f, int H, int W, int scales, cons
 size_t ics_img_guided_coef_floats(int H, int W, int coupling, int route);
 hipError_t ics_launch_img_guided(const float* src, int H, int W, int radius, float eps, float detail, int coupling, int route, float* coef, float* out,
                                  hipStream_t s);
+
+// ---- local Laplacian filter of device-resident images (ics_img_llf.hip): K remapped Gaussian pyramids, an interpolated Laplacian
+// pyramid, collapsed.  pyr: ics_img_llf_pyramid_floats floats (K + 1 pyramids of levels 1 .. J), r0 / r1: ics_img_llf_collapse_floats
+// floats each.  route 1: a reduce chain per sample; 2: one reduce launch per level for all samples, the frame read once.  coupling 0:
+// per channel (three passes through the same buffers), 1: the luma Y carries the filter.
+#define ICS_IMG_LLF_MAX_LEVELS 10         // (== include/ics_hip.h)
+#define ICS_IMG_LLF_MAX_SAMPLES 16        // (== include/ics_hip.h)
+size_t ics_img_llf_pyramid_floats(int H, int W, int levels, int samples);
+size_t ics_img_llf_collapse_floats(int H, int W);
+hipError_t ics_launch_img_llf(const float* src, int H, int W, float sigma, float detail, float edges, int levels, int samples, int coupling, int route,
+                              float* pyr, float* r0, float* r1, float* out, hipStream_t s);

@@ -80,7 +80,7 @@ def mask_window(i, top, bottom, left, right):
 def deblur_module(pic, filename, dest_path, blur_width, confidence=10, tolerance=1, quality="normal", bits=8,
                   mask=None, display=True, blur="static", preview=False, p=1, order=2, norm=1, priority=0, mask_size=255,
                   iterations=200, refocus=False, pyramid=True, solver=None, save=True, device_resident=None, sharpen=None, denoise=None,
-                  local_contrast=None, detail=None):
+                  local_contrast=None, detail=None, clarity=None):
     """deconvolve.py:65-368.  Extra keyword arguments (not in the reference): `pyramid=False` runs the
     single scale-1 level only, `solver` replaces `dc.richardson_lucy_MM` (tests record the calls),
     `save=False` returns the float image instead of writing the TIFF, `device_resident=True` keeps every frame in HBM
@@ -104,18 +104,24 @@ def deblur_module(pic, filename, dest_path, blur_width, confidence=10, tolerance
     "vector" unless given) on the deblurred frame, in the gamma-encoded domain, after `local_contrast`, before `sharpen` and before
     the final clip: the frame's guided-filter base layer plus `gain` times its detail -- a gain above 1 sharpens at radii of 8 to
     32 px without the halos a Gaussian mask of that size puts around the edges Richardson-Lucy has just restored, a gain below 1
-    smooths texture and keeps them; on the resident path the frame stays in HBM."""
+    smooths texture and keeps them; on the resident path the frame stays in HBM.
+    `clarity=(sigma, detail)`, `(sigma, detail, edges)` or `(sigma, detail, edges, coupling)`: `utils.local_laplacian` with these
+    arguments (edges 1, coupling "vector" unless given; default levels, 8 samples) on the deblurred frame, in the gamma-encoded
+    domain, after `denoise` and before `local_contrast`: the steps run coarse to fine -- tone and clarity at tens to hundreds of
+    pixels, then the scale gains, then the guided detail, then the mask, then the clip.  (0.2, 1.8) adds clarity, (0.2, 1, 0.6)
+    compresses the tonal range and keeps the detail; on the resident path the frame stays in HBM."""
     sharpen = _sharpen_args(sharpen)
     denoise = _denoise_args(denoise)
     local_contrast = _local_contrast_args(local_contrast)
     detail = _detail_args(detail)
+    clarity = _clarity_args(clarity)
     if device_resident is None:
         device_resident = solver is None and not display
     if device_resident:
         if solver is not None:
             raise ValueError("device_resident=True runs the GPU solver; `solver` cannot be replaced")
         return _deblur_device(pic, filename, dest_path, blur_width, confidence, tolerance, quality, bits, mask, display, blur, preview, p,
-                              order, norm, priority, mask_size, iterations, refocus, pyramid, save, sharpen, denoise, local_contrast, detail)
+                              order, norm, priority, mask_size, iterations, refocus, pyramid, save, sharpen, denoise, local_contrast, detail, clarity)
     rl = solver if solver is not None else dc.richardson_lucy_MM
     pic = np.ascontiguousarray(pic, dtype=np.float32)
     pic = pad_image(pic, (1, 1)).astype(np.float32)                       # :94
@@ -219,6 +225,9 @@ def deblur_module(pic, filename, dest_path, blur_width, confidence=10, tolerance
         pass
     if denoise is not None:
         deblured_image = utils.tv_denoise(np.ascontiguousarray(deblured_image, dtype=np.float32), *denoise)
+    if clarity is not None:
+        sigma, gain, edges, coupling = clarity
+        deblured_image = utils.local_laplacian(np.ascontiguousarray(deblured_image, dtype=np.float32), sigma, gain, edges, None, 8, coupling)
     if local_contrast is not None:
         gains, thresholds, coupling = local_contrast
         deblured_image = utils.wavelet_equalizer(np.ascontiguousarray(deblured_image, dtype=np.float32), gains, thresholds, 1.0, coupling)
@@ -315,6 +324,26 @@ def _detail_args(detail):
     return radius, eps, gain, coupling
 
 
+def _clarity_args(clarity):
+    """`clarity` of deblur_module -> None or (sigma, detail, edges, coupling)"""
+    if clarity is None:
+        return None
+    forms = "clarity takes (sigma, detail), (sigma, detail, edges) or (sigma, detail, edges, coupling)"
+    try:
+        clarity = tuple(clarity)
+    except TypeError:
+        raise ValueError("%s, got %r" % (forms, clarity))
+    if len(clarity) not in (2, 3, 4):
+        raise ValueError("%s, got %d values" % (forms, len(clarity)))
+    sigma, gain, edges, coupling = (clarity + (1.0, "vector")[len(clarity) - 2:])[:4]
+    from lib._native import llf_args
+    try:
+        sigma, gain, edges, _, _, coupling, _ = llf_args(sigma, gain, edges, None, 8, coupling)
+    except ValueError as exc:
+        raise ValueError("clarity: %s" % exc)
+    return sigma, gain, edges, coupling
+
+
 def _level_shape(i, M, N):
     """deconvolve.py:232-243 -- odd size of pyramid level `i`"""
     temp_width, temp_height = int(np.floor(i * N)), int(np.floor(i * M))
@@ -326,7 +355,8 @@ def _level_shape(i, M, N):
 
 
 def _deblur_device(pic, filename, dest_path, blur_width, confidence, tolerance, quality, bits, mask, display, blur, preview, p, order, norm,
-                   priority, mask_size, iterations, refocus, pyramid, save, sharpen=None, denoise=None, local_contrast=None, detail=None):
+                   priority, mask_size, iterations, refocus, pyramid, save, sharpen=None, denoise=None, local_contrast=None, detail=None,
+                   clarity=None):
     """`deblur_module` (deconvolve.py:65-368) with every frame resident in HBM: one upload of the picture,
     one download of the result; pad_image, gamma, the window views, the resize between pyramid levels and the solver all
     work on `lib._native.DeviceImage`s.  Line references as in `deblur_module` above."""
@@ -430,6 +460,10 @@ def _deblur_device(pic, filename, dest_path, blur_width, confidence, tolerance, 
         pass
     if denoise is not None:
         deb, old = deb.tv_denoise(*denoise), deb
+        old.close()
+    if clarity is not None:
+        sigma, gain, edges, coupling = clarity
+        deb, old = deb.local_laplacian(sigma, gain, edges, None, 8, coupling), deb
         old.close()
     if local_contrast is not None:
         gains, thresholds, coupling = local_contrast

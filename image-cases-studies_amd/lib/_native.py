@@ -90,6 +90,8 @@ IMG_WAVELET_MAX_SCALES = 8       # include/ics_hip.h ICS_IMG_WAVELET_MAX_SCALES:
 IMG_WAVELET_FUSED = 3            # include/ics_hip.h ICS_IMG_WAVELET_FUSED: scales the fused route runs in one launch on LDS tiles
 IMG_GUIDED_MAX_RADIUS = 32       # include/ics_hip.h ICS_IMG_GUIDED_MAX_RADIUS: largest window radius of the guided filter
 IMG_GUIDED_FUSED_RADIUS = 8      # include/ics_hip.h ICS_IMG_GUIDED_FUSED_RADIUS: largest radius of its one-launch route
+IMG_LLF_MAX_LEVELS = 10          # include/ics_hip.h ICS_IMG_LLF_MAX_LEVELS: pyramid levels of the local Laplacian filter
+IMG_LLF_MAX_SAMPLES = 16         # include/ics_hip.h ICS_IMG_LLF_MAX_SAMPLES: remapped copies it interpolates between
 _F32_MAX = float(np.finfo(np.float32).max)   # what _finite32 compares against
 
 
@@ -166,6 +168,7 @@ def load():
     lib.ics_img_tv_denoise.argtypes = [vp, cf, ci, ci, ci, C.POINTER(vp)]
     lib.ics_img_wavelet_equalize.argtypes = [vp, ci, vp, vp, cf, ci, ci, C.POINTER(vp)]
     lib.ics_img_guided.argtypes = [vp, ci, cf, cf, ci, ci, C.POINTER(vp)]
+    lib.ics_img_local_laplacian.argtypes = [vp, cf, cf, cf, ci, ci, ci, ci, C.POINTER(vp)]
     lib.ics_rl_upload_img.argtypes = [vp, vp, ci, ci, vp, ci, ci, vp]
     lib.ics_rl_download_img.argtypes = [vp, vp, ci, ci]
     lib.ics_group_create.argtypes = [ci, ci, ci, C.c_char_p, ci, C.POINTER(vp)]
@@ -187,7 +190,7 @@ def load():
                  "ics_rl_download", "ics_rl_run", "ics_rl_stage", "ics_rl_read", "ics_rl_write", "ics_rl_read_rows", "ics_rl_write_rows", "ics_rl_copy_rows", "ics_normalize_kernel",
                  "ics_tv", "ics_conv2d_symm", "ics_usm", "ics_bilateral", "ics_resize_bicubic", "ics_img_create", "ics_img_shape",
                  "ics_img_upload", "ics_img_upload_int", "ics_img_download", "ics_img_pad_edge", "ics_img_crop", "ics_img_paste", "ics_img_gamma", "ics_img_resize",
-                 "ics_img_convolve", "ics_img_usm", "ics_img_bilateral", "ics_img_tv_denoise", "ics_img_wavelet_equalize", "ics_img_guided",
+                 "ics_img_convolve", "ics_img_usm", "ics_img_bilateral", "ics_img_tv_denoise", "ics_img_wavelet_equalize", "ics_img_guided", "ics_img_local_laplacian",
                  "ics_rl_upload_img", "ics_rl_download_img", "ics_group_create", "ics_group_info", "ics_group_barrier",
                  "ics_group_allreduce_max", "ics_group_allreduce_sum", "ics_group_describe", "ics_group_allgather"):
         getattr(lib, name).restype = ci
@@ -301,6 +304,40 @@ def guided_args(radius, eps, detail=0.0, coupling="vector", route=0):
     if route == 2 and int(radius) > IMG_GUIDED_FUSED_RADIUS:
         raise ValueError("route 2 takes a radius up to %d, got %d" % (IMG_GUIDED_FUSED_RADIUS, int(radius)))
     return int(radius), float(eps), float(detail), coupling, int(route)
+
+
+def llf_levels(H, W):
+    """levels=None of DeviceImage.local_laplacian: the halvings (n -> (n + 1) // 2) that bring the longer side of an H x W picture to
+    16 or below, within 1 .. IMG_LLF_MAX_LEVELS"""
+    n, J = max(int(H), int(W)), 0
+    while n > 16:
+        n, J = (n + 1) // 2, J + 1
+    return min(max(J, 1), IMG_LLF_MAX_LEVELS)
+
+
+def llf_args(sigma, detail, edges=1.0, levels=None, samples=8, coupling="vector", route=0):
+    """the arguments of DeviceImage.local_laplacian checked (ValueError) and as (sigma, detail, edges, levels, samples, coupling,
+    route): three floats, an int or None (the picture's size decides: llf_levels), an int, a string, an int"""
+    def whole(v):
+        try:
+            return int(v) == v and not isinstance(v, bool)
+        except (TypeError, ValueError, OverflowError):
+            return False
+    if not _finite32(sigma, scalar=True) or not np.float32(sigma) > 0:
+        raise ValueError("sigma %r (must be finite and > 0)" % (sigma,))
+    if not _finite32(detail, scalar=True) or not np.float32(detail) >= 0:
+        raise ValueError("detail %r (must be finite and >= 0)" % (detail,))
+    if not _finite32(edges, scalar=True) or not np.float32(edges) > 0:
+        raise ValueError("edges %r (must be finite and > 0)" % (edges,))
+    if np.float32(detail) > np.float32(3) * np.float32(edges):
+        raise ValueError("detail %r above 3 edges = %r (the remap must stay monotone)" % (detail, 3 * edges))
+    if levels is not None and (not whole(levels) or not 1 <= int(levels) <= IMG_LLF_MAX_LEVELS):
+        raise ValueError("levels %r (None or an integer, 1 to %d)" % (levels, IMG_LLF_MAX_LEVELS))
+    if not whole(samples) or not 2 <= int(samples) <= IMG_LLF_MAX_SAMPLES:
+        raise ValueError("samples %r (an integer, 2 to %d)" % (samples, IMG_LLF_MAX_SAMPLES))
+    _coupling(coupling)
+    _route(route, "1: a reduce chain per sample, 2: the samples batched")
+    return float(sigma), float(detail), float(edges), None if levels is None else int(levels), int(samples), coupling, int(route)
 
 
 class Context:
@@ -519,6 +556,24 @@ class DeviceImage:
         unknown coupling or route."""
         radius, eps, detail, coupling, route = guided_args(radius, eps, detail, coupling, route)
         return self._new(load().ics_img_guided, radius, eps, detail, _coupling(coupling), route)
+
+    def local_laplacian(self, sigma, detail, edges=1.0, levels=None, samples=8, coupling="vector", route=0):
+        """Fast local Laplacian filter (Paris, Hasinoff, Kautz; sampled as Aubry et al.): `samples` copies of the signal are remapped
+        about g_k = k / (samples - 1) by r_g(i) = g + d (edges + (detail - edges) exp(-d^2 / (2 sigma^2))), d = i - g, each gets a
+        Gaussian pyramid of `levels` halvings (1 4 6 4 1 taps, symmetric boundary), and every coefficient of the output Laplacian
+        pyramid is interpolated between the two copies whose g_k bracket the un-remapped pyramid's value there; the pyramid is
+        collapsed.  detail is the gain of differences well below sigma (above 1: clarity, below 1: smoothing), edges that of
+        differences well above it (below 1 compresses the tonal range and keeps the detail); pixel values in [0, 1], values outside
+        are legal.  levels None: the halvings that bring the longer side to 16 or below (llf_levels).  coupling "channel": every
+        channel by itself; "vector": the luma 0.2126 R + 0.7152 G + 0.0722 B is filtered and its change added to the three channels,
+        no hue shift (csrc/ics_img_llf.hip; restated in tests/llf_ref.py).  route 0: the library's choice, 1: a reduce chain per
+        sample, 2: the samples batched, the frame read once; all give identical bits.  ValueError (before any native call): sigma or
+        edges not finite or <= 0, detail not finite or < 0 or above 3 edges, levels no integer in 1 .. 10, samples none in 2 .. 16,
+        unknown coupling or route."""
+        sigma, detail, edges, levels, samples, coupling, route = llf_args(sigma, detail, edges, levels, samples, coupling, route)
+        if levels is None:
+            levels = llf_levels(*self.shape[:2])
+        return self._new(load().ics_img_local_laplacian, sigma, detail, edges, levels, samples, _coupling(coupling), route)
 
     def close(self):
         if self._h:

@@ -432,6 +432,27 @@ int ics_img_wavelet_equalize(const ics_img *src, int scales, const float *gains,
 #define ICS_IMG_GUIDED_MAX_RADIUS 32
 #define ICS_IMG_GUIDED_FUSED_RADIUS 8
 int ics_img_guided(const ics_img *src, int radius, float eps, float detail, int coupling, int route, ics_img **out);
+/* Fast local Laplacian filter of a device image (Paris, Hasinoff, Kautz 2011; sampled as Aubry et al. 2014): contrast at scales of
+ * tens to hundreds of pixels lifted or smoothed without halos, and the tonal range compressed with the detail kept.
+ *   signal: coupling 0 (channel) each channel by itself; 1 (vector) Y = (0.2126 R + 0.7152 G) + 0.0722 B and out_c = in_c + (Y' - Y)
+ *   reduce, n -> (n + 1) / 2: taps 1 4 6 4 1 at 2 y - 2 .. 2 y + 2, indices folded as numpy.pad(mode="symmetric"),
+ *     (((a0 + a4) + 2 a2) + 4 a2) + 4 (a1 + a3) along y, then along x, then times 1 / 256 (the 6 split so that a constant stays exact)
+ *   expand to a size, indices clamped: position 2 k (((c[k-1] + c[k+1]) + 2 c[k]) + 4 c[k]) / 8, 2 k + 1 (c[k] + c[k+1]) / 2; y, then x
+ *   remap about g, d = i - g: r_g(i) = g + d (edges + (detail - edges) exp(-d d / (2 sigma^2)))
+ *   samples g_k = k / (samples - 1); G the Gaussian pyramid of the signal, P_k that of r_{g_k}(signal), L_k[l] = P_k[l] - expand(P_k[l+1])
+ *   level l < levels, pixel p: t = clamp(G[l](p) (samples - 1), 0, samples - 1), k0 = min(floor(t), samples - 2), f = t - k0,
+ *     OL[l](p) = a + f (b - a), a = L_k0[l](p), b = L_{k0+1}[l](p);  R[levels] = G[levels], R[l] = OL[l] + expand(R[l+1]); result R[0].
+ * detail: gain of differences well below sigma (above 1 clarity, below 1 smoothing); edges: gain of differences well above sigma
+ * (below 1 compresses the tonal range).  No FMA, one expf (restated in tests/llf_ref.py).  Every `levels` is legal for every size
+ * (sizes bottom out at 1) and values outside [0, 1] are legal (t is clamped).  route 1: a reduce chain per sample; 2: one reduce
+ * launch per level for all samples, the frame read once; 0: the library's choice.  The routes give identical bits, and so
+ * do two runs.  Queued like the other image filters; src is not written.  ICS_EINVAL: sigma not finite or <= 0, detail not finite or
+ * < 0, edges not finite or <= 0, detail > 3 edges (the remap would stop being monotone near 3.24 edges), levels outside
+ * 1 .. ICS_IMG_LLF_MAX_LEVELS, samples outside 2 .. ICS_IMG_LLF_MAX_SAMPLES, unknown coupling or route. */
+#define ICS_IMG_LLF_MAX_LEVELS 10
+#define ICS_IMG_LLF_MAX_SAMPLES 16
+int ics_img_local_laplacian(const ics_img *src, float sigma, float detail, float edges, int levels, int samples, int coupling, int route,
+                            ics_img **out);
 /* richardson_lucy_MM(image[iy:iy+M, ix:ix+N], u[uy:uy+uM, ux:ux+uN], psf, ...) with both windows taken from device
  * images (deconvolve.py:277-313 passes such views); psf is a host MK*MK*3 array as in ics_rl_upload. */
 int ics_rl_upload_img(ics_rl *job, const ics_img *image, int iy, int ix, const ics_img *u, int uy, int ux, const float *psf);

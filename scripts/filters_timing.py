@@ -1,6 +1,6 @@
 """Timing of the lib/utils.py filters on one seeded SIZE x SIZE RGB float32 picture (GPU box), one JSON line:
 
-    python scripts/filters_timing.py [SIZE=4096] [guided]       ("guided": that section alone)
+    python scripts/filters_timing.py [SIZE=4096] [guided | llf]       ("guided", "llf": that section alone)
 
   resident   the filters on a DeviceImage in HBM (csrc/ics_img_filters.hip): device time of the kernels (HIP events around them,
              ics_ctx_last_kernel_ms; warm, median of 25) and wall time of the queued call up to a stream synchronise
@@ -24,6 +24,10 @@
              kernel ms, median and minimum of 9 rounds in which the routes alternate, and TB/s on the 84 / 108 B/px model; "auto" is
              what route=0 takes.  For context the bilateral filter at the same radius (std_i 0.1, std_s radius / 2), or "refused"
              where its tile does not fit
+  llf        DeviceImage.local_laplacian (csrc/ics_img_llf.hip), sigma 0.2, detail 1.8, edges 1, K = 8 samples, default levels, both
+             couplings, route 1 (a reduce chain per sample: the frame read K + 1 times) and route 2 (the samples batched: read once):
+             kernel ms, median, minimum and maximum of 5 rounds in which the routes alternate, and TB/s on each route's level-0
+             bytes per pixel (144 / 48 vector, 168 / 72 channel; the levels below add a third); "auto" is what route=0 takes
   checks     the resident USM must not take longer than the three float64 calls, in kernel time and in wall time (a guard against a
              broken kernel, not a target); the exit status is 1 if one of them fails
 Starts no child process; a job script puts its own time limit around it."""
@@ -80,6 +84,31 @@ def guided_section(img, ctx, size):
     return res
 
 
+LLF_ARGS, LLF_SAMPLES, REPS_LLF = (0.2, 1.8, 1.0), 8, 5
+LLF_BYTES = {"vector": {1: 144, 2: 48}, "channel": {1: 168, 2: 72}}
+
+
+def llf_section(img, ctx, size):
+    res = {"sigma_detail_edges": LLF_ARGS, "samples": LLF_SAMPLES, "levels": _native.llf_levels(size, size), "level0_bytes_per_px": LLF_BYTES}
+    for coupling in ("channel", "vector"):
+        times = {1: [], 2: [], 0: []}
+        for route in times:
+            img.local_laplacian(*LLF_ARGS, None, LLF_SAMPLES, coupling, route=route).close()     # warm
+        ctx.synchronize()
+        for _ in range(REPS_LLF):                          # the routes alternate within a round
+            for route in times:
+                out = img.local_laplacian(*LLF_ARGS, None, LLF_SAMPLES, coupling, route=route)
+                times[route].append(ctx.last_kernel_ms())
+                out.close()
+        for route, ms in times.items():
+            med = float(np.median(ms))
+            row = {"kernel_ms": round(med, 4), "min_ms": round(float(np.min(ms)), 4), "max_ms": round(float(np.max(ms)), 4)}
+            if route:
+                row["TBps_on_its_level0_bytes"] = round(LLF_BYTES[coupling][route] * size * size / (med * 1e-3) / 1e12, 3)
+            res["%s_%s" % (coupling, {1: "route1", 2: "route2", 0: "auto"}[route])] = row
+    return res
+
+
 def main():
     size = int(sys.argv[1]) if len(sys.argv) > 1 else 4096
     ctx = _native.Context.get()
@@ -88,6 +117,9 @@ def main():
     img = _native.DeviceImage.from_host(pic, ctx)
     if sys.argv[2:] == ["guided"]:
         print(json.dumps({"size": size, "device": ctx.name, "guided": guided_section(img, ctx, size)}))
+        return 0
+    if sys.argv[2:] == ["llf"]:
+        print(json.dumps({"size": size, "device": ctx.name, "llf": llf_section(img, ctx, size)}))
         return 0
     ops = {"usm_gauss15": lambda s: utils.USM(s, 15, 2.5, 0.7, method="gauss"),
            "usm_bessel15": lambda s: utils.USM(s, 15, 3.0, 0.7, method="bessel"),
@@ -157,6 +189,7 @@ def main():
                 row["TBps_on_its_transits"] = round(WAVELET_TRANSITS[route] * 12 * size * size / (med * 1e-3) / 1e12, 3)
             res["wavelet_equalizer"]["%s_%s" % (coupling, {1: "route1", 2: "route2", 0: "auto"}[route])] = row
     res["guided"] = guided_section(img, ctx, size)
+    res["llf"] = llf_section(img, ctx, size)
     res["checks"] = {"%s_%s" % (name, what): res["resident"][name][what] <= res["per_channel_f64"][name][what]
                      for name in ("usm_gauss15", "usm_bessel15") for what in ("kernel_ms", "wall_ms")}
     print(json.dumps(res))
