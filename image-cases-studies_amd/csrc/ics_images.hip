@@ -1,5 +1,5 @@
 // ics_images.hip -- the ics_img_* entries of the C ABI (include/ics_hip.h).  Host side only; kernels live in ics_img.hip / ics_img_filters.hip /
-// ics_img_tvdenoise.hip / ics_img_wavelet.hip / ics_img_guided.hip / ics_img_llf.hip (what these five share: ics_img_px.h) / ics_resize.hip.
+// ics_img_tvdenoise.hip / ics_img_wavelet.hip / ics_img_noise.hip / ics_img_guided.hip / ics_img_llf.hip (what these six share: ics_img_px.h) / ics_resize.hip.
 #include "ics_host.h"
 
 using namespace ics_host;
@@ -30,7 +30,8 @@ extern "C" void ics_img_destroy(ics_img* m) {
 namespace {
 // An entry that makes a new image: *out, up to four pool temporaries and the ev0 / ev1 bracket around its kernels.  *out is NULL from
 // the start and stays NULL unless finish() returns ICS_OK; whatever is still held when the scope ends, on any return, goes back to
-// the pool (queued work of a context runs on its one stream: so does whatever reuses the blocks).
+// the pool (queued work of a context runs on its one stream: so does whatever reuses the blocks).  out == nullptr: an entry that
+// makes no image (ics_img_noise_estimate).
 struct ImgOp {
   ics_ctx* c; ics_img** out; const char* name;
   void* tmp[4] = {nullptr, nullptr, nullptr, nullptr};
@@ -38,7 +39,7 @@ struct ImgOp {
   bool bracket = false, ok = false;
   ImgOp(ics_ctx* ctx, ics_img** o, const char* entry) : c(ctx), out(o), name(entry) {}   // (*out: cleared by check_new)
   ImgOp(const ImgOp&) = delete;
-  ~ImgOp() { release(); if (!ok) { ics_img_destroy(*out); *out = nullptr; } }
+  ~ImgOp() { release(); if (!ok && out) { ics_img_destroy(*out); *out = nullptr; } }
   void release() { for (int i = 0; i < ntmp; ++i) c->pool.release(tmp[i]); ntmp = 0; }
   hipError_t alloc(void** p, size_t bytes) {
     if (ntmp == 4) return hipErrorInvalidValue;
@@ -47,9 +48,14 @@ struct ImgOp {
     return e;
   }
   hipError_t begin() { bracket = true; return hipEventRecord(c->ev0, c->stream); }
+  hipError_t end() {   // closes the bracket before finish(): for an entry that queues something behind its kernels
+    const hipError_t e = hipEventRecord(c->ev1, c->stream);
+    if (e == hipSuccess) c->ev_pending = true;
+    bracket = false;
+    return e;
+  }
   int finish(hipError_t e) {
-    if (bracket && e == hipSuccess) e = hipEventRecord(c->ev1, c->stream);
-    if (bracket && e == hipSuccess) c->ev_pending = true;
+    if (bracket && e == hipSuccess) e = end();
     release();
     ok = e == hipSuccess;   // (otherwise the destructor destroys *out)
     return ok ? ICS_OK : ics_set_error(e == hipErrorOutOfMemory ? ICS_ENOMEM : ICS_EHIP, "%s: %s", name, hipGetErrorString(e));
@@ -312,6 +318,43 @@ extern "C" int ics_img_wavelet_equalize(const ics_img* src, int scales, const fl
   if (e == hipSuccess) e = op.begin();
   if (e == hipSuccess) e = ics_launch_img_wavelet(src->d, H, W, scales, gains, thresholds, residual, coupling, route, tmp, (*out)->d, c->stream);
   return op.finish(e);
+}
+
+// ---- noise estimate of a device image (csrc/ics_img_noise.hip) -------------------------------------------------------------------
+// route 0: the keys route at every size.  Measured ("Noise estimate on a resident frame"; channel / vector): at 4096^2 it
+// takes 0.34 / 0.17 ms against 0.64 / 0.62, at 1024^2 0.073 / 0.055 against 0.103 / 0.078, and at 128^2, where the seven launches
+// are all there is, 0.046 / 0.031 against 0.045 / 0.031: no crossover.  It borrows 12 / 4 bytes per pixel from the pool; route 1 needs
+// nothing but the 24 KB block and stays callable.
+extern "C" int ics_img_noise_estimate(const ics_img* src, int coupling, int route, float median[3], float level[3], float sigma[3]) {
+  if (!src) return ics_set_error(ICS_EINVAL, "src is NULL");
+  if (!median) return ics_set_error(ICS_EINVAL, "median is NULL");
+  if (!level) return ics_set_error(ICS_EINVAL, "level is NULL");
+  if (!sigma) return ics_set_error(ICS_EINVAL, "sigma is NULL");
+  RC(check_coupling(coupling));
+  RC(check_route(route, "recompute", "keys"));
+  ics_ctx* c = src->ctx;
+  HIPCHK(hipSetDevice(c->device));
+  const int H = src->H, W = src->W;
+  if (route == 0) route = 2;
+  ImgOp op(c, nullptr, "img_noise_estimate");
+  unsigned *blk = nullptr, *keys = nullptr, bits[3] = {0u, 0u, 0u};
+  hipError_t e = op.alloc((void**)&blk, ics_img_noise_block_words() * sizeof(unsigned));
+  if (const size_t words = ics_img_noise_key_words(H, W, coupling, route); e == hipSuccess && words) e = op.alloc((void**)&keys, words * sizeof(unsigned));
+  if (e == hipSuccess) e = op.begin();
+  if (e == hipSuccess) e = ics_launch_img_noise(src->d, H, W, coupling, route, c->cus, blk, keys, c->stream);
+  if (e == hipSuccess) e = op.end();
+  if (e == hipSuccess) e = hipMemcpyAsync(bits, blk + ics_img_noise_result_word(), sizeof(bits), hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  RC(op.finish(e));
+  static const double E[] = ICS_IMG_NOISE_E;
+  const double kappa = coupling ? 1.5381722544550522 / sqrt(3.0) : 0.6744897501960817, per_channel = coupling ? sqrt(3.0) * E[0] : E[0];
+  for (int i = 0; i < 3; ++i) {
+    float m;
+    memcpy(&m, &bits[coupling ? 0 : i], sizeof(m));
+    const double lv = (double)m / kappa;
+    median[i] = m; level[i] = (float)lv; sigma[i] = (float)(lv / per_channel);
+  }
+  return ICS_OK;
 }
 
 // ---- guided filter of a device image (csrc/ics_img_guided.hip) ------------------------------------------------------------------

@@ -1,5 +1,5 @@
-// ics_img_px.h -- for ics_img_filters.hip, ics_img_tvdenoise.hip, ics_img_wavelet.hip, ics_img_guided.hip and ics_img_llf.hip only (everything here is local to
-// the unit that includes it): what their kernels and launchers share, the 12-byte pixel access, the symmetric fold, two launch helpers.
+// ics_img_px.h -- for ics_img_filters.hip, ics_img_tvdenoise.hip, ics_img_wavelet.hip, ics_img_guided.hip, ics_img_llf.hip and ics_img_noise.hip only (everything here is local to
+// the unit that includes it): what their kernels and launchers share, the 12-byte pixel access, the symmetric fold, the B3-spline pass, two launch helpers.
 #pragma once
 #include "ics_kernels.h"
 
@@ -25,6 +25,11 @@ __device__ __forceinline__ int symm(int i, int n) {
 }
 // ... with the division skipped inside the picture (ics_img_wavelet.hip): either form alone changes the code of the other unit's kernels
 __device__ __forceinline__ int wv_fold(int i, int n) { return (unsigned)i < (unsigned)n ? i : symm(i, n); }
+
+// one axis pass of the B3 spline (ics_img_wavelet.hip, ics_img_noise.hip): am2 .. ap2 at offsets -2 d .. 2 d
+__device__ __forceinline__ float wv_pass(float am2, float am1, float a0, float ap1, float ap2) {
+  return __fadd_rn(__fadd_rn(__fmul_rn(__fadd_rn(am2, ap2), 0.0625f), __fmul_rn(__fadd_rn(am1, ap1), 0.25f)), __fmul_rn(a0, 0.375f));
+}
 
 // a launch with more dynamic LDS than the default limit of 64 KB needs the kernel's limit raised first
 template <typename Kern>

@@ -43,11 +43,6 @@ namespace {
 
 struct wv_prm { float g[WVF], t[WVF]; };
 
-// one axis pass of the B3 spline: am2 .. ap2 at offsets -2 d .. 2 d
-__device__ __forceinline__ float wv_pass(float am2, float am1, float a0, float ap1, float ap2) {
-  return __fadd_rn(__fadd_rn(__fmul_rn(__fadd_rn(am2, ap2), 0.0625f), __fmul_rn(__fadd_rn(am1, ap1), 0.25f)), __fmul_rn(a0, 0.375f));
-}
-
 // acc += g * shrink(cur - nxt, t)
 template <bool VEC>
 __device__ __forceinline__ void wv_detail(const float cur[3], const float nxt[3], float t, float g, float acc[3]) {

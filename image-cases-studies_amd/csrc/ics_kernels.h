@@ -287,6 +287,18 @@ int ics_img_wavelet_frames(int scales, int route);
 hipError_t ics_launch_img_wavelet(const float* f, int H, int W, int scales, const float* gains, const float* thresholds, float residual,
                                   int coupling, int route, float* const tmp[2], float* out, hipStream_t s);
 
+// ---- noise estimate of device-resident images (ics_img_noise.hip): the exact lower median of the finest starlet detail scale ------
+// A radix select in three histogram passes with a one-workgroup select between them, no host round trip.  blk:
+// ics_img_noise_block_words words (histograms and state; zeroed by the launcher); afterwards the words from
+// ics_img_noise_result_word on hold the medians' bit patterns, three ("channel") or one ("vector").  route 1: every pass recomputes
+// the detail from the frame, keys unused; 2: the first pass writes the keys (ics_img_noise_key_words words), the later ones read them.
+// cus: compute units of the device (the persistent grids are sized by it).  f is only read.
+size_t ics_img_noise_block_words();
+size_t ics_img_noise_result_word();
+size_t ics_img_noise_key_words(int H, int W, int coupling, int route);
+size_t ics_img_noise_keys_lds(int coupling);
+hipError_t ics_launch_img_noise(const float* f, int H, int W, int coupling, int route, int cus, unsigned* blk, unsigned* keys, hipStream_t s);
+
 // ---- guided filter of device-resident images (ics_img_guided.hip): box means, a solve per pixel, base layer + detail * (src - base) --
 // route 1: coefficients to the planar frame `coef` (ics_img_guided_coef_floats floats), then the output; 2: one launch, coefficients
 // in LDS, radius <= ICS_IMG_GUIDED_FUSED_RADIUS, coef unused.  coupling 0: per channel, 1: the RGB pixel as the guide.

@@ -99,7 +99,9 @@ def deblur_module(pic, filename, dest_path, blur_width, confidence=10, tolerance
     arguments (residual 1, coupling "vector" unless given) on the deblurred frame, in the gamma-encoded domain, after `denoise`,
     before `sharpen` and before the final clip: the scale-by-scale form of the README's advice -- the 4 to 16 px detail that
     Richardson-Lucy leaves flat is lifted by the gains of scales 2 to 4 while the 1 px noise it amplified keeps gain 1 or is
-    thresholded away; on the resident path the frame stays in HBM.
+    thresholded away; on the resident path the frame stays in HBM.  thresholds "auto" or ("auto", strength): the noise the
+    deconvolution left in this frame is estimated where the frame lies (`utils.noise_estimate`, same coupling; only its few result
+    floats come back) and every scale is thresholded at `strength` (3 unless given) standard deviations of it.
     `detail=(radius, eps, gain)` or `(radius, eps, gain, coupling)`: `utils.guided_filter` with these arguments (coupling
     "vector" unless given) on the deblurred frame, in the gamma-encoded domain, after `local_contrast`, before `sharpen` and before
     the final clip: the frame's guided-filter base layer plus `gain` times its detail -- a gain above 1 sharpens at radii of 8 to
@@ -286,7 +288,8 @@ def _denoise_args(denoise):
 
 
 def _local_contrast_args(local_contrast):
-    """`local_contrast` of deblur_module -> None or (gains, thresholds or None, coupling), gains and thresholds as tuples of floats"""
+    """`local_contrast` of deblur_module -> None or (gains, thresholds or None, coupling), gains and thresholds as tuples of floats;
+    thresholds "auto" or ("auto", strength) as ("auto", strength)"""
     if local_contrast is None:
         return None
     try:
@@ -298,10 +301,12 @@ def _local_contrast_args(local_contrast):
     gains, thresholds, coupling = (local_contrast + (None, "vector")[len(local_contrast) - 1:])[:3]
     from lib._native import wavelet_args
     try:
-        wavelet_args(gains, thresholds, 1.0, coupling)
+        checked = wavelet_args(gains, thresholds, 1.0, coupling)
     except (ValueError, TypeError) as exc:
         raise ValueError("local_contrast: %s" % exc)
     as_floats = lambda v: tuple(float(x) for x in np.atleast_1d(np.asarray(v, dtype=np.float64)))     # noqa: E731
+    if isinstance(checked[1], tuple):                                    # "auto" or ("auto", strength): estimated on the frame it filters
+        return as_floats(gains), checked[1], coupling
     return as_floats(gains), None if thresholds is None else as_floats(thresholds), coupling
 
 

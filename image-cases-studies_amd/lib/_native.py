@@ -6,7 +6,9 @@ symbol-level tests can run on a GPU-less machine) but every compute entry point 
 """
 from __future__ import annotations
 
+import collections
 import ctypes as C
+import math
 import os
 
 import numpy as np
@@ -92,6 +94,10 @@ IMG_GUIDED_MAX_RADIUS = 32       # include/ics_hip.h ICS_IMG_GUIDED_MAX_RADIUS: 
 IMG_GUIDED_FUSED_RADIUS = 8      # include/ics_hip.h ICS_IMG_GUIDED_FUSED_RADIUS: largest radius of its one-launch route
 IMG_LLF_MAX_LEVELS = 10          # include/ics_hip.h ICS_IMG_LLF_MAX_LEVELS: pyramid levels of the local Laplacian filter
 IMG_LLF_MAX_SAMPLES = 16         # include/ics_hip.h ICS_IMG_LLF_MAX_SAMPLES: remapped copies it interpolates between
+IMG_NOISE_STRENGTH = 3.0         # include/ics_hip.h ICS_IMG_NOISE_STRENGTH: thresholds="auto" cuts this many standard deviations
+IMG_NOISE_E = (0.89079631027875839, 0.20066385102441897, 0.085507504753369934, 0.041217444374316202,      # include/ics_hip.h ICS_IMG_NOISE_E: e_j, the L2
+               0.020424966592781431, 0.01018975924921329, 0.0050920466808193074, 0.0025456694579151255)   # norm of the response of scale j to a unit impulse
+IMG_NOISE_KAPPA = {"channel": 0.6744897501960817, "vector": 1.5381722544550522 / math.sqrt(3.0)}            # median of |N(0, 1)|; of chi_3 over its rms
 _F32_MAX = float(np.finfo(np.float32).max)   # what _finite32 compares against
 
 
@@ -167,6 +173,7 @@ def load():
     lib.ics_img_bilateral.argtypes = [vp, ci, cf, cf, C.POINTER(vp)]
     lib.ics_img_tv_denoise.argtypes = [vp, cf, ci, ci, ci, C.POINTER(vp)]
     lib.ics_img_wavelet_equalize.argtypes = [vp, ci, vp, vp, cf, ci, ci, C.POINTER(vp)]
+    lib.ics_img_noise_estimate.argtypes = [vp, ci, ci, C.POINTER(cf), C.POINTER(cf), C.POINTER(cf)]
     lib.ics_img_guided.argtypes = [vp, ci, cf, cf, ci, ci, C.POINTER(vp)]
     lib.ics_img_local_laplacian.argtypes = [vp, cf, cf, cf, ci, ci, ci, ci, C.POINTER(vp)]
     lib.ics_rl_upload_img.argtypes = [vp, vp, ci, ci, vp, ci, ci, vp]
@@ -190,7 +197,7 @@ def load():
                  "ics_rl_download", "ics_rl_run", "ics_rl_stage", "ics_rl_read", "ics_rl_write", "ics_rl_read_rows", "ics_rl_write_rows", "ics_rl_copy_rows", "ics_normalize_kernel",
                  "ics_tv", "ics_conv2d_symm", "ics_usm", "ics_bilateral", "ics_resize_bicubic", "ics_img_create", "ics_img_shape",
                  "ics_img_upload", "ics_img_upload_int", "ics_img_download", "ics_img_pad_edge", "ics_img_crop", "ics_img_paste", "ics_img_gamma", "ics_img_resize",
-                 "ics_img_convolve", "ics_img_usm", "ics_img_bilateral", "ics_img_tv_denoise", "ics_img_wavelet_equalize", "ics_img_guided", "ics_img_local_laplacian",
+                 "ics_img_convolve", "ics_img_usm", "ics_img_bilateral", "ics_img_tv_denoise", "ics_img_wavelet_equalize", "ics_img_noise_estimate", "ics_img_guided", "ics_img_local_laplacian",
                  "ics_rl_upload_img", "ics_rl_download_img", "ics_group_create", "ics_group_info", "ics_group_barrier",
                  "ics_group_allreduce_max", "ics_group_allreduce_sum", "ics_group_describe", "ics_group_allgather"):
         getattr(lib, name).restype = ci
@@ -264,16 +271,63 @@ def _route(route, names):
     return int(route)
 
 
+NoiseEstimate = collections.namedtuple("NoiseEstimate", "median level sigma")
+
+
+def noise_args(coupling="vector", route=0):
+    """the arguments of DeviceImage.noise_estimate checked (ValueError) and as (coupling, route): a string, an int"""
+    _coupling(coupling)
+    return coupling, _route(route, "1: every pass recomputes the detail scale, 2: the first pass stores the keys")
+
+
+def _strength(strength):
+    if not _finite32(strength, scalar=True) or not float(strength) >= 0:
+        raise ValueError("strength %r (must be finite and >= 0)" % (strength,))
+    return float(strength)
+
+
+def auto_thresholds(level, scales, strength=IMG_NOISE_STRENGTH):
+    """The thresholds of the wavelet equaliser that cut `strength` standard deviations of the noise whose `level` noise_estimate
+    found (one value, or the three of "channel" coupling, of which the largest counts: the equaliser takes one threshold per scale):
+    t_j = strength * level * e_j / e_0 for j < scales, in double, as a float32 array.  strength 3 is the k-sigma rule of the starlet
+    literature: a convention, not a measurement."""
+    strength = _strength(strength)
+    try:
+        whole = int(scales) == scales and not isinstance(scales, bool)
+    except (TypeError, ValueError, OverflowError):
+        whole = False
+    if not whole or not 1 <= int(scales) <= IMG_WAVELET_MAX_SCALES:
+        raise ValueError("scales %r (an integer, 1 to %d)" % (scales, IMG_WAVELET_MAX_SCALES))
+    lv = np.atleast_1d(np.asarray(level, dtype=np.float64))
+    if lv.ndim != 1 or lv.size not in (1, 3) or not _finite32(lv) or np.any(lv < 0):
+        raise ValueError("level %r (one or three values, finite and >= 0)" % (level,))
+    top = float(lv.max())
+    return np.array([strength * top * IMG_NOISE_E[j] / IMG_NOISE_E[0] for j in range(int(scales))], dtype=np.float64).astype(np.float32)
+
+
+def _auto_form(thresholds):
+    """thresholds="auto" or ("auto", strength) -> ("auto", strength); anything else that is no string -> None"""
+    if isinstance(thresholds, str):
+        if thresholds != "auto":
+            raise ValueError("thresholds %r (one value per scale, None, \"auto\" or (\"auto\", strength))" % (thresholds,))
+        return ("auto", IMG_NOISE_STRENGTH)
+    if isinstance(thresholds, (tuple, list)) and len(thresholds) > 0 and isinstance(thresholds[0], str):
+        if len(thresholds) != 2 or thresholds[0] != "auto":
+            raise ValueError("thresholds %r (one value per scale, None, \"auto\" or (\"auto\", strength))" % (thresholds,))
+        return ("auto", _strength(thresholds[1]))
+    return None
+
+
 def wavelet_args(gains, thresholds=None, residual=1.0, coupling="vector", route=0):
     """the arguments of DeviceImage.wavelet_equalize checked (ValueError) and as (gains, thresholds or None, residual, coupling,
-    route): float32 arrays, a float, a string, an int"""
+    route): float32 arrays, a float, a string, an int; thresholds "auto" or ("auto", strength) come back as ("auto", strength)"""
     g = np.atleast_1d(np.asarray(gains, dtype=np.float64))
     if g.ndim != 1 or not 1 <= g.size <= IMG_WAVELET_MAX_SCALES:
         raise ValueError("gains: one value per scale, 1 to %d scales, got shape %s" % (IMG_WAVELET_MAX_SCALES, g.shape))
     if not _finite32(g):
         raise ValueError("gains %r (must be finite)" % (gains,))
-    t = None
-    if thresholds is not None:
+    t = _auto_form(thresholds)
+    if thresholds is not None and t is None:
         t = np.atleast_1d(np.asarray(thresholds, dtype=np.float64))
         if t.shape != g.shape:
             raise ValueError("thresholds: %s values for %d gains (one per scale, or None)" % (t.shape, g.size))
@@ -540,9 +594,30 @@ class DeviceImage:
         the three channels of a pixel are shrunk together by their magnitude, so the hue of a detail is kept.  route 0: the
         library's choice, 1: a launch per scale, 2: the first IMG_WAVELET_FUSED scales in one launch on LDS tiles; all give
         identical bits.  ValueError (before any native call): no or more than 8 gains, thresholds of another length, a value that
-        is not finite, a negative threshold, unknown coupling or route."""
+        is not finite, a negative threshold, unknown coupling or route.  thresholds "auto" or ("auto", strength): the noise of this
+        picture is estimated first (noise_estimate with the same coupling) and the thresholds are auto_thresholds(level, scales,
+        strength), strength 3 unless given: the finest scales lose what is noise by the 3 sigma rule, whatever the deblurring made
+        of it."""
         g, t, residual, coupling, route = wavelet_args(gains, thresholds, residual, coupling, route)
+        if isinstance(t, tuple):
+            t = auto_thresholds(self.noise_estimate(coupling).level, g.size, t[1])
         return self._new(load().ics_img_wavelet_equalize, int(g.size), _ptr(g), None if t is None else _ptr(t), residual, _coupling(coupling), route)
+
+    def noise_estimate(self, coupling="vector", route=0):
+        """The noise of the picture from the finest detail scale w_0 of the wavelet equaliser (Donoho and Johnstone's robust
+        estimator): NoiseEstimate(median, level, sigma), tuples of three floats for coupling "channel" (R, G, B) and of one for
+        "vector".  median: the exact lower median (rank (n - 1) // 2) of |w_0| of a channel, or of the magnitude of w_0 over the
+        three channels, found on the device by a radix select (csrc/ics_img_noise.hip; restated in tests/noise_ref.py); level =
+        median / IMG_NOISE_KAPPA[coupling], the rms of that quantity under Gaussian noise, which is what the equaliser's threshold
+        of scale 0 is measured in; sigma: the standard deviation per channel of white noise in the picture that gives this level.
+        Detail of the picture itself counts as noise where it fills more than half of the frame.  route 0: the library's choice, 1:
+        every pass of the select recomputes w_0, 2: the first pass stores the keys; all give identical bits.  Only the result
+        floats cross PCIe; the call waits for them.  ValueError (before any native call): unknown coupling or route."""
+        coupling, route = noise_args(coupling, route)
+        out = [(C.c_float * 3)() for _ in range(3)]
+        _check(load().ics_img_noise_estimate(self._h, _coupling(coupling), route, *out))
+        n = 3 if coupling == "channel" else 1
+        return NoiseEstimate(*(tuple(float(v) for v in a[:n]) for a in out))
 
     def guided_filter(self, radius, eps, detail=0.0, coupling="vector", route=0):
         """Guided filter with the picture as its own guide (He, Sun, Tang): the edge-preserving base layer q of the

@@ -17,7 +17,7 @@ The filters run on the GPU through libics_hip.so in float64 like the reference (
 convolve2d(mode="same", boundary="symm")); there is no CPU fallback for them.  Given a `lib._native.DeviceImage`
 (H x W x 3 float32 in HBM) instead of a 2-D array, the four filters work on it there, every channel on its own
 in float32, and return a new DeviceImage (csrc/ics_img_filters.hip): no transfer, no synchronisation; `tv_denoise`,
-`wavelet_equalizer`, `guided_filter` and `local_laplacian` (not in the reference; csrc/ics_img_tvdenoise.hip, csrc/ics_img_wavelet.hip,
+`wavelet_equalizer`, `noise_estimate`, `guided_filter` and `local_laplacian` (not in the reference; csrc/ics_img_tvdenoise.hip, csrc/ics_img_wavelet.hip,
 csrc/ics_img_guided.hip, csrc/ics_img_llf.hip) work on such an image or on an
 H x W x 3 array.  The colour tools of
 the reference (Lagrange_interpolation, grey_point, auto_vibrance, overlay, blending) and its dead
@@ -159,7 +159,9 @@ def wavelet_equalizer(src, gains, thresholds=None, residual=1.0, coupling="vecto
     thresholds=[0.03, 0.015, 0, 0, 0] removes noise from the two finest scales only.  coupling "vector" shrinks the three channels
     of a pixel together (no hue shift), "channel" each on its own.  A `lib._native.DeviceImage` gives a new DeviceImage (nothing
     crosses PCIe); an H x W x 3 array is uploaded once and the float32 result downloaded once (`DeviceImage.wavelet_equalize`,
-    csrc/ics_img_wavelet.hip)."""
+    csrc/ics_img_wavelet.hip).  thresholds="auto" or ("auto", strength) takes them from `noise_estimate` of this picture with the same
+    coupling: strength (3 unless given) standard deviations of its noise at every scale, estimated on the device from the resident
+    frame (only a few floats come back)."""
     if isinstance(src, _native.DeviceImage):
         return src.wavelet_equalize(gains, thresholds, residual, coupling)
     arr = np.asarray(src)
@@ -175,6 +177,29 @@ def wavelet_equalizer(src, gains, thresholds=None, residual=1.0, coupling="vecto
         return res.to_host()
     finally:
         res.close()
+
+
+def noise_estimate(src, coupling="vector"):
+    """Not in the reference's lib/utils.py (its README calls its algorithms "auto-adaptative, meaning that all the regularization
+    parameters are estimated by the algorithm based on statistical assumptions"; this does it for the filters that follow the
+    deconvolution): the noise of a picture from the finest scale of the B3-spline wavelet transform, by the median of its absolute
+    value (Donoho and Johnstone) -- robust against the edges and texture that a standard deviation would count as noise.  Returns
+    `lib._native.NoiseEstimate(median, level, sigma)`: tuples of three floats (R, G, B) for coupling "channel", of one for "vector"
+    (the magnitude over the three channels).  sigma is the standard deviation per channel of white noise that would give this
+    median; level is the rms of the quantity `wavelet_equalizer` thresholds at its finest scale, so that thresholds="auto" there is
+    `lib._native.auto_thresholds(level, scales)`.  A `lib._native.DeviceImage` is read where it lies; an H x W x 3 array is uploaded
+    once and nothing but the result floats comes back (`DeviceImage.noise_estimate`, csrc/ics_img_noise.hip)."""
+    if isinstance(src, _native.DeviceImage):
+        return src.noise_estimate(coupling)
+    arr = np.asarray(src)
+    if arr.ndim != 3 or arr.shape[2] != 3:
+        raise ValueError("expected a DeviceImage or an H x W x 3 array, got shape %s" % (arr.shape,))
+    _native.noise_args(coupling)                                         # refused before anything is uploaded
+    img = _native.DeviceImage.from_host(np.ascontiguousarray(arr, dtype=np.float32))
+    try:
+        return img.noise_estimate(coupling)
+    finally:
+        img.close()
 
 
 def guided_filter(src, radius, eps, detail=0.0, coupling="vector"):

@@ -414,6 +414,26 @@ int ics_img_tv_denoise(const ics_img *src, float weight, int iterations, int cou
 #define ICS_IMG_WAVELET_FUSED 3
 int ics_img_wavelet_equalize(const ics_img *src, int scales, const float *gains, const float *thresholds /* may be NULL */,
                              float residual, int coupling, int route, ics_img **out);
+/* Noise estimate of a device image from the finest detail scale of the wavelet equaliser above (Donoho and Johnstone's robust
+ * estimator; Starck and Murtagh for the starlet): w_0 = src - c_1 with exactly that arithmetic, and
+ *   coupling 0 (channel): median[c] = the lower median of |w_0| of channel c, three results;
+ *   coupling 1 (vector):  the lower median of m = sqrt(w_r^2 + w_g^2 + w_b^2), the squares added smallest first, in all three slots.
+ * The lower median of n = H W values is the one of rank (n - 1) / 2 (from 0) in ascending order: exact, an element of the population,
+ * found by a radix select on the device (no sort, no bins wider than one value); two runs and both routes give identical bits.  The
+ * picture is taken to be finite.  The host derives, in double from the float32 median and rounded to float32,
+ *   level = median / kappa, kappa = 0.6744897501960817 (channel: the median of |N(0, 1)|) or 1.5381722544550522 / sqrt(3) (vector: the
+ *     median of a chi with 3 degrees of freedom over its rms): the rms of the thresholded quantity at scale 0 under Gaussian noise;
+ *   sigma = level / e_0 (channel), level / (sqrt(3) e_0) (vector): the per-channel standard deviation of white noise in the picture,
+ * where e_j (ICS_IMG_NOISE_E) is the L2 norm of the response of w_j to a unit impulse.  A threshold of `strength` standard deviations
+ * at scale j is strength * level * e_j / e_0 (ICS_IMG_NOISE_STRENGTH: the 3 sigma rule); the Python layer's thresholds="auto" does
+ * this.  route 1: every pass of the select recomputes w_0 from src; 2: the first pass writes the keys to a pooled buffer (12 / 4 bytes
+ * per pixel), the later passes read them; 0: the library's choice.  Queued on the context's stream, its kernels bracketed
+ * for ics_ctx_last_kernel_ms; then the results are copied back and WAITED FOR: with ics_img_download this is the only image entry
+ * that synchronises.  src is not written.  ICS_EINVAL: src or an output NULL, unknown coupling or route. */
+#define ICS_IMG_NOISE_STRENGTH 3.0f
+#define ICS_IMG_NOISE_E {0.89079631027875839, 0.20066385102441897, 0.085507504753369934, 0.041217444374316202, \
+                         0.020424966592781431, 0.01018975924921329, 0.0050920466808193074, 0.0025456694579151255}
+int ics_img_noise_estimate(const ics_img *src, int coupling, int route, float median[3], float level[3], float sigma[3]);
 /* Guided filter of a device image with the picture as its own guide (He, Sun, Tang): an edge-preserving base layer q from box means
  * and one closed-form solve per pixel, and the detail src - q scaled back onto it.  I' = src - 0.5;
  *   mean(x) = the sum of x over the (2 radius + 1)^2 window clipped to the picture / its pixel count; a sum runs along x first, then

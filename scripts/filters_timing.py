@@ -1,6 +1,6 @@
 """Timing of the lib/utils.py filters on one seeded SIZE x SIZE RGB float32 picture (GPU box), one JSON line:
 
-    python scripts/filters_timing.py [SIZE=4096] [guided | llf]       ("guided", "llf": that section alone)
+    python scripts/filters_timing.py [SIZE=4096] [guided | llf | noise]       ("guided", "llf", "noise": that section alone)
 
   resident   the filters on a DeviceImage in HBM (csrc/ics_img_filters.hip): device time of the kernels (HIP events around them,
              ics_ctx_last_kernel_ms; warm, median of 25) and wall time of the queued call up to a stream synchronise
@@ -28,6 +28,13 @@
              couplings, route 1 (a reduce chain per sample: the frame read K + 1 times) and route 2 (the samples batched: read once):
              kernel ms, median, minimum and maximum of 5 rounds in which the routes alternate, and TB/s on each route's level-0
              bytes per pixel (144 / 48 vector, 168 / 72 channel; the levels below add a third); "auto" is what route=0 takes
+  noise      DeviceImage.noise_estimate (csrc/ics_img_noise.hip), both couplings, route 1 (every pass of the radix select recomputes the
+             detail scale: the frame read three times) and route 2 (the first pass stores the keys, 12 / 4 B/px, the later passes read
+             them): kernel ms, median and minimum of 9 rounds in which the routes alternate, the wall time of the call (it waits for
+             its result), and beside it the five-scale wavelet_equalize of the same run as the figure to read it against; on three
+             pictures that load the LDS histogram differently: "uniform" (the script's picture, keys spread over many bins),
+             "gauss" (a ramp with Gaussian noise of sigma 0.01: the keys of a noisy photograph, two to three octaves) and "flat" (a
+             constant: every key 0, every wave adds its count once); "auto" is what route=0 takes
   checks     the resident USM must not take longer than the three float64 calls, in kernel time and in wall time (a guard against a
              broken kernel, not a target); the exit status is 1 if one of them fails
 Starts no child process; a job script puts its own time limit around it."""
@@ -109,6 +116,44 @@ def llf_section(img, ctx, size):
     return res
 
 
+REPS_NOISE = 9
+
+
+def noise_section(img, ctx, size):
+    res = {"equalizer_gains": WAVELET_GAINS}
+    y, x = np.mgrid[0:size, 0:size].astype(np.float32)
+    ramp = (0.35 + 0.15 * (x + y) / max(size - 1, 1))[..., None]
+    gauss = _native.DeviceImage.from_host((ramp + np.random.default_rng(1).normal(0.0, 0.01, (size, size, 3))).astype(np.float32), ctx)
+    flat = _native.DeviceImage.from_host(np.full((size, size, 3), 0.375, np.float32), ctx)
+    del x, y, ramp
+    for name, pic in (("uniform", img), ("gauss", gauss), ("flat", flat)):
+        for coupling in ("channel", "vector"):
+            times, wall = {1: [], 2: [], 0: []}, {1: [], 2: [], 0: []}
+            for route in times:
+                est = pic.noise_estimate(coupling, route=route)     # warm
+            ctx.synchronize()
+            for _ in range(REPS_NOISE):                    # the routes alternate within a round
+                for route in times:
+                    t0 = time.perf_counter()
+                    pic.noise_estimate(coupling, route=route)
+                    wall[route].append((time.perf_counter() - t0) * 1e3)
+                    times[route].append(ctx.last_kernel_ms())
+            for route, ms in times.items():
+                res["%s_%s_%s" % (name, coupling, {1: "route1", 2: "route2", 0: "auto"}[route])] = {
+                    "kernel_ms": round(float(np.median(ms)), 4), "min_ms": round(float(np.min(ms)), 4), "wall_ms": round(float(np.median(wall[route])), 4)}
+            res["%s_%s_sigma" % (name, coupling)] = [round(v, 6) for v in est.sigma]
+            pic.wavelet_equalize(WAVELET_GAINS, WAVELET_THRESHOLDS, 1.0, coupling).close()     # warm
+            ms = []
+            for _ in range(REPS_NOISE):
+                out = pic.wavelet_equalize(WAVELET_GAINS, WAVELET_THRESHOLDS, 1.0, coupling)
+                ms.append(ctx.last_kernel_ms())
+                out.close()
+            res["%s_%s_wavelet_equalize_5" % (name, coupling)] = {"kernel_ms": round(float(np.median(ms)), 4), "min_ms": round(float(np.min(ms)), 4)}
+    gauss.close()
+    flat.close()
+    return res
+
+
 def main():
     size = int(sys.argv[1]) if len(sys.argv) > 1 else 4096
     ctx = _native.Context.get()
@@ -120,6 +165,9 @@ def main():
         return 0
     if sys.argv[2:] == ["llf"]:
         print(json.dumps({"size": size, "device": ctx.name, "llf": llf_section(img, ctx, size)}))
+        return 0
+    if sys.argv[2:] == ["noise"]:
+        print(json.dumps({"size": size, "device": ctx.name, "noise": noise_section(img, ctx, size)}))
         return 0
     ops = {"usm_gauss15": lambda s: utils.USM(s, 15, 2.5, 0.7, method="gauss"),
            "usm_bessel15": lambda s: utils.USM(s, 15, 3.0, 0.7, method="bessel"),
@@ -190,6 +238,7 @@ def main():
             res["wavelet_equalizer"]["%s_%s" % (coupling, {1: "route1", 2: "route2", 0: "auto"}[route])] = row
     res["guided"] = guided_section(img, ctx, size)
     res["llf"] = llf_section(img, ctx, size)
+    res["noise"] = noise_section(img, ctx, size)
     res["checks"] = {"%s_%s" % (name, what): res["resident"][name][what] <= res["per_channel_f64"][name][what]
                      for name in ("usm_gauss15", "usm_bessel15") for what in ("kernel_ms", "wall_ms")}
     print(json.dumps(res))
