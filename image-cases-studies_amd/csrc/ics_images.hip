@@ -1,5 +1,5 @@
 // ics_images.hip -- the ics_img_* entries of the C ABI (include/ics_hip.h).  Host side only; kernels live in ics_img.hip / ics_img_filters.hip /
-// ics_img_tvdenoise.hip / ics_img_wavelet.hip / ics_img_noise.hip / ics_img_guided.hip / ics_img_llf.hip (what these six share: ics_img_px.h) / ics_resize.hip.
+// ics_img_tvdenoise.hip / ics_img_wavelet.hip / ics_img_noise.hip / ics_img_despeckle.hip / ics_img_guided.hip / ics_img_llf.hip (what these seven share: ics_img_px.h) / ics_resize.hip.
 #include "ics_host.h"
 
 using namespace ics_host;
@@ -354,6 +354,39 @@ extern "C" int ics_img_noise_estimate(const ics_img* src, int coupling, int rout
     const double lv = (double)m / kappa;
     median[i] = m; level[i] = (float)lv; sigma[i] = (float)(lv / per_channel);
   }
+  return ICS_OK;
+}
+
+// ---- despeckle of a device image (csrc/ics_img_despeckle.hip) ----------------------------------------------------------------------
+// route 0: the tile route at every radius and size ("Despeckle on a resident frame": the timing table and the rule).
+extern "C" int ics_img_despeckle(const ics_img* src, int radius, const float threshold[3], int coupling, int route, ics_img** out, unsigned replaced[3]) {
+  RC(check_new(src, out));
+  if (!threshold) return ics_set_error(ICS_EINVAL, "threshold is NULL");
+  if (radius < 1 || radius > ICS_IMG_DESPECKLE_MAX_RADIUS) return ics_set_error(ICS_EINVAL, "radius = %d (1 .. %d)", radius, ICS_IMG_DESPECKLE_MAX_RADIUS);
+  RC(check_coupling(coupling));
+  for (int i = 0; i < (coupling ? 1 : 3); ++i)
+    if (!std::isfinite(threshold[i]) || !(threshold[i] >= 0.f))
+      return ics_set_error(ICS_EINVAL, "threshold[%d] = %g (must be finite and >= 0)", i, (double)threshold[i]);
+  RC(check_route(route, "windows from the frame", "tiles in LDS"));
+  ics_ctx* c = src->ctx;
+  HIPCHK(hipSetDevice(c->device));
+  const int H = src->H, W = src->W;
+  if (route == 0) route = 2;
+  ImgOp op(c, out, "img_despeckle");
+  RC(img_new(c, H, W, out));
+  const float t[3] = {threshold[0], coupling ? threshold[0] : threshold[1], coupling ? threshold[0] : threshold[2]};
+  unsigned *cnt = nullptr, got[3] = {0u, 0u, 0u};
+  hipError_t e = op.alloc((void**)&cnt, sizeof(got));
+  if (e == hipSuccess) e = hipMemsetAsync(cnt, 0, sizeof(got), c->stream);     // (before the bracket: last_kernel_ms is the kernel alone)
+  if (e == hipSuccess) e = op.begin();
+  if (e == hipSuccess) e = ics_launch_img_despeckle(src->d, H, W, radius, t, coupling, route, (*out)->d, cnt, c->stream);
+  if (e == hipSuccess && replaced) {                 // the counters and nothing else: the frame stays where it is
+    e = op.end();
+    if (e == hipSuccess) e = hipMemcpyAsync(got, cnt, sizeof(got), hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  }
+  RC(op.finish(e));
+  if (replaced) { replaced[0] = got[0]; replaced[1] = coupling ? 0u : got[1]; replaced[2] = coupling ? 0u : got[2]; }
   return ICS_OK;
 }
 

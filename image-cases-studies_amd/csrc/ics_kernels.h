@@ -308,6 +308,14 @@ size_t ics_img_guided_coef_floats(int H, int W, int coupling, int route);
 hipError_t ics_launch_img_guided(const float* src, int H, int W, int radius, float eps, float detail, int coupling, int route, float* coef, float* out,
                                  hipStream_t s);
 
+// ---- despeckle of device-resident images (ics_img_despeckle.hip): the median of the (2 radius + 1)^2 window by the integer order of the
+// float bits, put in place of a value that is further than a threshold from it.  t: three thresholds (coupling 1 reads t[0]); cnt:
+// three words, zeroed by the caller on the same stream (outside its kernel-time bracket), afterwards the replaced values per channel (coupling 0) or the replaced pixels in cnt[0]
+// (coupling 1).  route 1: a lane reads its windows from the frame; 2: a workgroup stages its tile and halo in LDS.  src is only read.
+#define ICS_IMG_DESPECKLE_MAX_RADIUS 2    // (== include/ics_hip.h)
+hipError_t ics_launch_img_despeckle(const float* src, int H, int W, int radius, const float t[3], int coupling, int route, float* out, unsigned* cnt,
+                                    hipStream_t s);
+
 // ---- local Laplacian filter of device-resident images (ics_img_llf.hip): K remapped Gaussian pyramids, an interpolated Laplacian
 // pyramid, collapsed.  pyr: ics_img_llf_pyramid_floats floats (K + 1 pyramids of levels 1 .. J), r0 / r1: ics_img_llf_collapse_floats
 // floats each.  route 1: a reduce chain per sample; 2: one reduce launch per level for all samples, the frame read once.  coupling 0:

@@ -80,7 +80,7 @@ def mask_window(i, top, bottom, left, right):
 def deblur_module(pic, filename, dest_path, blur_width, confidence=10, tolerance=1, quality="normal", bits=8,
                   mask=None, display=True, blur="static", preview=False, p=1, order=2, norm=1, priority=0, mask_size=255,
                   iterations=200, refocus=False, pyramid=True, solver=None, save=True, device_resident=None, sharpen=None, denoise=None,
-                  local_contrast=None, detail=None, clarity=None):
+                  local_contrast=None, detail=None, clarity=None, despeckle=None):
     """deconvolve.py:65-368.  Extra keyword arguments (not in the reference): `pyramid=False` runs the
     single scale-1 level only, `solver` replaces `dc.richardson_lucy_MM` (tests record the calls),
     `save=False` returns the float image instead of writing the TIFF, `device_resident=True` keeps every frame in HBM
@@ -111,7 +111,14 @@ def deblur_module(pic, filename, dest_path, blur_width, confidence=10, tolerance
     arguments (edges 1, coupling "vector" unless given; default levels, 8 samples) on the deblurred frame, in the gamma-encoded
     domain, after `denoise` and before `local_contrast`: the steps run coarse to fine -- tone and clarity at tens to hundreds of
     pixels, then the scale gains, then the guided detail, then the mask, then the clip.  (0.2, 1.8) adds clarity, (0.2, 1, 0.6)
-    compresses the tonal range and keeps the detail; on the resident path the frame stays in HBM."""
+    compresses the tonal range and keeps the detail; on the resident path the frame stays in HBM.
+    `despeckle=(threshold,)`, `(threshold, radius)` or `(threshold, radius, coupling)`: `utils.despeckle` with these arguments (radius
+    1, coupling "vector" unless given; threshold a value, three for "channel", "auto" or ("auto", strength)) on the INPUT picture, in
+    the gamma-encoded domain, before the odd-size padding and before either deconvolution phase: a hot or dead pixel, which
+    Richardson-Lucy would turn into a PSF-sized ring at every pyramid level, or a NaN, which would spread over the frame, is
+    replaced by the median of its window and nothing else is touched; one line "Despeckle : <counts> replaced" is printed.
+    `despeckle=("auto",)` takes six sigma of the picture's own noise.  On the resident path the frame stays in HBM."""
+    despeckle = _despeckle_args(despeckle)
     sharpen = _sharpen_args(sharpen)
     denoise = _denoise_args(denoise)
     local_contrast = _local_contrast_args(local_contrast)
@@ -123,13 +130,16 @@ def deblur_module(pic, filename, dest_path, blur_width, confidence=10, tolerance
         if solver is not None:
             raise ValueError("device_resident=True runs the GPU solver; `solver` cannot be replaced")
         return _deblur_device(pic, filename, dest_path, blur_width, confidence, tolerance, quality, bits, mask, display, blur, preview, p,
-                              order, norm, priority, mask_size, iterations, refocus, pyramid, save, sharpen, denoise, local_contrast, detail, clarity)
+                              order, norm, priority, mask_size, iterations, refocus, pyramid, save, despeckle, sharpen, denoise, local_contrast, detail, clarity)
     rl = solver if solver is not None else dc.richardson_lucy_MM
     pic = np.ascontiguousarray(pic, dtype=np.float32)
     pic = pad_image(pic, (1, 1)).astype(np.float32)                       # :94
     samples = 2 ** bits - 1                                               # :97
     pic = pic / samples
     pic = pic ** (1 / 2.2)                                                # :103
+    if despeckle is not None:
+        pic, replaced = utils.despeckle(np.ascontiguousarray(pic, dtype=np.float32), *despeckle, count=True)
+        print("Despeckle :", ", ".join(str(n) for n in replaced), "replaced")
     step = {"normal": 1e-3, "high": 5e-4, "veryhigh": 1e-4, "low": 5e-3}[quality]   # :106-113
     if blur_width < 3:
         raise ValueError("The blur width should be at least 3 pixels.")
@@ -287,6 +297,31 @@ def _denoise_args(denoise):
     return float(weight), int(iterations), coupling
 
 
+def _despeckle_args(despeckle):
+    """`despeckle` of deblur_module -> None or (threshold, radius, coupling): threshold a float, a tuple of three floats or
+    ("auto", strength)"""
+    if despeckle is None:
+        return None
+    forms = "despeckle takes (threshold,), (threshold, radius) or (threshold, radius, coupling)"
+    if isinstance(despeckle, str):
+        raise ValueError("%s, got %r" % (forms, despeckle))
+    try:
+        despeckle = tuple(despeckle)
+    except TypeError:
+        raise ValueError("%s, got %r" % (forms, despeckle))
+    if not 1 <= len(despeckle) <= 3:
+        raise ValueError("%s, got %d values" % (forms, len(despeckle)))
+    threshold, radius, coupling = (despeckle + (1, "vector")[len(despeckle) - 1:])[:3]
+    from lib._native import despeckle_args
+    try:
+        t, radius, coupling, _ = despeckle_args(threshold, radius, coupling)
+    except (ValueError, TypeError) as exc:
+        raise ValueError("despeckle: %s" % exc)
+    if t[0] != "auto":
+        t = t[0] if len(set(t)) == 1 and np.ndim(threshold) == 0 else t
+    return t, radius, coupling
+
+
 def _local_contrast_args(local_contrast):
     """`local_contrast` of deblur_module -> None or (gains, thresholds or None, coupling), gains and thresholds as tuples of floats;
     thresholds "auto" or ("auto", strength) as ("auto", strength)"""
@@ -360,8 +395,8 @@ def _level_shape(i, M, N):
 
 
 def _deblur_device(pic, filename, dest_path, blur_width, confidence, tolerance, quality, bits, mask, display, blur, preview, p, order, norm,
-                   priority, mask_size, iterations, refocus, pyramid, save, sharpen=None, denoise=None, local_contrast=None, detail=None,
-                   clarity=None):
+                   priority, mask_size, iterations, refocus, pyramid, save, despeckle=None, sharpen=None, denoise=None, local_contrast=None,
+                   detail=None, clarity=None):
     """`deblur_module` (deconvolve.py:65-368) with every frame resident in HBM: one upload of the picture,
     one download of the result; pad_image, gamma, the window views, the resize between pyramid levels and the solver all
     work on `lib._native.DeviceImage`s.  Line references as in `deblur_module` above."""
@@ -374,6 +409,10 @@ def _deblur_device(pic, filename, dest_path, blur_width, confidence, tolerance, 
     pic_d = raw.pad_edge(1, 1, 1, 1)                                        # :94
     raw.close()
     pic_d.gamma(2 ** bits - 1, 1 / 2.2)                                     # :97-103
+    if despeckle is not None:
+        (pic_d, replaced), old = pic_d.despeckle(*despeckle, count=True), pic_d
+        old.close()
+        print("Despeckle :", ", ".join(str(n) for n in replaced), "replaced")
     step = {"normal": 1e-3, "high": 5e-4, "veryhigh": 1e-4, "low": 5e-3}[quality]
     M, N, _ = pic_d.shape
     if mask is None:

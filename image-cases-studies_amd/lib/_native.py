@@ -94,6 +94,8 @@ IMG_GUIDED_MAX_RADIUS = 32       # include/ics_hip.h ICS_IMG_GUIDED_MAX_RADIUS: 
 IMG_GUIDED_FUSED_RADIUS = 8      # include/ics_hip.h ICS_IMG_GUIDED_FUSED_RADIUS: largest radius of its one-launch route
 IMG_LLF_MAX_LEVELS = 10          # include/ics_hip.h ICS_IMG_LLF_MAX_LEVELS: pyramid levels of the local Laplacian filter
 IMG_LLF_MAX_SAMPLES = 16         # include/ics_hip.h ICS_IMG_LLF_MAX_SAMPLES: remapped copies it interpolates between
+IMG_DESPECKLE_MAX_RADIUS = 2     # include/ics_hip.h ICS_IMG_DESPECKLE_MAX_RADIUS: 3 x 3 and 5 x 5 windows
+IMG_DESPECKLE_STRENGTH = 6.0     # include/ics_hip.h ICS_IMG_DESPECKLE_STRENGTH: threshold "auto" of despeckle is this many sigma of the noise
 IMG_NOISE_STRENGTH = 3.0         # include/ics_hip.h ICS_IMG_NOISE_STRENGTH: thresholds="auto" cuts this many standard deviations
 IMG_NOISE_E = (0.89079631027875839, 0.20066385102441897, 0.085507504753369934, 0.041217444374316202,      # include/ics_hip.h ICS_IMG_NOISE_E: e_j, the L2
                0.020424966592781431, 0.01018975924921329, 0.0050920466808193074, 0.0025456694579151255)   # norm of the response of scale j to a unit impulse
@@ -174,6 +176,7 @@ def load():
     lib.ics_img_tv_denoise.argtypes = [vp, cf, ci, ci, ci, C.POINTER(vp)]
     lib.ics_img_wavelet_equalize.argtypes = [vp, ci, vp, vp, cf, ci, ci, C.POINTER(vp)]
     lib.ics_img_noise_estimate.argtypes = [vp, ci, ci, C.POINTER(cf), C.POINTER(cf), C.POINTER(cf)]
+    lib.ics_img_despeckle.argtypes = [vp, ci, C.POINTER(cf), ci, ci, C.POINTER(vp), C.POINTER(C.c_uint)]
     lib.ics_img_guided.argtypes = [vp, ci, cf, cf, ci, ci, C.POINTER(vp)]
     lib.ics_img_local_laplacian.argtypes = [vp, cf, cf, cf, ci, ci, ci, ci, C.POINTER(vp)]
     lib.ics_rl_upload_img.argtypes = [vp, vp, ci, ci, vp, ci, ci, vp]
@@ -197,7 +200,7 @@ def load():
                  "ics_rl_download", "ics_rl_run", "ics_rl_stage", "ics_rl_read", "ics_rl_write", "ics_rl_read_rows", "ics_rl_write_rows", "ics_rl_copy_rows", "ics_normalize_kernel",
                  "ics_tv", "ics_conv2d_symm", "ics_usm", "ics_bilateral", "ics_resize_bicubic", "ics_img_create", "ics_img_shape",
                  "ics_img_upload", "ics_img_upload_int", "ics_img_download", "ics_img_pad_edge", "ics_img_crop", "ics_img_paste", "ics_img_gamma", "ics_img_resize",
-                 "ics_img_convolve", "ics_img_usm", "ics_img_bilateral", "ics_img_tv_denoise", "ics_img_wavelet_equalize", "ics_img_noise_estimate", "ics_img_guided", "ics_img_local_laplacian",
+                 "ics_img_convolve", "ics_img_usm", "ics_img_bilateral", "ics_img_tv_denoise", "ics_img_wavelet_equalize", "ics_img_noise_estimate", "ics_img_despeckle", "ics_img_guided", "ics_img_local_laplacian",
                  "ics_rl_upload_img", "ics_rl_download_img", "ics_group_create", "ics_group_info", "ics_group_barrier",
                  "ics_group_allreduce_max", "ics_group_allreduce_sum", "ics_group_describe", "ics_group_allgather"):
         getattr(lib, name).restype = ci
@@ -338,6 +341,41 @@ def wavelet_args(gains, thresholds=None, residual=1.0, coupling="vector", route=
         raise ValueError("residual %r (must be finite)" % (residual,))
     _coupling(coupling)
     return np.ascontiguousarray(g, dtype=np.float32), t, float(residual), coupling, _route(route, "1: a launch per scale, 2: the first scales fused")
+
+
+def despeckle_args(threshold, radius=1, coupling="vector", route=0):
+    """the arguments of DeviceImage.despeckle checked (ValueError) and as (threshold, radius, coupling, route): a tuple of floats --
+    three for "channel" (one value given: three times that value), one for "vector" -- or ("auto", strength) for "auto" and
+    ("auto", strength); an int, a string, an int"""
+    forms = "one value >= 0, three for coupling \"channel\", \"auto\" or (\"auto\", strength)"
+    _coupling(coupling)
+    if isinstance(threshold, str) or (isinstance(threshold, (tuple, list)) and len(threshold) > 0 and isinstance(threshold[0], str)):
+        if threshold != "auto" and (len(threshold) != 2 or threshold[0] != "auto"):
+            raise ValueError("threshold %r (%s)" % (threshold, forms))
+        try:
+            t = ("auto", IMG_DESPECKLE_STRENGTH if threshold == "auto" else _strength(threshold[1]))
+        except ValueError as exc:
+            raise ValueError("threshold %r: %s" % (threshold, exc))
+    else:
+        try:
+            a = np.asarray(threshold, dtype=np.float64)
+        except (TypeError, ValueError):
+            a = np.zeros((0,))
+        if a.shape not in ((), (1,), (3,)) or isinstance(threshold, bool):
+            raise ValueError("threshold %r (%s)" % (threshold, forms))
+        a = a.reshape(-1)
+        if a.size == 3 and coupling != "channel":
+            raise ValueError("threshold %r: three values need coupling \"channel\" (\"vector\" takes one)" % (threshold,))
+        if not _finite32(a) or np.any(a < 0):
+            raise ValueError("threshold %r (must be finite and >= 0)" % (threshold,))
+        t = tuple(float(v) for v in a) * (1 if a.size == 3 or coupling == "vector" else 3)
+    try:
+        whole = int(radius) == radius and not isinstance(radius, bool)
+    except (TypeError, ValueError, OverflowError):
+        whole = False
+    if not whole or not 1 <= int(radius) <= IMG_DESPECKLE_MAX_RADIUS:
+        raise ValueError("radius %r (an integer, 1 to %d)" % (radius, IMG_DESPECKLE_MAX_RADIUS))
+    return t, int(radius), coupling, _route(route, "1: windows read from the frame, 2: tiles staged in LDS")
 
 
 def guided_args(radius, eps, detail=0.0, coupling="vector", route=0):
@@ -618,6 +656,28 @@ class DeviceImage:
         _check(load().ics_img_noise_estimate(self._h, _coupling(coupling), route, *out))
         n = 3 if coupling == "channel" else 1
         return NoiseEstimate(*(tuple(float(v) for v in a[:n]) for a in out))
+
+    def despeckle(self, threshold, radius=1, coupling="vector", route=0, count=False):
+        """Thresholded median: removes impulses -- hot and dead sensor pixels, salt and pepper, NaN and inf -- and leaves every
+        other value bit for bit as it was; made for the frame before a deconvolution, which would spread each impulse over a
+        PSF-sized pattern.  med: the median of the (2 radius + 1)^2 window (radius 1 .. IMG_DESPECKLE_MAX_RADIUS, coordinates
+        clamped at the border), selected by the integer order of the float bits (-0 below +0, NaNs at the ends), so it is one of
+        the window's values; a value is replaced by it where not |value - med| <= threshold.  coupling "channel": every channel by
+        itself, one threshold or three; "vector": one threshold, and a pixel flagged in one channel has all three replaced (no
+        coloured remainder).  threshold 0 is the plain median filter.  threshold "auto" or ("auto", strength): strength (6 unless
+        given: IMG_DESPECKLE_STRENGTH) times the sigma of noise_estimate of this picture with the same coupling.  Returns a new
+        DeviceImage; count=True: (image, counts), the replaced values per channel ("channel", three ints) or the replaced pixels
+        ("vector", one) -- only then the call waits, for these counters.  route 0: the library's choice, 1: every lane reads its
+        windows from the frame, 2: tiles with their halo staged in LDS; all give identical bits (csrc/ics_img_despeckle.hip;
+        restated in tests/despeckle_ref.py).  ValueError (before any native call): a threshold that is negative, not finite, of
+        another form or three values for "vector", radius outside 1 .. 2, unknown coupling or route."""
+        t, radius, coupling, route = despeckle_args(threshold, radius, coupling, route)
+        if t[0] == "auto":
+            t = tuple(float(np.float32(t[1] * s)) for s in self.noise_estimate(coupling).sigma)
+        thr = (C.c_float * 3)(*(t * 3)[:3])
+        got = (C.c_uint * 3)() if count else None
+        img = self._new(lambda h, *a: load().ics_img_despeckle(h, *a, got), radius, thr, _coupling(coupling), route)
+        return (img, tuple(int(v) for v in got[:len(t)])) if count else img
 
     def guided_filter(self, radius, eps, detail=0.0, coupling="vector", route=0):
         """Guided filter with the picture as its own guide (He, Sun, Tang): the edge-preserving base layer q of the

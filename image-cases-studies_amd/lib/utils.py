@@ -17,7 +17,8 @@ The filters run on the GPU through libics_hip.so in float64 like the reference (
 convolve2d(mode="same", boundary="symm")); there is no CPU fallback for them.  Given a `lib._native.DeviceImage`
 (H x W x 3 float32 in HBM) instead of a 2-D array, the four filters work on it there, every channel on its own
 in float32, and return a new DeviceImage (csrc/ics_img_filters.hip): no transfer, no synchronisation; `tv_denoise`,
-`wavelet_equalizer`, `noise_estimate`, `guided_filter` and `local_laplacian` (not in the reference; csrc/ics_img_tvdenoise.hip, csrc/ics_img_wavelet.hip,
+`wavelet_equalizer`, `noise_estimate`, `despeckle`, `median_filter`, `guided_filter` and `local_laplacian` (not in the reference; csrc/ics_img_tvdenoise.hip, csrc/ics_img_wavelet.hip,
+csrc/ics_img_despeckle.hip,
 csrc/ics_img_guided.hip, csrc/ics_img_llf.hip) work on such an image or on an
 H x W x 3 array.  The colour tools of
 the reference (Lagrange_interpolation, grey_point, auto_vibrance, overlay, blending) and its dead
@@ -200,6 +201,41 @@ def noise_estimate(src, coupling="vector"):
         return img.noise_estimate(coupling)
     finally:
         img.close()
+
+
+def despeckle(src, threshold, radius=1, coupling="vector", count=False):
+    """Not in the reference's lib/utils.py, which has no rank filter: a thresholded median for the frame BEFORE the deconvolution.
+    Richardson-Lucy treats a hot pixel as signal and turns it into a PSF-sized ring; a NaN spreads over the frame.  A value is
+    replaced by the median of its (2 radius + 1)^2 window (radius 1 or 2) where it is further than `threshold` from it (or the
+    difference is NaN) and is otherwise returned bit for bit; a frame blurred by a PSF of 3 px or more holds no real one-pixel
+    detail, so nothing else is flagged.  threshold: one value (pixel values in [0, 1]), three for coupling "channel", or "auto" /
+    ("auto", strength): strength (6 unless given) times the sigma of `noise_estimate` of this picture.  coupling "vector" replaces
+    all three channels of a pixel flagged in one, "channel" treats every channel by itself.  count=True returns (result, counts):
+    what was replaced.  A `lib._native.DeviceImage` gives a new DeviceImage (nothing crosses PCIe); an H x W x 3 array is uploaded
+    once and the float32 result downloaded once (`DeviceImage.despeckle`, csrc/ics_img_despeckle.hip)."""
+    if isinstance(src, _native.DeviceImage):
+        return src.despeckle(threshold, radius, coupling, count=count)
+    arr = np.asarray(src)
+    if arr.ndim != 3 or arr.shape[2] != 3:
+        raise ValueError("expected a DeviceImage or an H x W x 3 array, got shape %s" % (arr.shape,))
+    _native.despeckle_args(threshold, radius, coupling)                  # refused before anything is uploaded
+    img = _native.DeviceImage.from_host(np.ascontiguousarray(arr, dtype=np.float32))
+    try:
+        res, counts = img.despeckle(threshold, radius, coupling, count=True)
+    finally:
+        img.close()
+    try:
+        return (res.to_host(), counts) if count else res.to_host()
+    finally:
+        res.close()
+
+
+def median_filter(src, radius=1):
+    """Not in the reference's lib/utils.py: the median of the (2 radius + 1)^2 window (radius 1 or 2, coordinates clamped at the
+    border) of every channel, `despeckle` with threshold 0.  The median is selected by the integer order of the float bits, so it is
+    defined for every input (NaN sorts at the ends) and is one of the window's values.  DeviceImage in, DeviceImage out; an
+    H x W x 3 array is uploaded once and the float32 result downloaded once."""
+    return despeckle(src, 0.0, radius, "channel")
 
 
 def guided_filter(src, radius, eps, detail=0.0, coupling="vector"):

@@ -473,6 +473,27 @@ int ics_img_guided(const ics_img *src, int radius, float eps, float detail, int 
 #define ICS_IMG_LLF_MAX_SAMPLES 16
 int ics_img_local_laplacian(const ics_img *src, float sigma, float detail, float edges, int levels, int samples, int coupling, int route,
                             ics_img **out);
+/* Despeckle of a device image: a thresholded median that removes impulses (hot and dead sensor pixels, salt and pepper, NaN / inf
+ * from an upstream tool) before a deconvolution would spread them, and leaves every other value bit for bit as it was.
+ *   order: values are ordered by the integer key of their bits b, key = b ^ 0xFFFFFFFF if the sign bit is set, else b | 0x80000000:
+ *     a total order, -0 below +0, NaNs at the two ends by sign; selection is by key, never by a floating-point compare
+ *   window of (y, x): the (2 radius + 1)^2 pixels at (clamp(y + dy, 0, H - 1), clamp(x + dx, 0, W - 1)): n = 9 or 25 values
+ *   med_c = the value of rank (n - 1) / 2 of channel c of the window in key order: one of the input values, no arithmetic
+ *   d_c = |src_c - med_c| (one float32 subtraction), hit_c = !(d_c <= t_c): a NaN difference counts as a hit
+ *   coupling 0 (channel): out_c = hit_c ? med_c : src_c with threshold[c]; replaced[c] = the hits of channel c
+ *   coupling 1 (vector): one threshold, threshold[0]; hit = hit_0 || hit_1 || hit_2, all three channels of a hit pixel become their
+ *     medians (a defect leaves no coloured remainder); replaced[0] = the hit pixels, replaced[1] = replaced[2] = 0.
+ * threshold 0 replaces every value that differs from its median: the plain median filter.  ICS_IMG_DESPECKLE_STRENGTH: the Python
+ * layer's threshold "auto" is this many sigma of ics_img_noise_estimate of the same frame (a convention).  Restated in
+ * tests/despeckle_ref.py; the result is a selection and the decision one correctly rounded subtraction, so routes, runs and the
+ * restatement agree bit for bit.  route 1: a lane reads its windows from the frame; 2: a workgroup stages its tile and halo in LDS; 0:
+ * the library's choice.  Queued like the other image filters, its kernel bracketed for ics_ctx_last_kernel_ms; src is not
+ * written.  replaced may be NULL; given, the three counters are copied back and WAITED FOR.  ICS_EINVAL (*out NULL): src, out or
+ * threshold NULL, radius outside 1 .. ICS_IMG_DESPECKLE_MAX_RADIUS, a threshold that is read and is negative, NaN or infinite,
+ * unknown coupling or route. */
+#define ICS_IMG_DESPECKLE_MAX_RADIUS 2
+#define ICS_IMG_DESPECKLE_STRENGTH 6.0f
+int ics_img_despeckle(const ics_img *src, int radius, const float threshold[3], int coupling, int route, ics_img **out, unsigned replaced[3]);
 /* richardson_lucy_MM(image[iy:iy+M, ix:ix+N], u[uy:uy+uM, ux:ux+uN], psf, ...) with both windows taken from device
  * images (deconvolve.py:277-313 passes such views); psf is a host MK*MK*3 array as in ics_rl_upload. */
 int ics_rl_upload_img(ics_rl *job, const ics_img *image, int iy, int ix, const ics_img *u, int uy, int ux, const float *psf);

@@ -1,6 +1,6 @@
 """Timing of the lib/utils.py filters on one seeded SIZE x SIZE RGB float32 picture (GPU box), one JSON line:
 
-    python scripts/filters_timing.py [SIZE=4096] [guided | llf | noise]       ("guided", "llf", "noise": that section alone)
+    python scripts/filters_timing.py [SIZE=4096] [guided | llf | noise | despeckle]       ("guided", "llf", "noise", "despeckle": that section alone)
 
   resident   the filters on a DeviceImage in HBM (csrc/ics_img_filters.hip): device time of the kernels (HIP events around them,
              ics_ctx_last_kernel_ms; warm, median of 25) and wall time of the queued call up to a stream synchronise
@@ -35,6 +35,14 @@
              pictures that load the LDS histogram differently: "uniform" (the script's picture, keys spread over many bins),
              "gauss" (a ramp with Gaussian noise of sigma 0.01: the keys of a noisy photograph, two to three octaves) and "flat" (a
              constant: every key 0, every wave adds its count once); "auto" is what route=0 takes
+  despeckle  DeviceImage.despeckle (csrc/ics_img_despeckle.hip), radius 1 and 2, both couplings, route 1 (a lane reads its windows from
+             the frame through the caches) and route 2 (a workgroup stages its tile and halo in LDS): threshold 0.1 on the script's
+             picture and "auto" on the "gauss" picture of the noise section (there the time includes nothing of the estimate: the
+             kernel bracket is the filter's own): kernel ms, median and minimum of 9 rounds in which the routes alternate, TB/s on the
+             model of 24 B/px (12 read, 12 written), and beside it DeviceImage.copy() of the same run (a device-to-device copy, the
+             same 24 B/px; it has no event bracket, so 16 copies are queued back to back and the wall time up to one stream
+             synchronise is divided by 16: launch and wait are paid once per round, not per copy) as the figure to read it against;
+             "auto" is what route=0 takes
   checks     the resident USM must not take longer than the three float64 calls, in kernel time and in wall time (a guard against a
              broken kernel, not a target); the exit status is 1 if one of them fails
 Starts no child process; a job script puts its own time limit around it."""
@@ -154,6 +162,50 @@ def noise_section(img, ctx, size):
     return res
 
 
+REPS_DESPECKLE, DESPECKLE_BYTES, DESPECKLE_COPIES = 9, 24, 16
+
+
+def despeckle_section(img, ctx, size):
+    res = {"model_bytes_per_px": DESPECKLE_BYTES}
+    y, x = np.mgrid[0:size, 0:size].astype(np.float32)
+    ramp = (0.35 + 0.15 * (x + y) / max(size - 1, 1))[..., None]
+    gauss = _native.DeviceImage.from_host((ramp + np.random.default_rng(1).normal(0.0, 0.01, (size, size, 3))).astype(np.float32), ctx)
+    del x, y, ramp
+    for name, pic, threshold in (("uniform_t0.1", img, 0.1), ("gauss_auto", gauss, "auto")):
+        for radius in (1, 2):
+            for coupling in ("channel", "vector"):
+                times = {1: [], 2: [], 0: []}
+                for route in times:
+                    out, counts = pic.despeckle(threshold, radius, coupling, route=route, count=True)     # warm
+                    out.close()
+                ctx.synchronize()
+                for _ in range(REPS_DESPECKLE):            # the routes alternate within a round
+                    for route in times:
+                        out = pic.despeckle(threshold, radius, coupling, route=route)
+                        times[route].append(ctx.last_kernel_ms())
+                        out.close()
+                for route, ms in times.items():
+                    med = float(np.median(ms))
+                    res["%s_r%d_%s_%s" % (name, radius, coupling, {1: "route1", 2: "route2", 0: "auto"}[route])] = {
+                        "kernel_ms": round(med, 4), "min_ms": round(float(np.min(ms)), 4),
+                        "TBps_on_model": round(DESPECKLE_BYTES * size * size / (med * 1e-3) / 1e12, 3)}
+                res["%s_r%d_%s_replaced" % (name, radius, coupling)] = list(counts)
+    img.copy().close()                                     # warm
+    ctx.synchronize()
+    wall = []
+    for _ in range(REPS_DESPECKLE):                        # COPIES queued back to back, one synchronise: launch and wait are paid once per round
+        t0 = time.perf_counter()
+        outs = [img.copy() for _ in range(DESPECKLE_COPIES)]
+        ctx.synchronize()
+        wall.append((time.perf_counter() - t0) * 1e3 / DESPECKLE_COPIES)
+        for out in outs:
+            out.close()
+    res["copy"] = {"ms_per_copy": round(float(np.median(wall)), 4), "min_ms": round(float(np.min(wall)), 4), "copies_per_round": DESPECKLE_COPIES,
+                   "TBps_on_model": round(DESPECKLE_BYTES * size * size / (float(np.median(wall)) * 1e-3) / 1e12, 3)}
+    gauss.close()
+    return res
+
+
 def main():
     size = int(sys.argv[1]) if len(sys.argv) > 1 else 4096
     ctx = _native.Context.get()
@@ -168,6 +220,9 @@ def main():
         return 0
     if sys.argv[2:] == ["noise"]:
         print(json.dumps({"size": size, "device": ctx.name, "noise": noise_section(img, ctx, size)}))
+        return 0
+    if sys.argv[2:] == ["despeckle"]:
+        print(json.dumps({"size": size, "device": ctx.name, "despeckle": despeckle_section(img, ctx, size)}))
         return 0
     ops = {"usm_gauss15": lambda s: utils.USM(s, 15, 2.5, 0.7, method="gauss"),
            "usm_bessel15": lambda s: utils.USM(s, 15, 3.0, 0.7, method="bessel"),
@@ -239,6 +294,7 @@ def main():
     res["guided"] = guided_section(img, ctx, size)
     res["llf"] = llf_section(img, ctx, size)
     res["noise"] = noise_section(img, ctx, size)
+    res["despeckle"] = despeckle_section(img, ctx, size)
     res["checks"] = {"%s_%s" % (name, what): res["resident"][name][what] <= res["per_channel_f64"][name][what]
                      for name in ("usm_gauss15", "usm_bessel15") for what in ("kernel_ms", "wall_ms")}
     print(json.dumps(res))
