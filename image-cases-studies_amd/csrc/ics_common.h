@@ -117,6 +117,9 @@ struct IcsDebug {
   std::atomic<int> small_iter;        // ICS_SMALL_ITER        0 = small frames run the multi-launch families instead of the cooperative iteration kernel (ics_small.hip); 2 = 64-pixel tiles too; default 1, 0 under rocprofv3
   std::atomic<int> fail_small_launch; // (test hook)           1 = the next cooperative launch of the small-frame kernel is refused once (the job falls back to the multi-launch path)
   std::atomic<int> small_trace;       // ICS_SMALL_TRACE       1 = every cooperative launch is followed by a drain and a phase timeline on stderr
+  std::atomic<int> pool_check;        // ICS_POOL_CHECK        (test hook) -1 off; 0 ... 255 = every block of the pool is filled with this byte when handed out, with a red zone that its release verifies (ics_pool.h)
+  std::atomic<int> pool_overruns;     // ICS_POOL_OVERRUNS     (test hook) red zones found written since the counter was last set to 0
+  std::atomic<int> pool_selftest;     // ICS_POOL_SELFTEST     (test hook) 1 = the next check-mode allocation writes one byte into its own red zone, once
   static int env_int(const char* name, int dflt) { const char* e = getenv(name); return (e && e[0]) ? atoi(e) : dflt; }
   IcsDebug() {
     max_wgs = env_int("ICS_TEST_MAX_WGS", 0);
@@ -146,6 +149,9 @@ struct IcsDebug {
     fail_small_launch = 0;
     overlap = env_int("ICS_OVERLAP", 1);
     pool_limit_mb = env_int("ICS_POOL_LIMIT_MB", -1);
+    pool_check = env_int("ICS_POOL_CHECK", -1);
+    pool_overruns = env_int("ICS_POOL_OVERRUNS", 0);
+    pool_selftest = env_int("ICS_POOL_SELFTEST", 0);
   }
 };
 // one instance per process (inline function, function-local static: initialised once, thread-safe)

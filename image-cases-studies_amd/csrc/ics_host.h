@@ -18,6 +18,7 @@
 #include "../../include/ics_hip.h"
 #include "ics_kernels.h"
 #include "ics_image_acc.h"
+#include "ics_pool.h"
 
 // -------------------------------------------------------------------------------------------------
 // the error channel: formats the message ics_last_error returns (thread-local, ics_context.hip) and returns `code`
@@ -33,52 +34,22 @@ int ics_set_error(int code, const char* fmt, ...);
 #define RC(x) do { int rc_ = (x); if (rc_ != ICS_OK) return rc_; } while (0)
 #define RC0(x) do { int rc0_ = (x); if (rc0_ != ICS_OK) return rc0_; } while (0)   // (inside Prof: its callers wrap it in RC)
 
-// Device memory of a context is recycled, not returned (round 4).  deblur_module creates a job and a handful of images per pyramid
-// level and phase (deconvolve.py:204-313); hipMalloc / hipFree cost 0.1 ... 0.7 ms each and hipFree synchronises the device: the
-// rocprof timeline of a device-resident 2048^2 run showed 42 % of its 0.19 s idle, most of it in front of the first kernel that
-// follows an allocation (profiles/r04_driver_trace_before.txt).  Blocks are rounded up to an eighth of their leading power of two
-// (<= 12.5 % slack), a freed block goes to the free list of its rounded size and serves the next request of that size.  Everything a
-// context allocates is used on its one stream, so a recycled block needs no synchronisation: the new owner's first operation is
-// ordered behind the old owner's last.  The cache is trimmed above `limit` bytes (default: a quarter of the device memory; env
-// ICS_POOL_LIMIT_MB / debug switch pool_limit_mb, read when a context is created) and emptied when an allocation fails.
-struct IcsPool {
-  std::mutex mu;
-  std::multimap<size_t, void*> free_;            // rounded size -> block
-  std::unordered_map<void*, size_t> size_of;     // every block handed out or cached -> rounded size
-  size_t cached = 0, limit = 0;
-  static size_t round_up(size_t b) {
-    if (b < 65536) b = 65536;
-    size_t p2 = 65536;
-    while (p2 * 2 <= b) p2 *= 2;                 // leading power of two
-    const size_t q = p2 / 8;
-    return (b + q - 1) / q * q;
+// The block pool of a context (ics_pool.h: recycling, rounding, and the check mode behind the debug switches pool_check /
+// pool_overruns / pool_selftest) over the four HIP calls it needs.  The fills go to the context's stream, like everything the owner
+// of a block queues; the read-back of a red zone waits for the whole device first (the overlapped statistics run on stream2).
+struct IcsPoolHip {
+  typedef hipError_t err_t;
+  hipStream_t stream = nullptr;                  // the context's (ics_ctx_create)
+  static hipError_t alloc(void** p, size_t bytes) { hipError_t e = hipMalloc(p, bytes); if (e != hipSuccess) (void)hipGetLastError(); return e; }
+  static void free(void* p) { (void)hipFree(p); }
+  hipError_t fill(void* p, int byte, size_t bytes) const { return hipMemsetAsync(p, byte, bytes, stream); }
+  static hipError_t copy_back(void* host, const void* p, size_t bytes) {
+    hipError_t e = hipDeviceSynchronize();
+    return e != hipSuccess ? e : hipMemcpy(host, p, bytes, hipMemcpyDeviceToHost);
   }
-  void trim(size_t keep) {                       // (mu held) largest first
-    while (cached > keep && !free_.empty()) {
-      auto it = std::prev(free_.end());
-      hipFree(it->second); size_of.erase(it->second); cached -= it->first; free_.erase(it);
-    }
-  }
-  hipError_t alloc(void** p, size_t bytes) {
-    const size_t r = round_up(bytes);
-    std::lock_guard<std::mutex> g(mu);
-    auto it = free_.find(r);
-    if (it != free_.end()) { *p = it->second; cached -= r; free_.erase(it); return hipSuccess; }
-    hipError_t e = hipMalloc(p, r);
-    if (e != hipSuccess) { (void)hipGetLastError(); trim(0); e = hipMalloc(p, r); }
-    if (e != hipSuccess) { (void)hipGetLastError(); *p = nullptr; return e; }
-    size_of[*p] = r;
-    return hipSuccess;
-  }
-  void release(void* p) {
-    if (!p) return;
-    std::lock_guard<std::mutex> g(mu);
-    auto it = size_of.find(p);
-    if (it == size_of.end()) { hipFree(p); return; }   // not ours
-    free_.emplace(it->second, p); cached += it->second;
-    if (cached > limit) trim(limit / 2);
-  }
-  void clear() { std::lock_guard<std::mutex> g(mu); trim(0); }
+};
+struct IcsPool : IcsPoolT<IcsPoolHip> {
+  IcsPool() : IcsPoolT<IcsPoolHip>(&ics_debug().pool_check, &ics_debug().pool_overruns, &ics_debug().pool_selftest) {}
 };
 
 struct ics_ctx {
@@ -90,6 +61,7 @@ struct ics_ctx {
   uint64_t hbm;
   void* scratch;            // device scratch of the standalone operators: grown on demand, kept between calls
   size_t scratch_bytes;
+  bool scratch_checked = false;   // the scratch was handed out in the pool's check mode (ctx_scratch)
   hipEvent_t ev0, ev1;      // device time of the last standalone operator (kernels only, no transfers)
   float last_ms;
   // small pinned staging area for host -> device parameters of queued operations (the Gaussian weights of ics_img_resize): the copy
@@ -189,12 +161,15 @@ namespace ics_host {
 
 // at least `bytes` of device scratch that persists between calls (no hipMalloc / hipFree per filter call)
 static inline int ctx_scratch(ics_ctx* c, size_t bytes, void** p) {
-  if (c->scratch_bytes < bytes) {
+  // (pool check mode: a block per call, so that the scratch is filled and its red zone verified like everything else; the first call
+  //  after the mode is switched off returns the last such block)
+  const bool check = ics_debug().pool_check.load(std::memory_order_relaxed) >= 0;
+  if (c->scratch_bytes < bytes || check || c->scratch_checked) {
     if (c->scratch) { c->pool.release(c->scratch); c->scratch = nullptr; c->scratch_bytes = 0; }
     const size_t want = bytes + bytes / 4;
     hipError_t e = c->pool.alloc(&c->scratch, want);
     if (e != hipSuccess) { (void)hipGetLastError(); c->scratch = nullptr; return ICS_ENOMEM; }
-    c->scratch_bytes = want;
+    c->scratch_bytes = want; c->scratch_checked = check;
   }
   *p = c->scratch;
   return ICS_OK;

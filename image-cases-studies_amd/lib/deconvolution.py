@@ -154,8 +154,10 @@ def _report(st, top, bottom, left, right, lambd):
         print("Convergence after %i iterations." % st.iterations_done)
     else:
         print("Did not converge after %i iterations. Don't use the result." % st.iterations_done)
-    print("Stats : autocovariance = %.6f | lamdba = %.0f | residual = %.6f | variance/noise = %.6f" % (
-        1000 * st.M_r / ((bottom - top) * (right - left) * 3), np.float32(lambd), st.Hu, st.varu))
+    # (an empty window: M_r is NaN and the reference, compiled with cdivision, prints nan -- a Python float would raise ZeroDivisionError)
+    with np.errstate(all="ignore"):
+        acov = np.float64(1000 * st.M_r) / np.float64((bottom - top) * (right - left) * 3)
+    print("Stats : autocovariance = %.6f | lamdba = %.0f | residual = %.6f | variance/noise = %.6f" % (acov, np.float32(lambd), st.Hu, st.varu))
     if st.has_nan:
         print("has NaN after DoF correction")
 

@@ -335,6 +335,21 @@ def route_map():
     return out
 
 
+def cheapest_per_route():
+    """{(tv_mode, legend character): the cheapest case of that route and tv_mode by M N MK^2 iters} over the cases the GPU matrix compares
+    with the oracle: one whole call per route for checks that repeat a call several times (tests/test_gpu_pool_check.py)"""
+    R = routes()
+    out = {}
+    for c in cases():
+        if c.id in EXCLUDED:
+            continue
+        key = (c.tv_mode, R[c.id])
+        cost = c.M * c.N * c.MK ** 2 * c.iters
+        if key not in out or cost < out[key][0]:
+            out[key] = (cost, c)
+    return {k: v[1] for k, v in out.items()}
+
+
 if __name__ == "__main__":
     import sys
     here = os.path.dirname(os.path.abspath(__file__))

@@ -96,6 +96,22 @@ def test_debug_switches_are_not_in_the_public_header_and_round_trip():
             assert "getenv" not in txt or f == "ics_group.hip", f      # (ICS_RCCL_LIB / ICS_GROUP_FORCE_RCCL: once per group)
 
 
+def test_pool_check_switches_exist_and_the_check_is_off_by_default():
+    """csrc/ics_pool.h: the check mode of the block pool sits behind three switches, none of them in the public header; off unless asked for"""
+    from lib import _native
+    hdr = open(HEADER).read()
+    for name in ("pool_check", "pool_overruns", "pool_selftest"):
+        assert name not in hdr
+        probe = -1 if name == "pool_check" else 0      # (0 is a fill byte: it would switch the check mode on)
+        old = _native.debug_set(name, probe)
+        assert _native.debug_set(name, old) == probe
+    if "ICS_POOL_CHECK" not in os.environ:
+        assert _native.debug_set("pool_check", -1) == -1
+    common = open(os.path.join(ROOT, "image-cases-studies_amd", "csrc", "ics_common.h")).read()
+    for env in ("ICS_POOL_CHECK", "ICS_POOL_OVERRUNS", "ICS_POOL_SELFTEST"):
+        assert 'env_int("%s"' % env in common, env
+
+
 def test_wrong_struct_size_is_refused_before_anything_else():
     """A caller built against another header (ics_rl_params grew in ABI 3) must get ICS_EINVAL, not a read past its struct."""
     from lib import _native

@@ -73,6 +73,9 @@ def test_mask_window_reference_tie_breaking():
     assert (t[1] - t[0]) % 2 == 1
 
 
+PSF_SUM_ATOL = 1e-4      # an estimated PSF sums to 1 per channel (also imported by tests/test_gpu_pool_check.py)
+
+
 @pytest.mark.gpu
 def test_deblur_module_end_to_end_on_gpu(tmp_path):
     """Full driver on a synthetic blurred picture: blind estimate on the mask window then non-blind pass."""
@@ -83,7 +86,7 @@ def test_deblur_module_end_to_end_on_gpu(tmp_path):
     out, psf = dv.deblur_module(pic, "gpu", str(tmp_path), 5, mask=[60, 70], mask_size=61, display=False, iterations=4,
                                 pyramid=True)
     assert out.shape == (120, 140, 3) and np.isfinite(out).all() and (tmp_path / "gpu.tif").exists()
-    assert np.all(psf >= 0) and np.allclose(psf.sum(axis=(0, 1)), 1, atol=1e-4)
+    assert np.all(psf >= 0) and np.allclose(psf.sum(axis=(0, 1)), 1, atol=PSF_SUM_ATOL)
 
 
 @pytest.mark.gpu
@@ -175,6 +178,10 @@ def test_driver_with_a_wide_blur_on_a_large_picture_takes_the_transform_tiles(de
     assert np.abs(out_t.astype(np.float64) - out_m).max() / 65535 < 5e-5, np.abs(out_t.astype(np.float64) - out_m).max()
 
 
+# gates of the device-image operations below (also imported by tests/test_gpu_pool_check.py)
+GAMMA_GATE, GAMMA_CLIP_GATE, RESIZE_GATE = 3e-7, 0.02, 1e-6
+
+
 @pytest.mark.gpu
 def test_device_image_operations_match_numpy():
     from lib import _native
@@ -190,11 +197,11 @@ def test_device_image_operations_match_numpy():
     ref = a.copy(); ref[4:14, 6:18] = a[0:10, 0:12]
     assert np.array_equal(e.to_host(), ref)
     g = d.copy(); g.gamma(2.0, 1 / 2.2)
-    assert np.abs(g.to_host() - (a / np.float32(2.0)) ** np.float32(1 / 2.2)).max() < 3e-7
+    assert np.abs(g.to_host() - (a / np.float32(2.0)) ** np.float32(1 / 2.2)).max() < GAMMA_GATE
     g = d.copy(); g.gamma(0.5, 2.2, 65535, clip01=True)
-    assert np.abs(g.to_host() - np.clip(a / np.float32(0.5), 0, 1) ** np.float32(2.2) * np.float32(65535)).max() < 0.02
+    assert np.abs(g.to_host() - np.clip(a / np.float32(0.5), 0, 1) ** np.float32(2.2) * np.float32(65535)).max() < GAMMA_CLIP_GATE
     r = d.resize(27, 31).to_host()
-    assert np.abs(r - ro.resize_scipy(a, (27, 31)).astype(np.float32)).max() < 1e-6
+    assert np.abs(r - ro.resize_scipy(a, (27, 31)).astype(np.float32)).max() < RESIZE_GATE
     with pytest.raises(_native.NativeError):
         d.crop(0, 38, 0, 45)
     # 8- and 16-bit pictures are converted on the device: exactly np.float32(v)

@@ -66,6 +66,9 @@ def test_driver_resize_goes_through_the_device(monkeypatch):
     assert np.array_equal(dv.resize_bicubic(img, img.shape), img.astype(np.float64))
 
 
+EXTREME_GATE = 1e-11     # float64 resize at large ratios against scipy (also imported by tests/test_gpu_pool_check.py)
+
+
 @pytest.mark.gpu
 def test_gpu_resize_extreme_ratios_and_many_calls():
     """large up- and down-scaling factors (wide anti-aliasing kernels), 2 x 2 sources, and a create / resize / destroy
@@ -76,7 +79,7 @@ def test_gpu_resize_extreme_ratios_and_many_calls():
     for src, dst in [((2, 2), (9, 7)), ((120, 90), (13, 11)), ((13, 11), (120, 90)), ((64, 3), (31, 5)), ((300, 300), (7, 299))]:
         img = rng.random((*src, 3))
         got = ctx.resize_bicubic(img, dst)
-        assert np.abs(got - ro.resize_scipy(img, dst)).max() < 1e-11, (src, dst)
+        assert np.abs(got - ro.resize_scipy(img, dst)).max() < EXTREME_GATE, (src, dst)
     a = rng.random((256, 256, 3), dtype=np.float32)
     first = None
     for i in range(60):

@@ -37,6 +37,22 @@ def test_every_route_of_each_tv_mode_has_a_case():
     assert not missing, "routes without a case of that tv_mode: %s" % "; ".join(missing)
 
 
+def test_every_route_of_every_tv_mode_has_a_cheapest_case():
+    """rc.cheapest_per_route, the whole calls tests/test_gpu_pool_check.py repeats on poisoned pool blocks: one per route of the table and
+    tv_mode, and it is the cheapest of its route"""
+    pick = rc.cheapest_per_route()
+    want = rc.table_routes()
+    leg = {v: k for k, v in rc.legend().items()}
+    missing = ["tv_mode %d: %s %s" % (m, r, list(leg[r])) for m in range(4) for r in sorted(want[m]) if (m, r) not in pick]
+    assert not missing, "routes without a case of that tv_mode: %s" % "; ".join(missing)
+    R = rc.routes()
+    cost = lambda c: c.M * c.N * c.MK ** 2 * c.iters
+    for (m, r), c in pick.items():
+        assert c.tv_mode == m and R[c.id] == r and c.id not in rc.EXCLUDED
+        assert all(cost(c) <= cost(o) for o in rc.cases() if o.tv_mode == m and R[o.id] == r and o.id not in rc.EXCLUDED), c.id
+    print("%d whole calls: %s" % (len(pick), " ".join("%d%s:%s" % (m, r, c.id) for (m, r), c in sorted(pick.items()))))
+
+
 def test_the_list_holds_every_switch_and_variant():
     cs = [c for c in rc.cases() if c.id not in rc.EXCLUDED]
     R = rc.routes()

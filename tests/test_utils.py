@@ -90,6 +90,12 @@ def test_gpu_bilateral_matches_oracle_and_properties():
     np.testing.assert_allclose(utils.bilateral_filter(src, 0, 0.2, 1.5), src, rtol=1e-14)   # radius 0 = identity
 
 
+# gates of the float64 stand-alone operators on the device (also imported by tests/test_gpu_pool_check.py)
+TV_NORM2_RTOL = 4e-7
+CONV_RTOL, CONV_ATOL, USM_ATOL = 1e-12, 1e-14, 1e-13
+BILATERAL_RTOL = 1e-11
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("order,norm", [(2, 1), (2, 2), (1, 1), (1, 2)])
 def test_gpu_tv_stencil_matches_oracle(ctx, order, norm):
@@ -105,7 +111,7 @@ def test_gpu_tv_stencil_matches_oracle(ctx, order, norm):
         if norm == 1:
             assert np.array_equal(out, ro)
         else:   # norm 2 ends in libm's powf(s, 0.5) (within 0.82 ulp) where the device rounds sqrt correctly
-            np.testing.assert_allclose(out, ro, rtol=4e-7, atol=0)   # sum of two such terms, then a division
+            np.testing.assert_allclose(out, ro, rtol=TV_NORM2_RTOL, atol=0)   # sum of two such terms, then a division
         assert np.all(out[0] == 0) and np.all(out[-1] == 0) and np.all(div[:, 0] == 0) and np.all(div[:, -1] == 0)
     flat = np.full((9, 9, 3), 0.5, np.float32)
     out, div = ctx.tv(flat, 1e-3, 2, 1)
@@ -125,7 +131,7 @@ def test_gpu_tv_against_the_reference_golden(ctx, golden_dir):
         if norm == 1:
             assert np.array_equal(out, z["out_" + key]), key
         else:
-            np.testing.assert_allclose(out, z["out_" + key], rtol=4e-7, atol=0)
+            np.testing.assert_allclose(out, z["out_" + key], rtol=TV_NORM2_RTOL, atol=0)
 
 
 def test_oracle_tv_equals_the_compiled_reference(golden_dir):
@@ -156,12 +162,12 @@ def test_gpu_blur_usm_4096_channel_against_scipy(ctx):
     ref = convolve2d(src, kern, mode="same", boundary="symm")
     out = utils.gaussian_blur(src, 15, 2.5)
     t_sep = ctx.last_kernel_ms()
-    np.testing.assert_allclose(out, ref, rtol=1e-12, atol=1e-14)
-    np.testing.assert_allclose(utils.USM(src, 15, 2.5, 0.8, method="gauss"), src + (src - ref) * 0.8, rtol=1e-12, atol=1e-13)
+    np.testing.assert_allclose(out, ref, rtol=CONV_RTOL, atol=CONV_ATOL)
+    np.testing.assert_allclose(utils.USM(src, 15, 2.5, 0.8, method="gauss"), src + (src - ref) * 0.8, rtol=CONV_RTOL, atol=USM_ATOL)
     k2 = rng.random((9, 7)); k2 /= k2.sum()
     out2 = ctx.conv2d_symm(src[:1500, :1300], k2)
     t_2d = ctx.last_kernel_ms()
-    np.testing.assert_allclose(out2, convolve2d(src[:1500, :1300], k2, mode="same", boundary="symm"), rtol=1e-12, atol=1e-14)
+    np.testing.assert_allclose(out2, convolve2d(src[:1500, :1300], k2, mode="same", boundary="symm"), rtol=CONV_RTOL, atol=CONV_ATOL)
     print("gaussian_blur 4096^2, 15x15 (separable): %.3f ms on the device; general 9x7 at 1500x1300: %.3f ms" % (t_sep, t_2d))
     assert t_sep < 20.0
 
@@ -173,5 +179,5 @@ def test_gpu_bilateral_1024_against_the_restatement(ctx):
     src = rng.random((1024, 1000))
     out = utils.bilateral_filter(src, 4, 0.15, 2.0)
     t = ctx.last_kernel_ms()
-    np.testing.assert_allclose(out, uo.bilateral_filter(src, 4, 0.15, 2.0), rtol=1e-11)
+    np.testing.assert_allclose(out, uo.bilateral_filter(src, 4, 0.15, 2.0), rtol=BILATERAL_RTOL)
     print("bilateral 1024x1000, radius 4: %.3f ms on the device" % t)
