@@ -73,7 +73,7 @@ hipError_t ics_launch_gradk_reduce_block(const float* partial, int nblocks, floa
 hipError_t ics_launch_band_reduce(const float* gr, const float* u, const float* ut, const IcsGeom& g, float lambd, int r0, int r1, uint32_t* red, hipStream_t s);
 hipError_t ics_launch_band_mask_e(float* e, const IcsGeom& g, int i0, int i1, hipStream_t s);
 
-// ---- channel-planar mirrors (ics_planar.hip) and the FFT-tile convolution (ics_conv_fft.hip) --------------------------------------------
+// ---- channel-planar mirrors (ics_planar.hip) and the transform tiles (ics_fft_tile.h: ics_conv_fft.hip, ics_gradk_fft.hip) --------------------------------------------
 // src / dst: buffer STARTS; rows [y0, y1), pixels [x0, x1) in u-frame coordinates (widened to 4-pixel groups), or the whole buffer
 hipError_t ics_launch_planar_convert(bool to_planar, const float* src, float* dst, const IcsGeom& g, bool whole, int y0, int y1, int x0, int x1, hipStream_t s);
 hipError_t ics_launch_update_planar(const IcsUpdateArgs& a, hipStream_t s);   // frame pointers = origins of planar mirrors
@@ -87,15 +87,8 @@ bool ics_conv_fft_blk_supported(int K);
 void ics_conv_fft_blk_shape(int K, int* blk_n, int* blk_k);
 hipError_t ics_launch_conv_fft_blk(int mode, const IcsConvArgs& c, const float* spec, int blk_n, int blk_k, hipStream_t s);
 hipError_t ics_launch_gradk_fft_blk(const float* u, const float* e, const IcsGeom& g, int blk_n, int blk_k, float* partial, float* gradk, hipStream_t s);
-// modes 0 and 1 of ics_launch_conv; `planar` = bit mask of the frames of `a` that are origins of planar mirrors (ICS_FFT_PL_*)
-#define ICS_FFT_PL_IN 1
-#define ICS_FFT_PL_OUT 2
-#define ICS_FFT_PL_F 4
-#define ICS_FFT_PL_U 8
-#define ICS_FFT_PL_UT 16
-#define ICS_FFT_PL_TV 32
-#define ICS_FFT_PL_ALL 63
-hipError_t ics_launch_conv_fft(int mode, const IcsConvArgs& a, const float* spec, int planar, hipStream_t s);
+// modes 0 and 1 of ics_launch_conv on the transform tiles; every frame of `a` is the origin of a channel-planar mirror
+hipError_t ics_launch_conv_fft(int mode, const IcsConvArgs& a, const float* spec, hipStream_t s);
 // mode 2 (k_conv_fft<2>): A1 + A2 + A3 in ONE unit per tile pair -- interior tiles stay in the frequency domain between the two convolutions
 // (one forward, one inverse transform; the image enters as the precomputed spectra of its windows), the tiles of the outer ring mask the
 // residual in between.  Valid output 128 - 2 K + 2 pixels a side: for small PSFs.  The residual frame is NOT written.

@@ -107,7 +107,7 @@ static int do_conv_fft(ics_rl* j, int mode, const ics_rl_params* p, int slot, Pr
     ics_conv_fft_blk_shape(j->g.K, &nb, &kb);
     HIPCHK(ics_launch_conv_fft_blk(mode, a, mode == 1 ? j->spec_corr : j->spec_conv, nb, kb, j->ctx->stream));
   } else
-  HIPCHK(ics_launch_conv_fft(mode, a, mode == 1 ? j->spec_corr : j->spec_conv, ICS_FFT_PL_ALL, j->ctx->stream));
+  HIPCHK(ics_launch_conv_fft(mode, a, mode == 1 ? j->spec_corr : j->spec_conv, j->ctx->stream));
   RC(pr.end());
   return ICS_OK;
 }

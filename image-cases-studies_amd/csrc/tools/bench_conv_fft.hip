@@ -1,17 +1,16 @@
-// bench_conv_fft.hip -- stand-alone harness for the overlap-save FFT convolution (ics_conv_fft.hip).
+// bench_conv_fft.hip -- stand-alone harness for the transform tiles (ics_fft_tile.h; its two units are included below).
 //   hipcc -O3 -std=c++17 --offload-arch=gfx950 -ffp-contract=off -I.. -I../../../include bench_conv_fft.hip -o bench_conv_fft
 //   ./bench_conv_fft emulate [M K N]     CPU emulation of the kernel's stages (host pass of the same functions, "threads" run one after
 //                                        the other per stage) against float64 direct sums over the whole output: no GPU needed
 //   ./bench_conv_fft M K [N] [reps]      GPU: both modes checked against float64 direct sums on sampled rows, then timed
 #include "../ics_conv_fft.hip"
+#include "../ics_gradk_fft.hip"
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <vector>
 
 namespace {
-
-int g_planar = 1;   // every frame the kernel touches is a channel-planar mirror (ics_common.h); the HWC form of round 5's first versions is gone
 
 struct Host {
   IcsGeom g;
@@ -113,7 +112,7 @@ void host_spectrum(const Host& h, int o, std::vector<v2f>& spec) {
 
 IcsConvArgs conv_args(const Host& h, int mode, const float* in, float* out, const float* f, const float* u, const float* ut, uint32_t* red) {
   IcsConvArgs a = {};
-  const size_t org = g_planar ? h.porg : h.org;
+  const size_t org = h.porg;   // every frame the kernels touch is a channel-planar mirror (ics_common.h)
   a.in = in + org; a.out = out + org; a.f = f + org; a.u = u + org; a.ut = ut + org; a.red = red; a.lambd = 10000.f; a.g = h.g;
   a.tv = nullptr; a.tv_kind = 0;
   return a;
@@ -147,12 +146,10 @@ int emulate(int M, int K, int N) {
   for (int mode = 0; mode < 2; ++mode) {
     std::vector<v2f> spec;
     host_spectrum(h, mode, spec);
-    std::vector<float> out(h.nf, 0.f), pout(g_planar ? h.pnf : 0, 0.f);
+    std::vector<float> out(h.nf, 0.f), pout(h.pnf, 0.f);
     uint32_t red[16] = {0};
     IcsFftArgs a;
-    if (g_planar) ics_conv_fft_fill_args(mode, conv_args(h, mode, mode == 0 ? h.pu.data() : h.pe.data(), pout.data(), h.pf.data(), h.pu.data(), h.put.data(), red), (const float*)spec.data(), &a);
-    else ics_conv_fft_fill_args(mode, conv_args(h, mode, mode == 0 ? h.u.data() : h.e.data(), out.data(), h.f.data(), h.u.data(), h.ut.data(), red), (const float*)spec.data(), &a);
-    a.planar = 63;
+    ics_conv_fft_fill_args(mode, conv_args(h, mode, mode == 0 ? h.pu.data() : h.pe.data(), pout.data(), h.pf.data(), h.pu.data(), h.put.data(), red), (const float*)spec.data(), &a);
     printf("mode %d: V %d x %d, tiles %d (x %d), units %d\n", mode, a.Vy, a.V, a.ntiles, a.tiles_x, a.nunits);
     const icsfft::Mem mem = icsfft::make_mem(a);
     std::vector<v2f> twl(ICS_FFT_TW_ENTRIES);
@@ -175,7 +172,7 @@ int emulate(int M, int K, int N) {
         if (mode == 0) icsfft::load_image(a, mem, u, t, fimg);
         else { icsfft::load_ops<true>(a, mem, u, t, 0, o); icsfft::load_ops<true>(a, mem, u, t, 1, o); }
         icsfft::QuadOut qo[2];
-        for (int tt = 0; tt < 2; ++tt) qo[tt].vo = icsfft::quad_lane(a, u, mem.lout, t, tt, qo[tt].rows, qo[tt].X);
+        for (int tt = 0; tt < 2; ++tt) qo[tt].vo = icsfft::quad_lane(a, u, mem.lay, t, tt, qo[tt].rows, qo[tt].X);
         const bool edge = u.ox[0] < a.ox0 || u.ox[0] + a.V > a.ox1 || u.ox[1] < a.ox0 || u.ox[1] + a.V > a.ox1;    // (as the kernel)
         for (int i = 0; i < 4; ++i) {
           v4f r[2];
@@ -186,7 +183,7 @@ int emulate(int M, int K, int N) {
         }
       }
     }
-    if (g_planar) from_planar(h, pout, out);
+    from_planar(h, pout, out);
     double wa;
     const double rel = check(h, mode, out, 1, &wa);
     printf("emulation %d x %d, K = %d, mode %d: max |d| = %.3e, relative to max |conv| = %.3e  %s\n", M, N, K, mode, wa, rel, rel < 5e-6 ? "OK" : "FAIL");
@@ -226,7 +223,6 @@ int emulate_gradk(int M, int K, int N) {
   IcsConvArgs c = conv_args(h, 0, h.pu.data(), h.pe.data(), h.pe.data(), h.pu.data(), h.pu.data(), nullptr);
   IcsFftArgs a;
   ics_conv_fft_fill_args(0, c, nullptr, &a);
-  a.planar = 63;
   const icsfft::Mem mem = icsfft::make_mem(a);
   std::vector<float> gk((size_t)K * K * 3, 0.f);
   const int npairs = (a.ntiles + 1) / 2;
@@ -268,7 +264,7 @@ int emulate_fused(int M, int K, int N) {
   std::vector<float> pout(h.pnf, 0.f);
   IcsFftArgs a;
   ics_conv_fft_fill_args(0, conv_args(h, 0, h.pu.data(), pout.data(), h.pf.data(), h.pu.data(), h.pu.data(), nullptr), (const float*)spec.data(), &a);
-  a.planar = 63; a.store_all = 1;
+  a.store_all = 1;
   const icsfft::Mem mem = icsfft::make_mem(a, 0);
   std::vector<float> gk((size_t)K * K * 3, 0.f);
   const int npairs = (a.ntiles + 1) / 2;
@@ -293,7 +289,7 @@ int emulate_fused(int M, int K, int N) {
         v4f fimg[2][4];
         icsfft::load_image(a, mem, u, t, fimg);
         icsfft::QuadOut qo[2];
-        for (int tt = 0; tt < 2; ++tt) qo[tt].vo = icsfft::quad_lane(a, u, mem.lout, t, tt, qo[tt].rows, qo[tt].X);
+        for (int tt = 0; tt < 2; ++tt) qo[tt].vo = icsfft::quad_lane(a, u, mem.lay, t, tt, qo[tt].rows, qo[tt].X);
         const bool edge = u.ox[0] < a.ox0 || u.ox[0] + a.V > a.ox1 || u.ox[1] < a.ox0 || u.ox[1] + a.V > a.ox1;
         for (int i = 0; i < 4; ++i) icsfft::residual_quads(a, mem, qo, edge, true, lds.data(), t, i, fimg);
       }
@@ -374,7 +370,6 @@ void emulate_mode(const Host& h, int mode, const std::vector<float>& pin, std::v
   uint32_t red[16] = {0};
   IcsFftArgs a;
   ics_conv_fft_fill_args(mode, conv_args(h, mode, pin.data(), pout.data(), h.pf.data(), h.pu.data(), h.put.data(), red), (const float*)spec.data(), &a);
-  a.planar = 63;
   const icsfft::Mem mem = icsfft::make_mem(a);
   for (int n = 0; n < a.nunits; ++n) {
     const icsfft::Unit u = icsfft::decode_unit(a, n);
@@ -393,7 +388,7 @@ void emulate_mode(const Host& h, int mode, const std::vector<float>& pin, std::v
       if (mode == 0) icsfft::load_image(a, mem, u, t, fimg);
       else { icsfft::load_ops<false>(a, mem, u, t, 0, o); icsfft::load_ops<false>(a, mem, u, t, 1, o); }
       icsfft::QuadOut qo[2];
-      for (int tt = 0; tt < 2; ++tt) qo[tt].vo = icsfft::quad_lane(a, u, mem.lout, t, tt, qo[tt].rows, qo[tt].X);
+      for (int tt = 0; tt < 2; ++tt) qo[tt].vo = icsfft::quad_lane(a, u, mem.lay, t, tt, qo[tt].rows, qo[tt].X);
       const bool edge = u.ox[0] < a.ox0 || u.ox[0] + a.V > a.ox1 || u.ox[1] < a.ox0 || u.ox[1] + a.V > a.ox1;
       for (int i = 0; i < 4; ++i) {
         v4f r[2];
@@ -426,7 +421,7 @@ int emulate_conv2(int M, int K, int N) {
   uint32_t red[16] = {0};
   IcsFftArgs a;
   ics_conv_fft_fill_args(2, conv_args(h, 1, h.pu.data(), pout.data(), h.pf.data(), h.pu.data(), h.put.data(), red), (const float*)spec0.data(), &a);
-  a.planar = 63; a.spec1 = spec1.data();
+  a.spec1 = spec1.data();
   std::vector<float> fspec((size_t)a.nunits * 8 * 1024 * 4, 0.f);
   a.fspec = fspec.data();
   printf("mode 2: V %d x %d, tiles %d (x %d), units %d, the last tile row / column stores %d / %d more\n", a.Vy, a.V, a.ntiles, a.tiles_x, a.nunits, a.ext_y, a.ext_x);
@@ -488,7 +483,7 @@ int emulate_conv2(int M, int K, int N) {
       icsfft::Ops o;
       icsfft::load_ops<false, true>(a, mem, u, t, 0, o); icsfft::load_ops<false, true>(a, mem, u, t, 1, o);
       icsfft::QuadOut qo[2];
-      for (int tt = 0; tt < 2; ++tt) qo[tt].vo = icsfft::quad_lane<true>(a, u, mem.lout, t, tt, qo[tt].rows, qo[tt].X);
+      for (int tt = 0; tt < 2; ++tt) qo[tt].vo = icsfft::quad_lane<true>(a, u, mem.lay, t, tt, qo[tt].rows, qo[tt].X);
       const bool edge = icsfft::unit_is_edge<true>(a, u);
       for (int i = 0; i < 4; ++i) {
         v4f r[2];
@@ -595,7 +590,6 @@ int emulate_blk(int M, int K, int N) {
     uint32_t red[16] = {0};
     IcsFftArgs a;
     ics_conv_fft_fill_args(mode, conv_args(h, mode, mode == 0 ? h.pu.data() : h.pe.data(), pout.data(), h.pf.data(), h.pu.data(), h.put.data(), red), (const float*)spec.data(), &a, nb, Kb);
-    a.planar = 63;
     const icsfft::Mem mem = icsfft::make_mem(a);
     for (int n = 0; n < a.nunits; ++n) {
       const icsfft::Unit u = icsfft::decode_unit(a, n);
@@ -624,7 +618,7 @@ int emulate_blk(int M, int K, int N) {
         if (mode == 0) icsfft::load_image(a, mem, u, t, fimg);
         else { icsfft::load_ops<false>(a, mem, u, t, 0, o); icsfft::load_ops<false>(a, mem, u, t, 1, o); }
         icsfft::QuadOut qo[2];
-        for (int tt = 0; tt < 2; ++tt) qo[tt].vo = icsfft::quad_lane(a, u, mem.lout, t, tt, qo[tt].rows, qo[tt].X);
+        for (int tt = 0; tt < 2; ++tt) qo[tt].vo = icsfft::quad_lane(a, u, mem.lay, t, tt, qo[tt].rows, qo[tt].X);
         const bool edge = u.ox[0] < a.ox0 || u.ox[0] + a.V > a.ox1 || u.ox[1] < a.ox0 || u.ox[1] + a.V > a.ox1;
         for (int i = 0; i < 4; ++i) {
           v4f r[2];
@@ -651,7 +645,7 @@ int emulate_blk(int M, int K, int N) {
       for (int qx = 0; qx < nb; ++qx) {
         IcsFftArgs a;
         ics_conv_fft_fill_args(0, c, nullptr, &a, nb, Kb);
-        a.planar = 63; a.lag_y = qy * Kb; a.lag_x = qx * Kb;
+        a.lag_y = qy * Kb; a.lag_x = qx * Kb;
         const icsfft::Mem mem = icsfft::make_mem(a);
         const int npairs = (a.ntiles + 1) / 2;
         for (int ch = 0; ch < 3; ++ch) {
@@ -691,13 +685,13 @@ int emulate_blk(int M, int K, int N) {
 int gpu(int M, int K, int N, int reps) {
   Host h = make_host(M, N, K);
   float *du, *de, *df, *dut, *dout, *dpsf, *dspec0, *dspec1; uint32_t* dred;
-  const size_t fb = (g_planar ? h.pnf : h.nf) * 4;
+  const size_t fb = h.pnf * 4;
   for (float** p : {&du, &de, &df, &dut, &dout}) CK(hipMalloc(p, fb));
   CK(hipMalloc(&dpsf, h.psf.size() * 4)); CK(hipMalloc(&dred, 1024)); CK(hipMemset(dred, 0, 1024));
   const size_t sf = ics_conv_fft_spectrum_floats();
   CK(hipMalloc(&dspec0, sf * 4)); CK(hipMalloc(&dspec1, sf * 4));
-  CK(hipMemcpy(du, (g_planar ? h.pu : h.u).data(), fb, hipMemcpyHostToDevice)); CK(hipMemcpy(de, (g_planar ? h.pe : h.e).data(), fb, hipMemcpyHostToDevice));
-  CK(hipMemcpy(df, (g_planar ? h.pf : h.f).data(), fb, hipMemcpyHostToDevice)); CK(hipMemcpy(dut, (g_planar ? h.put : h.ut).data(), fb, hipMemcpyHostToDevice));
+  CK(hipMemcpy(du, h.pu.data(), fb, hipMemcpyHostToDevice)); CK(hipMemcpy(de, h.pe.data(), fb, hipMemcpyHostToDevice));
+  CK(hipMemcpy(df, h.pf.data(), fb, hipMemcpyHostToDevice)); CK(hipMemcpy(dut, h.put.data(), fb, hipMemcpyHostToDevice));
   CK(hipMemcpy(dpsf, h.psf.data(), h.psf.size() * 4, hipMemcpyHostToDevice));
   CK(ics_launch_fft_spectrum(dpsf, K, dspec0, dspec1, 0));
   CK(hipDeviceSynchronize());
@@ -717,12 +711,11 @@ int gpu(int M, int K, int N, int reps) {
     CK(hipMemset(dout, 0, fb));
     IcsConvArgs a = conv_args(h, mode, mode == 0 ? du : de, dout, df, du, dut, dred);
     IcsFftArgs fa; ics_conv_fft_fill_args(mode, a, mode == 0 ? dspec0 : dspec1, &fa);
-    fa.planar = 63;
     CK(ics_launch_conv_fft_args(mode, fa, 0));
     CK(hipDeviceSynchronize());
     std::vector<float> out(h.nf, 0.f);
-    if (g_planar) { std::vector<float> po(h.pnf); CK(hipMemcpy(po.data(), dout, fb, hipMemcpyDeviceToHost)); from_planar(h, po, out); }
-    else CK(hipMemcpy(out.data(), dout, h.nf * 4, hipMemcpyDeviceToHost));
+    std::vector<float> po(h.pnf);
+    CK(hipMemcpy(po.data(), dout, fb, hipMemcpyDeviceToHost)); from_planar(h, po, out);
     double wa;
     const int step = (M <= 600) ? 1 : (M / 24) | 1;
     const double rel = check(h, mode, out, step, &wa);
@@ -770,7 +763,6 @@ int gpu(int M, int K, int N, int reps) {
     CK(hipMalloc(&dpart2, (size_t)768 * K * K * 4)); CK(hipMalloc(&dgk2, (size_t)3 * K * K * 4));
     IcsConvArgs a = conv_args(h, 0, du, dout, df, du, dut, dred);
     IcsFftArgs fa; ics_conv_fft_fill_args(0, a, dspec0, &fa);
-    fa.planar = 63;
     CK(ics_launch_conv_fft_args(0, fa, 0));
     CK(ics_launch_gradk_fft(du + h.porg, dout + h.porg, h.g, dpart, dgk, 0));
     CK(ics_launch_synth_gradk_fft(du + h.porg, df + h.porg, de2 + h.porg, dspec0, h.g, 0, 0, 0, 0, 1, dpart2, dgk2, 0));
@@ -807,7 +799,7 @@ int gpu(int M, int K, int N, int reps) {
     {   // f := conv(u) + noise, through mode 0 with a zero image, then noise added on the host
       std::vector<float> zero(h.pnf, 0.f);
       CK(hipMemcpy(df, zero.data(), fb, hipMemcpyHostToDevice));
-      IcsFftArgs fa; ics_conv_fft_fill_args(0, a0, dspec0, &fa); fa.planar = 63;
+      IcsFftArgs fa; ics_conv_fft_fill_args(0, a0, dspec0, &fa);
       CK(ics_launch_conv_fft_args(0, fa, 0)); CK(hipDeviceSynchronize());
       std::vector<float> pc(h.pnf);
       CK(hipMemcpy(pc.data(), dout, fb, hipMemcpyDeviceToHost));
@@ -823,9 +815,9 @@ int gpu(int M, int K, int N, int reps) {
     CK(hipMalloc(&dg1, fb)); CK(hipMalloc(&dg2, fb)); CK(hipMemset(dg1, 0, fb)); CK(hipMemset(dg2, 0, fb));
     const size_t nfs = ics_conv2_fft_fspec_floats(h.g);
     CK(hipMalloc(&dfs, nfs * 4));
-    IcsFftArgs f0; ics_conv_fft_fill_args(0, a0, dspec0, &f0); f0.planar = 63;
+    IcsFftArgs f0; ics_conv_fft_fill_args(0, a0, dspec0, &f0);
     IcsConvArgs a1 = conv_args(h, 1, dout, dg1, df, du, dut, dred);
-    IcsFftArgs f1; ics_conv_fft_fill_args(1, a1, dspec1, &f1); f1.planar = 63;
+    IcsFftArgs f1; ics_conv_fft_fill_args(1, a1, dspec1, &f1);
     IcsConvArgs a2 = conv_args(h, 1, du, dg2, df, du, dut, dred + 16);
     CK(hipMemset(dred, 0, 1024));
     CK(ics_launch_conv_fft_args(0, f0, 0)); CK(ics_launch_conv_fft_args(1, f1, 0));
