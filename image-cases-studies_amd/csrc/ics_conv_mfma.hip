@@ -26,7 +26,7 @@
 // 12 MFMAs (a row-contiguous fragment would serve 3 and the kernel would be LDS-bound).
 //
 // Kernel shape: persistent 4-wave workgroups walking 64x64-pixel tiles, two per CU -- or, with fragment rows 2 apart (two
-// accumulator sets per wave instead of four), 32x64 tiles, three per CU: launch_k() below picks per PSF size and frame.
+// accumulator sets per wave instead of four), 32x64 tiles, three per CU: conv_tile() below picks per PSF size and frame.
 //   * LDS (75 KB): the tile + halo as six fp16 planes (channel x hi/lo), rows grouped by y mod 4 so that the
 //     16 lane rows of a fragment are consecutive 160-B LDS rows (conflict-free for the b128 lane groups of
 //     gfx950, MI355X_MICROARCH.md LDS).  Two workgroups per CU: one's memory phases (conversion, epilogue)
@@ -48,22 +48,18 @@
 //     back-projection + step-size reductions).  Two barriers per tile (scale, planes written).
 #include "ics_common.h"
 #include "ics_image_acc.h"
+#include "ics_mfma_tile.h"
 #include <stdlib.h>
 #include <type_traits>
 
 namespace {
 
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-typedef _Float16 h4 __attribute__((ext_vector_type(4)));
-typedef float f4 __attribute__((ext_vector_type(4)));
-typedef uint32_t u4 __attribute__((ext_vector_type(4)));
-typedef float f32x4u __attribute__((ext_vector_type(4), aligned(4)));
-typedef uint32_t u3 __attribute__((ext_vector_type(3)));
+using namespace icsmm;
 
 // RS = row stride of a fragment = accumulator sets per wave and channel: a tile is 16 * RS rows high.
 //   RS = 4 (64 x 64 tiles, two workgroups per CU up to K = 15): one A-fragment read feeds 12 MFMAs per window.
 //   RS = 2 (32 x 64 tiles): half the planes, a third of the registers less -- three workgroups per CU up to K = 17 and two
-//   instead of one at K = 19, 21; twice the LDS reads per MFMA and 9 % more staged bytes.  launch_k() picks (measured).
+//   instead of one at K = 19, 21; twice the LDS reads per MFMA and 9 % more staged bytes.  conv_tile() picks (measured).
 // NH = 2 (K >= 23, where the planes leave room for one workgroup per CU only): 8 waves per workgroup; the two waves of a column
 //   block split the kernel rows ([0, K/2] and the rest), exchange their partial sums through LDS after the matrix phase and run
 //   the epilogue of two accumulator sets each.  Two waves per SIMD instead of one: every phase of a wave (conversion, LDS
@@ -86,12 +82,7 @@ struct MCfg {
   static constexpr int PLANE = LROWS * ROWB;     // bytes per (channel, hi/lo) plane
   static constexpr int DATA = 6 * PLANE;
   static constexpr int SCRATCH = DATA;
-  // weight rows in LDS: halves 8 .. K+24 of the zero-padded row Wp[idx] = W[idx - 15] (the taps sit at local
-  // halves 7 .. K+6, at least ten zeros follow): every 8-half window that meets a tap lies inside, and the
-  // all-zero windows are redirected to the zero tail
-  static constexpr int WROWB = (2 * (K + 17) + 3) & ~3;
-  static constexpr int WZERO = (K + 7) / 2;      // first all-zero dword of a row
-  static constexpr int WLDS = 3 * K * 2 * WROWB; // = the global weight table built by k_psf (ics_common.h), copied verbatim
+  static constexpr int WROWB = MmaWeights<K>::WROWB, WZERO = MmaWeights<K>::WZERO, WLDS = MmaWeights<K>::WLDS;   // weight rows in LDS
   // Row pairs (round 4).  With two windows a kernel row costs 2 x 32 columns of MFMA depth for its 16 + K - 1 <= 48 input columns,
   // and the matrix loop of these kernels runs at 85 % of the MFMA issue rate (without it 0.35 of 1.07 ms at 6144^2 / 31 x 31, with
   // two of the three split terms 0.83).  Two consecutive kernel rows a, a + 1 of one accumulator set read input rows r and r + 1;
@@ -121,48 +112,6 @@ struct MCfg {
   static_assert(16 + K - 1 <= 32 * NCH, "MFMA windows cover the taps of 16 output columns");
   static_assert(LDS_BYTES <= 160 * 1024, "LDS budget");
 };
-
-__device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) { return ics_wave_max_u32(v); }
-
-// power-of-two scale that brings a maximum magnitude m into [2^14, 2^15) (fp16 overflows at 65504);
-// 1 for m = 0 / Inf / NaN.  `inv` is the exact inverse.
-__device__ __forceinline__ void pow2_scale(float m, float& s, float& inv) {
-  const uint32_t e = (__float_as_uint(m) >> 23) & 0xFFu;
-  uint32_t sb = 127u;
-  if (m > 0.f && e != 255u) { sb = 268u - e; sb = sb > 240u ? 240u : sb; }
-  s = __uint_as_float(sb << 23);
-  inv = __uint_as_float((254u - sb) << 23);
-}
-
-// Buffer addressing (SGPR resource + 32-bit lane offset + SGPR/immediate offset): with flat 64-bit pointers
-// the compiler materialised one 64-bit VGPR base per load and spilled them.
-#define ICS_BUF_WORD3 0x00020000  /* gfx9 raw buffer: DATA_FORMAT = 32 */
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* p) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, 0x7FFFFFFF, ICS_BUF_WORD3);
-}
-
-// the staged rows of a tile: task t = (row, 4-pixel group) -> three dwordx4 loads (4-byte aligned).
-// `soff` = wave-uniform byte offset of the tile's first staged element.
-template <typename C>
-__device__ __forceinline__ void load_raw(f32x4u (&v)[C::NIT][3], __amdgpu_buffer_rsrc_t rs, int soff, int tid, int pitch) {
-#pragma unroll
-  for (int k = 0; k < C::NIT; ++k) {
-    int t = tid + k * C::NT;
-    t = t < C::NTASK ? t : C::NTASK - 1;  // clamp instead of predicating the load
-    const int row = t / C::XG, xg = t - row * C::XG;
-    const int toff = 4 * (row * pitch + 12 * xg);
-#pragma unroll
-    for (int h = 0; h < 3; ++h) v[k][h] = __builtin_bit_cast(f32x4u, __builtin_amdgcn_raw_buffer_load_b128(rs, toff + 16 * h, soff, 0));
-  }
-}
-
-// workgroup barrier that waits for this wave's LDS traffic only (__syncthreads() also waits for the global loads in flight)
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
-// a copy of `x` the optimiser cannot trace back: values derived from it are recomputed where they are used
-// instead of being hoisted out of the tile loop (where they were spilled -- and a scratch reload waits on
-// vmcnt, i.e. on the whole prefetch in flight)
-__device__ __forceinline__ int opaque(int x) { asm volatile("" : "+v"(x)); return x; }
 
 template <int K, int MODE, int RS, int NH>
 __global__ __launch_bounds__(256 * NH) __attribute__((amdgpu_waves_per_eu(MCfg<K, RS, NH>::WGS * NH, MCfg<K, RS, NH>::WGS * NH))) void k_conv_mfma(IcsConvArgs a) {
@@ -332,10 +281,7 @@ __global__ __launch_bounds__(256 * NH) __attribute__((amdgpu_waves_per_eu(MCfg<K
             h4 hi, lo;
 #pragma unroll
             for (int p = 0; p < 4; ++p) {
-              const float x = f[3 * p + c];
-              const _Float16 xh = (_Float16)x;
-              hi[p] = xh;
-              lo[p] = (_Float16)(x - (float)xh);   // (as one v_fma_mix from the raw value: 36 vector instructions fewer per tile, same time)
+              split_f16(f[3 * p + c], hi, lo, p);
             }
             *reinterpret_cast<h4*>(dst + (2 * c) * C::PLANE) = hi;
             *reinterpret_cast<h4*>(dst + (2 * c + 1) * C::PLANE) = lo;
@@ -400,7 +346,6 @@ __global__ __launch_bounds__(256 * NH) __attribute__((amdgpu_waves_per_eu(MCfg<K
         // funnel-shifted behind them.  The reads are volatile: as plain loads they were sunk to the shifts, and the wave
         // waited out the LDS latency in front of every step's MFMAs (466 cycles per step for 192 cycles of MFMA,
         // phase timeline of the matrix loop).
-        typedef uint32_t u2 __attribute__((ext_vector_type(2)));
         typedef const volatile __attribute__((address_space(3))) u2* lds_vu2p;
         u2 rawB[C::NCH][5];   // (hi, lo) dword pairs: the table interleaves the two split terms dword by dword
         auto issueB = [&](int ka) {
@@ -497,7 +442,6 @@ __global__ __launch_bounds__(256 * NH) __attribute__((amdgpu_waves_per_eu(MCfg<K
     auto matrix_phase_items = [&](auto i0c, auto i1c) {
       constexpr int I0 = decltype(i0c)::value, I1 = decltype(i1c)::value;
       constexpr int NP = (K - 1) / 2;
-      typedef uint32_t u2 __attribute__((ext_vector_type(2)));
       typedef const volatile __attribute__((address_space(3))) u2* lds_vu2p;
       const uint32_t wbase = (uint32_t)(uintptr_t)(lds_u32p)(lds + C::SCRATCH + 256);
       auto wof = [&](int bo, int rowadd) -> uint32_t {
@@ -813,7 +757,7 @@ __global__ __launch_bounds__(256 * NH) __attribute__((amdgpu_waves_per_eu(MCfg<K
     for (int c = 0; c < 3; ++c) {
       kg[c] = mgb[c] > 0x7F800000u ? 0xFFC00000u : ((rflags & 64u) ? ics_f2key(__uint_as_float(mgb[c])) : 0u);   // NaN propagates like np.amax
       ku[c] = mub[c] > 0x7F800000u ? 0xFFC00000u : ((rflags & 64u) ? ics_f2key(mu[c]) : 0u);
-      kg[c] = wave_max_u32(kg[c]); ku[c] = wave_max_u32(ku[c]);
+      kg[c] = ics_wave_max_u32(kg[c]); ku[c] = ics_wave_max_u32(ku[c]);
     }
     uint32_t* red_lds = reinterpret_cast<uint32_t*>(fscr);
     if (lane == 0) {
@@ -868,49 +812,37 @@ hipError_t launch_one(const IcsConvArgs& a, hipStream_t s) {
 //   0.184 / 0.218, K = 19 0.347 / 0.405 -> 0.325 / 0.364, K = 21 -5 % / -9 %, K = 23 .. 31 +10 .. 14 % (one workgroup per CU
 //   either way, and the A-fragment reads then bound the step); 1024^2 .. 3072^2, K <= 15: RS = 2 ahead by 3 .. 30 % (finer
 //   tiles balance the 256 CUs better).  Hence: K >= 23 -> 4; K = 15 .. 21 -> 2; K <= 13 -> 2 up to 3000 tiles of 64 x 64, else 4.
-template <int K> struct TileRs {
-  static constexpr bool has2 = K <= 21 || K >= 39;   // 39 .. 49: the planes of a 64-row tile do not fit the LDS
-  static constexpr bool has4 = K <= 13 || (K >= 23 && K <= 37);
-  // 16-row tiles (fragment rows 1 apart, one accumulator set; round 4) for frames that do not give every CU a 32-row tile: the 255-px
-  // windows of deblur_module's blind phase (45 tiles of 32 x 64 on 256 CUs) and 512^2 (128).  A fragment read then feeds 3 MFMAs only --
-  // irrelevant where a kernel is one chain of dependent round trips per workgroup; what counts is that the chain is half as long.
-  static constexpr bool has1 = K <= 15;
-};
-// does this frame take the 16-row tiles?  (fewer 32-row tiles than compute units)
-template <int K>
-static bool small_frame_rs1(int mode, const IcsGeom& g) {
-  if (!TileRs<K>::has1) return false;
-  const int frs = ics_debug().conv_rs.load(std::memory_order_relaxed);
-  if (frs == 1) return true;
-  if (frs == 2 || frs == 4) return false;
-  const long t32 = mode == 0 ? (long)((g.N + 63) / 64) * ((g.M + 31) / 32) : (long)g.tiles_x * ((g.uM + 31) / 32);
-  return t32 < (long)ics_device_cus(ics_current_device());
+// 16-row tiles (fragment rows 1 apart, one accumulator set; round 4, K <= 15) are for frames that do not give every CU a 32-row tile:
+// the 255-px windows of deblur_module's blind phase (45 tiles of 32 x 64 on 256 CUs) and 512^2 (128).  A fragment read then feeds 3 MFMAs
+// only -- irrelevant where a kernel is one chain of dependent round trips per workgroup; what counts is that the chain is half as long.
+// 8 waves (K >= 23, one workgroup per CU): the kernel rows split between the two waves of a column block (MCfg NH = 2).  Measured against
+// the 4-wave form: 4096^2 K = 23 0.417 / 0.485 -> 0.390 / 0.448 ms, 6144^2 K = 31 1.089 / 1.266 -> 1.077 / 1.197 ms; 39 .. 49: the planes
+// of a 64-row tile do not fit the LDS, 32-row tiles.
+// `conv_rs` = the debug switch: 1 forces the 16-row tiles, 2 / 4 a height where both are built (K <= 13) and no 16-row tiles.
+struct ConvTile { int rows; bool split; };   // tile height (16 / 32 / 64), 8-wave row split
+constexpr bool conv_tile_split(int K) { return K >= 23; }
+ConvTile conv_tile(int K, int mode, const IcsGeom& g, int cus, int conv_rs) {
+  if (K <= 15 && conv_rs != 2 && conv_rs != 4) {   // fewer 32-row tiles than compute units?
+    const long t32 = mode == 0 ? (long)((g.N + 63) / 64) * ((g.M + 31) / 32) : (long)g.tiles_x * ((g.uM + 31) / 32);
+    if (conv_rs == 1 || t32 < (long)cus) return {16, false};
+  }
+  if (conv_tile_split(K)) return {K >= 39 ? 32 : 64, true};
+  bool rs2 = K >= 15 || (long)g.tiles_x * g.tiles_y <= 3000;
+  if (K <= 13) rs2 = conv_rs == 2 ? true : (conv_rs == 4 ? false : rs2);   // test / harness hook
+  return {rs2 ? 32 : 64, false};
 }
+// the instances that are built: every form conv_tile() can return for K
+template <int K> struct TileRs {
+  static constexpr bool has1 = K <= 15, has2 = K <= 21 || K >= 39, has4 = K <= 13 || (K >= 23 && K <= 37);
+  static constexpr int NH = conv_tile_split(K) ? 2 : 1;
+};
 template <int K>
 hipError_t launch_k(int mode, const IcsConvArgs& a, hipStream_t s) {
-  if constexpr (TileRs<K>::has1) {
-    if (small_frame_rs1<K>(mode, a.g)) return mode == 0 ? launch_one<K, 0, 1>(a, s) : launch_one<K, 1, 1>(a, s);
-  }
-  bool rs2 = K >= 39 || (K <= 21 && (K >= 15 || (long)a.g.tiles_x * a.g.tiles_y <= 3000));
-  if (TileRs<K>::has2 && TileRs<K>::has4) {   // test / harness hook: force a tile height where both are built
-    const int frs = ics_debug().conv_rs.load(std::memory_order_relaxed);
-    rs2 = frs == 2 ? true : (frs == 4 ? false : rs2);
-  }
-  if constexpr (TileRs<K>::has2) {
-    if constexpr (K >= 39) {   // 39 .. 49: 32-row tiles with the kernel rows split between two waves per column block
-      if (rs2 || !TileRs<K>::has4) return mode == 0 ? launch_one<K, 0, 2, 2>(a, s) : launch_one<K, 1, 2, 2>(a, s);
-    } else {
-      if (rs2 || !TileRs<K>::has4) return mode == 0 ? launch_one<K, 0, 2>(a, s) : launch_one<K, 1, 2>(a, s);
-    }
-  }
-  if constexpr (TileRs<K>::has4) {
-    if constexpr (K >= 23) {
-      // one workgroup per CU: 8 waves, kernel rows split between the two waves of a column block (MCfg NH = 2).  Measured against the
-      // 4-wave form: 4096^2 K = 23 0.417 / 0.485 -> 0.390 / 0.448 ms, 6144^2 K = 31 1.089 / 1.266 -> 1.077 / 1.197 ms
-      return mode == 0 ? launch_one<K, 0, 4, 2>(a, s) : launch_one<K, 1, 4, 2>(a, s);
-    } else {
-      return mode == 0 ? launch_one<K, 0, 4>(a, s) : launch_one<K, 1, 4>(a, s);
-    }
+  constexpr int NH = TileRs<K>::NH;
+  switch (conv_tile(K, mode, a.g, ics_device_cus(ics_current_device()), ics_debug().conv_rs.load(std::memory_order_relaxed)).rows) {
+    case 16: if constexpr (TileRs<K>::has1) return mode == 0 ? launch_one<K, 0, 1>(a, s) : launch_one<K, 1, 1>(a, s); break;
+    case 32: if constexpr (TileRs<K>::has2) return mode == 0 ? launch_one<K, 0, 2, NH>(a, s) : launch_one<K, 1, 2, NH>(a, s); break;
+    case 64: if constexpr (TileRs<K>::has4) return mode == 0 ? launch_one<K, 0, 4, NH>(a, s) : launch_one<K, 1, 4, NH>(a, s); break;
   }
   return hipErrorInvalidValue;
 }
@@ -978,25 +910,15 @@ bool ics_conv_mfma_supported(int K) { return K >= 3 && K <= 49 && (K & 1); }   /
 // 64-row tiles -- two 32-wide windows per column block, one workgroup per CU -- and are ~8 % ahead with 32-row tiles).
 bool ics_conv_mfma_preferred(int K) { return ics_conv_mfma_supported(K); }
 
-// Tile height (fragment row stride RS = 2: 32 rows, 4: 64 rows) launch_k() picks for this PSF size and frame, 0 for the 8-wave
-// kernels (K >= 23): the caller prepares the accumulator-order image (ics_image_acc.h) of that layout for mode 0.
+// Tile height (fragment row stride RS = 2: 32 rows, 4: 64 rows) mode 0 runs with for this PSF size and frame (conv_tile() above), 0 for the
+// 16-row tiles and the 8-wave kernels: the caller prepares the accumulator-order image (ics_image_acc.h) of that layout.
 int ics_conv_mfma_rs(int K, const IcsGeom& g, int cus) {   // cus < 0: the current device's (launch paths); the shape-only describe path passes a count
-  if (K >= 23) return 0;
-  if (K <= 15) {   // 16-row tiles on small frames (TileRs::has1): no accumulator-order image for them
-    const int frs = ics_debug().conv_rs.load(std::memory_order_relaxed);
-    const long t32 = (long)((g.N + 63) / 64) * ((g.M + 31) / 32);
-    if ((frs == 1 || (frs == 0 && t32 < (long)(cus >= 0 ? cus : ics_device_cus(ics_current_device()))))) return 0;
-  }
-  bool rs2 = K <= 21 && (K >= 15 || (long)g.tiles_x * g.tiles_y <= 3000);
-  if (K <= 13) {   // both heights are built
-    const int frs = ics_debug().conv_rs.load(std::memory_order_relaxed);
-    rs2 = frs == 2 ? true : (frs == 4 ? false : rs2);
-  }
-  return rs2 ? 2 : 4;
+  const ConvTile t = conv_tile(K, 0, g, cus >= 0 ? cus : ics_device_cus(ics_current_device()), ics_debug().conv_rs.load(std::memory_order_relaxed));
+  return t.split || t.rows == 16 ? 0 : t.rows / 16;
 }
 
 // weight table: [c][a] rows of 2 * WROWB bytes, hi/lo dword-interleaved (the LDS image), then one float 1/s_w (ics_common.h)
-size_t ics_conv_mfma_table_floats(int K) { return (size_t)3 * K * 2 * (((2 * (K + 17) + 3) & ~3) / 4) + 4; }
+size_t ics_conv_mfma_table_floats(int K) { return (size_t)weight_lds_bytes(K) / 4 + 4; }
 
 hipError_t ics_launch_conv_mfma(int mode, const IcsConvArgs& a, hipStream_t s) {
   if ((mode != 0 && mode != 1) || !a.bt) return hipErrorInvalidValue;

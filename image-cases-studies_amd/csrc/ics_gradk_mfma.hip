@@ -26,15 +26,12 @@
 // with the strip walk u is read ~1.03x.  The scale of a tile covers the new rows and the maximum of the carried rows (tracked
 // per tile over exactly those rows, so a bright pixel does not dictate the scale of the tiles below it).
 #include "ics_kernels.h"
+#include "ics_mfma_tile.h"
 #include <type_traits>
 
 namespace {
 
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-typedef _Float16 h4 __attribute__((ext_vector_type(4)));
-typedef float f4 __attribute__((ext_vector_type(4)));
-typedef uint32_t u4 __attribute__((ext_vector_type(4)));
-typedef float f32x4u __attribute__((ext_vector_type(4), aligned(4)));
+using namespace icsmm;
 
 // priority slices between the two workgroups of a CU, 2^12 x 10 ns (ics_prio_turn, ics_common.h).  6144^2 / 31x31: 0.782 (off) -> 0.755 (2^10)
 // -> 0.747 ms (2^12); 4096^2 / 23x23 0.359 -> 0.342
@@ -66,19 +63,6 @@ struct GCfg {
   static constexpr int UIT = (UTASK + NTH - 1) / NTH, EIT = (ETASK + NTH - 1) / NTH;
   static_assert(WGS * LDS_BYTES <= 160 * 1024, "workgroups per CU");
 };
-
-#define ICS_BUF_WORD3 0x00020000  /* gfx9 raw buffer: DATA_FORMAT = 32 */
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* p) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, 0x7FFFFFFF, ICS_BUF_WORD3);
-}
-
-__device__ __forceinline__ void pow2_scale(float m, float& s, float& inv) {
-  const uint32_t e = (__float_as_uint(m) >> 23) & 0xFFu;
-  uint32_t sb = 127u;
-  if (m > 0.f && e != 255u) { sb = 268u - e; sb = sb > 240u ? 240u : sb; }
-  s = __uint_as_float(sb << 23);
-  inv = __uint_as_float((254u - sb) << 23);
-}
 
 __device__ __forceinline__ float wg_max(float m, float* scr, int wave, int lane) {
   m = ics_wave_max_f32(m);
@@ -114,10 +98,7 @@ __device__ __forceinline__ void split_store(const f32x4u (&v)[3], float s, unsig
     h4 hi, lo;
 #pragma unroll
     for (int p = 0; p < 4; ++p) {
-      const float x = f[3 * p + c];
-      const _Float16 xh = (_Float16)x;
-      hi[p] = xh;
-      lo[p] = (_Float16)(x - (float)xh);
+      split_f16(f[3 * p + c], hi, lo, p);
     }
     *reinterpret_cast<h4*>(dst + (2 * c) * plane_bytes) = hi;
     *reinterpret_cast<h4*>(dst + (2 * c + 1) * plane_bytes) = lo;
@@ -135,11 +116,7 @@ __device__ __forceinline__ void split_store_interleaved(const f32x4u (&v)[3], fl
   for (int c = 0; c < 3; ++c) {
     _Float16 hi[4], lo[4];
 #pragma unroll
-    for (int p = 0; p < 4; ++p) {
-      const float x = f[3 * p + c];
-      hi[p] = (_Float16)x;
-      lo[p] = (_Float16)(x - (float)hi[p]);
-    }
+    for (int p = 0; p < 4; ++p) split_f16(f[3 * p + c], hi, lo, p);
     const h8 w = {hi[0], hi[1], lo[0], lo[1], hi[2], hi[3], lo[2], lo[3]};
     *reinterpret_cast<h8*>(dst + c * chan_bytes) = w;
   }
@@ -190,8 +167,6 @@ __device__ __forceinline__ void load_tile(f32x4u (&pu)[GCfg<NB>::UIT][3], f32x4u
     load_group<PL, 0>(pe[k], rs_e, 4 * (row * pitch + 4 * XM * xg), se, plane_bytes);
   }
 }
-
-__device__ __forceinline__ int opaque(int x) { asm volatile("" : "+v"(x)); return x; }
 
 template <int NB, bool PL>
 __global__ __launch_bounds__(GCfg<NB>::NTH) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_gradk_mfma(IcsGradkArgs a) {
@@ -352,7 +327,6 @@ __global__ __launch_bounds__(GCfg<NB>::NTH) __attribute__((amdgpu_waves_per_eu(2
     // are requested in front of the 12 MFMAs of step i and shifted behind them; with single-chunk steps that costs no register
     // more than before (A fragments double-buffered, raw B dwords single, finished B fragments double).
     // The reads are volatile: plain loads were sunk to their first use.
-    typedef uint32_t u2 __attribute__((ext_vector_type(2)));
     constexpr int XS = NB == 1 ? NX : 1;                   // chunks per step
     constexpr int NSTEP = 3 * (C::TH / C::NW) * (NX / XS);
     constexpr int DEPTH = NB == 1 ? 2 : 1;                 // steps between request and use

@@ -63,6 +63,8 @@ struct IcsFusedArgs {
   IcsGeom g;
 };
 bool ics_synth_gradk_supported(int K);
+// tile height (IcsFusedArgs::rs) and grid size for this frame, from the persistent workgroups of the 64-row / 32-row form
+void ics_synth_gradk_plan(const IcsGeom& g, int blocks64, int blocks32, int* rs, int* nblocks);
 hipError_t ics_launch_synth_gradk(const IcsFusedArgs& a, int nblocks, hipStream_t s);
 // gradk[a][b][c] = sum over workgroups (double accumulation, fixed order)
 hipError_t ics_launch_gradk_reduce(const float* partial, int nblocks, float* gradk, const IcsGeom& g, hipStream_t s);

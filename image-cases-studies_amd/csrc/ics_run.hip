@@ -301,26 +301,16 @@ static int do_synth_gradk_fft(ics_rl* j, const ics_rl_params* p, int store_all, 
   return ICS_OK;
 }
 
-static constexpr int ICS_FUSED_DEFAULT_RS = 4;
 // A11 + A13 in one kernel (matrix-core path, MK <= 15): ics_synth_gradk_mfma.hip
 static int do_synth_gradk(ics_rl* j, const Route& r, const ics_rl_params* p, int store_all, Prof& pr) {
   IcsFusedArgs a;
   a.u = org(j, j->u); a.f = org(j, j->f); a.e_out = org(j, j->e); a.bt = j->bt_conv; a.partial = j->partial; a.g = j->g;
   a.wy0 = p->top + j->g.pad; a.wy1 = p->bottom + j->g.pad; a.wx0 = p->left + j->g.pad; a.wx1 = p->right + j->g.pad;
   a.store_all = store_all;
-  // tile height: 32-row tiles with three workgroups per CU, or 64-row tiles with two (ics_synth_gradk_mfma.hip); debug switch fused_rs
-  // Measured on MI355X (blind, ms per inner iteration, 64-row -> 32-row form): 255^2 (deblur_module's blind window: 16 tiles of 64 x 64 on
-  // 256 CUs) 0.1095 -> 0.0985, 1024^2 0.1415 -> 0.1316, 2048^2 0.275 -> 0.266; 4096^2 level (NOTES_r03.md 4c).  Hence 32-row tiles up to
-  // 2500 tiles of 64 x 64 (~3200^2), 64-row tiles above.
-  const int frs = ics_debug().fused_rs.load(std::memory_order_relaxed);
-  a.rs = frs == 2 || frs == 4 ? frs : ((long)j->g.tiles_x * j->g.tiles_y <= 2500 ? 2 : ICS_FUSED_DEFAULT_RS);
+  int nblocks;
+  ics_synth_gradk_plan(j->g, j->gradk_blocks, j->fused2_blocks, &a.rs, &nblocks);   // tile height and grid
   a.facc = nullptr;
   if (r.image_acc) { RC(ensure_image_acc(j, a.rs)); a.facc = j->facc[a.rs == 2 ? 0 : 1]; }
-  int nblocks = j->gradk_blocks;
-  if (a.rs == 2) {
-    const int tiles32 = ((j->g.N + 63) / 64) * ((j->g.M + 31) / 32);
-    nblocks = j->fused2_blocks < tiles32 ? j->fused2_blocks : tiles32;
-  }
   RC(pr.begin(ICS_K_SYNTH_GRADK));
   HIPCHK(ics_launch_synth_gradk(a, nblocks, j->ctx->stream));
   HIPCHK(ics_launch_gradk_reduce(j->partial, nblocks, j->gradk, j->g, j->ctx->stream));

@@ -31,6 +31,7 @@
 //     workgroup, reduced in double by k_gradk_reduce (ics_kernels.hip), deterministic.
 #include "ics_kernels.h"
 #include "ics_image_acc.h"
+#include "ics_mfma_tile.h"
 #include <type_traits>
 
 // Fair shares for the workgroups of one CU.  The walk is static (the partial sums of a workgroup must not depend on timing), every
@@ -47,124 +48,94 @@ namespace {
 
 constexpr int FUSED_SLICE = 10;
 
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-typedef _Float16 h4 __attribute__((ext_vector_type(4)));
-typedef float f4 __attribute__((ext_vector_type(4)));
-typedef uint32_t u4 __attribute__((ext_vector_type(4)));
-typedef uint32_t u2 __attribute__((ext_vector_type(2)));
-typedef float f32x4u __attribute__((ext_vector_type(4), aligned(4)));
+using namespace icsmm;
 
-// row classes of the u planes (rows c, c+4, ... contiguous): sizes and padded byte offsets.  The gradient reads 16 CONSECUTIVE rows
-// per A fragment (4 rows of each class) and always starts on an even row (one fragment serves the residual rows 2p and 2p + 1,
+// Layout of one workgroup's LDS for tiles of 16 NC rows x 64 columns: FCfg<K> (NC = 4, k_synth_gradk) and FCfg2<K> (NC = 2, k_synth_gradk2).
+// Row classes of the u planes (rows c, c + NC, ... contiguous): sizes and padded byte offsets.  The gradient reads 16 CONSECUTIVE rows
+// per A fragment (16 / NC rows of each class) and always starts on an even row (one fragment serves the residual rows 2p and 2p + 1,
 // see gradk_phase); the class bases are padded so that those reads spread over the banks -- brute-force search over the offsets
-// modulo 256 with the ds_read_b128 lane groups of gfx950: 6 LDS cycles on average over the two row phases (8 unpadded; 4 =
-// conflict-free, which the y-mod-4 grouping the convolution needs does not allow for consecutive rows)
-template <int K>
-struct FRows {
-  static constexpr int LROWS = 64 + K - 1, ROWB = 160;
-  static constexpr int cls_rows(int c) { return (LROWS - c + 3) / 4; }
-  static constexpr int want(int c) { return c == 0 ? 0 : (c == 1 ? 64 : (c == 2 ? 32 : 96)); }
-  static constexpr int cls_off(int c) {
-    if (c == 0) return 0;
-    int off = cls_off(c - 1) + cls_rows(c - 1) * ROWB;
-    while (off % 256 != want(c)) off += 16;
-    return off;
-  }
-};
-
-template <int K>
-struct FCfg {
+// modulo 256 with the ds_read_b128 lane groups of gfx950.  NC = 4: 6 LDS cycles on average over the two row phases (8 unpadded; 4 =
+// conflict-free, which the y-mod-4 grouping the convolution needs does not allow for consecutive rows); NC = 2, class 1 at 128: 4.
+template <int K, int NC>
+struct FTile : MmaWeights<K> {
+  using MmaWeights<K>::WLDS;
   static constexpr int PAD = K / 2;
-  static constexpr int TH = 64, TW = 64;
+  static constexpr int TH = 16 * NC, TW = 64;
   static constexpr int NW = 4, NT = 64 * NW;
   static constexpr int LROWS = TH + K - 1;           // staged u rows
   static constexpr int LCOLS = TW + 16;              // staged u columns [x0 - PAD, x0 - PAD + 80)
   static constexpr int ROWB = 2 * LCOLS;             // 160 bytes per plane row
-  static constexpr int OFF0 = 0, OFF1 = FRows<K>::cls_off(1), OFF2 = FRows<K>::cls_off(2), OFF3 = FRows<K>::cls_off(3);
-  static constexpr int cls_off(int c) { return c == 0 ? OFF0 : (c == 1 ? OFF1 : (c == 2 ? OFF2 : OFF3)); }
-  static constexpr int PLANE = ((OFF3 + FRows<K>::cls_rows(3) * ROWB + 32 + 15) / 16) * 16;   // + 32: the third chunk over-reads a row
+  static constexpr int cls_rows(int c) { return (LROWS - c + NC - 1) / NC; }
+  static constexpr int want(int c) { return NC == 2 ? 128 * c : (c == 0 ? 0 : (c == 1 ? 64 : (c == 2 ? 32 : 96))); }
+  static constexpr int padded_off(int c) {
+    if (c == 0) return 0;
+    int off = padded_off(c - 1) + cls_rows(c - 1) * ROWB;
+    while (off % 256 != want(c)) off += 16;
+    return off;
+  }
+  static constexpr int OFF1 = padded_off(1), OFF2 = padded_off(NC > 2 ? 2 : 1), OFF3 = padded_off(NC - 1);
+  static constexpr int cls_off(int c) { return NC == 2 ? (c ? OFF1 : 0) : (c == 0 ? 0 : (c == 1 ? OFF1 : (c == 2 ? OFF2 : OFF3))); }
+  // where a staged row sits inside a plane.  (The sum associates as it did when each kernel had a conversion of its own: the other order
+  // moves that kernel's instruction schedule.)
+  static __device__ __forceinline__ unsigned char* row_ptr(unsigned char* plane, int row) {
+    if (NC == 2) return plane + cls_off(row & 1) + (row >> 1) * ROWB;
+    return plane + (cls_off(row & 3) + (row >> 2) * ROWB);
+  }
+  static constexpr int PLANE = ((OFF3 + cls_rows(NC - 1) * ROWB + 32 + 15) / 16) * 16;   // + 32: the third chunk over-reads a row
   static constexpr int UOFF = 0;                       // [buffer][hi/lo] planes
   static constexpr int EROWB = 4 * LCOLS;              // 320 bytes: (hi, lo) dword pairs of 80 halves, x = -8 .. 71
   static constexpr int EOFF = 4 * PLANE;
   static constexpr int EBYTES = TH * EROWB + 64;       // + slack: the five-pair read of the last row
   static constexpr int SCR = EOFF + EBYTES;            // 256 bytes of floats
-  static constexpr int WROWB = (2 * (K + 17) + 3) & ~3;
-  static constexpr int WZERO = (K + 7) / 2;
-  static constexpr int WLDS = 3 * K * 2 * WROWB;
   static constexpr int WOFF = SCR + 256;
   // (the weight rows of ics_conv_mfma.hip's MCfg::WSPLIT form, restaged one channel at a time between the barriers, measured slower
   //  inside the iteration: 0.2739 -> 0.2767 ms -- the restaging sits on the critical path between the two barriers of a channel)
   static constexpr size_t LDS_BYTES = WOFF + WLDS;
-  static constexpr int NQ = K + 3;
+  static constexpr int NQ = K + NC - 1;
   static constexpr int XG = LCOLS / 4;
   static constexpr int NTASK = LROWS * XG;
   static constexpr int NIT = (NTASK + NT - 1) / NT;
+  static constexpr int MATES = NC == 4 ? 2 : 3;        // workgroups per CU
   static_assert(K >= 3 && K <= 15 && (K & 1), "one 32-wide MFMA window per column block, one 16-tap block");
-  static_assert(2 * LDS_BYTES <= 160 * 1024, "two workgroups per CU");
+  static_assert(MATES * LDS_BYTES <= 160 * 1024, "workgroups per CU");
 };
+template <int K> using FCfg = FTile<K, 4>;
+template <int K> using FCfg2 = FTile<K, 2>;
 
-#define ICS_BUF_WORD3 0x00020000  /* gfx9 raw buffer: DATA_FORMAT = 32 */
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* p) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, 0x7FFFFFFF, ICS_BUF_WORD3);
-}
-
-// power-of-two scale that brings a maximum magnitude m into [2^14, 2^15); 1 for m = 0 / Inf / NaN.  `inv` is the exact inverse.
-__device__ __forceinline__ void pow2_scale(float m, float& s, float& inv) {
-  const uint32_t e = (__float_as_uint(m) >> 23) & 0xFFu;
-  uint32_t sb = 127u;
-  if (m > 0.f && e != 255u) { sb = 268u - e; sb = sb > 240u ? 240u : sb; }
-  s = __uint_as_float(sb << 23);
-  inv = __uint_as_float((254u - sb) << 23);
-}
-
-__device__ __forceinline__ int opaque(int x) { asm volatile("" : "+v"(x)); return x; }
-
-// workgroup barrier that orders LDS traffic only.  __syncthreads() also waits for every outstanding global load (vmcnt(0)):
-// with the image operand or the next tile's rows in flight it stalled the whole workgroup for an HBM round trip.
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-// the matrix instructions and the funnel shift, short
-__device__ __forceinline__ f4 f_mfma32(h8 a, h8 b, f4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0); }
-__device__ __forceinline__ f4 f_mfma16(h4 a, h4 b, f4 c) { return __builtin_amdgcn_mfma_f32_16x16x16f16(a, b, c, 0, 0, 0); }
-__device__ __forceinline__ uint32_t f_align(uint32_t hi, uint32_t lo, uint32_t sh) { return __builtin_amdgcn_alignbit(hi, lo, sh); }
-
-template <typename C>
-__device__ __forceinline__ void load_raw(f32x4u (&v)[C::NIT][3], __amdgpu_buffer_rsrc_t rs, int soff, int tid, int pitch) {
-#pragma unroll
-  for (int k = 0; k < C::NIT; ++k) {
-    int t = tid + k * C::NT;
-    t = t < C::NTASK ? t : C::NTASK - 1;
-    const int row = t / C::XG, xg = t - row * C::XG;
-    const int toff = 4 * (row * pitch + 12 * xg);
-#pragma unroll
-    for (int h = 0; h < 3; ++h) v[k][h] = __builtin_bit_cast(f32x4u, __builtin_amdgcn_raw_buffer_load_b128(rs, toff + 16 * h, soff, 0));
+// Cross-wave reduction (fixed order) and partial write that closes both kernels, one channel per pass.  A statement macro like
+// ICS_FUSED_CHANNEL below: as a __forceinline__ function the same statements reach the optimiser in another block order, and the
+// schedule of every k_synth_gradk / k_synth_gradk2 instance moved.
+#define ICS_FUSED_WRITE_PARTIAL() \
+  float* red = reinterpret_cast<float*>(lds);   /* [wave][256]: element (row = 4*lg + r, col = li) at [r*64 + lane]; then [wave][64] carries */  \
+  float* dst = a.partial + (size_t)blockIdx.x * (3 * 16 * 16);                                                                                   \
+  _Pragma("unroll")                                                                                                                              \
+  for (int c = 0; c < 3; ++c) {                                                                                                                  \
+    __syncthreads();                                                                                                                             \
+    _Pragma("unroll")                                                                                                                            \
+    for (int r = 0; r < 4; ++r) red[wv * 256 + r * 64 + lane] = tot[c][r];                                                                       \
+    red[C::NW * 256 + wv * 64 + lane] = carry[c];                                                                                                \
+    __syncthreads();                                                                                                                             \
+    const int v = tid;                                                                                                                           \
+    float s = red[v];                                                                                                                            \
+    _Pragma("unroll")                                                                                                                            \
+    for (int w = 1; w < C::NW; ++w) s += red[w * 256 + v];   /* fixed order -> deterministic */                                                  \
+    const int l = v & 63, r = (v >> 6) & 3;                                                                                                      \
+    if (r == 3 && l < 48) {                                   /* tap row 4 lg + 3 also receives row 0 of the lane group above */                 \
+      _Pragma("unroll")                                                                                                                          \
+      for (int w = 0; w < C::NW; ++w) s += red[C::NW * 256 + w * 64 + l + 16];                                                                   \
+    }                                                                                                                                            \
+    const int ta = 4 * (l >> 4) + r, tb = l & 15;                                                                                                \
+    dst[(c * 16 + ta) * 16 + tb] = s;                                                                                                            \
   }
-}
 
-// one channel of the staged rows -> (hi, lo) fp16 planes, rows grouped by y mod 4
-template <typename C, int CH>
-__device__ __forceinline__ void convert_channel(const f32x4u (&raw)[C::NIT][3], float s_x, unsigned char* plane, int tid) {
-#pragma unroll
-  for (int k = 0; k < C::NIT; ++k) {
-    const int t = tid + k * C::NT;
-    if (t < C::NTASK) {
-      const int row = t / C::XG, xg = t - row * C::XG;
-      const int rc = row & 3;
-      const int coff = C::cls_off(rc) + (row >> 2) * C::ROWB;
-      unsigned char* dst = plane + coff + 8 * xg;
-      h4 hi, lo;
-#pragma unroll
-      for (int p = 0; p < 4; ++p) {
-        const int idx = 3 * p + CH;
-        const float x = raw[k][idx >> 2][idx & 3] * s_x;
-        const _Float16 xh = (_Float16)x;
-        hi[p] = xh;
-        lo[p] = (_Float16)(x - (float)xh);
-      }
-      *reinterpret_cast<h4*>(dst) = hi;
-      *reinterpret_cast<h4*>(dst + C::PLANE) = lo;
-    }
-  }
-}
+// residual of channel CH, its tile maximum and scale, e'(CH) planes: the same statement sequence in both kernels (their lambdas differ)
+#define ICS_FUSED_CHANNEL(CH)                                                                                           \
+    me = residual(CH);                                                                                                  \
+    if (lane == 0) fscr[8 + 4 * (CH) + wv] = me;                                                                        \
+    lds_barrier();     /* tile maximum; every wave is past the previous gradient phase: e' planes and u buffer free */  \
+    me = __builtin_fmaxf(__builtin_fmaxf(fscr[8 + 4 * (CH)], fscr[9 + 4 * (CH)]), __builtin_fmaxf(fscr[10 + 4 * (CH)], fscr[11 + 4 * (CH)])); \
+    pow2_scale(__builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, me))), s_e, inv_e);      \
+    write_e(s_e);
 
 template <int K, bool ACC>   // ACC: the image operand comes from the accumulator-order copy a.facc (ics_image_acc.h)
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_synth_gradk(IcsFusedArgs a) {
@@ -262,7 +233,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     load_raw<C>(raw, rs_in, 4 * ((a.g.ay + TORG + tyi * C::TH - C::PAD) * pitch + 3 * (a.g.ax + TORG + txi * C::TW - C::PAD)), tid, pitch);
   }
   __syncthreads();   // LDS initialised
-  constexpr int MATES = 2;                                                      // workgroups per CU
+  constexpr int MATES = C::MATES;
   const int team = (int)gridDim.x >= MATES ? (int)blockIdx.x / ((int)gridDim.x / MATES) % MATES : 0;
 
 #pragma unroll 1
@@ -420,9 +391,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
       for (int t = 0; t < 4; ++t)
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-          const float x = acc[t][r] * s_e;
-          const _Float16 xh = (_Float16)x;
-          const _Float16 xl = (_Float16)(x - (float)xh);
+          _Float16 xh, xl;
+          split_f16(acc[t][r] * s_e, xh, xl);
           const uint32_t P = (uint32_t)__builtin_bit_cast(unsigned short, xh) | ((uint32_t)__builtin_bit_cast(unsigned short, xl) << 16);
           const uint32_t Q = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)P, 0xB1, 0xF, 0xF, true);   // quad_perm [1,0,3,2]
           // even column: hi dword = (own hi, neighbour hi); odd column: lo dword = (neighbour lo, own lo)
@@ -577,14 +547,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     conv_phase(std::integral_constant<int, 0>{});
     float s_e, inv_e, me;
 
-#define ICS_FUSED_CHANNEL(CH)                                                                                           \
-    me = residual(CH);                                                                                                  \
-    if (lane == 0) fscr[8 + 4 * (CH) + wv] = me;                                                                        \
-    lds_barrier();     /* tile maximum; every wave is past the previous gradient phase: e' planes and u buffer free */  \
-    me = __builtin_fmaxf(__builtin_fmaxf(fscr[8 + 4 * (CH)], fscr[9 + 4 * (CH)]), __builtin_fmaxf(fscr[10 + 4 * (CH)], fscr[11 + 4 * (CH)])); \
-    pow2_scale(__builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, me))), s_e, inv_e);      \
-    write_e(s_e);
-
     ICS_FUSED_CHANNEL(0)
     convert_channel<C, 1>(raw, s_x, up + 2 * C::PLANE, opaque(tid));
     lds_barrier();                                                     // e'(0) and planes(1) visible
@@ -614,35 +576,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     lds_barrier();                                                     // e'(2) visible
     ics_prio_turn(FUSED_SLICE, team, MATES);
     gradk_phase(std::integral_constant<int, 2>{}, inv_x * inv_e);
-#undef ICS_FUSED_CHANNEL
   }
 
-  // ---- cross-wave reduction (fixed order) and partial write, one channel per pass ------------------------------------
-  float* red = reinterpret_cast<float*>(lds);   // [wave][256]: element (row = 4*lg + r, col = li) at [r*64 + lane]; then [wave][64] carries
-  float* dst = a.partial + (size_t)blockIdx.x * (3 * 16 * 16);
-#pragma unroll
-  for (int c = 0; c < 3; ++c) {
-    __syncthreads();
-#pragma unroll
-    for (int r = 0; r < 4; ++r) red[wv * 256 + r * 64 + lane] = tot[c][r];
-    red[C::NW * 256 + wv * 64 + lane] = carry[c];
-    __syncthreads();
-    {
-      const int v = tid;
-      float s = red[v];
-#pragma unroll
-      for (int w = 1; w < C::NW; ++w) s += red[w * 256 + v];   // fixed order -> deterministic
-      const int l = v & 63, r = (v >> 6) & 3;
-      if (r == 3 && l < 48) {                                   // tap row 4 lg + 3 also receives row 0 of the lane group above
-#pragma unroll
-        for (int w = 0; w < C::NW; ++w) s += red[C::NW * 256 + w * 64 + l + 16];
-      }
-      const int ta = 4 * (l >> 4) + r, tb = l & 15;
-      dst[(c * 16 + ta) * 16 + tb] = s;
-    }
-  }
+  ICS_FUSED_WRITE_PARTIAL()
 }
-
 
 // =====================================================================================================================
 // 32-row tiles, THREE workgroups per CU (round 3).  Same arithmetic as k_synth_gradk above, different shape:
@@ -658,78 +595,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 // What motivates it, measured on the 64-row kernel at 4096^2, K = 15: without any MFMA the kernel still takes 0.177 of its 0.265 ms -- a wave issues 6.2 k instructions per tile (25 k cycles of its 59 k) and
 // stalls for the rest; two waves per SIMD leave that unhidden.
 // =====================================================================================================================
-template <int K>
-struct FCfg2 {
-  static constexpr int PAD = K / 2;
-  static constexpr int TH = 32, TW = 64;
-  static constexpr int NW = 4, NT = 64 * NW;
-  static constexpr int LROWS = TH + K - 1;
-  static constexpr int LCOLS = TW + 16;
-  static constexpr int ROWB = 2 * LCOLS;                                   // 160
-  static constexpr int cls_rows(int c) { return (LROWS - c + 1) / 2; }
-  static constexpr int cls1_off() {
-    int off = cls_rows(0) * ROWB;
-    while (off % 256 != 128) off += 16;
-    return off;
-  }
-  static constexpr int OFF1 = cls1_off();
-  static constexpr int cls_off(int c) { return c == 0 ? 0 : OFF1; }
-  static constexpr int PLANE = ((OFF1 + cls_rows(1) * ROWB + 32 + 15) / 16) * 16;   // + 32: the third chunk over-reads a row
-  static constexpr int UOFF = 0;
-  static constexpr int EROWB = 4 * LCOLS;                                  // 320
-  static constexpr int EOFF = 4 * PLANE;
-  static constexpr int EBYTES = TH * EROWB + 64;
-  static constexpr int SCR = EOFF + EBYTES;
-  static constexpr int WROWB = (2 * (K + 17) + 3) & ~3;
-  static constexpr int WZERO = (K + 7) / 2;
-  static constexpr int WLDS = 3 * K * 2 * WROWB;
-  static constexpr int WOFF = SCR + 256;
-  static constexpr size_t LDS_BYTES = WOFF + WLDS;
-  static constexpr int NQ = K + 1;
-  static constexpr int XG = LCOLS / 4;
-  static constexpr int NTASK = LROWS * XG;
-  static constexpr int NIT = (NTASK + NT - 1) / NT;
-  static_assert(K >= 3 && K <= 15 && (K & 1), "one 32-wide MFMA window per column block, one 16-tap block");
-  static_assert(3 * LDS_BYTES <= 160 * 1024, "three workgroups per CU");
-};
-
-template <typename C>
-__device__ __forceinline__ void load_raw2(f32x4u (&v)[C::NIT][3], __amdgpu_buffer_rsrc_t rs, int soff, int tid, int pitch) {
-#pragma unroll
-  for (int k = 0; k < C::NIT; ++k) {
-    int t = tid + k * C::NT;
-    t = t < C::NTASK ? t : C::NTASK - 1;
-    const int row = t / C::XG, xg = t - row * C::XG;
-    const int toff = 4 * (row * pitch + 12 * xg);
-#pragma unroll
-    for (int h = 0; h < 3; ++h) v[k][h] = __builtin_bit_cast(f32x4u, __builtin_amdgcn_raw_buffer_load_b128(rs, toff + 16 * h, soff, 0));
-  }
-}
-
-// one channel of the staged rows -> (hi, lo) fp16 planes, rows grouped by y mod 2
-template <typename C, int CH>
-__device__ __forceinline__ void convert_channel2(const f32x4u (&raw)[C::NIT][3], float s_x, unsigned char* plane, int tid) {
-#pragma unroll
-  for (int k = 0; k < C::NIT; ++k) {
-    const int t = tid + k * C::NT;
-    if (t < C::NTASK) {
-      const int row = t / C::XG, xg = t - row * C::XG;
-      unsigned char* dst = plane + ((row & 1) ? C::OFF1 : 0) + (row >> 1) * C::ROWB + 8 * xg;
-      h4 hi, lo;
-#pragma unroll
-      for (int p = 0; p < 4; ++p) {
-        const int idx = 3 * p + CH;
-        const float x = raw[k][idx >> 2][idx & 3] * s_x;
-        const _Float16 xh = (_Float16)x;
-        hi[p] = xh;
-        lo[p] = (_Float16)(x - (float)xh);
-      }
-      *reinterpret_cast<h4*>(dst) = hi;
-      *reinterpret_cast<h4*>(dst + C::PLANE) = lo;
-    }
-  }
-}
-
 template <int K, bool ACC>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) void k_synth_gradk2(IcsFusedArgs a) {
   using C = FCfg2<K>;
@@ -777,7 +642,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
   f32x4u raw[C::NIT][3];
   if (tile < band1) {
     const int tyi = tile / tpr, txi = tile - tyi * tpr;
-    load_raw2<C>(raw, rs_in, 4 * ((a.g.ay + TORG + tyi * C::TH - C::PAD) * pitch + 3 * (a.g.ax + TORG + txi * C::TW - C::PAD)), tid, pitch);
+    load_raw<C>(raw, rs_in, 4 * ((a.g.ay + TORG + tyi * C::TH - C::PAD) * pitch + 3 * (a.g.ax + TORG + txi * C::TW - C::PAD)), tid, pitch);
   }
   {
     u4* z = reinterpret_cast<u4*>(lds);
@@ -924,9 +789,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
       for (int t = 0; t < 2; ++t)
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-          const float x = acc[t][r] * s_e;
-          const _Float16 xh = (_Float16)x;
-          const _Float16 xl = (_Float16)(x - (float)xh);
+          _Float16 xh, xl;
+          split_f16(acc[t][r] * s_e, xh, xl);
           const uint32_t P = (uint32_t)__builtin_bit_cast(unsigned short, xh) | ((uint32_t)__builtin_bit_cast(unsigned short, xl) << 16);
           const uint32_t Q = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)P, 0xB1, 0xF, 0xF, true);   // quad_perm [1,0,3,2]
           const uint32_t w = odd ? ((Q >> 16) | (P & 0xFFFF0000u)) : ((P & 0xFFFFu) | (Q << 16));
@@ -1015,29 +879,21 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
 
     // ================================ the tile ======================================================================
     unsigned char* const up = lds + C::UOFF;
-    convert_channel2<C, 0>(raw, s_x, up, opaque(tid));
+    convert_channel<C, 0>(raw, s_x, up, opaque(tid));
     lds_barrier();                                                     // planes of channel 0 visible
     load_img(0);
     conv_phase(std::integral_constant<int, 0>{});
     float s_e, inv_e, me;
 
-#define ICS_FUSED2_CHANNEL(CH)                                                                                          \
-    me = residual(CH);                                                                                                  \
-    if (lane == 0) fscr[8 + 4 * (CH) + wv] = me;                                                                        \
-    lds_barrier();     /* tile maximum; every wave is past the previous gradient phase: e' planes and u buffer free */  \
-    me = __builtin_fmaxf(__builtin_fmaxf(fscr[8 + 4 * (CH)], fscr[9 + 4 * (CH)]), __builtin_fmaxf(fscr[10 + 4 * (CH)], fscr[11 + 4 * (CH)])); \
-    pow2_scale(__builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, me))), s_e, inv_e);      \
-    write_e(s_e);
-
-    ICS_FUSED2_CHANNEL(0)
-    convert_channel2<C, 1>(raw, s_x, up + 2 * C::PLANE, opaque(tid));
+    ICS_FUSED_CHANNEL(0)
+    convert_channel<C, 1>(raw, s_x, up + 2 * C::PLANE, opaque(tid));
     lds_barrier();                                                     // e'(0) and planes(1) visible
     gradk_phase(std::integral_constant<int, 0>{}, inv_x * inv_e);
     load_img(1);
     conv_phase(std::integral_constant<int, 1>{});
 
-    ICS_FUSED2_CHANNEL(1)
-    convert_channel2<C, 2>(raw, s_x, up, opaque(tid));
+    ICS_FUSED_CHANNEL(1)
+    convert_channel<C, 2>(raw, s_x, up, opaque(tid));
     lds_barrier();                                                     // e'(1) and planes(2) visible
     gradk_phase(std::integral_constant<int, 1>{}, inv_x * inv_e);
     load_img(2);
@@ -1047,70 +903,51 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
       if (tile + nx < band1) {
         const int nt = tile + nx;
         const int nyi = nt / tpr, nxi = nt - nyi * tpr;
-        load_raw2<C>(raw, rs_in, 4 * ((a.g.ay + TORG + nyi * C::TH - C::PAD) * pitch + 3 * (a.g.ax + TORG + nxi * C::TW - C::PAD)), opaque(tid), pitch);
+        load_raw<C>(raw, rs_in, 4 * ((a.g.ay + TORG + nyi * C::TH - C::PAD) * pitch + 3 * (a.g.ax + TORG + nxi * C::TW - C::PAD)), opaque(tid), pitch);
       }
     };
     conv_phase(std::integral_constant<int, 2>{});
 
-    ICS_FUSED2_CHANNEL(2)
+    ICS_FUSED_CHANNEL(2)
     lds_barrier();                                                     // e'(2) visible
     gradk_phase(std::integral_constant<int, 2>{}, inv_x * inv_e);
     prefetch();
-#undef ICS_FUSED2_CHANNEL
   }
 
-  // ---- cross-wave reduction (fixed order) and partial write, one channel per pass: as k_synth_gradk -------------------------
-  float* red = reinterpret_cast<float*>(lds);
-  float* dst = a.partial + (size_t)blockIdx.x * (3 * 16 * 16);
-#pragma unroll
-  for (int c = 0; c < 3; ++c) {
-    __syncthreads();
-#pragma unroll
-    for (int r = 0; r < 4; ++r) red[wv * 256 + r * 64 + lane] = tot[c][r];
-    red[C::NW * 256 + wv * 64 + lane] = carry[c];
-    __syncthreads();
-    {
-      const int v = tid;
-      float s = red[v];
-#pragma unroll
-      for (int w = 1; w < C::NW; ++w) s += red[w * 256 + v];
-      const int l = v & 63, r = (v >> 6) & 3;
-      if (r == 3 && l < 48) {
-#pragma unroll
-        for (int w = 0; w < C::NW; ++w) s += red[C::NW * 256 + w * 64 + l + 16];
-      }
-      const int ta = 4 * (l >> 4) + r, tb = l & 15;
-      dst[(c * 16 + ta) * 16 + tb] = s;
-    }
-  }
-
+  ICS_FUSED_WRITE_PARTIAL()
 }
+#undef ICS_FUSED_CHANNEL
+#undef ICS_FUSED_WRITE_PARTIAL
 
-template <int K>
-hipError_t launch_k(const IcsFusedArgs& a, int nblocks, hipStream_t s) {
-  const int dev = ics_current_device();
-  const bool ACC = a.facc != nullptr;
-  if (a.rs == 2) {   // 32-row tiles, three workgroups per CU
-    using C = FCfg2<K>;
-    static std::atomic<bool> configured[2][ICS_MAX_DEVICES];
-    auto kern = ACC ? k_synth_gradk2<K, true> : k_synth_gradk2<K, false>;
-    if (hipError_t e = ics_configure_lds(configured[ACC ? 1 : 0], dev, kern, C::LDS_BYTES); e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, dim3(nblocks), dim3(C::NT), C::LDS_BYTES, s, a);
-    return hipGetLastError();
-  }
-  using C = FCfg<K>;
-  static std::atomic<bool> configured[2][ICS_MAX_DEVICES];
-  auto kern = ACC ? k_synth_gradk<K, true> : k_synth_gradk<K, false>;
-  if (hipError_t e = ics_configure_lds(configured[ACC ? 1 : 0], dev, kern, C::LDS_BYTES); e != hipSuccess) return e;
-  // every workgroup of the grid writes its partial block (the reduction reads `nblocks` of them): workgroups without a tile
-  // write zeros
+// every workgroup of the grid writes its partial block (the reduction reads `nblocks` of them): workgroups without a tile write zeros
+template <typename C, typename KERN>
+hipError_t launch_kernel(KERN kern, std::atomic<bool>* configured, const IcsFusedArgs& a, int nblocks, hipStream_t s) {
+  if (hipError_t e = ics_configure_lds(configured, ics_current_device(), kern, C::LDS_BYTES); e != hipSuccess) return e;
   hipLaunchKernelGGL(kern, dim3(nblocks), dim3(C::NT), C::LDS_BYTES, s, a);
   return hipGetLastError();
+}
+template <int K>
+hipError_t launch_k(const IcsFusedArgs& a, int nblocks, hipStream_t s) {
+  static std::atomic<bool> configured[4][ICS_MAX_DEVICES];   // per kernel and device
+  if (a.rs == 2) return a.facc ? launch_kernel<FCfg2<K>>(k_synth_gradk2<K, true>, configured[0], a, nblocks, s) : launch_kernel<FCfg2<K>>(k_synth_gradk2<K, false>, configured[1], a, nblocks, s);
+  return a.facc ? launch_kernel<FCfg<K>>(k_synth_gradk<K, true>, configured[2], a, nblocks, s) : launch_kernel<FCfg<K>>(k_synth_gradk<K, false>, configured[3], a, nblocks, s);
 }
 
 }  // namespace
 
 bool ics_synth_gradk_supported(int K) { return K >= 3 && K <= 15 && (K & 1); }
+
+// Tile height and grid: 32-row tiles with three workgroups per CU (k_synth_gradk2, rs = 2) or 64-row tiles with two (k_synth_gradk, rs = 4);
+// debug switch fused_rs.  Measured on MI355X (blind, ms per inner iteration, 64-row -> 32-row form): 255^2 (deblur_module's blind window:
+// 16 tiles of 64 x 64 on 256 CUs) 0.1095 -> 0.0985, 1024^2 0.1415 -> 0.1316, 2048^2 0.275 -> 0.266; 4096^2 level (NOTES_r03.md 4c).  Hence
+// 32-row tiles up to 2500 tiles of 64 x 64 (~3200^2), 64-row tiles above.  blocks64 / blocks32: the persistent workgroups of either form
+// (two / three per CU); the 32-row grid is clamped to its tiles.
+void ics_synth_gradk_plan(const IcsGeom& g, int blocks64, int blocks32, int* rs, int* nblocks) {
+  const int frs = ics_debug().fused_rs.load(std::memory_order_relaxed);
+  *rs = frs == 2 || frs == 4 ? frs : ((long)g.tiles_x * g.tiles_y <= 2500 ? 2 : 4);
+  const int tiles32 = ((g.N + 63) / 64) * ((g.M + 31) / 32);
+  *nblocks = *rs == 2 ? (blocks32 < tiles32 ? blocks32 : tiles32) : blocks64;
+}
 
 hipError_t ics_launch_synth_gradk(const IcsFusedArgs& a, int nblocks, hipStream_t s) {
   if (!a.bt) return hipErrorInvalidValue;

@@ -95,6 +95,47 @@ def test_matrix_core_convolution_both_tile_heights(MK, rs, debug_switch):
     assert np.all(np.abs(red[:3].astype(np.int64) - red2[:3].astype(np.int64)) < 64)   # max |g|: per-tile scales differ in the last bits
 
 
+# (PSF size, conv_rs) -> tile rows of the matrix-core convolution on a 200 x 190 frame, as csrc/ics_conv_mfma.hip states its rule (0 = the
+# launcher decides): 16-row tiles up to K = 15 where the frame has fewer 32-row tiles than the device has compute units (here 3 x 7; the
+# u-frame of the back-projection 4 x 7) or conv_rs = 1; else 32 rows for K = 15 .. 21 and for K <= 13 up to 3000 tiles of 64 x 64
+# (conv_rs = 2 / 4 forces either height there); 64 rows with the 8-wave split from K = 23.  Every conv_rs that selects a kernel built
+# for the size.
+TILE_ROWS = {(9, 0): 16, (9, 1): 16, (9, 2): 32, (9, 4): 64, (15, 0): 16, (15, 1): 16, (15, 2): 32, (17, 0): 32, (17, 2): 32, (23, 0): 64, (23, 4): 64}
+
+
+@pytest.mark.parametrize("MK,rs", sorted(TILE_ROWS))
+def test_tile_height_rule_and_accumulator_image_agree(MK, rs, debug_switch):
+    """The synthesis reads the image in accumulator order (ics_image_acc.h) in the layout of the tile height its launcher picks, and the
+    route says so exactly when such a copy is read: 32- or 64-row tiles below the 8-wave sizes (K < 23).  Both come from one rule
+    (csrc/ics_conv_mfma.hip); pinned at the PSF sizes on each side of its boundaries: the result equals, bit for bit, the run whose
+    epilogue reads the HWC image (planar_image = 0), and ics_rl_describe reports the copy for exactly those tile forms."""
+    from lib import _native as nv
+    M, N = 200, 190
+    ctx = nv.Context.get(0)
+    assert ctx.compute_units > 32, "the frame is meant to have fewer 32-row tiles than compute units"
+    case = orc.synth_case(M, N, MK, seed=MK, blind=False)
+    debug_switch("conv_rs", rs)
+    out = []
+    for planar in (1, 0):
+        debug_switch("planar_image", planar)
+        job = nv.RLJob(M, N, MK)
+        try:
+            job.upload(case["image"], case["u0"], case["psf0"])
+            p = job.params(10, 180, 20, 170, 1e9, 1, 1e-3, 10000.0, blind=False, conv=2)
+            route = job.describe(p)
+            assert route.conv_family == 1                       # matrix cores
+            st = job.run(p)
+            u, psf, psfc = job.download()
+            out.append((route.image_in_accumulator_order, u, psf, psfc, np.array([st.M_r, st.Hu, st.varu, st.dof_min, st.dof_max], np.float32)))
+        finally:
+            job.close()
+    rows = TILE_ROWS[(MK, rs)]
+    assert out[0][0] == (1 if rows in (32, 64) and MK < 23 else 0), (MK, rs, rows, out[0][0])
+    assert out[1][0] == 0
+    for a, b in zip(out[0][1:], out[1][1:]):
+        assert np.array_equal(a, b, equal_nan=True)
+
+
 # conv: 0 = ICS_CONV_AUTO, 1 = fp32 products (vector convolutions, fp32-MFMA gradient), 2 = matrix-core kernels
 @pytest.mark.parametrize("M,N,MK,blind,conv", [(64, 64, 15, False, 0), (65, 191, 15, False, 0), (130, 67, 9, True, 0), (257, 300, 15, True, 0),
                                                (40, 50, 31, False, 0), (100, 90, 45, True, 0), (80, 120, 63, True, 0), (70, 70, 21, True, 0),
