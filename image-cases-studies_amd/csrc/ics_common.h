@@ -102,7 +102,6 @@ struct IcsDebug {
   std::atomic<int> conv_rs;           // ICS_TEST_CONV_RS      0 launcher decides, 2 / 4 = force 32- / 64-row tiles where both are built
   std::atomic<int> conv_path;         // ICS_CONV_PATH         what ICS_CONV_AUTO resolves to: 0 default, 1 vector, 2 matrix, 3 fft (transform tiles, ics_conv_fft.hip)
   std::atomic<int> fused_gradk;       // ICS_FUSED_GRADK       0 = two-kernel A11 + A13 (like ICS_FLAG_NO_FUSED_GRADK)
-  std::atomic<int> update_wg_per_cu;  // ICS_UPDATE_WG_PER_CU  0 launcher decides
   std::atomic<int> update_kernel;     // ICS_UPDATE_KERNEL     0 = the pixel-group kernel everywhere
   std::atomic<int> fused_rs;          // ICS_FUSED_RS          0 launcher decides, 2 / 4 = tile height of the fused A11 + A13 kernel
   std::atomic<int> planar_image;      // ICS_PLANAR_IMAGE      0 = epilogues read the HWC image frame (no accumulator-order copy)
@@ -128,7 +127,6 @@ struct IcsDebug {
     const char* cp = getenv("ICS_CONV_PATH");
     conv_path = !cp ? 0 : (cp[0] == 'v' ? 1 : (cp[0] == 'm' ? 2 : (cp[0] == 'f' ? 3 : 0)));
     fused_gradk = env_int("ICS_FUSED_GRADK", 1);
-    update_wg_per_cu = env_int("ICS_UPDATE_WG_PER_CU", 0);
     update_kernel = env_int("ICS_UPDATE_KERNEL", 1);
     fused_rs = env_int("ICS_FUSED_RS", 0);
     planar_image = env_int("ICS_PLANAR_IMAGE", 1);
@@ -170,16 +168,10 @@ __host__ __device__ static inline float ics_key2f(uint32_t k) {
   v.u = (k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k;
   return v.f;
 }
-
-// The ratio of the DoF mask, (g - f)/(g + f)  (lib/deconvolution.pyx:499; g = raw back-projection, f = image), IEEE in every
-// case but one: g == f == 0 EXACTLY gives 1, not 0/0 = NaN.  Where image and u are exactly black the reference's g is the rounding
-// noise of its complex64 FFT (~1e-10, either sign) and (g - 0)/(g + 0) == 1 for every non-zero g, so the reference returns a
-// finite picture on frames with black bands; this library's convolutions return exact zeros there, and a single NaN would spread
-// over the whole frame through the next convolution and the NaN-propagating maxima.  g + f == 0 with g != 0 stays +-inf as in
-// the reference.  Contract and measurements: include/ics_hip.h ("DoF ratio"), tests/test_gpu_black.py.
-__device__ __forceinline__ float ics_dof_ratio(float g, float f) {
-  const float d = __fdiv_rn(__fsub_rn(g, f), __fadd_rn(g, f));
-  return (g == 0.f && f == 0.f) ? 1.0f : d;
+// ... with every NaN as the canonical +NaN, the largest key a float has: it propagates through an integer max like np.amax
+__host__ __device__ __forceinline__ uint32_t ics_key_of(float f) {
+  if (f != f) return 0xFFC00000u;
+  return ics_f2key(f);
 }
 
 // Persistent tile walks (ics_conv_mfma.hip, ics_synth_gradk_mfma.hip): workgroup b runs on XCD b % nb and walks the band of tiles
@@ -230,6 +222,18 @@ __device__ __forceinline__ uint32_t ics_wave_max_u32(uint32_t v) {
   const uint32_t r2 = (uint32_t)__builtin_amdgcn_readlane((int)v, 32), r3 = (uint32_t)__builtin_amdgcn_readlane((int)v, 48);
   const uint32_t a = r0 > r1 ? r0 : r1, b = r2 > r3 ? r2 : r3;
   return a > b ? a : b;
+}
+
+// The shuffle form (__shfl_xor = ds_bpermute) of the wave-wide integer maximum / minimum: the kernels outside the persistent tile loops
+__device__ __forceinline__ uint32_t ics_shfl_max_u32(uint32_t v) {
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) { uint32_t o = (uint32_t)__shfl_xor((int)v, off, 64); v = v > o ? v : o; }
+  return v;
+}
+__device__ __forceinline__ uint32_t ics_shfl_min_u32(uint32_t v) {
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) { uint32_t o = (uint32_t)__shfl_xor((int)v, off, 64); v = v < o ? v : o; }
+  return v;
 }
 
 // Reduction slots written by the back-projection kernel (one set per inner iteration).

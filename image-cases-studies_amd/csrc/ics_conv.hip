@@ -26,6 +26,7 @@
 // formulation needed for MFMA would waste >= 50 % of the matrix pipe on the Toeplitz band
 // (DESIGN.md), so this path is VALU by design.
 #include "ics_common.h"
+#include "ics_update.h"
 
 namespace {
 
@@ -53,21 +54,6 @@ struct ConvCfg {
 typedef float f32x4u __attribute__((ext_vector_type(4), aligned(4)));
 
 typedef float f32x2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) {
-    uint32_t o = (uint32_t)__shfl_xor((int)v, off, 64);
-    v = v > o ? v : o;
-  }
-  return v;
-}
-
-__device__ __forceinline__ uint32_t key_of(float f) {
-  // canonical positive NaN so that a NaN propagates through the integer max like np.amax does
-  if (f != f) return 0xFFC00000u;
-  return ics_f2key(f);
-}
 
 // LDS row (ap + 2*rp) -> strip registers of row pair rp (ds_read_b128, 16-B aligned by construction)
 template <typename C, int R>
@@ -167,12 +153,12 @@ __global__ __launch_bounds__(16 * NTY) __attribute__((amdgpu_waves_per_eu(WPE, W
     for (int c = 0; c < 3; ++c) {
       const float maxu = ics_key2f(a.red[ICS_RED_MAXU + c]);
       const float maxg = ics_key2f(a.red[ICS_RED_MAXG + c]);
-      dt[c] = __fdiv_rn(__fmul_rn(a.step, maxu), __fadd_rn(maxg, 1e-15f));
+      dt[c] = ics_step_dt(a.step, maxu, maxg);
       if (blockIdx.x == 0 && tid == 0) {
         a.scal[ICS_SC_DT + c] = dt[c]; a.scal[ICS_SC_MAXU + c] = maxu; a.scal[ICS_SC_MAXG + c] = maxg;
       }
     }
-    uint32_t kmin = 0xFFFFFFFFu, kmax = 0u, knan = 0u;
+    IcsDofKeys dof = ICS_DOF_NONE;
     const float lambd = a.lambd;
     const ptrdiff_t base = (ptrdiff_t)(y0 - C::PAD) * pitch + 3 * (x0 - C::PAD);
     constexpr int LW4 = C::LW_USED / 4;
@@ -210,18 +196,13 @@ __global__ __launch_bounds__(16 * NTY) __attribute__((amdgpu_waves_per_eu(WPE, W
             const int x = x0 - C::PAD + pxr;
             const float uo = pu[k][jj], to = pt[k][jj], go = pg[k][jj], fo = pf[k][jj];
             const float dtc = c == 0 ? dt[0] : (c == 1 ? dt[1] : dt[2]);
-            const float g = __fadd_rn(__fmul_rn(lambd, go), __fmul_rn(__fsub_rn(uo, to), 0.5f));
-            float un = __fsub_rn(uo, __fmul_rn(dtc, g));
+            const float g = ics_mm_g(lambd, go, uo, to);
+            float un = ics_step_u(uo, dtc, g);
             own[jj] = yown && (pxr >= C::PAD) && (pxr < C::PAD + C::TW) && (x < a.g.uN);
             if (yin && (x >= C::PAD) && (x < C::PAD + a.g.N)) {
-              const float d = ics_dof_ratio(go, fo);
-              float D = __fmul_rn(d, d);
-              if (!a.blind) D = __fdiv_rn(D, lambd);
-              un = __fadd_rn(__fmul_rn(__fsub_rn(1.0f, D), un), __fmul_rn(D, fo));
-              if (a.want_dof && own[jj]) {
-                if (D != D) knan = 1u;
-                else { const uint32_t kk = ics_f2key(D); kmin = kmin < kk ? kmin : kk; kmax = kmax > kk ? kmax : kk; }
-              }
+              const float D = ics_dof_mask(go, fo, lambd, a.blind);
+              un = ics_dof_blend(D, un, fo);
+              if (a.want_dof && own[jj]) ICS_DOF_NOTE(dof, D);
             }
             un4[jj] = un;
           }
@@ -238,6 +219,7 @@ __global__ __launch_bounds__(16 * NTY) __attribute__((amdgpu_waves_per_eu(WPE, W
       }
     }
     if (a.want_dof) {
+      uint32_t kmin = dof.kmin, kmax = dof.kmax, knan = dof.knan;
 #pragma unroll
       for (int off = 32; off >= 1; off >>= 1) {
         const uint32_t o1 = (uint32_t)__shfl_xor((int)kmin, off, 64); kmin = kmin < o1 ? kmin : o1;
@@ -357,9 +339,9 @@ __global__ __launch_bounds__(16 * NTY) __attribute__((amdgpu_waves_per_eu(WPE, W
             if (a.tv_kind >= 2)                                                                  // PAM: G = T + lambd*gradu
               g = (float)((double)a.tv[o + 3*p+c] + (double)__fmul_rn(lambd, acc[r][3*p+c]));
             else if (a.tv_kind == 1 && y >= 1 && y <= a.g.uM - 2 && xp + p >= 1 && xp + p <= a.g.uN - 2)   // active MM-TV, pyx:517
-              g = (float)(((double)a.tv[o + 3*p+c] + (double)__fmul_rn(lambd, acc[r][3*p+c])) + (double)__fsub_rn(uv[3*p+c], tv[3*p+c]) / 4.0);
+              g = ics_mm_g_tv(a.tv[o + 3*p+c], lambd, acc[r][3*p+c], uv[3*p+c], tv[3*p+c]);
             else
-              g = __fadd_rn(__fmul_rn(lambd, acc[r][3*p+c]), __fmul_rn(__fsub_rn(uv[3*p+c], tv[3*p+c]), 0.5f));
+              g = ics_mm_g(lambd, acc[r][3*p+c], uv[3*p+c], tv[3*p+c]);
             mg[c] = __builtin_fmaxf(mg[c], __builtin_fabsf(g));   // maxnum drops NaN: tracked separately
             mu[c] = __builtin_fmaxf(mu[c], uv[3*p+c]);
             nan_g[c] |= (g != g); nan_u[c] |= (uv[3*p+c] != uv[3*p+c]);
@@ -386,7 +368,7 @@ __global__ __launch_bounds__(16 * NTY) __attribute__((amdgpu_waves_per_eu(WPE, W
     for (int c = 0; c < 3; ++c) {
       kg[c] = nan_g[c] ? 0xFFC00000u : (any ? ics_f2key(mg[c]) : 0u);   // NaN propagates like np.amax
       ku[c] = nan_u[c] ? 0xFFC00000u : (any ? ics_f2key(mu[c]) : 0u);
-      kg[c] = wave_max_u32(kg[c]); ku[c] = wave_max_u32(ku[c]);
+      kg[c] = ics_shfl_max_u32(kg[c]); ku[c] = ics_shfl_max_u32(ku[c]);
     }
     __syncthreads();  // all waves are done reading the tile
     uint32_t* red_lds = reinterpret_cast<uint32_t*>(lds);

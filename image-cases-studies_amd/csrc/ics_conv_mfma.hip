@@ -49,6 +49,7 @@
 #include "ics_common.h"
 #include "ics_image_acc.h"
 #include "ics_mfma_tile.h"
+#include "ics_update.h"
 #include <stdlib.h>
 #include <type_traits>
 
@@ -718,9 +719,9 @@ __global__ __launch_bounds__(256 * NH) __attribute__((amdgpu_waves_per_eu(MCfg<K
                 if (TVOP && a.tv_kind >= 2)
                   g = (float)((double)Tv + (double)__fmul_rn(lambd, av[c]));
                 else if (TVOP && a.tv_kind == 1 && y >= 1 && y <= a.g.uM - 2 && colx >= 1 && colx <= a.g.uN - 2)
-                  g = (float)(((double)Tv + (double)__fmul_rn(lambd, av[c])) + (double)__fsub_rn(uv, tv) / 4.0);
+                  g = ics_mm_g_tv(Tv, lambd, av[c], uv, tv);
                 else
-                  g = __fadd_rn(__fmul_rn(lambd, av[c]), __fmul_rn(__fsub_rn(uv, tv), 0.5f));
+                  g = ics_mm_g(lambd, av[c], uv, tv);
                 const uint32_t gb = __float_as_uint(g) & 0x7FFFFFFFu, ub = __float_as_uint(uv) & 0x7FFFFFFFu;
                 mgb[c] = mgb[c] > gb ? mgb[c] : gb;
                 mub[c] = mub[c] > ub ? mub[c] : ub;

@@ -53,6 +53,7 @@
 #include "ics_common.h"
 #include "ics_kernels.h"
 #include "ics_fft_math.h"
+#include "ics_update.h"
 #include <algorithm>
 #include <cassert>
 
@@ -69,14 +70,8 @@ constexpr int ICS_FFT_MAX_K = 85;
 
 #if defined(__HIP_DEVICE_COMPILE__)
 #define ICS_FFT_UNIFORM(x) __builtin_amdgcn_readfirstlane(x)
-#define ICS_FSUB(a, b) __fsub_rn(a, b)
-#define ICS_FADD(a, b) __fadd_rn(a, b)
-#define ICS_FMUL(a, b) __fmul_rn(a, b)
-#else   /* host pass: the CPU emulation of tools/bench_conv_fft.hip (-ffp-contract=off: the same single roundings) */
+#else   /* host pass: the CPU emulation of tools/bench_conv_fft.hip (single roundings there too: ICS_FSUB etc. of ics_update.h) */
 #define ICS_FFT_UNIFORM(x) (x)
-#define ICS_FSUB(a, b) ((a) - (b))
-#define ICS_FADD(a, b) ((a) + (b))
-#define ICS_FMUL(a, b) ((a) * (b))
 #endif
 
 namespace icsfft {
@@ -573,9 +568,6 @@ ICS_FFT_HD void stage_g(v2f* lds, int tid) {
   for (int m = 0; m < 16; ++m) cp[8 * m * ICS_FFT_PITCH] = v[m];
 }
 
-// canonical positive NaN so that a NaN propagates through the integer max like np.amax does (ics_conv.hip)
-ICS_FFT_HD uint32_t key_of(float f) { return (f != f) ? 0xFFC00000u : ics_f2key(f); }
-
 // Epilogue (row-quad ownership): the arithmetic of ics_conv.hip on 4 consecutive pixels of a row at a time, operands and results as
 // dwordx4.  On gfx9 vmcnt counts loads and stores alike and retires them in order: a load issued behind a store waits out the store's round
 // trip to L2.  So within a unit every operand load is issued before the first store: mode 0 requests the image quads of both tiles before
@@ -755,7 +747,7 @@ ICS_FFT_HD void maxima_quad(const IcsFftArgs& a, const Unit& u, int tid, int t, 
     float g;
     if (TV && a.c.tv_kind >= 2) { g = (float)((double)tv + (double)ICS_FMUL(lambd, rv)); r[e] = g; }     // PAM: G = T + lambd*gradu, stored (o.b holds T)
     else
-      g = ICS_FADD(ICS_FMUL(lambd, rv), ICS_FMUL(ICS_FSUB(uv, tv), 0.5f));                                          // pyx:519
+      g = ics_mm_g(lambd, rv, uv, tv);
     if (edge) {                                        // (wave-uniform) first / last tile of a tile row: per-pixel column test
       const bool ok = row_ok && X >= a.ox0 && X < a.ox1;
       qg = __builtin_elementwise_max(qg, ok ? (fbits(g) & 0x7FFFFFFFu) : 0u);

@@ -3,6 +3,7 @@
 
 #include "ics_kernels.h"
 #include "ics_tv.h"
+#include "ics_update.h"
 
 namespace {
 
@@ -15,32 +16,8 @@ constexpr int ICS_TVMM_SEG = 8;
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
-__device__ __forceinline__ uint32_t key_of(float f) {
-  if (f != f) return 0xFFC00000u;  // canonical +NaN: propagates through an integer max like np.amax
-  return ics_f2key(f);
-}
-__device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) { uint32_t o = (uint32_t)__shfl_xor((int)v, off, 64); v = v > o ? v : o; }
-  return v;
-}
-__device__ __forceinline__ uint32_t wave_min_u32(uint32_t v) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) { uint32_t o = (uint32_t)__shfl_xor((int)v, off, 64); v = v < o ? v : o; }
-  return v;
-}
-
-// =================================================================================================
-// A5 + A6 + A8 + A10 (lib/deconvolution.pyx:499-552), one pass over the u-frame.
-//   DoF   = ((gradu - image)/(gradu + image))^2 [ / lambd when non-blind ]      (:499-502, interior)
-//   g     = lambd*gradu + (u - ut)/2.                                           (:519, else-branch)
-//   dt_k  = step*(max u_k + 0)/(max|g_k| + 1e-15)                               (:524, 1/(M*N) == 0)
-//   u    -= dt_k * g                                                            (:531)
-//   u     = (1 - DoF)*u + DoF*image   on the interior                           (:552)
-// A9 (:534-549) subtracts exactly zero from `image` and is therefore omitted.
-// Every operation is rounded separately (__f*_rn) like the reference's C / numpy float32 code.
-// Memory-bound: 4 frame reads + 1 write (60 B/px), dwordx4 on the flattened x*3+c axis.
-// =================================================================================================
+// A5 + A6 + A8 + A10 (the arithmetic: ics_update.h), one thread = 4 pixels of a row.  Memory-bound: 4 frame reads + 1 write (60 B/px),
+// dwordx4 on the flattened x*3+c axis.  Launched only under the debug switch update_kernel = 0 (tests/test_gpu_black.py).
 __global__ __launch_bounds__(256) void k_update(IcsUpdateArgs a) {
   const IcsGeom& G = a.geo;
   const int ngx = G.tiles_x * 16;  // groups of 4 px per row
@@ -50,7 +27,7 @@ __global__ __launch_bounds__(256) void k_update(IcsUpdateArgs a) {
   for (int c = 0; c < 3; ++c) {
     const float maxu = ics_key2f(a.red[ICS_RED_MAXU + c]);
     const float maxg = ics_key2f(a.red[ICS_RED_MAXG + c]);
-    dt[c] = __fdiv_rn(__fmul_rn(a.step, maxu), __fadd_rn(maxg, 1e-15f));
+    dt[c] = ics_step_dt(a.step, maxu, maxg);
     if (blockIdx.x == 0 && threadIdx.x == 0) {
       a.scal[ICS_SC_DT + c] = dt[c]; a.scal[ICS_SC_MAXU + c] = maxu; a.scal[ICS_SC_MAXG + c] = maxg;
     }
@@ -59,9 +36,9 @@ __global__ __launch_bounds__(256) void k_update(IcsUpdateArgs a) {
   if (a.tv_kind == 1) {  // pyx:548: dt = step*(max image_k + 0)/(max|gradu_k| + 1e-15) with gradu = T
 #pragma unroll
     for (int c = 0; c < 3; ++c)
-      dt2[c] = __fdiv_rn(__fmul_rn(a.step, ics_key2f(a.red[ICS_RED_MAXF + c])), __fadd_rn(ics_key2f(a.red[ICS_RED_MAXT + c]), 1e-15f));
+      dt2[c] = ICS_STEP_DT(a.step, ics_key2f(a.red[ICS_RED_MAXF + c]), ics_key2f(a.red[ICS_RED_MAXT + c]));
   }
-  uint32_t kmin = 0xFFFFFFFFu, kmax = 0u, knan = 0u;
+  IcsDofKeys dof = ICS_DOF_NONE;
   const float lambd = a.lambd;
   for (long gid = (long)blockIdx.x * 256 + threadIdx.x; gid < total; gid += (long)gridDim.x * 256) {
     const int y = (int)(gid / ngx);
@@ -93,23 +70,18 @@ __global__ __launch_bounds__(256) void k_update(IcsUpdateArgs a) {
         if (a.tv_kind >= 2)                                                    // PAM: the back-projection pass wrote G = T + lambd*gradu
           g = gv[i];
         else if (a.tv_kind == 1 && y >= 1 && y <= G.uM - 2 && x >= 1 && x <= G.uN - 2)   // pyx:517 (TV_ut_L1 != 0 and TV_u_L1 != 0)
-          g = (float)(((double)Tv[i] + (double)__fmul_rn(lambd, gv[i])) + (double)__fsub_rn(uv[i], tv[i]) / 4.0);
+          g = ics_mm_g_tv(Tv[i], lambd, gv[i], uv[i], tv[i]);
         else
-          g = __fadd_rn(__fmul_rn(lambd, gv[i]), __fmul_rn(__fsub_rn(uv[i], tv[i]), 0.5f));
-        float un = __fsub_rn(uv[i], __fmul_rn(dt[c], g));
+          g = ics_mm_g(lambd, gv[i], uv[i], tv[i]);
+        float un = ics_step_u(uv[i], dt[c], g);
         if (inside && a.tv_kind < 2) {   // (PAM has no DoF blend)
-          const float d = ics_dof_ratio(gv[i], fv[i]);
-          float D = __fmul_rn(d, d);
-          if (!a.blind) D = __fdiv_rn(D, lambd);
+          const float D = ics_dof_mask(gv[i], fv[i], lambd, a.blind);
           if (a.tv_kind == 1) {  // pyx:549: image -= dt*gradu/lambd, then the blend uses the updated image
             fv[i] = __fsub_rn(fv[i], __fdiv_rn(__fmul_rn(dt2[c], Tv[i]), lambd));
             a.f_rw[o + i] = fv[i];
           }
-          un = __fadd_rn(__fmul_rn(__fsub_rn(1.0f, D), un), __fmul_rn(D, fv[i]));
-          if (a.want_dof) {
-            if (D != D) knan = 1u;
-            else { const uint32_t k = ics_f2key(D); kmin = kmin < k ? kmin : k; kmax = kmax > k ? kmax : k; }
-          }
+          un = ics_dof_blend(D, un, fv[i]);
+          if (a.want_dof) ICS_DOF_NOTE(dof, D);
         }
         uv[i] = un;
       }
@@ -127,7 +99,7 @@ __global__ __launch_bounds__(256) void k_update(IcsUpdateArgs a) {
     }
   }
   if (a.want_dof) {  // wave shuffle -> one atomic per wave (grid is capped, so a few thousand atomics)
-    kmin = wave_min_u32(kmin); kmax = wave_max_u32(kmax); knan = wave_max_u32(knan);
+    const uint32_t kmin = ics_shfl_min_u32(dof.kmin), kmax = ics_shfl_max_u32(dof.kmax), knan = ics_shfl_max_u32(dof.knan);
     if ((threadIdx.x & 63) == 0) {
       atomicMin(a.dofkeys + 0, kmin); atomicMax(a.dofkeys + 1, kmax);
       if (knan) atomicOr(a.dofkeys + 2, 1u);
@@ -319,7 +291,7 @@ __global__ __launch_bounds__(256) void k_tvterm(IcsTvTermArgs a, int seg_fast) {
   for (int c = 0; c < 3; ++c) {
     uint32_t kt = nan_t[c] ? 0xFFC00000u : ics_f2key(mt[c]);
     uint32_t kf = nan_f[c] ? 0xFFC00000u : (any_f ? ics_f2key(mf[c]) : 0u);
-    kt = wave_max_u32(kt); kf = wave_max_u32(kf);
+    kt = ics_shfl_max_u32(kt); kf = ics_shfl_max_u32(kf);
     if ((threadIdx.x & 63) == 0) { shk[threadIdx.x >> 6][c] = kt; shk[threadIdx.x >> 6][3 + c] = kf; }
   }
   __syncthreads();
@@ -449,7 +421,7 @@ __global__ __launch_bounds__(256) void k_tvterm_pam(IcsTvTermArgs a, int TVSEG /
 #pragma unroll
   for (int c = 0; c < 3; ++c) {
     uint32_t kt = nan_t[c] ? 0xFFC00000u : ics_f2key(mt[c]);
-    kt = wave_max_u32(kt);
+    kt = ics_shfl_max_u32(kt);
     if ((threadIdx.x & 63) == 0) shk[threadIdx.x >> 6][c] = kt;
   }
   __syncthreads();
@@ -695,7 +667,7 @@ __global__ __launch_bounds__(ICS_PSF_THREADS) void k_psf(IcsPsfArgs a) {
     uint32_t kp = 0u, kg = 0u;
     if (BIG) {
       for (int i = tid; i < n; i += NTHR) {
-        const uint32_t k1 = key_of(p[i]), k2 = key_of(__builtin_fabsf(a.gradk[i]));
+        const uint32_t k1 = ics_key_of(p[i]), k2 = ics_key_of(__builtin_fabsf(a.gradk[i]));
         kp = kp > k1 ? kp : k1; kg = kg > k2 ? kg : k2;
       }
     } else {
@@ -703,16 +675,16 @@ __global__ __launch_bounds__(ICS_PSF_THREADS) void k_psf(IcsPsfArgs a) {
       for (int r = 0; r < GR; ++r) {
         const int i = tid + r * NTHR;
         if (i < n) {
-          const uint32_t k1 = key_of(p[i]), k2 = key_of(__builtin_fabsf(gk[r]));
+          const uint32_t k1 = ics_key_of(p[i]), k2 = ics_key_of(__builtin_fabsf(gk[r]));
           kp = kp > k1 ? kp : k1; kg = kg > k2 ? kg : k2;
         }
       }
     }
-    kp = wave_max_u32(kp); kg = wave_max_u32(kg);
+    kp = ics_shfl_max_u32(kp); kg = ics_shfl_max_u32(kg);
     if ((tid & 63) == 0) { atomicMax(&sred[0], kp); atomicMax(&sred[1], kg); }
     __syncthreads();
     const float maxp = ics_key2f(sred[0]), maxg = ics_key2f(sred[1]);
-    const float dtpsf = __fdiv_rn(__fmul_rn(__fdiv_rn(a.step, (float)K), maxp), __fadd_rn(maxg, 1e-15f));
+    const float dtpsf = ics_step_dt(__fdiv_rn(a.step, (float)K), maxp, maxg);
     if (tid == 0) a.scal[ICS_SC_DTPSF] = dtpsf;
     if (BIG) {
       for (int i = tid; i < n; i += NTHR) {
@@ -786,8 +758,8 @@ __global__ __launch_bounds__(ICS_PSF_THREADS) void k_psf(IcsPsfArgs a) {
   // kernel row Wp[idx] = W[a][idx - 15][c], i.e. the taps at local halves 7 .. K+6 and zeros around them.
   if (a.bt_conv && a.bt_corr) {
     uint32_t km = 0u;
-    for (int i = tid; i < n; i += NTHR) { const uint32_t k1 = key_of(__builtin_fabsf(p[i])); km = km > k1 ? km : k1; }
-    km = wave_max_u32(km);
+    for (int i = tid; i < n; i += NTHR) { const uint32_t k1 = ics_key_of(__builtin_fabsf(p[i])); km = km > k1 ? km : k1; }
+    km = ics_shfl_max_u32(km);
     if ((tid & 63) == 0) atomicMax(&sred[2], km);
     __syncthreads();
     const float m = ics_key2f(sred[2]);
@@ -828,7 +800,7 @@ __global__ __launch_bounds__(ICS_PSF_THREADS) void k_psf(IcsPsfArgs a) {
 // in flight per lane.  A float's channel is (flat index) mod 3: with r = (first flat index of the lane) mod 3 the lane's
 // element e has channel (r + e) mod 3 and pixel q + (r + e >= 3).  Loads are streaming (nt): nothing read here is read
 // again before ~1 GB of other traffic, and default loads evicted what the next kernel re-reads (0.197 -> 0.173 ms).
-// Same arithmetic, bit-identical to k_update.  TVK: 0 shipped mode, 1 active MM-TV, 2 PAM (kinds 2 and 3).
+// The arithmetic is ics_update.h, as in k_update.  TVK: 0 shipped mode, 1 active MM-TV, 2 PAM (kinds 2 and 3).
 template <int TVK>
 __global__ __launch_bounds__(256) void k_update_rows(IcsUpdateArgs a) {
   const IcsGeom& G = a.geo;
@@ -837,14 +809,14 @@ __global__ __launch_bounds__(256) void k_update_rows(IcsUpdateArgs a) {
   for (int c = 0; c < 3; ++c) {
     const float maxu = ics_key2f(a.red[ICS_RED_MAXU + c]);
     const float maxg = ics_key2f(a.red[ICS_RED_MAXG + c]);
-    dt[c] = __fdiv_rn(__fmul_rn(a.step, maxu), __fadd_rn(maxg, 1e-15f));
+    dt[c] = ics_step_dt(a.step, maxu, maxg);
     if (TVK == 1)   // pyx:548: dt = step*(max image_k + 0)/(max|gradu_k| + 1e-15) with gradu = T
-      dt2[c] = __fdiv_rn(__fmul_rn(a.step, ics_key2f(a.red[ICS_RED_MAXF + c])), __fadd_rn(ics_key2f(a.red[ICS_RED_MAXT + c]), 1e-15f));
+      dt2[c] = ICS_STEP_DT(a.step, ics_key2f(a.red[ICS_RED_MAXF + c]), ics_key2f(a.red[ICS_RED_MAXT + c]));
     if (blockIdx.x == 0 && threadIdx.x == 0) {
       a.scal[ICS_SC_DT + c] = dt[c]; a.scal[ICS_SC_MAXU + c] = maxu; a.scal[ICS_SC_MAXG + c] = maxg;
     }
   }
-  uint32_t kmin = 0xFFFFFFFFu, kmax = 0u, knan = 0u;
+  IcsDofKeys dof = ICS_DOF_NONE;
   const float lambd = a.lambd;
   const int lane = threadIdx.x & 63;
   const int rowf = 3 * G.uN;                       // floats per row
@@ -893,24 +865,19 @@ __global__ __launch_bounds__(256) void k_update_rows(IcsUpdateArgs a) {
         if (TVK == 2)                                                            // PAM: the back-projection pass wrote G = T + lambd*gradu
           g = gv;
         else if (TVK == 1 && y >= 1 && y <= G.uM - 2 && x >= 1 && x <= G.uN - 2)   // pyx:517 (TV_ut_L1 != 0 and TV_u_L1 != 0)
-          g = (float)(((double)Tq[s][e] + (double)__fmul_rn(lambd, gv)) + (double)__fsub_rn(uv, tq[s][e]) / 4.0);
+          g = ics_mm_g_tv(Tq[s][e], lambd, gv, uv, tq[s][e]);
         else
-          g = __fadd_rn(__fmul_rn(lambd, gv), __fmul_rn(__fsub_rn(uv, tq[s][e]), 0.5f));
-        float un = __fsub_rn(uv, __fmul_rn(dtr[e % 3], g));
+          g = ics_mm_g(lambd, gv, uv, tq[s][e]);
+        float un = ics_step_u(uv, dtr[e % 3], g);
         if (inside && TVK != 2) {   // (PAM has no DoF blend)
           float fv = fq[s][e];
-          const float d = ics_dof_ratio(gv, fv);
-          float D = __fmul_rn(d, d);
-          if (!a.blind) D = __fdiv_rn(D, lambd);
+          const float D = ics_dof_mask(gv, fv, lambd, a.blind);
           if (TVK == 1) {  // pyx:549: image -= dt*gradu/lambd, then the blend uses the updated image
             fv = __fsub_rn(fv, __fdiv_rn(__fmul_rn(dt2r[e % 3], Tq[s][e]), lambd));
             fn4[e] = fv;
           }
-          un = __fadd_rn(__fmul_rn(__fsub_rn(1.0f, D), un), __fmul_rn(D, fv));
-          if (a.want_dof) {
-            if (D != D) knan = 1u;
-            else { const uint32_t k = ics_f2key(D); kmin = kmin < k ? kmin : k; kmax = kmax > k ? kmax : k; }
-          }
+          un = ics_dof_blend(D, un, fv);
+          if (a.want_dof) ICS_DOF_NOTE(dof, D);
         }
         un4[e] = un;
       }
@@ -934,19 +901,7 @@ __global__ __launch_bounds__(256) void k_update_rows(IcsUpdateArgs a) {
       }
     }
   }
-  if (a.want_dof) {   // wave -> workgroup -> one atomic per workgroup and value, skipped where the running extremum already covers it
-    __shared__ uint32_t shd[4][3];
-    kmin = wave_min_u32(kmin); kmax = wave_max_u32(kmax); knan = wave_max_u32(knan);
-    if ((threadIdx.x & 63) == 0) { shd[threadIdx.x >> 6][0] = kmin; shd[threadIdx.x >> 6][1] = kmax; shd[threadIdx.x >> 6][2] = knan; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-#pragma unroll
-      for (int w = 1; w < 4; ++w) { kmin = kmin < shd[w][0] ? kmin : shd[w][0]; kmax = kmax > shd[w][1] ? kmax : shd[w][1]; knan |= shd[w][2]; }
-      if (kmin < a.dofkeys[0]) atomicMin(a.dofkeys + 0, kmin);
-      if (kmax > a.dofkeys[1]) atomicMax(a.dofkeys + 1, kmax);
-      if (knan) atomicOr(a.dofkeys + 2, 1u);
-    }
-  }
+  if (a.want_dof) ICS_DOF_FLUSH_WORKGROUP4(dof, a.dofkeys);
 }
 
 // ---- row bands: the two global quantities of an inner iteration restricted to the rows a band owns -------
@@ -969,8 +924,8 @@ __global__ __launch_bounds__(256) void k_band_reduce(const float* __restrict__ g
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       const float uv = uq[e];
-      const float g = __fadd_rn(__fmul_rn(lambd, gq[e]), __fmul_rn(__fsub_rn(uv, tq[e]), 0.5f));
-      const uint32_t k1 = f + e < rowf ? key_of(__builtin_fabsf(g)) : 0u, k2 = f + e < rowf ? key_of(uv) : 0u;
+      const float g = ics_mm_g(lambd, gq[e], uv, tq[e]);
+      const uint32_t k1 = f + e < rowf ? ics_key_of(__builtin_fabsf(g)) : 0u, k2 = f + e < rowf ? ics_key_of(uv) : 0u;
 #pragma unroll
       for (int cc = 0; cc < 3; ++cc) if (cc == c) { kg[cc] = kg[cc] > k1 ? kg[cc] : k1; ku[cc] = ku[cc] > k2 ? ku[cc] : k2; }
       c = c == 2 ? 0 : c + 1;
@@ -978,7 +933,7 @@ __global__ __launch_bounds__(256) void k_band_reduce(const float* __restrict__ g
   }
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
 #pragma unroll
-  for (int c = 0; c < 3; ++c) { kg[c] = wave_max_u32(kg[c]); ku[c] = wave_max_u32(ku[c]); }
+  for (int c = 0; c < 3; ++c) { kg[c] = ics_shfl_max_u32(kg[c]); ku[c] = ics_shfl_max_u32(ku[c]); }
   if (lane == 0) {
 #pragma unroll
     for (int c = 0; c < 3; ++c) { sh[wave * 8 + c] = kg[c]; sh[wave * 8 + 3 + c] = ku[c]; }
@@ -1052,14 +1007,7 @@ hipError_t ics_launch_tvterm(const IcsTvTermArgs& a, hipStream_t s) {
 hipError_t ics_launch_update(const IcsUpdateArgs& a, hipStream_t s) {
   const long total = (long)a.geo.uM * a.geo.tiles_x * 16;
   long blocks = (total + 255) / 256;
-  // Few long-lived workgroups stream best here.  k_update_rows at 4096^2 (4 reads + 1 write, 1.0 GB), segments per loop
-  // iteration x workgroups per CU: 3x2 0.173 ms, 4x2 0.167, 4x3 0.164, 4x4 0.170, 6x2 0.164, 6x4 0.180.
-  // ... and at smaller frames fewer still: 2048^2 0.0568 / 0.0526 / 0.0565 ms and 3072^2 0.119 / 0.099 / 0.102 ms with 1 / 2 / 3 per CU,
-  // 1024^2 0.0252 / 0.0265 / 0.0299
-  const long px = (long)a.geo.uM * a.geo.uN;
-  const int per_cu_env = ics_debug().update_wg_per_cu.load(std::memory_order_relaxed);
-  const int per_cu = per_cu_env > 0 ? per_cu_env : (px >= 12000000L ? 3 : (px >= 1500000L ? 2 : 1));
-  const long cap = (long)ics_device_cus(ics_current_device()) * (per_cu > 0 ? per_cu : 3);
+  const long cap = (long)ics_device_cus(ics_current_device()) * ics_update_wgs_per_cu((long)a.geo.uM * a.geo.uN);
   if (blocks > cap) blocks = cap;
   const int rows_kernel = ics_debug().update_kernel.load(std::memory_order_relaxed);   // 0: the pixel-group kernel everywhere
   const int tvk = (a.tv && a.tv_kind) ? (a.tv_kind >= 2 ? 2 : 1) : 0;

@@ -6,25 +6,15 @@
 // window loads alone).  During a run that uses it, the frames therefore live as three planes each, and the kernels between the
 // convolutions run on the planes as well:
 //   k_hwc_to_planar / k_planar_to_hwc   run boundaries (whole frames), and the stop-test window (A18 / A19 read HWC frames)
-//   k_update_planar                     A5 + A6 + A8 + A10 (lib/deconvolution.pyx:499-552) -- the arithmetic of k_update_rows, operation for
-//                                       operation (every operation rounded separately), so the results are bit-identical to the HWC pass
+//   k_update_planar                     A5 + A6 + A8 + A10 (lib/deconvolution.pyx:499-552) -- the functions of ics_update.h, as k_update_rows
+//                                       applies them: bit-identical to the HWC pass
 // The PSF gradient reads planes through a template flag of its own kernel (ics_gradk_mfma.hip).
 #include "ics_kernels.h"
+#include "ics_update.h"
 
 namespace {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) { uint32_t o = (uint32_t)__shfl_xor((int)v, off, 64); v = v > o ? v : o; }
-  return v;
-}
-__device__ __forceinline__ uint32_t wave_min_u32(uint32_t v) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) { uint32_t o = (uint32_t)__shfl_xor((int)v, off, 64); v = v < o ? v : o; }
-  return v;
-}
 
 // One thread = 4 consecutive pixels of a buffer row: 3 dwordx4 of HWC <-> one dwordx4 per plane.  Rows [r0, r1) and pixel groups [q0, q1)
 // in BUFFER coordinates (row 0 = first allocated row, pixel 0 = first pixel of a row; ax is a multiple of 4, so frame pixel 0 starts a group).
@@ -59,10 +49,7 @@ __global__ __launch_bounds__(256) void k_planar_convert(const float* __restrict_
   }
 }
 
-// A5 + A6 + A8 + A10 on planes: one thread = 4 consecutive pixels of one channel row (dwordx4 per operand).
-//   g   = lambd*gradu + (u - ut)/2.                       (pyx:519)
-//   dt  = step*max u_c / (max|g_c| + 1e-15)               (pyx:524)
-//   u  -= dt*g; interior: D = ((gradu - f)/(gradu + f))^2 [/ lambd]; u = (1 - D) u + D f    (pyx:499-502, 531, 552)
+// A5 + A6 + A8 + A10 (ics_update.h) on planes: one thread = 4 consecutive pixels of one channel row (dwordx4 per operand).
 __global__ __launch_bounds__(256) void k_update_planar(IcsUpdateArgs a, int ppitch, size_t plane) {
   const IcsGeom& G = a.geo;
   float dt[3];
@@ -70,12 +57,12 @@ __global__ __launch_bounds__(256) void k_update_planar(IcsUpdateArgs a, int ppit
   for (int c = 0; c < 3; ++c) {
     const float maxu = ics_key2f(a.red[ICS_RED_MAXU + c]);
     const float maxg = ics_key2f(a.red[ICS_RED_MAXG + c]);
-    dt[c] = __fdiv_rn(__fmul_rn(a.step, maxu), __fadd_rn(maxg, 1e-15f));
+    dt[c] = ics_step_dt(a.step, maxu, maxg);
     if (blockIdx.x == 0 && threadIdx.x == 0) {
       a.scal[ICS_SC_DT + c] = dt[c]; a.scal[ICS_SC_MAXU + c] = maxu; a.scal[ICS_SC_MAXG + c] = maxg;
     }
   }
-  uint32_t kmin = 0xFFFFFFFFu, kmax = 0u, knan = 0u;
+  IcsDofKeys dof = ICS_DOF_NONE;
   const float lambd = a.lambd;
   const int nq = (G.uN + 3) / 4;
   const long per_plane = (long)G.uM * nq, total = 3 * per_plane;
@@ -97,18 +84,13 @@ __global__ __launch_bounds__(256) void k_update_planar(IcsUpdateArgs a, int ppit
       const bool inside = yin && (x >= G.pad) && (x < G.pad + G.N);
       const float uv = uq[e], gv = gq[e];
       // (PAM kinds: the back-projection wrote G = T + lambd gradu; no DoF blend -- k_update_rows, ics_kernels.hip)
-      const float g = a.tv_kind >= 2 ? gv : __fadd_rn(__fmul_rn(lambd, gv), __fmul_rn(__fsub_rn(uv, tq[e]), 0.5f));
-      float un = __fsub_rn(uv, __fmul_rn(dtc, g));
+      const float g = a.tv_kind >= 2 ? gv : ics_mm_g(lambd, gv, uv, tq[e]);
+      float un = ics_step_u(uv, dtc, g);
       if (inside && a.tv_kind < 2) {
         const float fv = fq[e];
-        const float d = ics_dof_ratio(gv, fv);
-        float D = __fmul_rn(d, d);
-        if (!a.blind) D = __fdiv_rn(D, lambd);
-        un = __fadd_rn(__fmul_rn(__fsub_rn(1.0f, D), un), __fmul_rn(D, fv));
-        if (a.want_dof) {
-          if (D != D) knan = 1u;
-          else { const uint32_t k = ics_f2key(D); kmin = kmin < k ? kmin : k; kmax = kmax > k ? kmax : k; }
-        }
+        const float D = ics_dof_mask(gv, fv, lambd, a.blind);
+        un = ics_dof_blend(D, un, fv);
+        if (a.want_dof) ICS_DOF_NOTE(dof, D);
       }
       un4[e] = un;
     }
@@ -119,19 +101,7 @@ __global__ __launch_bounds__(256) void k_update_planar(IcsUpdateArgs a, int ppit
         if (x0 + e < G.uN) a.u_out[o + e] = un4[e];
     }
   }
-  if (a.want_dof) {
-    __shared__ uint32_t shd[4][3];
-    kmin = wave_min_u32(kmin); kmax = wave_max_u32(kmax); knan = wave_max_u32(knan);
-    if ((threadIdx.x & 63) == 0) { shd[threadIdx.x >> 6][0] = kmin; shd[threadIdx.x >> 6][1] = kmax; shd[threadIdx.x >> 6][2] = knan; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-#pragma unroll
-      for (int w = 1; w < 4; ++w) { kmin = kmin < shd[w][0] ? kmin : shd[w][0]; kmax = kmax > shd[w][1] ? kmax : shd[w][1]; knan |= shd[w][2]; }
-      if (kmin < a.dofkeys[0]) atomicMin(a.dofkeys + 0, kmin);
-      if (kmax > a.dofkeys[1]) atomicMax(a.dofkeys + 1, kmax);
-      if (knan) atomicOr(a.dofkeys + 2, 1u);
-    }
-  }
+  if (a.want_dof) ICS_DOF_FLUSH_WORKGROUP4(dof, a.dofkeys);
 }
 
 }  // namespace
@@ -158,11 +128,8 @@ hipError_t ics_launch_planar_convert(bool to_planar, const float* src, float* ds
 
 // the update pass on planar mirrors: the frame pointers of `a` are ORIGINS of planar buffers (plane 0)
 hipError_t ics_launch_update_planar(const IcsUpdateArgs& a, hipStream_t s) {
-  const long px = (long)a.geo.uM * a.geo.uN;
-  const int per_cu_env = ics_debug().update_wg_per_cu.load(std::memory_order_relaxed);
-  const int per_cu = per_cu_env > 0 ? per_cu_env : (px >= 12000000L ? 3 : (px >= 1500000L ? 2 : 1));
   long blocks = (3 * (long)a.geo.uM * ((a.geo.uN + 3) / 4) + 255) / 256;
-  const long cap = (long)ics_device_cus(ics_current_device()) * per_cu * 2;
+  const long cap = (long)ics_device_cus(ics_current_device()) * ics_update_wgs_per_cu((long)a.geo.uM * a.geo.uN) * 2;
   if (blocks > cap) blocks = cap;
   hipLaunchKernelGGL(k_update_planar, dim3((unsigned)blocks), dim3(256), 0, s, a, ics_ppitch(a.geo), ics_plane_floats(a.geo));
   return hipGetLastError();

@@ -22,14 +22,10 @@
 // counter w % 16), all watched by one wave-wide load per workgroup, monotone over the run (grid_barrier below).
 #include "ics_common.h"
 #include "ics_kernels.h"
+#include "ics_update.h"
 
 namespace {
 
-
-__device__ __forceinline__ uint32_t key_of(float f) {
-  if (f != f) return 0xFFC00000u;   // canonical NaN: propagates through the integer max like np.amax
-  return ics_f2key(f);
-}
 __device__ __forceinline__ float ld_coh(const float* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ void st_coh(float* p, float v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ uint32_t ld_coh(const uint32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
@@ -249,8 +245,8 @@ __global__ __launch_bounds__(NT) void k_small_iter(IcsSmallArgs A) {
       sG[y * pT + x] = s;
       if (fy < G.uM && fx < G.uN) {
         const float uv = sU[(y + 2 * pad) * pU + x + 2 * pad];
-        const float g6 = __fadd_rn(__fmul_rn(A.lambd, s), __fmul_rn(__fsub_rn(uv, sUT[y * pT + x]), 0.5f));
-        const uint32_t k1 = key_of(__builtin_fabsf(g6)), k2 = key_of(uv);
+        const float g6 = ics_mm_g(A.lambd, s, uv, sUT[y * pT + x]);
+        const uint32_t k1 = ics_key_of(__builtin_fabsf(g6)), k2 = ics_key_of(uv);
         kg = kg > k1 ? kg : k1; ku = ku > k2 ? ku : k2;
       }
     }
@@ -276,30 +272,25 @@ __global__ __launch_bounds__(NT) void k_small_iter(IcsSmallArgs A) {
       maxg = ics_key2f(k0); maxu = ics_key2f(k1);
       if (t == 0 && tid == 0) { red[ICS_RED_MAXG + c] = k0; red[ICS_RED_MAXU + c] = k1; }   // (where the multi-launch path leaves them)
     }
-    const float dt = __fdiv_rn(__fmul_rn(A.step, maxu), __fadd_rn(maxg, 1e-15f));
+    const float dt = ics_step_dt(A.step, maxu, maxg);
     if (t == 0 && tid == 0) { A.scal[ICS_SC_DT + c] = dt; A.scal[ICS_SC_MAXU + c] = maxu; A.scal[ICS_SC_MAXG + c] = maxg; }
-    uint32_t kmin = 0xFFFFFFFFu, kmax = 0u, knan = 0u;
+    IcsDofKeys dof = ICS_DOF_NONE;
     for (int i = tid; i < T * T; i += NT) {
       const int y = udiv(i, P.m_T), x = i - y * T, fy = ty0 + y, fx = tx0 + x;
       if (fy >= G.uM || fx >= G.uN) continue;
       const float uv = sU[(y + 2 * pad) * pU + x + 2 * pad], gv = sG[y * pT + x];
-      const float g6 = __fadd_rn(__fmul_rn(A.lambd, gv), __fmul_rn(__fsub_rn(uv, sUT[y * pT + x]), 0.5f));
-      float un = __fsub_rn(uv, __fmul_rn(dt, g6));
+      const float g6 = ics_mm_g(A.lambd, gv, uv, sUT[y * pT + x]);
+      float un = ics_step_u(uv, dt, g6);
       if (fy >= pad && fy < pad + G.M && fx >= pad && fx < pad + G.N) {
         const float fv = sF[(y + pad) * pE + x + pad];
-        const float d = ics_dof_ratio(gv, fv);
-        float D = __fmul_rn(d, d);
-        if (!A.blind) D = __fdiv_rn(D, A.lambd);
-        un = __fadd_rn(__fmul_rn(__fsub_rn(1.0f, D), un), __fmul_rn(D, fv));
-        if (last) {
-          if (D != D) knan = 1u;
-          else { const uint32_t k = ics_f2key(D); kmin = kmin < k ? kmin : k; kmax = kmax > k ? kmax : k; }
-        }
+        const float D = ics_dof_mask(gv, fv, A.lambd, A.blind);
+        un = ics_dof_blend(D, un, fv);
+        if (last) ICS_DOF_NOTE(dof, D);
       }
       st_coh(A.u_out + fy * pitch + 3 * fx + c, un);
     }
     if (last) {   // DoF keys of the outer iteration (pyx:593): one set of atomics per workgroup
-      kmax = ics_wave_max_u32(kmax); knan = ics_wave_max_u32(knan); kmin = ~ics_wave_max_u32(~kmin);
+      const uint32_t kmax = ics_wave_max_u32(dof.kmax), knan = ics_wave_max_u32(dof.knan), kmin = ~ics_wave_max_u32(~dof.kmin);
       if ((tid & 63) == 0) { atomicMin(&skeys[2], kmin); atomicMax(&skeys[3], kmax); atomicMax(&skeys[4], knan); }
       __syncthreads();
       if (tid == 0) { atomicMin(A.dofkeys + 0, skeys[2]); atomicMax(A.dofkeys + 1, skeys[3]); if (skeys[4]) atomicOr(A.dofkeys + 2, 1u); }
@@ -372,13 +363,13 @@ __global__ __launch_bounds__(NT) void k_small_iter(IcsSmallArgs A) {
 #pragma unroll
       for (int r = 0; r < NG; ++r) {
         const int i = tid + r * NT;
-        if (i < n3) { const uint32_t k1 = key_of(sPSF[i]), k2 = key_of(__builtin_fabsf(gv[r])); kp = kp > k1 ? kp : k1; kq = kq > k2 ? kq : k2; }
+        if (i < n3) { const uint32_t k1 = ics_key_of(sPSF[i]), k2 = ics_key_of(__builtin_fabsf(gv[r])); kp = kp > k1 ? kp : k1; kq = kq > k2 ? kq : k2; }
       }
       kp = ics_wave_max_u32(kp); kq = ics_wave_max_u32(kq);
       if ((tid & 63) == 0) { atomicMax(&skeys[5], kp); atomicMax(&skeys[6], kq); }
       __syncthreads();
       const float maxp = ics_key2f(skeys[5]), maxq = ics_key2f(skeys[6]);
-      const float dtpsf = __fdiv_rn(__fmul_rn(__fdiv_rn(A.step, (float)K), maxp), __fadd_rn(maxq, 1e-15f));
+      const float dtpsf = ics_step_dt(__fdiv_rn(A.step, (float)K), maxp, maxq);
       const bool writer = wg == 0;
       if (writer && tid == 0) A.scal[ICS_SC_DTPSF] = dtpsf;
 #pragma unroll

@@ -38,8 +38,9 @@ def gradk64(u, e):
     return np.stack([orc._conv_direct(urot[..., c], e[..., c], "valid") for c in range(3)], axis=-1)
 
 
-def update_f32(u, ut, g_raw, image, step, lambd, blind, pad):
-    """A5-A10 in numpy float32 with the reference's rounding (lib/deconvolution.pyx:499-552)."""
+def update_f32(u, ut, g_raw, image, step, lambd, blind, pad, maxima=False):
+    """A5-A10 in numpy float32 with the reference's rounding (lib/deconvolution.pyx:499-552).  Returns (u, dt, DoF), with `maxima` also
+    the per-channel max u and max |g| the step sizes were taken from."""
     F = np.float32
     step, lambd = F(step), F(lambd)
     M, N = image.shape[:2]
@@ -50,14 +51,15 @@ def update_f32(u, ut, g_raw, image, step, lambd, blind, pad):
         if not blind:
             DoF = DoF / lambd
         g = ((lambd * g_raw).astype(np.float64) + (u - ut).astype(np.float64) / 2.0).astype(np.float32)
-        dt = np.zeros(3, np.float32)
+        dt, maxu, maxg = np.zeros(3, np.float32), np.zeros(3, np.float32), np.zeros(3, np.float32)
         for k in range(3):
-            dt[k] = F(step * np.amax(u[..., k])) / F(np.amax(np.abs(g[..., k])) + F(1e-15))
+            maxu[k], maxg[k] = np.amax(u[..., k]), np.amax(np.abs(g[..., k]))
+            dt[k] = F(step * maxu[k]) / F(maxg[k] + F(1e-15))
         un = u.copy()
         for k in range(3):
             un[..., k] -= dt[k] * g[..., k]
         un[inter] = (F(1.0) - DoF) * un[inter] + DoF * image
-    return un, dt, DoF
+    return (un, dt, DoF, maxu, maxg) if maxima else (un, dt, DoF)
 
 
 def psf_step_f32(psf, gradk, step, MK, correlation):

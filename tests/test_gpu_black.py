@@ -4,7 +4,7 @@ The DoF mask is ((gradu - image)/(gradu + image))^2.  In a region where image an
 rounding noise of its complex64 FFT and the ratio is 1 for every non-zero noise value: the compiled reference returns a finite
 picture there unless one noise value happens to be exactly 0 (then its whole frame is NaN).  The device convolutions are
 exact, gradu = 0, and IEEE 0/0 would make every such frame NaN; the library defines the ratio as 1 where gradu == image == 0
-(include/ics_hip.h "DoF ratio", csrc/ics_common.h ics_dof_ratio).  tests/golden/rl_black.npz (oracle/make_golden_black.py)
+(include/ics_hip.h "DoF ratio", csrc/ics_update.h ics_dof_ratio).  tests/golden/rl_black.npz (oracle/make_golden_black.py)
 holds the COMPILED REFERENCE's results on 36 such frames: where it returned a finite picture (22 of the 24 row-band cases)
 the device result must match it at the north-star gate; in every case it must be finite and match the float64-direct oracle,
 which carries the same rule (oracle/rl_mm_oracle.py dof_ratio).
@@ -134,15 +134,40 @@ def test_black_band_through_the_row_band_path(golden_dir, name):
     assert er < TOL and epr < TOL
 
 
+def _key(f):
+    """ics_f2key (csrc/ics_common.h)"""
+    b = int(np.float32(f).view(np.uint32))
+    return (~b & 0xFFFFFFFF) if b & 0x80000000 else (b | 0x80000000)
+
+
+# 96 x 80 / 9: rows of 264 floats, whole 16-byte groups; 41 x 53 / 5: uN = 57 and rows of 171 floats -- the pixel-group tail of k_update,
+# the `f0 + 3 < rowf` tail of k_update_rows and the `x0 + 3 < uN` tail of k_update_planar
+UPDATE_SHAPES = [(96, 80, 9), (41, 53, 5)]
+UPDATE_CASES = [pytest.param(k, s, id=k if s == UPDATE_SHAPES[0] else "%s-%dx%d" % (k, s[0], s[1]))
+                for s in UPDATE_SHAPES for k in ("rows", "pixel_groups", "fused_update_synth", "planar")]
+
+
+def test_update_stage_shapes_hold_deep_black_pixels():
+    """CPU: the image half of the 0/0 condition -- each shape holds more than 1000 values whose whole (2K-1)^2 window is black"""
+    from scipy.ndimage import minimum_filter
+    for M, N, MK in UPDATE_SHAPES:
+        case = orc.black_case(M, N, MK, "band_mid", seed=5)
+        deep = minimum_filter(case["black"].astype(np.uint8), size=2 * MK - 1, mode="nearest").astype(bool)
+        assert np.all(case["image"][deep] == 0) and 3 * deep.sum() > 1000, (M, N, MK)
+        if (M, N, MK) == (41, 53, 5):
+            assert 3 * deep.sum() == 10 * 53 * 3
+
+
 @pytest.mark.gpu
-@pytest.mark.parametrize("kernel", ["rows", "pixel_groups", "fused_update_synth"])
+@pytest.mark.parametrize("kernel,shape", UPDATE_CASES)
 @pytest.mark.parametrize("blind", [False, True])
-def test_black_band_update_stage_is_bit_exact(blind, kernel, debug_switch):
+def test_black_band_update_stage_is_bit_exact(blind, kernel, shape, debug_switch):
     """A5-A10 on a frame whose back-projection and image hold exact zeros: every update kernel (k_update_rows, k_update, the
-    opt-in fused update + convolution) against the numpy float32 restatement, rule included, bit for bit."""
+    opt-in fused update + convolution, k_update_planar on the mirrors) against the numpy float32 restatement, rule included, bit for
+    bit: u, the recorded step sizes and maxima, and the DoF keys."""
     from lib import _native as nv
     from helpers import update_f32
-    M, N, MK = 96, 80, 9
+    M, N, MK = shape
     pad = MK // 2
     case = orc.black_case(M, N, MK, "band_mid", seed=5, blind=blind)
     rng = np.random.default_rng(1)
@@ -164,12 +189,18 @@ def test_black_band_update_stage_is_bit_exact(blind, kernel, debug_switch):
         gi = g_raw[pad:-pad, pad:-pad]
         both = (gi == 0) & (case["image"] == 0)
         assert both.sum() > 1000, "no exact 0/0 pixels: the case does not exercise the rule"
+        if kernel == "planar":   # the same stage on the channel-planar mirrors (the exact convolutions above stay the fp32 ones)
+            p = job.params(*orc.default_window(M, N, MK), 1e9, 1, 1e-3, 10000.0, blind=blind, conv=nv.CONV_FFT)
         job.stage(nv.STAGE_UPDATE_SYNTH if kernel == "fused_update_synth" else nv.STAGE_UPDATE, p)
         got = job.read(nv.BUF_U)
-        sc = job.scalars()
+        sc = job.read(nv.BUF_SCALARS)
+        keys = job.red_keys()
     finally:
         job.close()
-    want, dt, DoF = update_f32(u, ut, g_raw, case["image"], 1e-3, 10000.0, blind, pad)
+    want, dt, DoF, maxu, maxg = update_f32(u, ut, g_raw, case["image"], 1e-3, 10000.0, blind, pad, maxima=True)
     assert not np.isnan(want).any() and not np.isnan(got).any()
     assert np.array_equal(got, want)
     assert DoF[both].min() == DoF[both].max() == (np.float32(1.0) if blind else np.float32(1.0) / np.float32(10000.0))
+    print("dt", sc[0:3], dt, "max u", sc[3:6], maxu, "max |g|", sc[6:9], maxg, "DoF keys", keys[12:15], _key(DoF.min()), _key(DoF.max()))
+    assert np.array_equal(sc[0:3], dt) and np.array_equal(sc[3:6], maxu) and np.array_equal(sc[6:9], maxg)
+    assert int(keys[12]) == _key(DoF.min()) and int(keys[13]) == _key(DoF.max()) and int(keys[14]) == 0
