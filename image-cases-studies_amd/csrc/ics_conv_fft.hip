@@ -1,6 +1,7 @@
 // ics_conv_fft.hip -- transform tiles (ics_fft_tile.h): the convolutions k_conv_fft<0|1|2> and, for wide PSFs, k_conv_fft_blk<0|1>, the image
-// spectra of mode 2, the weight spectra, and the arguments every tile kernel is launched with (ics_conv_fft_fill_args).
+// spectra of mode 2, the weight spectra (k_fft_spectrum; with the PSF step in front of them: k_psf_spectra), and the arguments every tile kernel is launched with (ics_conv_fft_fill_args).
 #include "ics_fft_tile.h"
+#include "ics_psf_step.h"
 #include <algorithm>
 #include <cassert>
 #include <mutex>
@@ -377,6 +378,113 @@ __global__ __launch_bounds__(256) void k_fft_spectrum(const float* __restrict__ 
   }
 }
 
+// ---- A14 ... A17 + both spectra in one launch (blind runs on the tiles, PSF sizes <= ICS_FFT_MAX_K) ---------------------------------------------
+// k_psf and k_fft_spectrum were two dependent launches of 1 and 96 workgroups in every blind inner iteration, with nothing to run beside
+// them and 6 ... 7 us of idle device between them.  Here the 96 workgroups of the spectrum launch each redo the small step on a private
+// LDS copy of the PSF -- the same instructions on the same inputs, hence the same bits in every workgroup, and no workgroup waits for
+// another -- and then transform their share of it exactly as k_fft_spectrum does.  Workgroup 0 alone stores psf_next, psf_caller, dtpsf
+// and the `frozen` flag, and alone reads that flag.  The PSF is read from a.psf and written to a.psf_next: workgroup 0 may finish before
+// another workgroup has started.  Neither the row-pair tables nor the fp16 Toeplitz tables are packed: no tile kernel reads them.
+// (Also summing the gradient's blocks here, every workgroup for itself in the order of k_gradk_fft_reduce, was built and measured:
+//  bit-identical and slower at every size -- 4096^2 blind, ms per inner iteration, folded / k_gradk_fft_reduce as a launch:
+//  15 x 15 0.6704 / 0.6612, 25 x 25 0.8565 / 0.8005, 31 x 31 0.9466 / 0.8670; the launch it saves costs 5.3 us + a kernel boundary, the
+//  redundant sums 25 us at 15 x 15 -- 3 K^2 values x 255 blocks per workgroup from L2 in dependent batches.  NOTES_r07.md.)
+
+// GR = gradient values per thread at the largest PSF of the instance (value i = tid + r * 1024, as the PSF's own copy loop)
+template <int GR>
+__global__ __launch_bounds__(1024) void k_psf_spectra(IcsPsfSpectraArgs a) {
+  constexpr int NTHR = 1024;
+  extern __shared__ __attribute__((aligned(16))) double sm[];   // [128][2] twiddles, [K][32][2] G, then the PSF: [K][K][3] floats
+  __shared__ uint32_t sred[2];
+  __shared__ float ssum[3];
+  const int K = a.K, KK = K * K, n = 3 * KK, tid = threadIdx.x;
+  double* twd = sm;
+  double* Gs = sm + 256;
+  float* p = reinterpret_cast<float*>(Gs + 64 * K);
+  const bool first = blockIdx.x == 0;
+  const int frozen = first ? *a.frozen : 1;
+  if (tid < 128) {
+    double sn, cs;
+    sincospi((double)tid / 64.0, &sn, &cs);
+    twd[2 * tid] = cs; twd[2 * tid + 1] = -sn;
+  }
+  if (tid < 2) sred[tid] = 0u;
+  for (int i = tid; i < n; i += NTHR) p[i] = a.psf[i];
+  // ---- phase 1: the gradient (everything the step needs from global memory is requested up front) ----
+  float gk[GR];
+#pragma unroll
+  for (int r = 0; r < GR; ++r) { const int i = tid + r * NTHR; gk[r] = i < n ? a.gradk[i] : 0.f; }
+  __syncthreads();
+  // ---- phase 2: A14 ... A17 (ics_psf_step.h) ----
+  uint32_t kp = 0u, kg = 0u;
+#pragma unroll
+  for (int r = 0; r < GR; ++r) {
+    const int i = tid + r * NTHR;
+    if (i < n) {
+      const uint32_t k1 = ics_key_of(p[i]), k2 = ics_key_of(__builtin_fabsf(gk[r]));
+      kp = kp > k1 ? kp : k1; kg = kg > k2 ? kg : k2;
+    }
+  }
+  kp = ics_shfl_max_u32(kp); kg = ics_shfl_max_u32(kg);
+  if ((tid & 63) == 0) { atomicMax(&sred[0], kp); atomicMax(&sred[1], kg); }
+  __syncthreads();
+  const float dtpsf = ics_psf_dt(a.step, K, ics_key2f(sred[0]), ics_key2f(sred[1]));
+  if (first && tid == 0) a.scal[ICS_SC_DTPSF] = dtpsf;
+#pragma unroll
+  for (int r = 0; r < GR; ++r) {
+    const int i = tid + r * NTHR;
+    if (i < n) {
+      p[i] = ics_psf_step_px(p[i], dtpsf, gk[r]);
+      if (!frozen) a.psf_caller[i] = p[i];
+    }
+  }
+  __syncthreads();
+  if (a.correlation) {
+    for (int i = tid; i < KK; i += NTHR) {
+      const float mval = ics_psf_mean3(p[3 * i], p[3 * i + 1], p[3 * i + 2]);
+      p[3 * i] = mval; p[3 * i + 1] = mval; p[3 * i + 2] = mval;
+    }
+    __syncthreads();
+  }
+  for (int i = tid; i < n; i += NTHR) p[i] = ics_psf_clamp(p[i]);
+  __syncthreads();
+  if (tid < 3) ssum[tid] = ics_psf_channel_sum(p, KK, tid);
+  __syncthreads();
+  const bool detach = a.correlation != 0;
+  for (int i = tid; i < n; i += NTHR) {
+    p[i] = ics_psf_norm(p[i], ssum[i % 3]);
+    if (first) a.psf_next[i] = p[i];
+    if (!frozen && !detach) a.psf_caller[i] = p[i];
+  }
+  if (first && tid == 0 && detach) *a.frozen = 1;
+  __syncthreads();
+  // ---- phase 3: the two loops of k_fft_spectrum (whole PSF: one block of K x K taps), fed from the LDS copy ----
+  const int o = blockIdx.x / 48, c = (blockIdx.x / 16) % 3, kx0 = ((blockIdx.x >> 2) & 3) * 32, ky0 = (blockIdx.x & 3) * 32;
+  for (int i = tid; i < K * 32; i += NTHR) {
+    const int aa = i >> 5, kx = kx0 + (i & 31);
+    double re = 0.0, im = 0.0;
+    for (int b = 0; b < K; ++b) {
+      const double wv = o == 0 ? (double)p[((K - 1 - aa) * K + (K - 1 - b)) * 3 + c] : (double)p[(aa * K + b) * 3 + c];
+      const int t = (b * kx) & 127;
+      re += wv * twd[2 * t]; im += wv * twd[2 * t + 1];
+    }
+    Gs[2 * i] = re; Gs[2 * i + 1] = im;
+  }
+  __syncthreads();
+  for (int i = tid; i < 32 * 32; i += NTHR) {
+    const int ky = ky0 + (i >> 5), kxl = i & 31;
+    double re = 0.0, im = 0.0;
+    for (int aa = 0; aa < K; ++aa) {
+      const double gr = Gs[2 * (aa * 32 + kxl)], gi = Gs[2 * (aa * 32 + kxl) + 1];
+      const int t = (aa * ky) & 127;
+      const double wr = twd[2 * t], wi = twd[2 * t + 1];
+      re += gr * wr - gi * wi; im += gr * wi + gi * wr;
+    }
+    const double sc = 1.0 / (128.0 * 128.0);
+    reinterpret_cast<v2f*>(o == 0 ? a.spec_conv : a.spec_corr)[spec_index(c, ky, kx0 + kxl)] = (v2f){(float)(re * sc), (float)(-im * sc)};
+  }
+}
+
 }  // namespace icsfft
 
 // ---- launchers -----------------------------------------------------------------------------------------------------------------------------
@@ -387,6 +495,23 @@ hipError_t ics_launch_fft_spectrum(const float* psf, int K, float* spec_conv, fl
   const int nb = blk_n > 0 ? blk_n : 1, Kb = blk_n > 0 ? blk_k : K;
   const size_t lds = (256 + (size_t)Kb * 32 * 2) * sizeof(double);   // 35 KB at 65, 46 KB at 85
   hipLaunchKernelGGL(icsfft::k_fft_spectrum, dim3(96, nb * nb), dim3(256), lds, s, psf, K, reinterpret_cast<v2f*>(spec_conv), reinterpret_cast<v2f*>(spec_corr), nb, Kb);
+  return hipGetLastError();
+}
+
+// (dynamic LDS: twiddles + G + the PSF = 15 KB at 15 x 15, 130 KB at 85 x 85 of the CU's 160)
+hipError_t ics_launch_psf_spectra(const IcsPsfSpectraArgs& a, hipStream_t s) {
+  if (a.K < 3 || a.K > ICS_FFT_MAX_K) return hipErrorInvalidValue;
+  auto bytes = [](int K) { return (256 + (size_t)K * 64) * sizeof(double) + (size_t)3 * K * K * sizeof(float); };
+  // two instances: the sizes mode 2 of the tiles serves keep three gradient values a thread, the others up to 22
+  constexpr int K_FEW = 31, GR_FEW = (3 * K_FEW * K_FEW + 1023) / 1024, GR_ALL = (3 * ICS_FFT_MAX_K * ICS_FFT_MAX_K + 1023) / 1024;
+  static std::atomic<bool> cfg_few[ICS_MAX_DEVICES], cfg_all[ICS_MAX_DEVICES];
+  if (a.K <= K_FEW) {
+    if (hipError_t e = ics_configure_lds(cfg_few, ics_current_device(), icsfft::k_psf_spectra<GR_FEW>, bytes(K_FEW)); e != hipSuccess) return e;
+    hipLaunchKernelGGL((icsfft::k_psf_spectra<GR_FEW>), dim3(96), dim3(1024), bytes(a.K), s, a);
+  } else {
+    if (hipError_t e = ics_configure_lds(cfg_all, ics_current_device(), icsfft::k_psf_spectra<GR_ALL>, bytes(ICS_FFT_MAX_K)); e != hipSuccess) return e;
+    hipLaunchKernelGGL((icsfft::k_psf_spectra<GR_ALL>), dim3(96), dim3(1024), bytes(a.K), s, a);
+  }
   return hipGetLastError();
 }
 

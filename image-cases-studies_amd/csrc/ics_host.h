@@ -86,6 +86,10 @@ struct ics_rl {
   float* facc[2];                       // the image in accumulator order for 32-row / 64-row tiles (ics_image_acc.h), allocated on first use
   bool facc_valid[2];                   // ... and whether it still mirrors the image frame
   float *psf, *gradk, *wconv, *wcorr, *psf_caller, *partial;
+  // k_psf_spectra (blind runs on the tiles, Route::psf1) reads `psf` and writes `psf_next`; do_psf exchanges the two pointers behind the
+  // launch, so whatever is queued afterwards -- kernels, copies to and from psf_bak, downloads -- takes the stepped PSF through `psf` in
+  // stream order.  No pointer to either buffer is kept across launches.
+  float* psf_next;
   size_t partial_floats;                // size of `partial`
   float* psf_work;                      // PSF sizes above 63: working copy of k_psf (3*K*K floats), else NULL
   // overlap of the statistics with the next outer iteration: the reduction slots / DoF keys of outer iteration i are the set i & 1
@@ -287,6 +291,7 @@ struct Route {
   int gradk;            // the PSF gradient, GK_FUSED_MATRIX ... GK_FUSED_TILES (resolved for non-blind parameters too: the stage API)
   bool image_acc;       // the residual's epilogues read the accumulator-order copy of the image where their tile height has one (ics_image_acc.h)
   bool acc_order;       // ... and a run of these parameters does (ics_rl_route.image_in_accumulator_order)
+  bool psf1;            // internal (not in ics_rl_route): blind inner iterations of a tile run step the PSF and build both spectra in one launch (k_psf_spectra)
   bool overlap;         // the statistics of outer iteration i on the second stream beside iteration i + 1; else a drain at every outer boundary
 };
 

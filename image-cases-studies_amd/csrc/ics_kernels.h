@@ -107,6 +107,23 @@ hipError_t ics_launch_gradk_fft(const float* u, const float* e, const IcsGeom& g
 // ics_launch_conv_fft(0) followed by ics_launch_gradk_fft
 hipError_t ics_launch_synth_gradk_fft(const float* u, const float* f, float* e, const float* spec, const IcsGeom& g, int wy0, int wy1, int wx0, int wx1, int store_all,
                                       float* partial, float* gradk, hipStream_t s);
+// A14 ... A17 and both weight spectra in ONE launch (k_psf_spectra, ics_conv_fft.hip; PSF sizes the tiles take whole, <= 85): every one
+// of the 96 workgroups of the spectrum launch steps a private copy of the PSF (ics_psf_step.h) and transforms its share of it; workgroup 0
+// stores the results.  No workgroup waits for another, so the PSF is read from `psf` and written to `psf_next`: the caller exchanges
+// the two afterwards.
+struct IcsPsfSpectraArgs {
+  const float* psf;     // [K][K][3] local psf before the step
+  float* psf_next;      // ... and after it (another buffer)
+  float* psf_caller;    // as IcsPsfArgs
+  const float* gradk;   // [K][K][3]
+  float* scal;          // ICS_SC_DTPSF recorded
+  int* frozen;          // as IcsPsfArgs; read and written by workgroup 0 alone
+  float* spec_conv;     // the two spectra (ics_launch_fft_spectrum)
+  float* spec_corr;
+  float step;
+  int K, correlation;
+};
+hipError_t ics_launch_psf_spectra(const IcsPsfSpectraArgs& a, hipStream_t s);
 
 // ---- zero-fill of up to ICS_ZERO_MAX device blocks in one launch (the ~24 buffers of a new job: one launch instead of 24 memsets) ----
 #define ICS_ZERO_MAX 32

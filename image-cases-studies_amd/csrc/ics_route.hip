@@ -13,7 +13,7 @@ bool ics_host::psf_supported(int K) { return ics_conv_supported(K) || ics_big_su
 // ---- routing ------------------------------------------------------------------------------------------------------------------------
 // Which kernels a run or a stage launches is decided in ONE place, resolve_route (below check_params), from the geometry, the parameters,
 // the weight tables the job owns, its sticky fallbacks and the routing switches (ics_common.h IcsDebug: conv_path, fused_gradk,
-// planar_image, fft_gradk, fft_fused, fft_conv2, small_iter, overlap -- read nowhere else).  ics_rl_run and ics_rl_stage resolve it once and
+// planar_image, fft_gradk, fft_fused, fft_conv2, fft_psf1, small_iter, overlap -- read nowhere else).  ics_rl_run and ics_rl_stage resolve it once and
 // hand it to the do_* helpers, which dispatch on it; ics_rl_describe copies it.  Family numbers: those of ics_rl_route (include/ics_hip.h); the Route itself: ics_host.h.
 
 // The FFT-tile pipeline (ics_conv_fft.hip; round 5): A1 / A3 / A11 as LDS-resident 128 x 128 overlap-save transforms on planar mirrors,
@@ -143,6 +143,11 @@ Route ics_host::resolve_route(const ics_rl* j, const ics_rl_params* p, bool in_r
   else if (K >= 33 && !vector && (psf_blocks_only(K) || r.tiles || matrix_req || path != 1)) r.gradk = GK_SPLIT;
   else if (ics_big_supported(K)) r.gradk = GK_SIZED;
   else r.gradk = matrix_gk ? GK_MATRIX : GK_FP32;
+
+  // The PSF step of a blind inner iteration on the tiles as ONE launch behind the fused A11 + A13 unit (k_psf_spectra, ics_conv_fft.hip): inside
+  // ics_rl_run, shipped loop, PSF sizes the tiles take whole.  Tap blocks, the two-kernel gradient, the PAM kinds, single stages and every other
+  // route keep k_psf + k_fft_spectrum; ICS_FFT_PSF1=0 restores that pair here too.
+  r.psf1 = in_run && r.tiles && shipped && r.gradk == GK_FUSED_TILES && ics_conv_fft_supported(K) && sw(d.fft_psf1) != 0;
 
   // Small frames (ics_small.hip): every (tile, channel) of the u-frame on a compute unit of its own, the operands of the five inner iterations
   // resident in LDS, ONE cooperative launch per outer iteration instead of 25 - 30.  What ICS_CONV_AUTO picks for the shipped loop when the

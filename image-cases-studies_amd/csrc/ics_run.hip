@@ -318,8 +318,22 @@ static int do_synth_gradk(ics_rl* j, const Route& r, const ics_rl_params* p, int
   return ICS_OK;
 }
 
-static int do_psf(ics_rl* j, const ics_rl_params* p, Prof& pr) {
+// A14 ... A17 and the weights of the next convolutions.  Route::psf1 (tile runs): one launch, k_psf_spectra, which steps the PSF and builds
+// both spectra -- and nothing else: the row-pair tables wconv / wcorr and the fp16 Toeplitz tables bt_conv / bt_corr, which no tile kernel
+// reads, stay as the run's first pack_weights left them.  Everything that reads them packs them first: ics_rl_run before its loop, every
+// convolution stage of ics_rl_stage (ICS_STAGE_PSF_UPDATE through k_psf itself), ics_rl_upload / ics_rl_write of a PSF, undo() of the
+// overlapped loop and the small-frame fallback in RunLoop::body; a run does not leave the tiles half way, and after an error return
+// (FftScope) the next run or stage is one of those.
+static int do_psf(ics_rl* j, const Route& r, const ics_rl_params* p, Prof& pr) {
   RC(pr.begin(ICS_K_PSF_UPDATE));
+  if (r.psf1) {
+    IcsPsfSpectraArgs a;
+    a.psf = j->psf; a.psf_next = j->psf_next; a.psf_caller = j->psf_caller; a.gradk = j->gradk; a.scal = j->scal; a.frozen = j->flags;
+    a.spec_conv = j->spec_conv; a.spec_corr = j->spec_corr; a.step = p->step_factor; a.K = j->g.K; a.correlation = p->correlation;
+    if (!a.spec_conv || !a.spec_corr) return ics_set_error(ICS_ESTATE, "FFT pipeline: no weight spectra");
+    HIPCHK(ics_launch_psf_spectra(a, j->ctx->stream));
+    { float* t = j->psf; j->psf = j->psf_next; j->psf_next = t; }   // what is queued from here on reads the stepped PSF
+  } else
   RC(pack_weights(j, 1, p->step_factor, p->correlation, j->ctx->stream));
   RC(pr.end());
   return ICS_OK;
@@ -497,7 +511,7 @@ struct RunLoop {
           else RC(do_conv(j, r, 0, p, itt, 0, pr));
         }
         if (!(fused_gk || fused_fft)) RC(do_gradk(j, r, pr));   // A12+A13
-        RC(do_psf(j, p, pr));                                 // A14-A17
+        RC(do_psf(j, r, p, pr));                              // A14-A17
       } else if (fuse && !last) {
         RC(do_conv(j, r, 2, p, itt, 0, pr));                  // A5-A10 fused with A1+A2 of itt+1
         have_e = true;
@@ -773,7 +787,7 @@ extern "C" int ics_rl_stage(ics_rl* j, int stage, const ics_rl_params* p) {
       HIPCHK(hipMemsetAsync(j->red, 0, 8 * ICS_RED_STRIDE * sizeof(uint32_t), s));
       RC(do_conv2(j, p, 0, pr));
       break;
-    case ICS_STAGE_PSF_UPDATE: RC(do_psf(j, p, pr)); break;
+    case ICS_STAGE_PSF_UPDATE: RC(do_psf(j, r, p, pr)); break;
     case ICS_STAGE_MAJORIZE: RC(do_majorize(j, pr)); break;
     case ICS_STAGE_STATS:
       HIPCHK(hipMemsetAsync(j->dacc, 0, 8 * sizeof(double), s));
