@@ -1,5 +1,5 @@
 // ics_images.hip -- the ics_img_* entries of the C ABI (include/ics_hip.h).  Host side only; kernels live in ics_img.hip / ics_img_filters.hip /
-// ics_img_tvdenoise.hip / ics_img_wavelet.hip / ics_img_noise.hip / ics_img_despeckle.hip / ics_img_guided.hip / ics_img_llf.hip (what these seven share: ics_img_px.h) / ics_resize.hip.
+// ics_img_tvdenoise.hip / ics_img_wavelet.hip / ics_img_noise.hip / ics_img_despeckle.hip / ics_img_blurwidth.hip / ics_img_guided.hip / ics_img_llf.hip (what these eight share: ics_img_px.h) / ics_resize.hip.
 #include "ics_host.h"
 
 using namespace ics_host;
@@ -387,6 +387,38 @@ extern "C" int ics_img_despeckle(const ics_img* src, int radius, const float thr
   }
   RC(op.finish(e));
   if (replaced) { replaced[0] = got[0]; replaced[1] = coupling ? 0u : got[1]; replaced[2] = coupling ? 0u : got[2]; }
+  return ICS_OK;
+}
+
+// ---- blur profile of a device image (csrc/ics_img_blurwidth.hip) --------------------------------------------------------------------
+// One route (a second summation order would buy nothing).  The rule that turns the profiles into a width is twenty lines on
+// 2 (max_lag + 1) numbers and lives on the host (lib/_native.py blur_extent).
+extern "C" int ics_img_blur_profile(const ics_img* src, int y0, int y1, int x0, int x1, int max_lag, double* ax, double* ay, long long* nx, long long* ny) {
+  if (!src) return ics_set_error(ICS_EINVAL, "src is NULL");
+  if (!ax || !ay || !nx || !ny) return ics_set_error(ICS_EINVAL, "an output (ax, ay, nx, ny) is NULL");
+  const int H = src->H, W = src->W;
+  if (y0 < 0 || x0 < 0 || y1 > H || x1 > W || y0 >= y1 || x0 >= x1)
+    return ics_set_error(ICS_EINVAL, "window [%d, %d) x [%d, %d) (not empty, inside the %d x %d frame)", y0, y1, x0, x1, H, W);
+  if (max_lag < 0 || max_lag > ICS_IMG_BLURWIDTH_MAX_LAG) return ics_set_error(ICS_EINVAL, "max_lag = %d (0 .. %d)", max_lag, ICS_IMG_BLURWIDTH_MAX_LAG);
+  ics_ctx* c = src->ctx;
+  HIPCHK(hipSetDevice(c->device));
+  const int hw = y1 - y0, ww = x1 - x0, n = max_lag + 1;
+  ImgOp op(c, nullptr, "img_blur_profile");
+  float* partial = nullptr;
+  double *result = nullptr, got[2 * (ICS_IMG_BLURWIDTH_MAX_LAG + 1)];
+  hipError_t e = op.alloc((void**)&partial, ics_img_blurwidth_partial_floats(hw, ww, max_lag) * sizeof(float));
+  if (e == hipSuccess) e = op.alloc((void**)&result, 2 * n * sizeof(double));
+  if (e == hipSuccess) e = op.begin();
+  if (e == hipSuccess) e = ics_launch_img_blurwidth(src->d, H, W, y0, y1, x0, x1, max_lag, c->cus, partial, result, c->stream);
+  if (e == hipSuccess) e = op.end();
+  if (e == hipSuccess) e = hipMemcpyAsync(got, result, 2 * n * sizeof(double), hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  RC(op.finish(e));
+  for (int l = 0; l < n; ++l) {
+    ax[l] = got[l]; ay[l] = got[n + l];
+    nx[l] = ww - 1 - l > 0 ? (long long)hw * (ww - 1 - l) : 0;
+    ny[l] = hw - 1 - l > 0 ? (long long)ww * (hw - 1 - l) : 0;
+  }
   return ICS_OK;
 }
 

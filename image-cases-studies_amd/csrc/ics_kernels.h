@@ -338,3 +338,15 @@ size_t ics_img_llf_pyramid_floats(int H, int W, int levels, int samples);
 size_t ics_img_llf_collapse_floats(int H, int W);
 hipError_t ics_launch_img_llf(const float* src, int H, int W, float sigma, float detail, float edges, int levels, int samples, int coupling, int route,
                               float* pyr, float* r0, float* r1, float* out, hipStream_t s);
+
+// ---- blur width of device-resident images (ics_img_blurwidth.hip): the autocorrelation of the luma's differences along x and y over
+// the window [y0, y1) x [x0, x1), lags 0 .. L <= ICS_IMG_BLURWIDTH_MAX_LAG.  partial: ics_img_blurwidth_partial_floats floats, every
+// one written ([tile][axis][lag], float32 sums of one tile); result: 2 (L + 1) doubles, [axis][lag], the sums over the tiles in tile
+// order divided by the pair counts (0 where there is no pair).  cus: compute units of the device (the persistent grid is sized by it
+// and capped by the max_wgs switch).  One route; f is only read.
+#define ICS_IMG_BLURWIDTH_MAX_LAG 128     // (== include/ics_hip.h)
+size_t ics_img_blurwidth_lds(int L);
+long ics_img_blurwidth_tiles(int hw, int ww);
+size_t ics_img_blurwidth_partial_floats(int hw, int ww, int L);
+hipError_t ics_launch_img_blurwidth(const float* f, int H, int W, int y0, int y1, int x0, int x1, int L, int cus, float* partial, double* result,
+                                    hipStream_t s);

@@ -117,8 +117,14 @@ def deblur_module(pic, filename, dest_path, blur_width, confidence=10, tolerance
     the gamma-encoded domain, before the odd-size padding and before either deconvolution phase: a hot or dead pixel, which
     Richardson-Lucy would turn into a PSF-sized ring at every pyramid level, or a NaN, which would spread over the frame, is
     replaced by the median of its window and nothing else is touched; one line "Despeckle : <counts> replaced" is printed.
-    `despeckle=("auto",)` takes six sigma of the picture's own noise.  On the resident path the frame stays in HBM."""
+    `despeckle=("auto",)` takes six sigma of the picture's own noise.  On the resident path the frame stays in HBM.
+    `blur_width="auto"` or `("auto", max_width)` (max_width 63 unless given, odd): the width is read from the picture
+    (`utils.estimate_blur_width`: the autocorrelation of the derivatives, the reference's "TODO : automatically evaluate blur size"),
+    on the gamma-encoded frame the solver will see, after `despeckle` and before the odd-size padding, over the mask box where `mask`
+    is given and over the whole frame otherwise; one line "Blur width : 9 (x 8.41, y 7.63)" is printed and everything runs as if
+    that integer had been passed.  On the resident path the frame is read where it lies and only the profiles come back."""
     despeckle = _despeckle_args(despeckle)
+    auto_width = _blur_width_args(blur_width)
     sharpen = _sharpen_args(sharpen)
     denoise = _denoise_args(denoise)
     local_contrast = _local_contrast_args(local_contrast)
@@ -141,11 +147,13 @@ def deblur_module(pic, filename, dest_path, blur_width, confidence=10, tolerance
         pic, replaced = utils.despeckle(np.ascontiguousarray(pic, dtype=np.float32), *despeckle, count=True)
         print("Despeckle :", ", ".join(str(n) for n in replaced), "replaced")
     step = {"normal": 1e-3, "high": 5e-4, "veryhigh": 1e-4, "low": 5e-3}[quality]   # :106-113
-    if blur_width < 3:
-        raise ValueError("The blur width should be at least 3 pixels.")
-    elif blur_width % 2 == 0:
-        raise ValueError("The blur width should be odd. You can use %i." % (blur_width + 1))
+    if auto_width is None:
+        if blur_width < 3:
+            raise ValueError("The blur width should be at least 3 pixels.")
+        elif blur_width % 2 == 0:
+            raise ValueError("The blur width should be odd. You can use %i." % (blur_width + 1))
     M, N = pic.shape[0], pic.shape[1]
+    whole_frame = mask is None
     if mask is None:
         mask = [M // 2, N // 2]
     top, bottom = mask[0] - mask_size // 2, mask[0] + mask_size // 2       # :138-141
@@ -153,6 +161,8 @@ def deblur_module(pic, filename, dest_path, blur_width, confidence=10, tolerance
     print("Mask size :", (bottom - top + 1), "×", (right - left + 1))
     if not (top > 0 and bottom < M and left > 0 and right < N):
         raise ValueError("The mask is outside the picture boundaries. Move its center inside or reduce the blur size.")
+    if auto_width is not None:
+        blur_width = _auto_blur_width(pic, auto_width, None if whole_frame else (top, bottom + 1, left, right + 1))
     correlation = {"static": False, "motion": True}[blur]                 # :154-157
     tolerance /= 100.
     odd_vert = odd_hor = False
@@ -297,6 +307,30 @@ def _denoise_args(denoise):
     return float(weight), int(iterations), coupling
 
 
+def _blur_width_args(blur_width):
+    """`blur_width` of deblur_module -> None for a number (the reference's two checks apply to it) or the max_width of "auto" /
+    ("auto", max_width), checked (ValueError)"""
+    if isinstance(blur_width, str):
+        if blur_width != "auto":
+            raise ValueError("blur_width takes an odd integer, \"auto\" or (\"auto\", max_width), got %r" % (blur_width,))
+        return utils.blur_width_args()
+    if isinstance(blur_width, (tuple, list)):
+        if len(blur_width) != 2 or blur_width[0] != "auto":
+            raise ValueError("blur_width takes an odd integer, \"auto\" or (\"auto\", max_width), got %r" % (blur_width,))
+        try:
+            return utils.blur_width_args(blur_width[1])
+        except ValueError as exc:
+            raise ValueError("blur_width: %s" % exc)
+    return None
+
+
+def _auto_blur_width(frame, max_width, window):
+    """the estimate on the frame (an array or a DeviceImage), its one printed line, the width"""
+    est = utils.estimate_blur_width(frame, max_width, window)
+    print("Blur width : %d (x %.2f, y %.2f)" % est)
+    return est.width
+
+
 def _despeckle_args(despeckle):
     """`despeckle` of deblur_module -> None or (threshold, radius, coupling): threshold a float, a tuple of three floats or
     ("auto", strength)"""
@@ -401,10 +435,12 @@ def _deblur_device(pic, filename, dest_path, blur_width, confidence, tolerance, 
     one download of the result; pad_image, gamma, the window views, the resize between pyramid levels and the solver all
     work on `lib._native.DeviceImage`s.  Line references as in `deblur_module` above."""
     from lib._native import DeviceImage
-    if blur_width < 3:
-        raise ValueError("The blur width should be at least 3 pixels.")
-    elif blur_width % 2 == 0:
-        raise ValueError("The blur width should be odd. You can use %i." % (blur_width + 1))
+    auto_width = _blur_width_args(blur_width)
+    if auto_width is None:
+        if blur_width < 3:
+            raise ValueError("The blur width should be at least 3 pixels.")
+        elif blur_width % 2 == 0:
+            raise ValueError("The blur width should be odd. You can use %i." % (blur_width + 1))
     raw = DeviceImage.from_host(pic)              # (uint8 / uint16 pictures cross PCIe as they are and become float32 on the device)
     pic_d = raw.pad_edge(1, 1, 1, 1)                                        # :94
     raw.close()
@@ -415,6 +451,7 @@ def _deblur_device(pic, filename, dest_path, blur_width, confidence, tolerance, 
         print("Despeckle :", ", ".join(str(n) for n in replaced), "replaced")
     step = {"normal": 1e-3, "high": 5e-4, "veryhigh": 1e-4, "low": 5e-3}[quality]
     M, N, _ = pic_d.shape
+    whole_frame = mask is None
     if mask is None:
         mask = [M // 2, N // 2]
     top, bottom = mask[0] - mask_size // 2, mask[0] + mask_size // 2
@@ -422,6 +459,8 @@ def _deblur_device(pic, filename, dest_path, blur_width, confidence, tolerance, 
     print("Mask size :", (bottom - top + 1), "×", (right - left + 1))
     if not (top > 0 and bottom < M and left > 0 and right < N):
         raise ValueError("The mask is outside the picture boundaries. Move its center inside or reduce the blur size.")
+    if auto_width is not None:
+        blur_width = _auto_blur_width(pic_d, auto_width, None if whole_frame else (top, bottom + 1, left, right + 1))
     correlation = {"static": False, "motion": True}[blur]
     tolerance /= 100.
     odd_vert = odd_hor = False

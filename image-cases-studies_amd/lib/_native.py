@@ -96,6 +96,7 @@ IMG_LLF_MAX_LEVELS = 10          # include/ics_hip.h ICS_IMG_LLF_MAX_LEVELS: pyr
 IMG_LLF_MAX_SAMPLES = 16         # include/ics_hip.h ICS_IMG_LLF_MAX_SAMPLES: remapped copies it interpolates between
 IMG_DESPECKLE_MAX_RADIUS = 2     # include/ics_hip.h ICS_IMG_DESPECKLE_MAX_RADIUS: 3 x 3 and 5 x 5 windows
 IMG_DESPECKLE_STRENGTH = 6.0     # include/ics_hip.h ICS_IMG_DESPECKLE_STRENGTH: threshold "auto" of despeckle is this many sigma of the noise
+IMG_BLURWIDTH_MAX_LAG = 128      # include/ics_hip.h ICS_IMG_BLURWIDTH_MAX_LAG: largest lag of DeviceImage.blur_profile
 IMG_NOISE_STRENGTH = 3.0         # include/ics_hip.h ICS_IMG_NOISE_STRENGTH: thresholds="auto" cuts this many standard deviations
 IMG_NOISE_E = (0.89079631027875839, 0.20066385102441897, 0.085507504753369934, 0.041217444374316202,      # include/ics_hip.h ICS_IMG_NOISE_E: e_j, the L2
                0.020424966592781431, 0.01018975924921329, 0.0050920466808193074, 0.0025456694579151255)   # norm of the response of scale j to a unit impulse
@@ -176,6 +177,7 @@ def load():
     lib.ics_img_tv_denoise.argtypes = [vp, cf, ci, ci, ci, C.POINTER(vp)]
     lib.ics_img_wavelet_equalize.argtypes = [vp, ci, vp, vp, cf, ci, ci, C.POINTER(vp)]
     lib.ics_img_noise_estimate.argtypes = [vp, ci, ci, C.POINTER(cf), C.POINTER(cf), C.POINTER(cf)]
+    lib.ics_img_blur_profile.argtypes = [vp, ci, ci, ci, ci, ci, C.POINTER(cd), C.POINTER(cd), C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]
     lib.ics_img_despeckle.argtypes = [vp, ci, C.POINTER(cf), ci, ci, C.POINTER(vp), C.POINTER(C.c_uint)]
     lib.ics_img_guided.argtypes = [vp, ci, cf, cf, ci, ci, C.POINTER(vp)]
     lib.ics_img_local_laplacian.argtypes = [vp, cf, cf, cf, ci, ci, ci, ci, C.POINTER(vp)]
@@ -200,7 +202,7 @@ def load():
                  "ics_rl_download", "ics_rl_run", "ics_rl_stage", "ics_rl_read", "ics_rl_write", "ics_rl_read_rows", "ics_rl_write_rows", "ics_rl_copy_rows", "ics_normalize_kernel",
                  "ics_tv", "ics_conv2d_symm", "ics_usm", "ics_bilateral", "ics_resize_bicubic", "ics_img_create", "ics_img_shape",
                  "ics_img_upload", "ics_img_upload_int", "ics_img_download", "ics_img_pad_edge", "ics_img_crop", "ics_img_paste", "ics_img_gamma", "ics_img_resize",
-                 "ics_img_convolve", "ics_img_usm", "ics_img_bilateral", "ics_img_tv_denoise", "ics_img_wavelet_equalize", "ics_img_noise_estimate", "ics_img_despeckle", "ics_img_guided", "ics_img_local_laplacian",
+                 "ics_img_convolve", "ics_img_usm", "ics_img_bilateral", "ics_img_tv_denoise", "ics_img_wavelet_equalize", "ics_img_noise_estimate", "ics_img_blur_profile", "ics_img_despeckle", "ics_img_guided", "ics_img_local_laplacian",
                  "ics_rl_upload_img", "ics_rl_download_img", "ics_group_create", "ics_group_info", "ics_group_barrier",
                  "ics_group_allreduce_max", "ics_group_allreduce_sum", "ics_group_describe", "ics_group_allgather"):
         getattr(lib, name).restype = ci
@@ -281,6 +283,78 @@ def noise_args(coupling="vector", route=0):
     """the arguments of DeviceImage.noise_estimate checked (ValueError) and as (coupling, route): a string, an int"""
     _coupling(coupling)
     return coupling, _route(route, "1: every pass recomputes the detail scale, 2: the first pass stores the keys")
+
+
+BlurProfile = collections.namedtuple("BlurProfile", "ax ay nx ny")
+BLUR_SATURATED = math.inf        # blur_extent of a profile that does not end within its lags
+
+
+def blur_profile_args(max_lag, window, shape):
+    """the arguments of DeviceImage.blur_profile checked (ValueError) and as (max_lag, (y0, y1, x0, x1)); shape: (H, W, ...) of the frame"""
+    try:
+        whole = int(max_lag) == max_lag and not isinstance(max_lag, bool)
+    except (TypeError, ValueError, OverflowError):
+        whole = False
+    if not whole or not 0 <= int(max_lag) <= IMG_BLURWIDTH_MAX_LAG:
+        raise ValueError("max_lag %r (an integer, 0 to %d)" % (max_lag, IMG_BLURWIDTH_MAX_LAG))
+    H, W = int(shape[0]), int(shape[1])
+    if window is None:
+        window = (0, H, 0, W)
+    try:
+        y0, y1, x0, x1 = (int(v) for v in window)
+        exact = all(int(v) == v for v in window)
+    except (TypeError, ValueError):
+        y0 = y1 = x0 = x1 = 0
+        exact = False
+    if not exact or not (0 <= y0 < y1 <= H and 0 <= x0 < x1 <= W):
+        raise ValueError("window %r ((y0, y1, x0, x1), half-open, not empty, inside the %d x %d frame)" % (window, H, W))
+    return int(max_lag), (y0, y1, x0, x1)
+
+
+def blur_extent(A):
+    """The width in pixels that one derivative-autocorrelation profile A[0 .. L] (DeviceImage.blur_profile) describes, in double.  The
+    profile of a picture blurred by a box, a disc or a motion line is a triangle whose base is the PSF's extent along the axis.
+    P = A[2] + 2 (A[2] - A[3]) is its peak with the picture's white noise taken out (which touches lags 0 and 1 only); h the largest
+    lag up to which A stays at or above P / 2 from lag 2 on.  h >= 3: the zero crossing of the least-squares line through lags 2 .. h,
+    BLUR_SATURATED if the line does not fall or crosses beyond L.  Otherwise the first lag >= 2 at or below 0.05 P (BLUR_SATURATED if
+    none).  1 where P is not positive or the profile has fewer than 4 lags.  Restated in tests/blur_width_ref.py.  ValueError: a
+    profile that is not finite (a NaN in the frame: despeckle first)."""
+    A = np.asarray(A, dtype=np.float64)
+    if A.ndim != 1:
+        raise ValueError("a profile is one-dimensional, got shape %s" % (A.shape,))
+    if not np.isfinite(A).all():
+        raise ValueError("the blur profile is not finite: the frame holds NaN or inf (despeckle it first)")
+    L = A.size - 1
+    if A.size < 4:
+        return 1.0
+    P = A[2] + 2.0 * (A[2] - A[3])
+    if not P > 0:
+        return 1.0
+    h = 1
+    while h + 1 <= L and A[h + 1] >= 0.5 * P:
+        h += 1
+    if h >= 3:
+        l, a = np.arange(2, h + 1, dtype=np.float64), A[2:h + 1]
+        lm, am = l.mean(), a.mean()
+        slope = float(((l - lm) * (a - am)).sum() / ((l - lm) ** 2).sum())
+        if not slope < 0:
+            return BLUR_SATURATED
+        cross = float(lm - am / slope)
+        return BLUR_SATURATED if cross > L else cross
+    for l in range(2, L + 1):
+        if A[l] <= 0.05 * P:
+            return float(l)
+    return BLUR_SATURATED
+
+
+def blur_width_from(ax, ay):
+    """the odd PSF size for deblur_module from the two profiles: max(3, the smallest odd integer >= max(blur_extent(ax),
+    blur_extent(ay)) - 1e-9).  ValueError: a saturated or non-finite profile."""
+    e = max(blur_extent(ax), blur_extent(ay))
+    if e == BLUR_SATURATED:
+        raise ValueError("saturated blur profile: the blur is wider than the lags reach")
+    n = int(math.ceil(e - 1e-9))
+    return max(3, n if n % 2 else n + 1)
 
 
 def _strength(strength):
@@ -656,6 +730,26 @@ class DeviceImage:
         _check(load().ics_img_noise_estimate(self._h, _coupling(coupling), route, *out))
         n = 3 if coupling == "channel" else 1
         return NoiseEstimate(*(tuple(float(v) for v in a[:n]) for a in out))
+
+    def blur_profile(self, max_lag, window=None):
+        """The autocorrelation of the picture's derivatives along x and y, lags 0 .. max_lag <= IMG_BLURWIDTH_MAX_LAG, over the
+        half-open window (y0, y1, x0, x1) (None: the whole frame): BlurProfile(ax, ay, nx, ny), float64 profiles and int64 pair
+        counts of max_lag + 1 entries.  Y = (R + G + B) / 3, dx = Y[y, x+1] - Y[y, x], ax[l] = the mean of dx[y, x] dx[y, x+l] over
+        the pairs inside the window, ay likewise along y; 0 where there is no pair (csrc/ics_img_blurwidth.hip; restated in
+        tests/blur_width_ref.py).  Products and tile sums are float32 in one fixed order, the tiles are summed in double: two calls
+        give identical bits.  blur_extent / blur_width_from read the width from the profiles.  Only the profiles cross PCIe; the
+        call waits for them.  ValueError (before any native call): max_lag no integer in 0 .. 128, a window that is empty or not
+        inside the frame; after it: a profile that is not finite (NaN or inf in the frame: despeckle first)."""
+        max_lag, (y0, y1, x0, x1) = blur_profile_args(max_lag, window, self.shape)
+        n = max_lag + 1
+        ax, ay = np.empty(n, np.float64), np.empty(n, np.float64)
+        nx, ny = np.empty(n, np.int64), np.empty(n, np.int64)
+        dp, lp = C.POINTER(C.c_double), C.POINTER(C.c_longlong)
+        _check(load().ics_img_blur_profile(self._h, y0, y1, x0, x1, max_lag, ax.ctypes.data_as(dp), ay.ctypes.data_as(dp),
+                                           nx.ctypes.data_as(lp), ny.ctypes.data_as(lp)))
+        if not (np.isfinite(ax).all() and np.isfinite(ay).all()):
+            raise ValueError("the blur profile is not finite: the frame holds NaN or inf (despeckle it first)")
+        return BlurProfile(ax, ay, nx, ny)
 
     def despeckle(self, threshold, radius=1, coupling="vector", route=0, count=False):
         """Thresholded median: removes impulses -- hot and dead sensor pixels, salt and pepper, NaN and inf -- and leaves every

@@ -31,6 +31,7 @@ Notes on reference quirks that are kept:
 """
 from __future__ import annotations
 
+import collections
 import os
 import struct
 import time
@@ -201,6 +202,58 @@ def noise_estimate(src, coupling="vector"):
         return img.noise_estimate(coupling)
     finally:
         img.close()
+
+
+BlurWidth = collections.namedtuple("BlurWidth", "width extent_x extent_y")
+
+
+def blur_width_args(max_width=63):
+    """`max_width` of estimate_blur_width checked (ValueError): an odd integer, 3 to IMG_BLURWIDTH_MAX_LAG - 1"""
+    top = _native.IMG_BLURWIDTH_MAX_LAG - 1
+    try:
+        whole = int(max_width) == max_width and not isinstance(max_width, bool)
+    except (TypeError, ValueError, OverflowError):
+        whole = False
+    if not whole or not 3 <= int(max_width) <= top or int(max_width) % 2 == 0:
+        raise ValueError("max_width %r (an odd integer, 3 to %d)" % (max_width, top))
+    return int(max_width)
+
+
+def estimate_blur_width(src, max_width=63, window=None):
+    """Not in the reference, whose driver leaves it open (deconvolve.py:122, "TODO : automatically evaluate blur size") while its README
+    names an ill-chosen blur size as what keeps a pyramid step from converging: the `blur_width` of `deblur_module` from the picture.
+    The derivative of a sharp picture is close to white along its axis, so the derivative of a blurred one correlates with itself
+    over as many pixels as the PSF is wide (Yitzhaky and Kopeika).  The autocorrelation of the luma's differences along x and along
+    y is taken on the device, lags 0 .. max_width + 1 (`DeviceImage.blur_profile`, csrc/ics_img_blurwidth.hip); the host reads the
+    base of each profile's triangle (`lib._native.blur_extent`: half-maximum line fit, lags 0 and 1 left to the picture's noise).
+    Returns BlurWidth(width, extent_x, extent_y): the extents in pixels and width = the smallest odd integer at or above the larger
+    one, 3 at least.  window (y0, y1, x0, x1), half-open: the region to look at (None: the whole frame).  A `lib._native.DeviceImage`
+    is read where it lies; an H x W x 3 array is uploaded once and only the profiles come back.  It cannot see a blur thinner than its
+    projection on the axes (a diagonal line reads as its extents along x and y), a defocus that varies over the frame (it reads an average), or a
+    picture that was never sharp (its own softness adds to the width).  ValueError: max_width not an odd integer in 3 .. 127, a bad
+    window, a frame with NaN or inf (despeckle first), and "blur wider than max_width" where a profile does not end within the lags."""
+    max_width = blur_width_args(max_width)
+    if isinstance(src, _native.DeviceImage):
+        img, own = src, False
+        _native.blur_profile_args(max_width + 1, window, img.shape)
+    else:
+        arr = np.asarray(src)
+        if arr.ndim != 3 or arr.shape[2] != 3:
+            raise ValueError("expected a DeviceImage or an H x W x 3 array, got shape %s" % (arr.shape,))
+        _native.blur_profile_args(max_width + 1, window, arr.shape)         # refused before anything is uploaded
+        img, own = _native.DeviceImage.from_host(np.ascontiguousarray(arr, dtype=np.float32)), True
+    try:
+        prof = img.blur_profile(max_width + 1, window)
+    finally:
+        if own:
+            img.close()
+    ex, ey = _native.blur_extent(prof.ax), _native.blur_extent(prof.ay)
+    if max(ex, ey) == _native.BLUR_SATURATED:
+        raise ValueError("blur wider than max_width = %d (a profile does not end within %d lags): raise max_width" % (max_width, max_width + 1))
+    width = _native.blur_width_from(prof.ax, prof.ay)
+    if width > max_width:
+        raise ValueError("blur wider than max_width = %d (x %.2f, y %.2f)" % (max_width, ex, ey))
+    return BlurWidth(width, ex, ey)
 
 
 def despeckle(src, threshold, radius=1, coupling="vector", count=False):

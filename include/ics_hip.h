@@ -494,6 +494,22 @@ int ics_img_local_laplacian(const ics_img *src, float sigma, float detail, float
 #define ICS_IMG_DESPECKLE_MAX_RADIUS 2
 #define ICS_IMG_DESPECKLE_STRENGTH 6.0f
 int ics_img_despeckle(const ics_img *src, int radius, const float threshold[3], int coupling, int route, ics_img **out, unsigned replaced[3]);
+/* Blur profile of a device image: the autocorrelation of the picture's derivatives along x and along y, from which the blur width is
+ * read (the derivative of a sharp picture is close to white along its axis, so that of a blurred one correlates with itself over
+ * as many pixels as the PSF is wide and no further; Yitzhaky and Kopeika).  Over the half-open window [y0, y1) x [x0, x1):
+ *   Y = (R + G + B) * (1 / 3), every operation rounded once to float32
+ *   dx[y,x] = Y[y,x+1] - Y[y,x], dy[y,x] = Y[y+1,x] - Y[y,x], for both pixels inside the window
+ *   Sx(l) = the sum over the window of dx[y,x] * dx[y,x+l] for every pair inside it, nx(l) = the number of such pairs
+ *     = (y1 - y0) * max(x1 - x0 - 1 - l, 0); Sy(l), ny(l) likewise with dy along y;  l = 0 .. max_lag
+ *   ax[l] = Sx(l) / nx(l), ay[l] = Sy(l) / ny(l), 0 where the count is 0.
+ * Products and the sums inside a tile of 32 x 64 difference values are float32, in one fixed order; the tiles are summed in row-major
+ * order and divided in double.  No atomics: two runs give identical bits.  ax, ay, nx, ny hold max_lag + 1 entries each.  The rule
+ * that turns a profile into an extent (half-maximum line fit, lags 0 and 1 left to the picture's noise) is the Python layer's
+ * blur_extent; it is restated with the profiles in tests/blur_width_ref.py.  One route.  Queued on the context's stream, its kernels
+ * bracketed for ics_ctx_last_kernel_ms, then the 2 (max_lag + 1) doubles are copied back and WAITED FOR.  src is not written.
+ * ICS_EINVAL: src or an output NULL, an empty window or one outside the frame, max_lag < 0 or > ICS_IMG_BLURWIDTH_MAX_LAG. */
+#define ICS_IMG_BLURWIDTH_MAX_LAG 128
+int ics_img_blur_profile(const ics_img *src, int y0, int y1, int x0, int x1, int max_lag, double *ax, double *ay, long long *nx, long long *ny);
 /* richardson_lucy_MM(image[iy:iy+M, ix:ix+N], u[uy:uy+uM, ux:ux+uN], psf, ...) with both windows taken from device
  * images (deconvolve.py:277-313 passes such views); psf is a host MK*MK*3 array as in ics_rl_upload. */
 int ics_rl_upload_img(ics_rl *job, const ics_img *image, int iy, int ix, const ics_img *u, int uy, int ux, const float *psf);

@@ -1,6 +1,6 @@
 """Timing of the lib/utils.py filters on one seeded SIZE x SIZE RGB float32 picture (GPU box), one JSON line:
 
-    python scripts/filters_timing.py [SIZE=4096] [guided | llf | noise | despeckle]       ("guided", "llf", "noise", "despeckle": that section alone)
+    python scripts/filters_timing.py [SIZE=4096] [guided | llf | noise | despeckle | blurwidth]       (a section name: that section alone)
 
   resident   the filters on a DeviceImage in HBM (csrc/ics_img_filters.hip): device time of the kernels (HIP events around them,
              ics_ctx_last_kernel_ms; warm, median of 25) and wall time of the queued call up to a stream synchronise
@@ -43,6 +43,12 @@
              same 24 B/px; it has no event bracket, so 16 copies are queued back to back and the wall time up to one stream
              synchronise is divided by 16: launch and wait are paid once per round, not per copy) as the figure to read it against;
              "auto" is what route=0 takes
+  blurwidth  lib.utils.estimate_blur_width on the resident frame (csrc/ics_img_blurwidth.hip) at max_width 15, 63 and 127: kernel ms of
+             the two launches (median and minimum of 9 rounds) and the wall time of the call (it waits for its profiles), the lags and
+             the LDS bytes per workgroup; beside it DeviceImage.copy() of the same frame as in the despeckle section, and
+             `deblur_module` end to end at blur 15 on the 8-bit picture bench.py uses (frames resident, iterations 20, the second
+             call), which the estimate precedes; "one_nonblind_outer_ms" = 5 x the README's 0.47 ms per inner iteration at 4096^2 is
+             what the estimate at max_width 63 is to stay under
   checks     the resident USM must not take longer than the three float64 calls, in kernel time and in wall time (a guard against a
              broken kernel, not a target); the exit status is 1 if one of them fails
 Starts no child process; a job script puts its own time limit around it."""
@@ -206,6 +212,53 @@ def despeckle_section(img, ctx, size):
     return res
 
 
+BLURWIDTH_MAX_WIDTHS = (15, 63, 127)
+
+
+def blurwidth_section(img, ctx, size):
+    import contextlib
+    import io
+    sys.path.insert(0, os.path.join(ROOT, "image-cases-studies_amd"))
+    import deconvolve as dv
+    res = {}
+    for mw in BLURWIDTH_MAX_WIDTHS:
+        img.blur_profile(mw + 1)                           # warm
+        ctx.synchronize()
+        kernel, wall = [], []
+        for _ in range(REPS_DESPECKLE):
+            t0 = time.perf_counter()
+            prof = img.blur_profile(mw + 1)
+            wall.append((time.perf_counter() - t0) * 1e3)
+            kernel.append(ctx.last_kernel_ms())
+        res["max_width_%d" % mw] = {"lags": mw + 2, "kernel_ms": round(float(np.median(kernel)), 4), "min_ms": round(float(np.min(kernel)), 4),
+                                    "wall_ms": round(float(np.median(wall)), 4),
+                                    "lds_bytes": 4 * (32 * (64 + 128 + 1) + (32 + mw + 2) * 64 + 2 * (mw + 2) * 4),
+                                    "extents": [round(e, 3) if np.isfinite(e) else "saturated" for e in (_native.blur_extent(prof.ax), _native.blur_extent(prof.ay))]}
+    img.copy().close()                                     # warm
+    ctx.synchronize()
+    wall = []
+    for _ in range(REPS_DESPECKLE):
+        t0 = time.perf_counter()
+        outs = [img.copy() for _ in range(DESPECKLE_COPIES)]
+        ctx.synchronize()
+        wall.append((time.perf_counter() - t0) * 1e3 / DESPECKLE_COPIES)
+        for out in outs:
+            out.close()
+    res["copy"] = {"ms_per_copy": round(float(np.median(wall)), 4), "min_ms": round(float(np.min(wall)), 4), "copies_per_round": DESPECKLE_COPIES}
+    coarse = np.random.default_rng(0).random((size // 8 + 2, size // 8 + 2, 3))
+    pic = (np.repeat(np.repeat(coarse, 8, 0), 8, 1)[:size, :size] * 200 + 20).astype(np.uint8)
+    dt = None
+    for _ in range(2):                                     # the first call builds the jobs
+        with contextlib.redirect_stdout(io.StringIO()):
+            t0 = time.perf_counter()
+            dv.deblur_module(pic, "t", ".", 15, mask=[size // 2, size // 2], mask_size=min(255, size // 2 - 3), display=False, iterations=20, save=False,
+                             device_resident=True)
+            dt = time.perf_counter() - t0
+    res["deblur_module_blur15_seconds"] = round(dt, 4)
+    res["one_nonblind_outer_ms"] = round(5 * 0.47, 2)
+    return res
+
+
 def main():
     size = int(sys.argv[1]) if len(sys.argv) > 1 else 4096
     ctx = _native.Context.get()
@@ -220,6 +273,9 @@ def main():
         return 0
     if sys.argv[2:] == ["noise"]:
         print(json.dumps({"size": size, "device": ctx.name, "noise": noise_section(img, ctx, size)}))
+        return 0
+    if sys.argv[2:] == ["blurwidth"]:
+        print(json.dumps({"size": size, "device": ctx.name, "blurwidth": blurwidth_section(img, ctx, size)}))
         return 0
     if sys.argv[2:] == ["despeckle"]:
         print(json.dumps({"size": size, "device": ctx.name, "despeckle": despeckle_section(img, ctx, size)}))
@@ -295,6 +351,7 @@ def main():
     res["llf"] = llf_section(img, ctx, size)
     res["noise"] = noise_section(img, ctx, size)
     res["despeckle"] = despeckle_section(img, ctx, size)
+    res["blurwidth"] = blurwidth_section(img, ctx, size)
     res["checks"] = {"%s_%s" % (name, what): res["resident"][name][what] <= res["per_channel_f64"][name][what]
                      for name in ("usm_gauss15", "usm_bessel15") for what in ("kernel_ms", "wall_ms")}
     print(json.dumps(res))
