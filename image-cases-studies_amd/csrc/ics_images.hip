@@ -1,5 +1,5 @@
 // ics_images.hip -- the ics_img_* entries of the C ABI (include/ics_hip.h).  Host side only; kernels live in ics_img.hip / ics_img_filters.hip /
-// ics_img_tvdenoise.hip / ics_img_wavelet.hip / ics_img_noise.hip / ics_img_despeckle.hip / ics_img_blurwidth.hip / ics_img_guided.hip / ics_img_llf.hip (what these eight share: ics_img_px.h) / ics_resize.hip.
+// ics_img_tvdenoise.hip / ics_img_wavelet.hip / ics_img_noise.hip / ics_img_despeckle.hip / ics_img_blurwidth.hip / ics_img_mask.hip / ics_img_guided.hip / ics_img_llf.hip (what these nine share: ics_img_px.h) / ics_resize.hip.
 #include "ics_host.h"
 
 using namespace ics_host;
@@ -419,6 +419,42 @@ extern "C" int ics_img_blur_profile(const ics_img* src, int y0, int y1, int x0, 
     nx[l] = ww - 1 - l > 0 ? (long long)hw * (ww - 1 - l) : 0;
     ny[l] = hw - 1 - l > 0 ? (long long)ww * (hw - 1 - l) : 0;
   }
+  return ICS_OK;
+}
+
+// ---- window scores of a device image (csrc/ics_img_mask.hip) ----------------------------------------------------------------------
+// One route.  The cells and the candidate table stay on the device; the five result numbers, and the score map where asked for, come back.
+extern "C" int ics_img_window_scores(const ics_img* src, int y0, int y1, int x0, int x1, int size, float clip, int* box_y, int* box_x, double* score, double* trace,
+                                     long long* clipped, double* map, int map_rows, int map_cols) {
+  if (!src) return ics_set_error(ICS_EINVAL, "src is NULL");
+  if (!box_y || !box_x || !score || !trace || !clipped) return ics_set_error(ICS_EINVAL, "an output (box_y, box_x, score, trace, clipped) is NULL");
+  const int H = src->H, W = src->W;
+  if (y0 < 0 || x0 < 0 || y1 > H || x1 > W || y0 >= y1 || x0 >= x1)
+    return ics_set_error(ICS_EINVAL, "region [%d, %d) x [%d, %d) (not empty, inside the %d x %d frame)", y0, y1, x0, x1, H, W);
+  if (size < ICS_IMG_MASK_CELL) return ics_set_error(ICS_EINVAL, "size = %d (at least %d)", size, ICS_IMG_MASK_CELL);
+  const int hr = y1 - y0, wr = x1 - x0;
+  if (hr < size || wr < size) return ics_set_error(ICS_EINVAL, "region of %d x %d pixels, smaller than the box (size = %d)", hr, wr, size);
+  if (!(clip > 0.f)) return ics_set_error(ICS_EINVAL, "clip = %g (above 0; inf keeps every finite pixel)", (double)clip);
+  const int nci = ics_img_mask_candidates(hr, size), ncj = ics_img_mask_candidates(wr, size);
+  if (map && (map_rows != nci || map_cols != ncj)) return ics_set_error(ICS_EINVAL, "map of %d x %d scores (the candidate grid is %d x %d)", map_rows, map_cols, nci, ncj);
+  ics_ctx* c = src->ctx;
+  HIPCHK(hipSetDevice(c->device));
+  const size_t cand = (size_t)nci * ncj;
+  ImgOp op(c, nullptr, "img_window_scores");
+  float* cells = nullptr;
+  double *table = nullptr, *result = nullptr, got[5];
+  hipError_t e = op.alloc((void**)&cells, (size_t)ics_img_mask_cells(hr, size) * ics_img_mask_cells(wr, size) * 4 * sizeof(float));
+  if (e == hipSuccess) e = op.alloc((void**)&table, 3 * cand * sizeof(double));
+  if (e == hipSuccess) e = op.alloc((void**)&result, sizeof got);
+  if (e == hipSuccess) e = op.begin();
+  if (e == hipSuccess) e = ics_launch_img_mask(src->d, H, W, y0, y1, x0, x1, size, clip, c->cus, cells, table, result, c->stream);
+  if (e == hipSuccess) e = op.end();
+  if (e == hipSuccess) e = hipMemcpyAsync(got, result, sizeof got, hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess && map) e = hipMemcpyAsync(map, table, cand * sizeof(double), hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  RC(op.finish(e));
+  *box_y = y0 + ICS_IMG_MASK_CELL * (int)got[0]; *box_x = x0 + ICS_IMG_MASK_CELL * (int)got[1];
+  *score = got[2]; *trace = got[3]; *clipped = (long long)got[4];
   return ICS_OK;
 }
 

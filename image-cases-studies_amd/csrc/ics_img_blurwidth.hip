@@ -36,7 +36,7 @@ static_assert(ACTW == 64 && ACTH % ACTWAVES == 0 && ACTPX * ACTWAVES == ACTH && 
 __device__ __forceinline__ float bw_luma(const float* __restrict__ p) {
   float v[3];
   ld3(p, v);
-  return __fmul_rn(__fadd_rn(__fadd_rn(v[0], v[1]), v[2]), 0.333333343267440796f);   // float32(1 / 3)
+  return px_luma(v);
 }
 
 // the halving exchange: ACTCH sums per lane in, the sum over the wave of sum number bw_wave_slot(lane) out, in every lane

@@ -350,3 +350,17 @@ long ics_img_blurwidth_tiles(int hw, int ww);
 size_t ics_img_blurwidth_partial_floats(int hw, int ww, int L);
 hipError_t ics_launch_img_blurwidth(const float* f, int H, int W, int y0, int y1, int x0, int x1, int L, int cus, float* partial, double* result,
                                     hipStream_t s);
+
+// ---- mask choice on device-resident images (ics_img_mask.hip): the box of `size` pixels a side inside the region [y0, y1) x [x0, x1) on
+// which the blind phase should estimate the PSF: per 16 x 16 cell the structure tensor of the luma differences and the number of
+// unusable pixels (a channel at or above clip, NaN, inf), per candidate box (origins on the 16-px grid) the smaller eigenvalue over its
+// whole cells, then the arg-max.  ics_img_mask_candidates / ics_img_mask_cells: boxes and cells along one axis of that extent (0: the
+// region is smaller than the box).  cells: 4 floats per cell, every one written; table: 3 doubles per candidate (score[], trace[],
+// clipped[] as 64-bit integers), every one written; result: 5 doubles {i, j, score, trace, clipped}.  cus: compute units of the device
+// (the persistent grid of the cell kernel is sized by it and capped by the max_wgs switch).  One route; f is only read.
+#define ICS_IMG_MASK_CELL 16              // (== include/ics_hip.h)
+size_t ics_img_mask_lds();
+int ics_img_mask_candidates(int extent, int size);
+int ics_img_mask_cells(int extent, int size);
+hipError_t ics_launch_img_mask(const float* f, int H, int W, int y0, int y1, int x0, int x1, int size, float clip, int cus, float* cells, double* table, double* result,
+                               hipStream_t s);

@@ -122,9 +122,16 @@ def deblur_module(pic, filename, dest_path, blur_width, confidence=10, tolerance
     (`utils.estimate_blur_width`: the autocorrelation of the derivatives, the reference's "TODO : automatically evaluate blur size"),
     on the gamma-encoded frame the solver will see, after `despeckle` and before the odd-size padding, over the mask box where `mask`
     is given and over the whole frame otherwise; one line "Blur width : 9 (x 8.41, y 7.63)" is printed and everything runs as if
-    that integer had been passed.  On the resident path the frame is read where it lies and only the profiles come back."""
+    that integer had been passed.  On the resident path the frame is read where it lies and only the profiles come back.
+    `mask="auto"` or `("auto", clip)` (clip 0.99 unless given): the centre of the PSF-estimation box is chosen from the picture
+    (`utils.best_mask`: the box whose structure tensor of luma differences has the largest smaller eigenvalue -- edges in every
+    orientation -- pixels with a channel at or above `clip` left out), on the gamma-encoded frame the solver will see, after
+    `despeckle`, before the automatic blur width (which is then read over the chosen box) and before the odd-size padding, among the
+    boxes that lie inside the picture; one line "Mask : [95, 143] (score 2.93e-03, clipped 0.0 %)" is printed before "Mask size :" and
+    everything runs as if that centre had been passed.  On the resident path the frame is read where it lies."""
     despeckle = _despeckle_args(despeckle)
     auto_width = _blur_width_args(blur_width)
+    auto_mask = _mask_args(mask)
     sharpen = _sharpen_args(sharpen)
     denoise = _denoise_args(denoise)
     local_contrast = _local_contrast_args(local_contrast)
@@ -153,6 +160,8 @@ def deblur_module(pic, filename, dest_path, blur_width, confidence=10, tolerance
         elif blur_width % 2 == 0:
             raise ValueError("The blur width should be odd. You can use %i." % (blur_width + 1))
     M, N = pic.shape[0], pic.shape[1]
+    if auto_mask is not None:
+        mask = _auto_mask(pic, mask_size, auto_mask)
     whole_frame = mask is None
     if mask is None:
         mask = [M // 2, N // 2]
@@ -331,6 +340,43 @@ def _auto_blur_width(frame, max_width, window):
     return est.width
 
 
+def _mask_args(mask):
+    """`mask` of deblur_module -> None for None or a centre [y, x] of two integers, the clip level of "auto" / ("auto", clip), checked
+    (ValueError)"""
+    from lib import _native
+    form = "mask takes None, a centre [y, x] of two integers, \"auto\" or (\"auto\", clip), got %r" % (mask,)
+    if mask is None:
+        return None
+    if isinstance(mask, str):
+        if mask != "auto":
+            raise ValueError(form)
+        return 0.99
+    if not isinstance(mask, (list, tuple, np.ndarray)):
+        raise ValueError(form)
+    pair = len(mask) == 2
+    if pair and isinstance(mask[0], str):
+        if mask[0] != "auto":
+            raise ValueError(form)
+        try:
+            return _native.window_scores_args(_native.IMG_MASK_CELL, None, mask[1], (_native.IMG_MASK_CELL, _native.IMG_MASK_CELL))[2]
+        except ValueError as exc:
+            raise ValueError("mask: %s" % exc)
+    if not pair or not all(isinstance(v, (int, np.integer)) and not isinstance(v, bool) for v in mask):
+        raise ValueError(form)
+    return None
+
+
+def _auto_mask(frame, mask_size, clip):
+    """the choice on the 1-px-padded frame (an array or a DeviceImage) among the boxes the reference's boundary test accepts, its one
+    printed line, the centre"""
+    M, N = frame.shape[0], frame.shape[1]
+    if 2 * (mask_size // 2) + 1 > min(M, N) - 2:
+        raise ValueError("The mask is outside the picture boundaries. Move its center inside or reduce the blur size.")
+    got = utils.best_mask(frame, mask_size, clip, (1, M - 1, 1, N - 1))
+    print("Mask : [%d, %d] (score %.2e, clipped %.1f %%)" % (got.center_y, got.center_x, got.score, 100.0 * got.clipped))
+    return [got.center_y, got.center_x]
+
+
 def _despeckle_args(despeckle):
     """`despeckle` of deblur_module -> None or (threshold, radius, coupling): threshold a float, a tuple of three floats or
     ("auto", strength)"""
@@ -436,6 +482,7 @@ def _deblur_device(pic, filename, dest_path, blur_width, confidence, tolerance, 
     work on `lib._native.DeviceImage`s.  Line references as in `deblur_module` above."""
     from lib._native import DeviceImage
     auto_width = _blur_width_args(blur_width)
+    auto_mask = _mask_args(mask)
     if auto_width is None:
         if blur_width < 3:
             raise ValueError("The blur width should be at least 3 pixels.")
@@ -451,6 +498,8 @@ def _deblur_device(pic, filename, dest_path, blur_width, confidence, tolerance, 
         print("Despeckle :", ", ".join(str(n) for n in replaced), "replaced")
     step = {"normal": 1e-3, "high": 5e-4, "veryhigh": 1e-4, "low": 5e-3}[quality]
     M, N, _ = pic_d.shape
+    if auto_mask is not None:
+        mask = _auto_mask(pic_d, mask_size, auto_mask)
     whole_frame = mask is None
     if mask is None:
         mask = [M // 2, N // 2]

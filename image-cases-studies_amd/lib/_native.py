@@ -97,6 +97,7 @@ IMG_LLF_MAX_SAMPLES = 16         # include/ics_hip.h ICS_IMG_LLF_MAX_SAMPLES: re
 IMG_DESPECKLE_MAX_RADIUS = 2     # include/ics_hip.h ICS_IMG_DESPECKLE_MAX_RADIUS: 3 x 3 and 5 x 5 windows
 IMG_DESPECKLE_STRENGTH = 6.0     # include/ics_hip.h ICS_IMG_DESPECKLE_STRENGTH: threshold "auto" of despeckle is this many sigma of the noise
 IMG_BLURWIDTH_MAX_LAG = 128      # include/ics_hip.h ICS_IMG_BLURWIDTH_MAX_LAG: largest lag of DeviceImage.blur_profile
+IMG_MASK_CELL = 16               # include/ics_hip.h ICS_IMG_MASK_CELL: DeviceImage.window_scores ranks boxes on this grid and scores whole cells of this side
 IMG_NOISE_STRENGTH = 3.0         # include/ics_hip.h ICS_IMG_NOISE_STRENGTH: thresholds="auto" cuts this many standard deviations
 IMG_NOISE_E = (0.89079631027875839, 0.20066385102441897, 0.085507504753369934, 0.041217444374316202,      # include/ics_hip.h ICS_IMG_NOISE_E: e_j, the L2
                0.020424966592781431, 0.01018975924921329, 0.0050920466808193074, 0.0025456694579151255)   # norm of the response of scale j to a unit impulse
@@ -178,6 +179,8 @@ def load():
     lib.ics_img_wavelet_equalize.argtypes = [vp, ci, vp, vp, cf, ci, ci, C.POINTER(vp)]
     lib.ics_img_noise_estimate.argtypes = [vp, ci, ci, C.POINTER(cf), C.POINTER(cf), C.POINTER(cf)]
     lib.ics_img_blur_profile.argtypes = [vp, ci, ci, ci, ci, ci, C.POINTER(cd), C.POINTER(cd), C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]
+    lib.ics_img_window_scores.argtypes = [vp, ci, ci, ci, ci, ci, cf, C.POINTER(ci), C.POINTER(ci), C.POINTER(cd), C.POINTER(cd), C.POINTER(C.c_longlong),
+                                          C.POINTER(cd), ci, ci]
     lib.ics_img_despeckle.argtypes = [vp, ci, C.POINTER(cf), ci, ci, C.POINTER(vp), C.POINTER(C.c_uint)]
     lib.ics_img_guided.argtypes = [vp, ci, cf, cf, ci, ci, C.POINTER(vp)]
     lib.ics_img_local_laplacian.argtypes = [vp, cf, cf, cf, ci, ci, ci, ci, C.POINTER(vp)]
@@ -202,7 +205,7 @@ def load():
                  "ics_rl_download", "ics_rl_run", "ics_rl_stage", "ics_rl_read", "ics_rl_write", "ics_rl_read_rows", "ics_rl_write_rows", "ics_rl_copy_rows", "ics_normalize_kernel",
                  "ics_tv", "ics_conv2d_symm", "ics_usm", "ics_bilateral", "ics_resize_bicubic", "ics_img_create", "ics_img_shape",
                  "ics_img_upload", "ics_img_upload_int", "ics_img_download", "ics_img_pad_edge", "ics_img_crop", "ics_img_paste", "ics_img_gamma", "ics_img_resize",
-                 "ics_img_convolve", "ics_img_usm", "ics_img_bilateral", "ics_img_tv_denoise", "ics_img_wavelet_equalize", "ics_img_noise_estimate", "ics_img_blur_profile", "ics_img_despeckle", "ics_img_guided", "ics_img_local_laplacian",
+                 "ics_img_convolve", "ics_img_usm", "ics_img_bilateral", "ics_img_tv_denoise", "ics_img_wavelet_equalize", "ics_img_noise_estimate", "ics_img_blur_profile", "ics_img_window_scores", "ics_img_despeckle", "ics_img_guided", "ics_img_local_laplacian",
                  "ics_rl_upload_img", "ics_rl_download_img", "ics_group_create", "ics_group_info", "ics_group_barrier",
                  "ics_group_allreduce_max", "ics_group_allreduce_sum", "ics_group_describe", "ics_group_allgather"):
         getattr(lib, name).restype = ci
@@ -355,6 +358,40 @@ def blur_width_from(ax, ay):
         raise ValueError("saturated blur profile: the blur is wider than the lags reach")
     n = int(math.ceil(e - 1e-9))
     return max(3, n if n % 2 else n + 1)
+
+
+WindowScores = collections.namedtuple("WindowScores", "box_y box_x score trace clipped map")
+
+
+def window_scores_args(size, region, clip, shape):
+    """the arguments of DeviceImage.window_scores checked (ValueError) and as (size, (y0, y1, x0, x1), clip); shape: (H, W, ...) of the
+    frame.  Runs without a device."""
+    try:
+        whole = int(size) == size and not isinstance(size, bool)
+    except (TypeError, ValueError, OverflowError):
+        whole = False
+    if not whole or not IMG_MASK_CELL <= int(size) < 2 ** 31:
+        raise ValueError("size %r (the box side: an integer, at least %d)" % (size, IMG_MASK_CELL))
+    H, W = int(shape[0]), int(shape[1])
+    if region is None:
+        region = (0, H, 0, W)
+    try:
+        y0, y1, x0, x1 = (int(v) for v in region)
+        exact = all(int(v) == v for v in region)
+    except (TypeError, ValueError):
+        y0 = y1 = x0 = x1 = 0
+        exact = False
+    if not exact or not (0 <= y0 < y1 <= H and 0 <= x0 < x1 <= W):
+        raise ValueError("region %r ((y0, y1, x0, x1), half-open, not empty, inside the %d x %d frame)" % (region, H, W))
+    if y1 - y0 < int(size) or x1 - x0 < int(size):
+        raise ValueError("region %r of %d x %d pixels is smaller than the box (size %d)" % (region, y1 - y0, x1 - x0, int(size)))
+    try:
+        level = float(np.float32(clip)) if not isinstance(clip, (bool, str)) else math.nan
+    except (TypeError, ValueError, OverflowError):
+        level = math.nan
+    if not level > 0:
+        raise ValueError("clip %r (a number above 0; inf keeps every finite pixel)" % (clip,))
+    return int(size), (y0, y1, x0, x1), level
 
 
 def _strength(strength):
@@ -750,6 +787,28 @@ class DeviceImage:
         if not (np.isfinite(ax).all() and np.isfinite(ay).all()):
             raise ValueError("the blur profile is not finite: the frame holds NaN or inf (despeckle it first)")
         return BlurProfile(ax, ay, nx, ny)
+
+    def window_scores(self, size, region=None, clip=0.99, scores=False):
+        """The box of `size` pixels a side, inside the half-open region (y0, y1, x0, x1) (None: the whole frame), on which a blind
+        deconvolution should estimate the PSF: WindowScores(box_y, box_x, score, trace, clipped, map).  The score of a box is the
+        smaller eigenvalue of its structure tensor of luma differences -- strong edges in EVERY orientation -- with the pixels
+        that have a channel at or above `clip` (or a NaN or an inf) left out of the sums; trace is the mean squared gradient, clipped
+        the number of such pixels.  Boxes are ranked on a grid of IMG_MASK_CELL pixels from the region's origin and scored over
+        their whole cells, the inner 16 (size // 16) pixels; the largest score wins, ties go to the lowest box_y, then box_x
+        (csrc/ics_img_mask.hip, include/ics_hip.h; restated in tests/mask_ref.py).  box_y, box_x: the box's origin in the frame.
+        scores=True: map is the float64 array of every candidate's score, else None.  Cell sums are float32 in one fixed order, the
+        cells of a box are added in double: two calls give identical bits.  Only these few numbers cross PCIe; the call waits for
+        them.  ValueError (before any native call): size no integer >= 16, a region that is empty, not inside the frame or smaller
+        than the box, clip not above 0; after it: a score that is not finite (values beyond float32's range with clip=inf)."""
+        size, (y0, y1, x0, x1), clip = window_scores_args(size, region, clip, self.shape)
+        rows, cols = (y1 - y0 - size) // IMG_MASK_CELL + 1, (x1 - x0 - size) // IMG_MASK_CELL + 1
+        grid = np.empty((rows, cols), np.float64) if scores else None
+        by, bx, sc, tr, bad = C.c_int(), C.c_int(), C.c_double(), C.c_double(), C.c_longlong()
+        _check(load().ics_img_window_scores(self._h, y0, y1, x0, x1, size, clip, C.byref(by), C.byref(bx), C.byref(sc), C.byref(tr), C.byref(bad),
+                                            grid.ctypes.data_as(C.POINTER(C.c_double)) if scores else None, rows, cols))
+        if not (math.isfinite(sc.value) and math.isfinite(tr.value)) or (scores and not np.isfinite(grid).all()):
+            raise ValueError("the window score is not finite: the frame holds values beyond float32's range (lower clip)")
+        return WindowScores(by.value, bx.value, sc.value, tr.value, bad.value, grid)
 
     def despeckle(self, threshold, radius=1, coupling="vector", route=0, count=False):
         """Thresholded median: removes impulses -- hot and dead sensor pixels, salt and pepper, NaN and inf -- and leaves every

@@ -256,6 +256,52 @@ def estimate_blur_width(src, max_width=63, window=None):
     return BlurWidth(width, ex, ey)
 
 
+MaskChoice = collections.namedtuple("MaskChoice", "center_y center_x score trace clipped")
+
+
+def best_mask_args(mask_size, clip, region, shape):
+    """the arguments of best_mask checked (ValueError, without a device) and as (box side, region, clip): the box deblur_module cuts
+    for `mask_size` is 2 (mask_size // 2) + 1 pixels a side"""
+    try:
+        whole = int(mask_size) == mask_size and not isinstance(mask_size, bool)
+    except (TypeError, ValueError, OverflowError):
+        whole = False
+    if not whole or 2 * (int(mask_size) // 2) + 1 < _native.IMG_MASK_CELL:
+        raise ValueError("mask_size %r (an integer, at least %d)" % (mask_size, _native.IMG_MASK_CELL))
+    return _native.window_scores_args(2 * (int(mask_size) // 2) + 1, region, clip, shape)
+
+
+def best_mask(src, mask_size=255, clip=0.99, region=None):
+    """Not in the reference, whose README has the user select "a specific zone to refine the PSF": the `mask` of `deblur_module` from
+    the picture.  The blind phase estimates the PSF on one box of the frame; a box of sky or bokeh gives it nothing to estimate from,
+    a box with one dominant edge direction leaves the PSF free along that direction, and clipped pixels break the linear blur model
+    Richardson-Lucy assumes.  The box chosen is the one whose structure tensor of luma differences has the largest SMALLER eigenvalue
+    (Shi and Tomasi's criterion on a whole window), pixels with a channel at or above `clip` left out (`DeviceImage.window_scores`,
+    csrc/ics_img_mask.hip).  Returns MaskChoice(center_y, center_x, score, trace, clipped): the centre to pass as `mask=` with this
+    `mask_size` (box origin + mask_size // 2, the box being 2 (mask_size // 2) + 1 pixels a side), the box's score and mean squared
+    gradient, and the fraction of the scored pixels that are clipped.  region (y0, y1, x0, x1), half-open: where the box may lie
+    (None: the whole frame).  A `lib._native.DeviceImage` is read where it lies; an H x W x 3 array is uploaded once and a few numbers
+    come back.  It ranks boxes on a 16-px grid from the region's origin, scores the inner 16 (side // 16) pixels of a box, and
+    prefers the sharpest textured zone: under a blur that varies over the frame that is the zone in focus, not necessarily the
+    subject.  ValueError: mask_size below 16, a bad region or one smaller than the box, clip not above 0."""
+    if isinstance(src, _native.DeviceImage):
+        img, own = src, False
+        size, region, clip = best_mask_args(mask_size, clip, region, img.shape)
+    else:
+        arr = np.asarray(src)
+        if arr.ndim != 3 or arr.shape[2] != 3:
+            raise ValueError("expected a DeviceImage or an H x W x 3 array, got shape %s" % (arr.shape,))
+        size, region, clip = best_mask_args(mask_size, clip, region, arr.shape)   # refused before anything is uploaded
+        img, own = _native.DeviceImage.from_host(np.ascontiguousarray(arr, dtype=np.float32)), True
+    try:
+        got = img.window_scores(size, region, clip)
+    finally:
+        if own:
+            img.close()
+    scored = float(_native.IMG_MASK_CELL * (size // _native.IMG_MASK_CELL)) ** 2
+    return MaskChoice(got.box_y + size // 2, got.box_x + size // 2, got.score, got.trace, got.clipped / scored)
+
+
 def despeckle(src, threshold, radius=1, coupling="vector", count=False):
     """Not in the reference's lib/utils.py, which has no rank filter: a thresholded median for the frame BEFORE the deconvolution.
     Richardson-Lucy treats a hot pixel as signal and turns it into a PSF-sized ring; a NaN spreads over the frame.  A value is

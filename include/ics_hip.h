@@ -510,6 +510,28 @@ int ics_img_despeckle(const ics_img *src, int radius, const float threshold[3], 
  * ICS_EINVAL: src or an output NULL, an empty window or one outside the frame, max_lag < 0 or > ICS_IMG_BLURWIDTH_MAX_LAG. */
 #define ICS_IMG_BLURWIDTH_MAX_LAG 128
 int ics_img_blur_profile(const ics_img *src, int y0, int y1, int x0, int x1, int max_lag, double *ax, double *ay, long long *nx, long long *ny);
+/* Window scores of a device image: the box of `size` pixels a side, inside the half-open region [y0, y1) x [x0, x1), on which the blind
+ * phase should estimate the PSF.  A window is good for that when it holds strong edges in every orientation (one dominant direction
+ * leaves the PSF free along it) and no clipped pixels (they break the linear blur model): the score is the smaller eigenvalue of the
+ * window's structure tensor of luma differences (Shi and Tomasi's criterion on a whole window), clipped pixels taken out of the sums.
+ *   usable: fabsf(v) < clip for all three channels (a NaN or an inf is never usable; clip = inf keeps every finite pixel)
+ *   Y = (R + G + B) * (1 / 3), every operation rounded once to float32
+ *   dx[y,x] = Y[y,x+1] - Y[y,x] where x + 1 < x1 and both pixels are usable, else 0; dy[y,x] = Y[y+1,x] - Y[y,x] likewise with y + 1 < y1
+ *   cells of 16 x 16 pixels, n = size / 16, off = (size - 16 n) / 2, the grid anchored at (y0 + off, x0 + off); per cell
+ *     Sxx = sum dx dx, Syy = sum dy dy, Sxy = sum dx dy (float32, one fixed order, no contraction) and the number of unusable pixels
+ *   candidates: boxes with origin (y0 + 16 i, x0 + 16 j), i = 0 .. (y1 - y0 - size) / 16, j likewise; box (i, j) is scored over the
+ *     cells [i, i + n) x [j, j + n) -- the whole cells centred in the box, its inner 16 n pixels -- added in double in row-major order:
+ *     trace = (Sxx + Syy) / (16 n)^2, score = max(0, (Sxx + Syy - sqrt((Sxx - Syy)^2 + 4 Sxy^2)) / 2 / (16 n)^2), clipped = the count
+ *   choice: the largest score, ties to the lowest i, then the lowest j (a flat or wholly clipped frame: box (0, 0), score 0).
+ * box_y, box_x: the origin of the chosen box in the frame (y0 + 16 i, x0 + 16 j); score, trace, clipped: its values.  map (may be
+ * NULL): the score of every candidate, row-major, map_rows x map_cols == the candidate grid.  No atomics: two runs give identical bits.
+ * One route.  Queued on the context's stream, its kernels bracketed for ics_ctx_last_kernel_ms, then the result block (and the map) is
+ * copied back and WAITED FOR.  src is not written.  ICS_EINVAL, the message naming the argument: src or a scalar output NULL, a region
+ * that is empty or outside the frame, size < 16, a region smaller than size on either axis, clip not positive (or NaN), a map of
+ * another shape than the candidate grid. */
+#define ICS_IMG_MASK_CELL 16
+int ics_img_window_scores(const ics_img *src, int y0, int y1, int x0, int x1, int size, float clip, int *box_y, int *box_x, double *score, double *trace,
+                          long long *clipped, double *map, int map_rows, int map_cols);
 /* richardson_lucy_MM(image[iy:iy+M, ix:ix+N], u[uy:uy+uM, ux:ux+uN], psf, ...) with both windows taken from device
  * images (deconvolve.py:277-313 passes such views); psf is a host MK*MK*3 array as in ics_rl_upload. */
 int ics_rl_upload_img(ics_rl *job, const ics_img *image, int iy, int ix, const ics_img *u, int uy, int ux, const float *psf);

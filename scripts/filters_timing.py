@@ -1,6 +1,6 @@
 """Timing of the lib/utils.py filters on one seeded SIZE x SIZE RGB float32 picture (GPU box), one JSON line:
 
-    python scripts/filters_timing.py [SIZE=4096] [guided | llf | noise | despeckle | blurwidth]       (a section name: that section alone)
+    python scripts/filters_timing.py [SIZE=4096] [guided | llf | noise | despeckle | blurwidth | mask]       (a section name: that section alone)
 
   resident   the filters on a DeviceImage in HBM (csrc/ics_img_filters.hip): device time of the kernels (HIP events around them,
              ics_ctx_last_kernel_ms; warm, median of 25) and wall time of the queued call up to a stream synchronise
@@ -49,6 +49,10 @@
              `deblur_module` end to end at blur 15 on the 8-bit picture bench.py uses (frames resident, iterations 20, the second
              call), which the estimate precedes; "one_nonblind_outer_ms" = 5 x the README's 0.47 ms per inner iteration at 4096^2 is
              what the estimate at max_width 63 is to stay under
+  mask       DeviceImage.window_scores on the resident frame (csrc/ics_img_mask.hip) at mask_size 63, 255 and 1023 (those that fit the
+             frame), clip 0.99: kernel ms of the three launches (median and minimum of 9 rounds), the wall time of the call (it waits
+             for its five numbers), the candidates, the cells per box and the LDS bytes per workgroup of the cell kernel; beside it
+             DeviceImage.copy() of the same frame as in the despeckle section (24 B/px against the 12 B/px this operator reads)
   checks     the resident USM must not take longer than the three float64 calls, in kernel time and in wall time (a guard against a
              broken kernel, not a target); the exit status is 1 if one of them fails
 Starts no child process; a job script puts its own time limit around it."""
@@ -212,6 +216,21 @@ def despeckle_section(img, ctx, size):
     return res
 
 
+def copy_row(img, ctx):
+    """DeviceImage.copy() of the frame, queued back to back as in the despeckle section"""
+    img.copy().close()                                     # warm
+    ctx.synchronize()
+    wall = []
+    for _ in range(REPS_DESPECKLE):
+        t0 = time.perf_counter()
+        outs = [img.copy() for _ in range(DESPECKLE_COPIES)]
+        ctx.synchronize()
+        wall.append((time.perf_counter() - t0) * 1e3 / DESPECKLE_COPIES)
+        for out in outs:
+            out.close()
+    return {"ms_per_copy": round(float(np.median(wall)), 4), "min_ms": round(float(np.min(wall)), 4), "copies_per_round": DESPECKLE_COPIES}
+
+
 BLURWIDTH_MAX_WIDTHS = (15, 63, 127)
 
 
@@ -234,17 +253,7 @@ def blurwidth_section(img, ctx, size):
                                     "wall_ms": round(float(np.median(wall)), 4),
                                     "lds_bytes": 4 * (32 * (64 + 128 + 1) + (32 + mw + 2) * 64 + 2 * (mw + 2) * 4),
                                     "extents": [round(e, 3) if np.isfinite(e) else "saturated" for e in (_native.blur_extent(prof.ax), _native.blur_extent(prof.ay))]}
-    img.copy().close()                                     # warm
-    ctx.synchronize()
-    wall = []
-    for _ in range(REPS_DESPECKLE):
-        t0 = time.perf_counter()
-        outs = [img.copy() for _ in range(DESPECKLE_COPIES)]
-        ctx.synchronize()
-        wall.append((time.perf_counter() - t0) * 1e3 / DESPECKLE_COPIES)
-        for out in outs:
-            out.close()
-    res["copy"] = {"ms_per_copy": round(float(np.median(wall)), 4), "min_ms": round(float(np.min(wall)), 4), "copies_per_round": DESPECKLE_COPIES}
+    res["copy"] = copy_row(img, ctx)
     coarse = np.random.default_rng(0).random((size // 8 + 2, size // 8 + 2, 3))
     pic = (np.repeat(np.repeat(coarse, 8, 0), 8, 1)[:size, :size] * 200 + 20).astype(np.uint8)
     dt = None
@@ -256,6 +265,29 @@ def blurwidth_section(img, ctx, size):
             dt = time.perf_counter() - t0
     res["deblur_module_blur15_seconds"] = round(dt, 4)
     res["one_nonblind_outer_ms"] = round(5 * 0.47, 2)
+    return res
+
+
+MASK_SIZES = (63, 255, 1023)
+
+
+def mask_section(img, ctx, size):
+    res = {"clip": 0.99, "lds_bytes": 4 * (64 + 1) ** 2}
+    for ms in MASK_SIZES:
+        if ms > size:
+            continue
+        img.window_scores(ms)                              # warm
+        ctx.synchronize()
+        kernel, wall = [], []
+        for _ in range(REPS_DESPECKLE):
+            t0 = time.perf_counter()
+            got = img.window_scores(ms)
+            wall.append((time.perf_counter() - t0) * 1e3)
+            kernel.append(ctx.last_kernel_ms())
+        res["mask_size_%d" % ms] = {"candidates": ((size - ms) // _native.IMG_MASK_CELL + 1) ** 2, "cells_per_box": (ms // _native.IMG_MASK_CELL) ** 2,
+                                    "kernel_ms": round(float(np.median(kernel)), 4), "min_ms": round(float(np.min(kernel)), 4),
+                                    "wall_ms": round(float(np.median(wall)), 4), "box": [got.box_y, got.box_x], "score": got.score}
+    res["copy"] = copy_row(img, ctx)
     return res
 
 
@@ -276,6 +308,9 @@ def main():
         return 0
     if sys.argv[2:] == ["blurwidth"]:
         print(json.dumps({"size": size, "device": ctx.name, "blurwidth": blurwidth_section(img, ctx, size)}))
+        return 0
+    if sys.argv[2:] == ["mask"]:
+        print(json.dumps({"size": size, "device": ctx.name, "mask": mask_section(img, ctx, size)}))
         return 0
     if sys.argv[2:] == ["despeckle"]:
         print(json.dumps({"size": size, "device": ctx.name, "despeckle": despeckle_section(img, ctx, size)}))
@@ -352,6 +387,7 @@ def main():
     res["noise"] = noise_section(img, ctx, size)
     res["despeckle"] = despeckle_section(img, ctx, size)
     res["blurwidth"] = blurwidth_section(img, ctx, size)
+    res["mask"] = mask_section(img, ctx, size)
     res["checks"] = {"%s_%s" % (name, what): res["resident"][name][what] <= res["per_channel_f64"][name][what]
                      for name in ("usm_gauss15", "usm_bessel15") for what in ("kernel_ms", "wall_ms")}
     print(json.dumps(res))
