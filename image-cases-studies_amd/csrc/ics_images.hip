@@ -1,5 +1,5 @@
 // ics_images.hip -- the ics_img_* entries of the C ABI (include/ics_hip.h).  Host side only; kernels live in ics_img.hip / ics_img_filters.hip /
-// ics_img_tvdenoise.hip / ics_img_wavelet.hip / ics_img_noise.hip / ics_img_despeckle.hip / ics_img_blurwidth.hip / ics_img_mask.hip / ics_img_guided.hip / ics_img_llf.hip (what these nine share: ics_img_px.h) / ics_resize.hip.
+// ics_img_tvdenoise.hip / ics_img_wavelet.hip / ics_img_noise.hip / ics_img_despeckle.hip / ics_img_blurwidth.hip / ics_img_mask.hip / ics_img_guided.hip / ics_img_llf.hip (what these nine share: ics_img_px.h) / ics_img_wiener.hip / ics_resize.hip.
 #include "ics_host.h"
 
 using namespace ics_host;
@@ -456,6 +456,50 @@ extern "C" int ics_img_window_scores(const ics_img* src, int y0, int y1, int x0,
   *box_y = y0 + ICS_IMG_MASK_CELL * (int)got[0]; *box_x = x0 + ICS_IMG_MASK_CELL * (int)got[1];
   *score = got[2]; *trace = got[3]; *clipped = (long long)got[4];
   return ICS_OK;
+}
+
+// ---- Wiener deconvolution of a device image (csrc/ics_img_wiener.hip) -------------------------------------------------------------
+// One route.  Two spectrum frames and a block of tables from the pool; the PSF goes up planar through put_table.
+static int wiener_shape(int H, int W, int K, int* Py, int* Px) {
+  if (H < 1 || W < 1) return ics_set_error(ICS_EINVAL, "bad image size %d x %d", H, W);
+  if (K < 3 || K > ICS_PSF_MAX || !(K & 1)) return ics_set_error(ICS_EINVAL, "K = %d (odd, 3 .. %d)", K, ICS_PSF_MAX);
+  if (K > H || K > W) return ics_set_error(ICS_EINVAL, "K = %d above the smaller side of the %d x %d frame", K, H, W);
+  if (!ics_img_wiener_sizes(H, W, K, Py, Px))
+    return ics_set_error(ICS_ENOSUP, "a %d x %d frame with a %d x %d PSF needs a transform of %d x %d points (H + K - 1, W + K - 1); the limit is %d a side",
+                         H, W, K, K, H + K - 1, W + K - 1, ICS_IMG_WIENER_MAX);
+  return ICS_OK;
+}
+extern "C" int ics_img_wiener_plan(int H, int W, int K, int* Py, int* Px, size_t* workspace_bytes) {
+  int py = 0, px = 0;
+  RC(wiener_shape(H, W, K, &py, &px));
+  if (Py) *Py = py;
+  if (Px) *Px = px;
+  if (workspace_bytes) *workspace_bytes = 2 * ics_img_wiener_frame_bytes(py, px) + ics_img_wiener_table_bytes(K, py, px);
+  return ICS_OK;
+}
+extern "C" int ics_img_wiener(const ics_img* src, const float* psf, int K, float balance, ics_img** out) {
+  RC(check_new(src, out));
+  if (!psf) return ics_set_error(ICS_EINVAL, "psf is NULL");
+  if (!std::isfinite(balance) || !(balance > 0.f)) return ics_set_error(ICS_EINVAL, "balance = %g (must be finite and > 0)", (double)balance);
+  const int H = src->H, W = src->W;
+  int Py = 0, Px = 0;
+  RC(wiener_shape(H, W, K, &Py, &Px));
+  ics_ctx* c = src->ctx;
+  HIPCHK(hipSetDevice(c->device));
+  std::vector<float> planar((size_t)3 * K * K);
+  for (int ch = 0; ch < 3; ++ch)
+    for (int i = 0; i < K * K; ++i) planar[(size_t)ch * K * K + i] = psf[(size_t)3 * i + ch];
+  ImgOp op(c, out, "img_wiener");
+  RC(img_new(c, H, W, out));
+  float2 *A = nullptr, *B = nullptr;
+  void* tables = nullptr;
+  hipError_t e = op.alloc((void**)&A, ics_img_wiener_frame_bytes(Py, Px));
+  if (e == hipSuccess) e = op.alloc((void**)&B, ics_img_wiener_frame_bytes(Py, Px));
+  if (e == hipSuccess) e = op.alloc(&tables, ics_img_wiener_table_bytes(K, Py, Px));
+  if (e == hipSuccess) e = put_table(c, ics_img_wiener_psf_slot(tables, K, Py, Px), planar);
+  if (e == hipSuccess) e = op.begin();
+  if (e == hipSuccess) e = ics_launch_img_wiener(src->d, H, W, K, balance, Py, Px, A, B, tables, (*out)->d, c->stream);
+  return op.finish(e);
 }
 
 // ---- guided filter of a device image (csrc/ics_img_guided.hip) ------------------------------------------------------------------

@@ -1,0 +1,287 @@
+// ics_img_wiener.hip -- Wiener deconvolution of a device-resident image by a known PSF (ics_img_wiener, include/ics_hip.h): H x W x 3
+// float32, HWC, contiguous; the PSF K x K per channel, every channel of sum 1.  One 2-D transform of the whole frame, fp32, no atomics,
+// every sum in one fixed order: two runs give identical bits.  Restated in float64 in tests/wiener_ref.py.
+//
+//   Py, Px   = the smallest powers of two >= H + K - 1, W + K - 1 (ics_img_wiener_sizes), at most WN_MAX
+//   ext      : the frame extended to Py x Px so that the wrap-around carries no step: along y, for every column, rows H .. Py - 1 are
+//              (1 - t / g) f[H - 1] + (t / g) f[0], g = Py - H + 1, t = 1 .. g - 1; then the same along x on all Py rows
+//   Hc       = the transform of channel c of the PSF, zero padded, its centre tap rolled to (0, 0)
+//   L(ky,kx) = 4 sin^2(pi ky / Py) + 4 sin^2(pi kx / Px)  (= 4 - 2 cos(2 pi ky / Py) - 2 cos(2 pi kx / Px), the Laplacian's transfer)
+//   G        = conj(Hc) / (|Hc|^2 + balance L^2);  out_c = real(inverse transform(G * transform(ext_c)))[:H, :W], nothing clipped
+//
+// The line transform (wn_fft): a Stockham autosort transform of one line of N = 2^n points in LDS, radix 4 with one leading radix-2
+// stage where n is odd, N / 4 butterflies a stage over the workgroup's lanes, the line ping-ponging between two buffers of N float2.
+// Stage reads are four runs of consecutive float2 (conflict free), its writes go out at a stride of p float2.  A lane takes two
+// butterflies of a stage at a time, all their loads before the arithmetic.  Twiddles come from one table per axis, laid out by stage:
+// the stage of sub-transform length p reads {w, w^2, w^3}, w = exp(-2 pi i k / 4p), of its k = 0 .. p - 1 as 3 p consecutive float2 at
+// offset p - p0 (p0 = 1, or 2 behind the radix-2 stage), N - p0 float2 in all -- a wave's 64 lanes read 1.5 KB in a row.  (One table
+// exp(-2 pi i m / N) read at a stride of N / 4p was the first form: in the middle stages every lane of a load hit a cache line of its
+// own, and the three loads were what a stage took: the whole filter at 4096^2, K = 15 took 9.30 ms, 1.8 ms of it per pass over the
+// 3 x 8192 lines of 8192 points, against 6.63 ms now.)
+//
+// Seven kernels, two frames A, B of 3 Py Px float2 each (a spectrum is never read along a column: lines of 8192 points leave room
+// for one column per workgroup, and 8-byte reads a row apart are what ics_stats.hip measured as its slowest pass):
+//   k_img_wn_tables    : the two twiddle tables and 4 sin^2 along y and x, in double, rounded once
+//   k_img_wn_rows      : a workgroup forms row y of channel c of ext (pixel rows from the image, extension rows from its first and last
+//                        row), transforms it and writes A[c][y][:]; all Py rows
+//   k_img_wn_transpose : A[c][y][kx] -> B[c][kx][y] in 32 x 32 tiles through LDS, 256-byte segments on both sides
+//   k_img_wn_psf_rows  : the K non-zero rows of the rolled PSF -> Hr[c][r][:]
+//   k_img_wn_psf_cols  : column kx of Hc from the K values Hr[c][:][kx] at their rolled places, transformed; G / (Py Px) -> A[c][kx][:]
+//                        (A is free between the two transposes)
+//   k_img_wn_cols      : the line B[c][kx][:] forward, times G, inverse, the line staying in LDS in between; written back in place
+//   k_img_wn_transpose : B[c][kx][y < H] -> A[c][y][kx]
+//   k_img_wn_inv_rows  : rows y < H inverse, the real part of the first W points -> out
+#include "ics_kernels.h"
+
+namespace {
+
+#define WN_MAX ICS_IMG_WIENER_MAX              // longest line: two buffers of it are 128 KB of the 160 KB of LDS
+#define WN_LANES 1024                          // lanes of a line's workgroup at most (N / 4 below 4096 points, 64 at least)
+#define WN_TILE 32                             // the transposes' tile side
+
+__device__ __forceinline__ float2 wn_add(float2 a, float2 b) { return make_float2(a.x + b.x, a.y + b.y); }
+__device__ __forceinline__ float2 wn_sub(float2 a, float2 b) { return make_float2(a.x - b.x, a.y - b.y); }
+__device__ __forceinline__ float2 wn_mul(float2 a, float2 b) { return make_float2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x); }
+
+// the line in x (written by the whole workgroup, a barrier passed since) -> its transform, unscaled, in the returned buffer (x or y), a
+// barrier passed.  tw: the table of this N (wn_table)
+template <bool INV>
+__device__ __forceinline__ float2* wn_fft(float2* x, float2* y, int N, int logN, const float2* __restrict__ tw) {
+  const int tid = threadIdx.x, nthr = blockDim.x;
+  int p = 1;
+  if (logN & 1) {
+    const int t = N >> 1;
+    for (int b = tid; b < t; b += nthr) {
+      const float2 u0 = x[b], u1 = x[b + t];
+      y[2 * b] = wn_add(u0, u1);
+      y[2 * b + 1] = wn_sub(u0, u1);
+    }
+    __syncthreads();
+    float2* tmp = x; x = y; y = tmp;
+    p = 2;
+  }
+  const int t = N >> 2, p0 = p;
+  for (; p < N; p <<= 2) {
+    const float2* __restrict__ ws = tw + (p - p0);
+    for (int b0 = tid; b0 < t; b0 += 2 * nthr) {
+      float2 u[2][4], w[2][3];
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        const int b = b0 + h * nthr;
+        if (b < t) {
+          const int k = b & (p - 1);
+#pragma unroll
+          for (int q = 0; q < 4; ++q) u[h][q] = x[b + q * t];
+#pragma unroll
+          for (int q = 0; q < 3; ++q) w[h][q] = ws[3 * k + q];
+        }
+      }
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        const int b = b0 + h * nthr;
+        if (b < t) {
+          const int k = b & (p - 1), j = ((b - k) << 2) + k;
+          if (INV) { w[h][0].y = -w[h][0].y; w[h][1].y = -w[h][1].y; w[h][2].y = -w[h][2].y; }
+          const float2 u0 = u[h][0], u1 = wn_mul(u[h][1], w[h][0]), u2 = wn_mul(u[h][2], w[h][1]), u3 = wn_mul(u[h][3], w[h][2]);
+          const float2 v0 = wn_add(u0, u2), v1 = wn_sub(u0, u2), v2 = wn_add(u1, u3), d = wn_sub(u1, u3);
+          const float2 v3 = INV ? make_float2(-d.y, d.x) : make_float2(d.y, -d.x);   // -+ i d
+          y[j] = wn_add(v0, v2);
+          y[j + p] = wn_add(v1, v3);
+          y[j + 2 * p] = wn_sub(v0, v2);
+          y[j + 3 * p] = wn_sub(v1, v3);
+        }
+      }
+    }
+    __syncthreads();
+    float2* tmp = x; x = y; y = tmp;
+  }
+  return x;
+}
+
+// entry i of the table of an N-point line (N - p0 entries): stage p = p0, 4 p0, ... holds {w, w^2, w^3}(k), k < p, from offset p - p0
+__device__ __forceinline__ float2 wn_table(int i, int logN) {
+  int p = (logN & 1) ? 2 : 1, off = 0;
+  while (i >= off + 3 * p) { off += 3 * p; p <<= 2; }
+  const int r = i - off, k = r / 3, m = r - 3 * k + 1;
+  const double a = (double)(k * m) / (double)(2 * p);            // exp(-2 pi i k m / 4p)
+  return make_float2((float)cospi(a), (float)-sinpi(a));
+}
+
+__global__ __launch_bounds__(256) void k_img_wn_tables(float2* __restrict__ twy, float2* __restrict__ twx, float* __restrict__ lamy, float* __restrict__ lamx, int Py, int Px,
+                                                       int logPy, int logPx) {
+  const int P0 = Py > Px ? Py : Px;
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < P0; i += gridDim.x * 256) {
+    if (i < Py - ((logPy & 1) ? 2 : 1)) twy[i] = wn_table(i, logPy);
+    if (i < Px - ((logPx & 1) ? 2 : 1)) twx[i] = wn_table(i, logPx);
+    if (i < Py) { const double s = sinpi((double)i / (double)Py); lamy[i] = (float)(4.0 * s * s); }
+    if (i < Px) { const double s = sinpi((double)i / (double)Px); lamx[i] = (float)(4.0 * s * s); }
+  }
+}
+
+// grid (3, Py), the three channels of a row side by side: row blockIdx.y of channel blockIdx.x of the extended frame -> A[c][y][:]
+__global__ __launch_bounds__(WN_LANES) void k_img_wn_rows(const float* __restrict__ f, int H, int W, int Py, int Px, int logPx, const float2* __restrict__ tw,
+                                                          float2* __restrict__ A) {
+  extern __shared__ __attribute__((aligned(16))) float2 sm[];
+  const int c = blockIdx.x, y = blockIdx.y, tid = threadIdx.x, nthr = blockDim.x;
+  const long pitch = 3L * W;
+  const bool ext = y >= H;
+  const float* r0 = f + (long)(ext ? H - 1 : y) * pitch + c;   // the row itself, or the last one
+  const float* r1 = f + c;                                     // the first one
+  const float ty = ext ? (float)(y - H + 1) / (float)(Py - H + 1) : 0.f;
+  const auto px = [&](int x) { return ext ? (1.f - ty) * r0[3L * x] + ty * r1[3L * x] : r0[3L * x]; };
+  const float last = px(W - 1), first = px(0), gx = (float)(Px - W + 1);
+  for (int j = tid; j < Px; j += nthr) {
+    float v;
+    if (j < W) v = px(j);
+    else { const float t = (float)(j - W + 1) / gx; v = (1.f - t) * last + t * first; }
+    sm[j] = make_float2(v, 0.f);
+  }
+  __syncthreads();
+  const float2* r = wn_fft<false>(sm, sm + Px, Px, logPx, tw);
+  float2* o = A + ((long)c * Py + y) * Px;
+  for (int j = tid; j < Px; j += nthr) o[j] = r[j];
+}
+
+// grid (ceil(clim / 32), ceil(R / 32), 3): in[plane][R][C] -> out[plane][C][R] for the columns below clim
+__global__ __launch_bounds__(256) void k_img_wn_transpose(const float2* __restrict__ in, int R, int C, int clim, float2* __restrict__ out) {
+  __shared__ float2 tile[WN_TILE][WN_TILE + 1];
+  const int c0 = blockIdx.x * WN_TILE, r0 = blockIdx.y * WN_TILE, tx = threadIdx.x & (WN_TILE - 1), ty = threadIdx.x / WN_TILE;
+  const long plane = (long)blockIdx.z * R * C;
+#pragma unroll
+  for (int k = 0; k < WN_TILE; k += 256 / WN_TILE) {
+    const int r = r0 + ty + k, c = c0 + tx;
+    if (r < R && c < clim) tile[ty + k][tx] = in[plane + (long)r * C + c];
+  }
+  __syncthreads();
+#pragma unroll
+  for (int k = 0; k < WN_TILE; k += 256 / WN_TILE) {
+    const int c = c0 + ty + k, r = r0 + tx;
+    if (c < clim && r < R) out[plane + (long)c * R + r] = tile[tx][ty + k];
+  }
+}
+
+// grid (K, 3): row r of channel c of the PSF (planar, [3][K][K]), zero padded to Px points, tap K / 2 at point 0 -> Hr[c][r][:]
+__global__ __launch_bounds__(WN_LANES) void k_img_wn_psf_rows(const float* __restrict__ psf, int K, int Px, int logPx, const float2* __restrict__ tw,
+                                                              float2* __restrict__ Hr) {
+  extern __shared__ __attribute__((aligned(16))) float2 sm[];
+  const int r = blockIdx.x, c = blockIdx.y, tid = threadIdx.x, nthr = blockDim.x;
+  const float* p = psf + ((long)c * K + r) * K;
+  for (int j = tid; j < Px; j += nthr) {
+    int t = j + K / 2;
+    if (t >= Px) t -= Px;
+    sm[j] = make_float2(t < K ? p[t] : 0.f, 0.f);
+  }
+  __syncthreads();
+  const float2* q = wn_fft<false>(sm, sm + Px, Px, logPx, tw);
+  float2* o = Hr + ((long)c * K + r) * Px;
+  for (int j = tid; j < Px; j += nthr) o[j] = q[j];
+}
+
+// grid (Px, 3): column kx of Hc, then G scaled by `scale` = 1 / (Py Px) (a power of two: exact) -> G[c][kx][:]
+__global__ __launch_bounds__(WN_LANES) void k_img_wn_psf_cols(const float2* __restrict__ Hr, int K, int Py, int Px, int logPy, const float2* __restrict__ tw,
+                                                              const float* __restrict__ lamy, const float* __restrict__ lamx, float balance, float scale,
+                                                              float2* __restrict__ G) {
+  extern __shared__ __attribute__((aligned(16))) float2 sm[];
+  const int kx = blockIdx.x, c = blockIdx.y, tid = threadIdx.x, nthr = blockDim.x;
+  const float2* h = Hr + (long)c * K * Px + kx;
+  for (int j = tid; j < Py; j += nthr) {
+    int t = j + K / 2;
+    if (t >= Py) t -= Py;
+    sm[j] = t < K ? h[(long)t * Px] : make_float2(0.f, 0.f);
+  }
+  __syncthreads();
+  const float2* q = wn_fft<false>(sm, sm + Py, Py, logPy, tw);
+  const float lx = lamx[kx];
+  float2* o = G + ((long)c * Px + kx) * Py;
+  for (int j = tid; j < Py; j += nthr) {
+    const float2 v = q[j];
+    const float lam = lamy[j] + lx;
+    const float den = (v.x * v.x + v.y * v.y) + balance * (lam * lam);
+    o[j] = make_float2(__fdiv_rn(v.x, den) * scale, __fdiv_rn(-v.y, den) * scale);
+  }
+}
+
+// grid (Px, 3): the line B[c][kx][:] -> inverse(G * forward(line)), in place
+__global__ __launch_bounds__(WN_LANES) void k_img_wn_cols(float2* __restrict__ B, const float2* __restrict__ G, int Py, int logPy, const float2* __restrict__ tw) {
+  extern __shared__ __attribute__((aligned(16))) float2 sm[];
+  const int tid = threadIdx.x, nthr = blockDim.x;
+  const long line = ((long)blockIdx.y * gridDim.x + blockIdx.x) * Py;
+  float2* l = B + line;
+  const float2* g = G + line;
+  for (int j = tid; j < Py; j += nthr) sm[j] = l[j];
+  __syncthreads();
+  float2* r = wn_fft<false>(sm, sm + Py, Py, logPy, tw);
+  for (int j = tid; j < Py; j += nthr) r[j] = wn_mul(r[j], g[j]);
+  __syncthreads();
+  const float2* q = wn_fft<true>(r, r == sm ? sm + Py : sm, Py, logPy, tw);
+  for (int j = tid; j < Py; j += nthr) l[j] = q[j];
+}
+
+// grid (3, H): A[c][y][:] inverse, the real part of the first W points -> out[y][:][c]
+__global__ __launch_bounds__(WN_LANES) void k_img_wn_inv_rows(const float2* __restrict__ A, int W, int Py, int Px, int logPx, const float2* __restrict__ tw,
+                                                              float* __restrict__ out) {
+  extern __shared__ __attribute__((aligned(16))) float2 sm[];
+  const int c = blockIdx.x, y = blockIdx.y, tid = threadIdx.x, nthr = blockDim.x;
+  const float2* l = A + ((long)c * Py + y) * Px;
+  for (int j = tid; j < Px; j += nthr) sm[j] = l[j];
+  __syncthreads();
+  const float2* q = wn_fft<true>(sm, sm + Px, Px, logPx, tw);
+  float* o = out + (long)y * 3 * W + c;
+  for (int j = tid; j < W; j += nthr) o[3L * j] = q[j].x;
+}
+
+int wn_log2(int v) { int k = 0; while ((1 << k) < v) ++k; return k; }
+int wn_lanes(int P) { const int t = P / 4; return t < 64 ? 64 : (t > WN_LANES ? WN_LANES : t); }
+
+}  // namespace
+
+// transform sizes of an H x W frame and a K x K PSF; 0: a side would be above ICS_IMG_WIENER_MAX
+int ics_img_wiener_sizes(int H, int W, int K, int* Py, int* Px) {
+  if ((long)H + K - 1 > WN_MAX || (long)W + K - 1 > WN_MAX) return 0;
+  *Py = 1 << wn_log2(H + K - 1); *Px = 1 << wn_log2(W + K - 1);
+  return 1;
+}
+size_t ics_img_wiener_frame_bytes(int Py, int Px) { return (size_t)3 * Py * Px * sizeof(float2); }
+// the small block: Hr (3 K Px float2), the twiddles of the two axes (Py and Px float2, a few unused), 4 sin^2 along y and x, the planar PSF
+size_t ics_img_wiener_table_bytes(int K, int Py, int Px) {
+  return ((size_t)3 * K * Px + Py + Px) * sizeof(float2) + ((size_t)Py + Px + (size_t)3 * K * K) * sizeof(float);
+}
+float* ics_img_wiener_psf_slot(void* tables, int K, int Py, int Px) {
+  return reinterpret_cast<float*>(reinterpret_cast<float2*>(tables) + (size_t)3 * K * Px + Py + Px) + Py + Px;
+}
+size_t ics_img_wiener_lds(int P) { return (size_t)2 * P * sizeof(float2); }
+
+hipError_t ics_launch_img_wiener(const float* f, int H, int W, int K, float balance, int Py, int Px, float2* A, float2* B, void* tables, float* out, hipStream_t s) {
+  if (!f || !A || !B || !tables || !out || H < 1 || W < 1 || K < 3 || !(K & 1) || K > H || K > W) return hipErrorInvalidValue;
+  if (Py < H + K - 1 || Px < W + K - 1 || Py > WN_MAX || Px > WN_MAX || (Py & (Py - 1)) || (Px & (Px - 1))) return hipErrorInvalidValue;
+  const int P0 = Py > Px ? Py : Px, logPy = wn_log2(Py), logPx = wn_log2(Px);
+  float2* Hr = reinterpret_cast<float2*>(tables);
+  float2* twy = Hr + (size_t)3 * K * Px;
+  float2* twx = twy + Py;
+  float* lamy = reinterpret_cast<float*>(twx + Px);
+  float* lamx = lamy + Py;
+  const float* psf = lamx + Px;                  // (== ics_img_wiener_psf_slot: uploaded by the caller)
+  const size_t ldsy = ics_img_wiener_lds(Py), ldsx = ics_img_wiener_lds(Px);
+  if (ldsy > 64 * 1024 || ldsx > 64 * 1024) {    // lines of 8192 points: 128 KB of dynamic LDS
+    static std::atomic<bool> cfg[5][ICS_MAX_DEVICES];
+    const int dev = ics_current_device();
+    const size_t top = ics_img_wiener_lds(WN_MAX);
+    hipError_t e = ics_configure_lds(cfg[0], dev, k_img_wn_rows, top);
+    if (e == hipSuccess) e = ics_configure_lds(cfg[1], dev, k_img_wn_psf_rows, top);
+    if (e == hipSuccess) e = ics_configure_lds(cfg[2], dev, k_img_wn_psf_cols, top);
+    if (e == hipSuccess) e = ics_configure_lds(cfg[3], dev, k_img_wn_cols, top);
+    if (e == hipSuccess) e = ics_configure_lds(cfg[4], dev, k_img_wn_inv_rows, top);
+    if (e != hipSuccess) return e;
+  }
+  const float scale = 1.f / ((float)Py * (float)Px);
+  const auto tiles = [](int n) { return (unsigned)((n + WN_TILE - 1) / WN_TILE); };
+  hipLaunchKernelGGL(k_img_wn_tables, dim3((unsigned)((P0 + 255) / 256)), dim3(256), 0, s, twy, twx, lamy, lamx, Py, Px, logPy, logPx);
+  hipLaunchKernelGGL(k_img_wn_rows, dim3(3, (unsigned)Py), dim3(wn_lanes(Px)), ldsx, s, f, H, W, Py, Px, logPx, twx, A);
+  hipLaunchKernelGGL(k_img_wn_transpose, dim3(tiles(Px), tiles(Py), 3), dim3(256), 0, s, A, Py, Px, Px, B);
+  hipLaunchKernelGGL(k_img_wn_psf_rows, dim3((unsigned)K, 3), dim3(wn_lanes(Px)), ldsx, s, psf, K, Px, logPx, twx, Hr);
+  hipLaunchKernelGGL(k_img_wn_psf_cols, dim3((unsigned)Px, 3), dim3(wn_lanes(Py)), ldsy, s, Hr, K, Py, Px, logPy, twy, lamy, lamx, balance, scale, A);
+  hipLaunchKernelGGL(k_img_wn_cols, dim3((unsigned)Px, 3), dim3(wn_lanes(Py)), ldsy, s, B, A, Py, logPy, twy);
+  hipLaunchKernelGGL(k_img_wn_transpose, dim3(tiles(H), tiles(Px), 3), dim3(256), 0, s, B, Px, Py, H, A);
+  hipLaunchKernelGGL(k_img_wn_inv_rows, dim3(3, (unsigned)H), dim3(wn_lanes(Px)), ldsx, s, A, W, Py, Px, logPx, twx, out);
+  return hipGetLastError();
+}

@@ -364,3 +364,17 @@ int ics_img_mask_candidates(int extent, int size);
 int ics_img_mask_cells(int extent, int size);
 hipError_t ics_launch_img_mask(const float* f, int H, int W, int y0, int y1, int x0, int x1, int size, float clip, int cus, float* cells, double* table, double* result,
                                hipStream_t s);
+
+// ---- Wiener deconvolution of device-resident images (ics_img_wiener.hip): one 2-D transform of the periodically extended frame, the
+// filter conj(Hc) / (|Hc|^2 + balance L^2) per channel, the inverse.  ics_img_wiener_sizes: the transform sizes (powers of two >=
+// H + K - 1, W + K - 1), 0 where one would be above ICS_IMG_WIENER_MAX.  A, B: ics_img_wiener_frame_bytes each; tables:
+// ics_img_wiener_table_bytes, its ics_img_wiener_psf_slot holding the PSF as [3][K][K] (every channel of sum 1) before the launch.
+// ics_img_wiener_lds: dynamic LDS of a line kernel at P points.  One route; f is only read.
+#define ICS_IMG_WIENER_MAX 8192           // (== include/ics_hip.h)
+int ics_img_wiener_sizes(int H, int W, int K, int* Py, int* Px);
+size_t ics_img_wiener_frame_bytes(int Py, int Px);
+size_t ics_img_wiener_table_bytes(int K, int Py, int Px);
+float* ics_img_wiener_psf_slot(void* tables, int K, int Py, int Px);
+size_t ics_img_wiener_lds(int P);
+hipError_t ics_launch_img_wiener(const float* f, int H, int W, int K, float balance, int Py, int Px, float2* A, float2* B, void* tables, float* out,
+                                 hipStream_t s);

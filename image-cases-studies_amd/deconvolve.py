@@ -80,7 +80,7 @@ def mask_window(i, top, bottom, left, right):
 def deblur_module(pic, filename, dest_path, blur_width, confidence=10, tolerance=1, quality="normal", bits=8,
                   mask=None, display=True, blur="static", preview=False, p=1, order=2, norm=1, priority=0, mask_size=255,
                   iterations=200, refocus=False, pyramid=True, solver=None, save=True, device_resident=None, sharpen=None, denoise=None,
-                  local_contrast=None, detail=None, clarity=None, despeckle=None):
+                  local_contrast=None, detail=None, clarity=None, despeckle=None, nonblind="rl"):
     """deconvolve.py:65-368.  Extra keyword arguments (not in the reference): `pyramid=False` runs the
     single scale-1 level only, `solver` replaces `dc.richardson_lucy_MM` (tests record the calls),
     `save=False` returns the float image instead of writing the TIFF, `device_resident=True` keeps every frame in HBM
@@ -128,7 +128,13 @@ def deblur_module(pic, filename, dest_path, blur_width, confidence=10, tolerance
     orientation -- pixels with a channel at or above `clip` left out), on the gamma-encoded frame the solver will see, after
     `despeckle`, before the automatic blur width (which is then read over the chosen box) and before the odd-size padding, among the
     boxes that lie inside the picture; one line "Mask : [95, 143] (score 2.93e-03, clipped 0.0 %)" is printed before "Mask size :" and
-    everything runs as if that centre had been passed.  On the resident path the frame is read where it lies."""
+    everything runs as if that centre had been passed.  On the resident path the frame is read where it lies.
+    `nonblind="rl"` (the default: the reference's second phase, the loop on the whole frame), `"wiener"` or `("wiener", balance)`
+    (balance 0.01 unless given): the blind phase runs as ever, and the second phase is one `utils.wiener` of the full-resolution
+    gamma-encoded frame with the PSF the blind phase returned -- milliseconds where the loop takes most of the run, to try a PSF on
+    the whole picture; "===== WIENER DECONVOLUTION =====" and one line "Wiener : balance 0.01, 8192 × 8192 transform" are printed,
+    and `denoise`, `clarity`, ... and the clip follow as after the loop.  On the resident path the frame stays in HBM."""
+    wiener_balance = _nonblind_args(nonblind)
     despeckle = _despeckle_args(despeckle)
     auto_width = _blur_width_args(blur_width)
     auto_mask = _mask_args(mask)
@@ -143,7 +149,8 @@ def deblur_module(pic, filename, dest_path, blur_width, confidence=10, tolerance
         if solver is not None:
             raise ValueError("device_resident=True runs the GPU solver; `solver` cannot be replaced")
         return _deblur_device(pic, filename, dest_path, blur_width, confidence, tolerance, quality, bits, mask, display, blur, preview, p,
-                              order, norm, priority, mask_size, iterations, refocus, pyramid, save, despeckle, sharpen, denoise, local_contrast, detail, clarity)
+                              order, norm, priority, mask_size, iterations, refocus, pyramid, save, despeckle, sharpen, denoise, local_contrast, detail, clarity,
+                              *(() if wiener_balance is None else (wiener_balance,)))       # (nonblind="rl": the call as it always was)
     rl = solver if solver is not None else dc.richardson_lucy_MM
     pic = np.ascontiguousarray(pic, dtype=np.float32)
     pic = pad_image(pic, (1, 1)).astype(np.float32)                       # :94
@@ -192,6 +199,9 @@ def deblur_module(pic, filename, dest_path, blur_width, confidence=10, tolerance
     deblured_image = pic
     try:
         for case in ["blind", "non-blind"]:                               # :193
+            if case == "non-blind" and wiener_balance is not None:
+                deblured_image = _wiener_phase(pic, psf, wiener_balance)
+                break
             print("\n===== %s DECONVOLUTION =====" % case)
             deblured_image = pic.copy()
             lambd = confidence * 1000                                     # :200
@@ -281,6 +291,31 @@ def deblur_module(pic, filename, dest_path, blur_width, confidence=10, tolerance
     if save:
         utils.save(deblured_image, filename, dest_path)
     return deblured_image, psf
+
+
+def _nonblind_args(nonblind):
+    """`nonblind` of deblur_module -> None for "rl" (the loop) or the balance of "wiener" / ("wiener", balance), checked (ValueError)"""
+    form = "nonblind takes \"rl\", \"wiener\" or (\"wiener\", balance), got %r" % (nonblind,)
+    if isinstance(nonblind, str):
+        if nonblind not in ("rl", "wiener"):
+            raise ValueError(form)
+        return None if nonblind == "rl" else 0.01
+    if not isinstance(nonblind, (tuple, list)) or len(nonblind) != 2 or not isinstance(nonblind[0], str) or nonblind[0] != "wiener":
+        raise ValueError(form)
+    from lib import _native
+    if not _native._finite32(nonblind[1], scalar=True) or not np.float32(nonblind[1]) > 0:
+        raise ValueError("nonblind: balance %r (must be finite and > 0)" % (nonblind[1],))
+    return float(nonblind[1])
+
+
+def _wiener_phase(frame, psf, balance):
+    """the second phase of deblur_module(nonblind="wiener") on the full-resolution gamma-encoded frame (an array or a DeviceImage):
+    its two printed lines, the filtered frame"""
+    from lib import _native
+    print("\n===== WIENER DECONVOLUTION =====")
+    plan = _native.wiener_plan(frame.shape[0], frame.shape[1], np.shape(psf)[0])
+    print("Wiener : balance %g, %d × %d transform" % (balance, plan.Py, plan.Px))
+    return utils.wiener(frame, psf, balance)
 
 
 def _sharpen_args(sharpen):
@@ -476,7 +511,7 @@ def _level_shape(i, M, N):
 
 def _deblur_device(pic, filename, dest_path, blur_width, confidence, tolerance, quality, bits, mask, display, blur, preview, p, order, norm,
                    priority, mask_size, iterations, refocus, pyramid, save, despeckle=None, sharpen=None, denoise=None, local_contrast=None,
-                   detail=None, clarity=None):
+                   detail=None, clarity=None, wiener_balance=None):
     """`deblur_module` (deconvolve.py:65-368) with every frame resident in HBM: one upload of the picture,
     one download of the result; pad_image, gamma, the window views, the resize between pyramid levels and the solver all
     work on `lib._native.DeviceImage`s.  Line references as in `deblur_module` above."""
@@ -537,6 +572,12 @@ def _deblur_device(pic, filename, dest_path, blur_width, confidence, tolerance, 
         for case in ["blind", "non-blind"]:
             _native.Context.get().synchronize()
             t_case = time.perf_counter()
+            if case == "non-blind" and wiener_balance is not None:
+                deb, old = _wiener_phase(pic_d, psf, wiener_balance), deb
+                old.close()
+                _native.Context.get().synchronize()
+                phases[case] = time.perf_counter() - t_case
+                break
             print("\n===== %s DECONVOLUTION =====" % case)
             deb.close()
             deb = pic_d.copy()

@@ -97,6 +97,7 @@ IMG_LLF_MAX_SAMPLES = 16         # include/ics_hip.h ICS_IMG_LLF_MAX_SAMPLES: re
 IMG_DESPECKLE_MAX_RADIUS = 2     # include/ics_hip.h ICS_IMG_DESPECKLE_MAX_RADIUS: 3 x 3 and 5 x 5 windows
 IMG_DESPECKLE_STRENGTH = 6.0     # include/ics_hip.h ICS_IMG_DESPECKLE_STRENGTH: threshold "auto" of despeckle is this many sigma of the noise
 IMG_BLURWIDTH_MAX_LAG = 128      # include/ics_hip.h ICS_IMG_BLURWIDTH_MAX_LAG: largest lag of DeviceImage.blur_profile
+IMG_WIENER_MAX = 8192            # include/ics_hip.h ICS_IMG_WIENER_MAX: longest line of DeviceImage.wiener's transform (H + K - 1, W + K - 1 at most)
 IMG_MASK_CELL = 16               # include/ics_hip.h ICS_IMG_MASK_CELL: DeviceImage.window_scores ranks boxes on this grid and scores whole cells of this side
 IMG_NOISE_STRENGTH = 3.0         # include/ics_hip.h ICS_IMG_NOISE_STRENGTH: thresholds="auto" cuts this many standard deviations
 IMG_NOISE_E = (0.89079631027875839, 0.20066385102441897, 0.085507504753369934, 0.041217444374316202,      # include/ics_hip.h ICS_IMG_NOISE_E: e_j, the L2
@@ -184,6 +185,8 @@ def load():
     lib.ics_img_despeckle.argtypes = [vp, ci, C.POINTER(cf), ci, ci, C.POINTER(vp), C.POINTER(C.c_uint)]
     lib.ics_img_guided.argtypes = [vp, ci, cf, cf, ci, ci, C.POINTER(vp)]
     lib.ics_img_local_laplacian.argtypes = [vp, cf, cf, cf, ci, ci, ci, ci, C.POINTER(vp)]
+    lib.ics_img_wiener.argtypes = [vp, vp, ci, cf, C.POINTER(vp)]
+    lib.ics_img_wiener_plan.argtypes = [ci, ci, ci, C.POINTER(ci), C.POINTER(ci), C.POINTER(C.c_size_t)]
     lib.ics_rl_upload_img.argtypes = [vp, vp, ci, ci, vp, ci, ci, vp]
     lib.ics_rl_download_img.argtypes = [vp, vp, ci, ci]
     lib.ics_group_create.argtypes = [ci, ci, ci, C.c_char_p, ci, C.POINTER(vp)]
@@ -205,7 +208,7 @@ def load():
                  "ics_rl_download", "ics_rl_run", "ics_rl_stage", "ics_rl_read", "ics_rl_write", "ics_rl_read_rows", "ics_rl_write_rows", "ics_rl_copy_rows", "ics_normalize_kernel",
                  "ics_tv", "ics_conv2d_symm", "ics_usm", "ics_bilateral", "ics_resize_bicubic", "ics_img_create", "ics_img_shape",
                  "ics_img_upload", "ics_img_upload_int", "ics_img_download", "ics_img_pad_edge", "ics_img_crop", "ics_img_paste", "ics_img_gamma", "ics_img_resize",
-                 "ics_img_convolve", "ics_img_usm", "ics_img_bilateral", "ics_img_tv_denoise", "ics_img_wavelet_equalize", "ics_img_noise_estimate", "ics_img_blur_profile", "ics_img_window_scores", "ics_img_despeckle", "ics_img_guided", "ics_img_local_laplacian",
+                 "ics_img_convolve", "ics_img_usm", "ics_img_bilateral", "ics_img_tv_denoise", "ics_img_wavelet_equalize", "ics_img_noise_estimate", "ics_img_blur_profile", "ics_img_window_scores", "ics_img_despeckle", "ics_img_guided", "ics_img_local_laplacian", "ics_img_wiener", "ics_img_wiener_plan",
                  "ics_rl_upload_img", "ics_rl_download_img", "ics_group_create", "ics_group_info", "ics_group_barrier",
                  "ics_group_allreduce_max", "ics_group_allreduce_sum", "ics_group_describe", "ics_group_allgather"):
         getattr(lib, name).restype = ci
@@ -507,6 +510,44 @@ def guided_args(radius, eps, detail=0.0, coupling="vector", route=0):
     if route == 2 and int(radius) > IMG_GUIDED_FUSED_RADIUS:
         raise ValueError("route 2 takes a radius up to %d, got %d" % (IMG_GUIDED_FUSED_RADIUS, int(radius)))
     return int(radius), float(eps), float(detail), coupling, int(route)
+
+
+WienerPlan = collections.namedtuple("WienerPlan", "Py Px workspace_bytes")
+
+
+def wiener_args(psf, balance, shape):
+    """the arguments of DeviceImage.wiener checked (ValueError) and as (psf, balance): the K x K x 3 float32 PSF, every channel
+    normalised to sum 1 in float64, and a float; shape: (H, W, ...) of the frame"""
+    try:
+        k = np.array(psf, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError("psf %r (a K x K or K x K x 3 array)" % (psf,))
+    if k.ndim == 2:
+        k = np.dstack((k, k, k))
+    if k.ndim != 3 or k.shape[0] != k.shape[1] or k.shape[2] != 3:
+        raise ValueError("psf of shape %s (K x K or K x K x 3)" % (k.shape,))
+    K, H, W = k.shape[0], int(shape[0]), int(shape[1])
+    if K % 2 == 0 or not 3 <= K <= 255:
+        raise ValueError("psf of %d x %d taps (K odd, 3 to 255)" % (K, K))
+    if K > min(H, W):
+        raise ValueError("psf of %d x %d taps, larger than the %d x %d frame" % (K, K, H, W))
+    if not _finite32(k):
+        raise ValueError("psf with values that are not finite")
+    sums = k.sum(axis=(0, 1))
+    if not (sums > 0).all():
+        raise ValueError("psf channel sums %s (every one must be > 0)" % (tuple(float(v) for v in sums),))
+    if not _finite32(balance, scalar=True) or not np.float32(balance) > 0:
+        raise ValueError("balance %r (must be finite and > 0)" % (balance,))
+    return np.ascontiguousarray(k / sums, dtype=np.float32), float(balance)
+
+
+def wiener_plan(H, W, K):
+    """ics_img_wiener_plan: WienerPlan(Py, Px, workspace_bytes) of DeviceImage.wiener on an H x W frame with a K x K PSF -- the
+    transform sizes (the smallest powers of two >= H + K - 1, W + K - 1) and the device bytes it takes from the pool beside the result
+    (no device needed).  NativeError: K even or outside 3 .. 255 or above min(H, W); a side above IMG_WIENER_MAX (ICS_ENOSUP)."""
+    py, px, ws = C.c_int(0), C.c_int(0), C.c_size_t(0)
+    _check(load().ics_img_wiener_plan(int(H), int(W), int(K), C.byref(py), C.byref(px), C.byref(ws)))
+    return WienerPlan(py.value, px.value, int(ws.value))
 
 
 def llf_levels(H, W):
@@ -862,6 +903,21 @@ class DeviceImage:
         if levels is None:
             levels = llf_levels(*self.shape[:2])
         return self._new(load().ics_img_local_laplacian, sigma, detail, edges, levels, samples, _coupling(coupling), route)
+
+    def wiener(self, psf, balance=0.01):
+        """Wiener deconvolution by a known PSF, the fast non-blind step beside the Richardson-Lucy loop: with Hc the transform of
+        channel c of the PSF (K x K or K x K x 3, K odd, 3 .. 255, normalised here to sum 1 per channel) and L the transfer of the
+        discrete Laplacian, out_c = real(ifft2(conj(Hc) / (|Hc|^2 + balance L^2) * fft2(ext_c)))[:H, :W] on one transform of the
+        whole frame, extended to the next powers of two >= H + K - 1, W + K - 1 by a linear ramp from the last row (column) back to
+        the first, so that the wrap-around carries no step (csrc/ics_img_wiener.hip; restated in float64 in tests/wiener_ref.py).
+        balance trades noise against sharpness: 1e-2 for a clean frame, 1e-1 for a noisy one.  Nothing is clipped and nothing keeps
+        the result positive: expect faint negative lobes beside strong edges.  A box or line PSF has exact spectral zeros, where
+        balance alone carries the result; a delta PSF does not return the input (1 / (1 + balance L^2) is a low-pass); a NaN spreads
+        over the whole frame (despeckle first).  Two calls give identical bits.  ValueError (before any native call): a PSF that is
+        not square, of even or unsupported size, larger than the frame, not finite or with a channel sum <= 0; balance not finite or
+        <= 0.  NativeError (ICS_ENOSUP): H + K - 1 or W + K - 1 above IMG_WIENER_MAX."""
+        psf, balance = wiener_args(psf, balance, self.shape)
+        return self._new(load().ics_img_wiener, _ptr(psf), psf.shape[0], balance)
 
     def close(self):
         if self._h:

@@ -532,6 +532,25 @@ int ics_img_blur_profile(const ics_img *src, int y0, int y1, int x0, int x1, int
 #define ICS_IMG_MASK_CELL 16
 int ics_img_window_scores(const ics_img *src, int y0, int y1, int x0, int x1, int size, float clip, int *box_y, int *box_x, double *score, double *trace,
                           long long *clipped, double *map, int map_rows, int map_cols);
+/* Wiener deconvolution of a device image by a known PSF: a regularised inverse filter on one 2-D transform of the whole frame, the
+ * fast non-blind step beside the Richardson-Lucy loop.  psf: K x K x 3 host floats (HWC like ics_rl_upload), K odd, 3 .. 255,
+ * K <= min(H, W), every channel of sum 1 (the Python layer normalises); balance > 0.
+ *   Py, Px = the smallest powers of two >= H + K - 1, W + K - 1
+ *   ext: the frame extended to Py x Px without a step at the wrap-around: along y, for every column, rows H .. Py - 1 are
+ *     (1 - t / g) f[H - 1] + (t / g) f[0], g = Py - H + 1, t = 1 .. g - 1; then the same along x on all Py rows with W and Px
+ *   Hc = the transform of channel c of the PSF, zero padded to Py x Px, its centre tap (K / 2, K / 2) rolled to (0, 0)
+ *   L(ky, kx) = 4 - 2 cos(2 pi ky / Py) - 2 cos(2 pi kx / Px)   (the Laplacian skimage.restoration.wiener regularises with)
+ *   G = conj(Hc) / (|Hc|^2 + balance L^2);  out_c = real(inverse transform(G transform(ext_c)))[:H, :W].  Nothing is clipped.
+ * float32 throughout, no atomics: two runs give identical bits (restated in float64 in tests/wiener_ref.py).  A delta PSF does not
+ * return the input (G = 1 / (1 + balance L^2) is a low-pass); a NaN spreads over the whole frame.  Queued like the other image
+ * filters, its kernels bracketed for ics_ctx_last_kernel_ms; src is not written.  ICS_EINVAL (*out NULL): src, psf or out NULL, K even
+ * or outside 3 .. 255 or above min(H, W), balance not finite or <= 0.  ICS_ENOSUP: H + K - 1 or W + K - 1 above
+ * ICS_IMG_WIENER_MAX (a line and its ping-pong copy fill the LDS of a compute unit).
+ * ics_img_wiener_plan: the transform sizes and the device bytes such a call takes from the context's pool (no device needed); same
+ * checks on H, W, K. */
+#define ICS_IMG_WIENER_MAX 8192
+int ics_img_wiener(const ics_img *src, const float *psf, int K, float balance, ics_img **out);
+int ics_img_wiener_plan(int H, int W, int K, int *Py, int *Px, size_t *workspace_bytes);
 /* richardson_lucy_MM(image[iy:iy+M, ix:ix+N], u[uy:uy+uM, ux:ux+uN], psf, ...) with both windows taken from device
  * images (deconvolve.py:277-313 passes such views); psf is a host MK*MK*3 array as in ics_rl_upload. */
 int ics_rl_upload_img(ics_rl *job, const ics_img *image, int iy, int ix, const ics_img *u, int uy, int ux, const float *psf);
