@@ -9,7 +9,7 @@
 //   L(ky,kx) = 4 sin^2(pi ky / Py) + 4 sin^2(pi kx / Px)  (= 4 - 2 cos(2 pi ky / Py) - 2 cos(2 pi kx / Px), the Laplacian's transfer)
 //   G        = conj(Hc) / (|Hc|^2 + balance L^2);  out_c = real(inverse transform(G * transform(ext_c)))[:H, :W], nothing clipped
 //
-// The line transform (wn_fft): a Stockham autosort transform of one line of N = 2^n points in LDS, radix 4 with one leading radix-2
+// The line transform (wn_fft, ics_wn_fft.h, shared with ics_img_tvdeconv.hip): a Stockham autosort transform of one line of N = 2^n points in LDS, radix 4 with one leading radix-2
 // stage where n is odd, N / 4 butterflies a stage over the workgroup's lanes, the line ping-ponging between two buffers of N float2.
 // Stage reads are four runs of consecutive float2 (conflict free), its writes go out at a stride of p float2.  A lane takes two
 // butterflies of a stage at a time, all their loads before the arithmetic.  Twiddles come from one table per axis, laid out by stage:
@@ -31,81 +31,13 @@
 //   k_img_wn_cols      : the line B[c][kx][:] forward, times G, inverse, the line staying in LDS in between; written back in place
 //   k_img_wn_transpose : B[c][kx][y < H] -> A[c][y][kx]
 //   k_img_wn_inv_rows  : rows y < H inverse, the real part of the first W points -> out
-#include "ics_kernels.h"
+#include "ics_wn_fft.h"
 
 namespace {
 
 #define WN_MAX ICS_IMG_WIENER_MAX              // longest line: two buffers of it are 128 KB of the 160 KB of LDS
 #define WN_LANES 1024                          // lanes of a line's workgroup at most (N / 4 below 4096 points, 64 at least)
 #define WN_TILE 32                             // the transposes' tile side
-
-__device__ __forceinline__ float2 wn_add(float2 a, float2 b) { return make_float2(a.x + b.x, a.y + b.y); }
-__device__ __forceinline__ float2 wn_sub(float2 a, float2 b) { return make_float2(a.x - b.x, a.y - b.y); }
-__device__ __forceinline__ float2 wn_mul(float2 a, float2 b) { return make_float2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x); }
-
-// the line in x (written by the whole workgroup, a barrier passed since) -> its transform, unscaled, in the returned buffer (x or y), a
-// barrier passed.  tw: the table of this N (wn_table)
-template <bool INV>
-__device__ __forceinline__ float2* wn_fft(float2* x, float2* y, int N, int logN, const float2* __restrict__ tw) {
-  const int tid = threadIdx.x, nthr = blockDim.x;
-  int p = 1;
-  if (logN & 1) {
-    const int t = N >> 1;
-    for (int b = tid; b < t; b += nthr) {
-      const float2 u0 = x[b], u1 = x[b + t];
-      y[2 * b] = wn_add(u0, u1);
-      y[2 * b + 1] = wn_sub(u0, u1);
-    }
-    __syncthreads();
-    float2* tmp = x; x = y; y = tmp;
-    p = 2;
-  }
-  const int t = N >> 2, p0 = p;
-  for (; p < N; p <<= 2) {
-    const float2* __restrict__ ws = tw + (p - p0);
-    for (int b0 = tid; b0 < t; b0 += 2 * nthr) {
-      float2 u[2][4], w[2][3];
-#pragma unroll
-      for (int h = 0; h < 2; ++h) {
-        const int b = b0 + h * nthr;
-        if (b < t) {
-          const int k = b & (p - 1);
-#pragma unroll
-          for (int q = 0; q < 4; ++q) u[h][q] = x[b + q * t];
-#pragma unroll
-          for (int q = 0; q < 3; ++q) w[h][q] = ws[3 * k + q];
-        }
-      }
-#pragma unroll
-      for (int h = 0; h < 2; ++h) {
-        const int b = b0 + h * nthr;
-        if (b < t) {
-          const int k = b & (p - 1), j = ((b - k) << 2) + k;
-          if (INV) { w[h][0].y = -w[h][0].y; w[h][1].y = -w[h][1].y; w[h][2].y = -w[h][2].y; }
-          const float2 u0 = u[h][0], u1 = wn_mul(u[h][1], w[h][0]), u2 = wn_mul(u[h][2], w[h][1]), u3 = wn_mul(u[h][3], w[h][2]);
-          const float2 v0 = wn_add(u0, u2), v1 = wn_sub(u0, u2), v2 = wn_add(u1, u3), d = wn_sub(u1, u3);
-          const float2 v3 = INV ? make_float2(-d.y, d.x) : make_float2(d.y, -d.x);   // -+ i d
-          y[j] = wn_add(v0, v2);
-          y[j + p] = wn_add(v1, v3);
-          y[j + 2 * p] = wn_sub(v0, v2);
-          y[j + 3 * p] = wn_sub(v1, v3);
-        }
-      }
-    }
-    __syncthreads();
-    float2* tmp = x; x = y; y = tmp;
-  }
-  return x;
-}
-
-// entry i of the table of an N-point line (N - p0 entries): stage p = p0, 4 p0, ... holds {w, w^2, w^3}(k), k < p, from offset p - p0
-__device__ __forceinline__ float2 wn_table(int i, int logN) {
-  int p = (logN & 1) ? 2 : 1, off = 0;
-  while (i >= off + 3 * p) { off += 3 * p; p <<= 2; }
-  const int r = i - off, k = r / 3, m = r - 3 * k + 1;
-  const double a = (double)(k * m) / (double)(2 * p);            // exp(-2 pi i k m / 4p)
-  return make_float2((float)cospi(a), (float)-sinpi(a));
-}
 
 __global__ __launch_bounds__(256) void k_img_wn_tables(float2* __restrict__ twy, float2* __restrict__ twx, float* __restrict__ lamy, float* __restrict__ lamx, int Py, int Px,
                                                        int logPy, int logPx) {
@@ -251,10 +183,20 @@ float* ics_img_wiener_psf_slot(void* tables, int K, int Py, int Px) {
 }
 size_t ics_img_wiener_lds(int P) { return (size_t)2 * P * sizeof(float2); }
 
+// the two passes ics_img_tvdeconv.hip shares with this unit: the tables of the two axes, and in[plane][R][C] -> out[plane][C][R] for the
+// columns below clim on three planes
+void ics_launch_img_wiener_tables(float2* twy, float2* twx, float* lamy, float* lamx, int Py, int Px, hipStream_t s) {
+  const int P0 = Py > Px ? Py : Px;
+  hipLaunchKernelGGL(k_img_wn_tables, dim3((unsigned)((P0 + 255) / 256)), dim3(256), 0, s, twy, twx, lamy, lamx, Py, Px, wn_log2(Py), wn_log2(Px));
+}
+void ics_launch_img_wiener_transpose(const float2* in, int R, int C, int clim, float2* out, hipStream_t s) {
+  hipLaunchKernelGGL(k_img_wn_transpose, dim3((unsigned)((clim + WN_TILE - 1) / WN_TILE), (unsigned)((R + WN_TILE - 1) / WN_TILE), 3), dim3(256), 0, s, in, R, C, clim, out);
+}
+
 hipError_t ics_launch_img_wiener(const float* f, int H, int W, int K, float balance, int Py, int Px, float2* A, float2* B, void* tables, float* out, hipStream_t s) {
   if (!f || !A || !B || !tables || !out || H < 1 || W < 1 || K < 3 || !(K & 1) || K > H || K > W) return hipErrorInvalidValue;
   if (Py < H + K - 1 || Px < W + K - 1 || Py > WN_MAX || Px > WN_MAX || (Py & (Py - 1)) || (Px & (Px - 1))) return hipErrorInvalidValue;
-  const int P0 = Py > Px ? Py : Px, logPy = wn_log2(Py), logPx = wn_log2(Px);
+  const int logPy = wn_log2(Py), logPx = wn_log2(Px);
   float2* Hr = reinterpret_cast<float2*>(tables);
   float2* twy = Hr + (size_t)3 * K * Px;
   float2* twx = twy + Py;
@@ -274,14 +216,13 @@ hipError_t ics_launch_img_wiener(const float* f, int H, int W, int K, float bala
     if (e != hipSuccess) return e;
   }
   const float scale = 1.f / ((float)Py * (float)Px);
-  const auto tiles = [](int n) { return (unsigned)((n + WN_TILE - 1) / WN_TILE); };
-  hipLaunchKernelGGL(k_img_wn_tables, dim3((unsigned)((P0 + 255) / 256)), dim3(256), 0, s, twy, twx, lamy, lamx, Py, Px, logPy, logPx);
+  ics_launch_img_wiener_tables(twy, twx, lamy, lamx, Py, Px, s);
   hipLaunchKernelGGL(k_img_wn_rows, dim3(3, (unsigned)Py), dim3(wn_lanes(Px)), ldsx, s, f, H, W, Py, Px, logPx, twx, A);
-  hipLaunchKernelGGL(k_img_wn_transpose, dim3(tiles(Px), tiles(Py), 3), dim3(256), 0, s, A, Py, Px, Px, B);
+  ics_launch_img_wiener_transpose(A, Py, Px, Px, B, s);
   hipLaunchKernelGGL(k_img_wn_psf_rows, dim3((unsigned)K, 3), dim3(wn_lanes(Px)), ldsx, s, psf, K, Px, logPx, twx, Hr);
   hipLaunchKernelGGL(k_img_wn_psf_cols, dim3((unsigned)Px, 3), dim3(wn_lanes(Py)), ldsy, s, Hr, K, Py, Px, logPy, twy, lamy, lamx, balance, scale, A);
   hipLaunchKernelGGL(k_img_wn_cols, dim3((unsigned)Px, 3), dim3(wn_lanes(Py)), ldsy, s, B, A, Py, logPy, twy);
-  hipLaunchKernelGGL(k_img_wn_transpose, dim3(tiles(H), tiles(Px), 3), dim3(256), 0, s, B, Px, Py, H, A);
+  ics_launch_img_wiener_transpose(B, Px, Py, H, A, s);
   hipLaunchKernelGGL(k_img_wn_inv_rows, dim3(3, (unsigned)H), dim3(wn_lanes(Px)), ldsx, s, A, W, Py, Px, logPx, twx, out);
   return hipGetLastError();
 }

@@ -378,3 +378,17 @@ float* ics_img_wiener_psf_slot(void* tables, int K, int Py, int Px);
 size_t ics_img_wiener_lds(int P);
 hipError_t ics_launch_img_wiener(const float* f, int H, int W, int K, float balance, int Py, int Px, float2* A, float2* B, void* tables, float* out,
                                  hipStream_t s);
+// two of its passes, for ics_img_tvdeconv.hip: the twiddle tables of the two axes (Py, Px float2, a few unused) with 4 sin^2 along y and
+// x, and the tiled transpose in[plane][R][C] -> out[plane][C][R] of three planes for the columns below clim
+void ics_launch_img_wiener_tables(float2* twy, float2* twx, float* lamy, float* lamx, int Py, int Px, hipStream_t s);
+void ics_launch_img_wiener_transpose(const float2* in, int R, int C, int clim, float2* out, hipStream_t s);
+
+// ---- TV-regularised deconvolution of device-resident images (ics_img_tvdeconv.hip): split-Bregman iterations on the transform of
+// ics_img_wiener.hip (its sizes, its extension, its tables), a shrinkage of the gradient per pixel and a solve that is diagonal under
+// the transform.  workspace: ics_img_tvd_workspace_bytes, one block; ics_img_tvd_tables: the tables inside it, laid out as
+// ics_img_wiener_table_bytes, their ics_img_wiener_psf_slot holding the PSF as [3][K][K] (every channel of sum 1) before the launch.
+// coupling: 0 every channel by its own gradient magnitude, 1 the three by their common one.  One route; f is only read.
+size_t ics_img_tvd_workspace_bytes(int K, int Py, int Px);
+void* ics_img_tvd_tables(void* workspace, int Py, int Px);
+hipError_t ics_launch_img_tv_deconvolve(const float* f, int H, int W, int K, float mu, float beta, int iterations, int coupling, int Py, int Px, void* workspace, float* out,
+                                        hipStream_t s);

@@ -133,8 +133,13 @@ def deblur_module(pic, filename, dest_path, blur_width, confidence=10, tolerance
     (balance 0.01 unless given): the blind phase runs as ever, and the second phase is one `utils.wiener` of the full-resolution
     gamma-encoded frame with the PSF the blind phase returned -- milliseconds where the loop takes most of the run, to try a PSF on
     the whole picture; "===== WIENER DECONVOLUTION =====" and one line "Wiener : balance 0.01, 8192 × 8192 transform" are printed,
-    and `denoise`, `clarity`, ... and the clip follow as after the loop.  On the resident path the frame stays in HBM."""
-    wiener_balance = _nonblind_args(nonblind)
+    and `denoise`, `clarity`, ... and the clip follow as after the loop.  On the resident path the frame stays in HBM.
+    `nonblind="tv"`, `("tv", fidelity)`, `("tv", fidelity, iterations)` or `("tv", fidelity, iterations, coupling)` (fidelity 2000, 10
+    iterations, coupling "vector" unless given; the penalty is 10): likewise, the second phase being one `utils.tv_deconvolve` -- the
+    loop's total-variation prior on `wiener`'s transform, tens of milliseconds, lower fidelity for noisier frames;
+    "===== TV DECONVOLUTION =====" and one line "TV : fidelity 2000, penalty 10, 10 iterations, vector, 8192 × 8192 transform" are
+    printed."""
+    fast_phase = _nonblind_args(nonblind)
     despeckle = _despeckle_args(despeckle)
     auto_width = _blur_width_args(blur_width)
     auto_mask = _mask_args(mask)
@@ -150,7 +155,7 @@ def deblur_module(pic, filename, dest_path, blur_width, confidence=10, tolerance
             raise ValueError("device_resident=True runs the GPU solver; `solver` cannot be replaced")
         return _deblur_device(pic, filename, dest_path, blur_width, confidence, tolerance, quality, bits, mask, display, blur, preview, p,
                               order, norm, priority, mask_size, iterations, refocus, pyramid, save, despeckle, sharpen, denoise, local_contrast, detail, clarity,
-                              *(() if wiener_balance is None else (wiener_balance,)))       # (nonblind="rl": the call as it always was)
+                              *(() if fast_phase is None else (fast_phase,)))       # (nonblind="rl": the call as it always was)
     rl = solver if solver is not None else dc.richardson_lucy_MM
     pic = np.ascontiguousarray(pic, dtype=np.float32)
     pic = pad_image(pic, (1, 1)).astype(np.float32)                       # :94
@@ -199,8 +204,8 @@ def deblur_module(pic, filename, dest_path, blur_width, confidence=10, tolerance
     deblured_image = pic
     try:
         for case in ["blind", "non-blind"]:                               # :193
-            if case == "non-blind" and wiener_balance is not None:
-                deblured_image = _wiener_phase(pic, psf, wiener_balance)
+            if case == "non-blind" and fast_phase is not None:
+                deblured_image = _fast_phase(pic, psf, fast_phase)
                 break
             print("\n===== %s DECONVOLUTION =====" % case)
             deblured_image = pic.copy()
@@ -294,18 +299,50 @@ def deblur_module(pic, filename, dest_path, blur_width, confidence=10, tolerance
 
 
 def _nonblind_args(nonblind):
-    """`nonblind` of deblur_module -> None for "rl" (the loop) or the balance of "wiener" / ("wiener", balance), checked (ValueError)"""
-    form = "nonblind takes \"rl\", \"wiener\" or (\"wiener\", balance), got %r" % (nonblind,)
+    """`nonblind` of deblur_module -> None for "rl" (the loop), the balance of "wiener" / ("wiener", balance), or
+    ("tv", fidelity, iterations, coupling) of "tv" / ("tv", fidelity[, iterations[, coupling]]), checked (ValueError)"""
+    form = ("nonblind takes \"rl\", \"wiener\", (\"wiener\", balance), \"tv\" or (\"tv\", fidelity[, iterations[, coupling]]), got %r"
+            % (nonblind,))
     if isinstance(nonblind, str):
-        if nonblind not in ("rl", "wiener"):
+        if nonblind not in ("rl", "wiener", "tv"):
             raise ValueError(form)
-        return None if nonblind == "rl" else 0.01
-    if not isinstance(nonblind, (tuple, list)) or len(nonblind) != 2 or not isinstance(nonblind[0], str) or nonblind[0] != "wiener":
+        return {"rl": None, "wiener": 0.01, "tv": ("tv",) + _TV_PHASE}[nonblind]
+    if not isinstance(nonblind, (tuple, list)) or len(nonblind) < 2 or not isinstance(nonblind[0], str):
         raise ValueError(form)
     from lib import _native
+    if nonblind[0] == "tv" and len(nonblind) <= 4:
+        fidelity, iterations, coupling = tuple(nonblind[1:]) + _TV_PHASE[len(nonblind) - 1:]
+        try:                                      # (the PSF is the blind phase's: a stand-in passes its checks here)
+            _, fidelity, _, iterations, coupling = _native.tv_deconvolve_args(np.ones((3, 3)), fidelity, _TV_PENALTY, iterations, coupling, (3, 3))
+        except ValueError as exc:
+            raise ValueError("nonblind: %s" % exc)
+        return ("tv", fidelity, iterations, coupling)
+    if len(nonblind) != 2 or nonblind[0] != "wiener":
+        raise ValueError(form)
     if not _native._finite32(nonblind[1], scalar=True) or not np.float32(nonblind[1]) > 0:
         raise ValueError("nonblind: balance %r (must be finite and > 0)" % (nonblind[1],))
     return float(nonblind[1])
+
+
+_TV_PHASE = (2000.0, 10, "vector")      # fidelity, iterations, coupling of nonblind="tv" where not given
+_TV_PENALTY = 10.0
+
+
+def _fast_phase(frame, psf, choice):
+    """the second phase of deblur_module where `nonblind` is not the loop (`choice`: what _nonblind_args returned)"""
+    if isinstance(choice, tuple):
+        return _tv_phase(frame, psf, *choice[1:])
+    return _wiener_phase(frame, psf, choice)
+
+
+def _tv_phase(frame, psf, fidelity, iterations, coupling):
+    """the second phase of deblur_module(nonblind="tv") on the full-resolution gamma-encoded frame (an array or a DeviceImage): its
+    two printed lines, the deconvolved frame"""
+    from lib import _native
+    print("\n===== TV DECONVOLUTION =====")
+    plan = _native.tv_deconvolve_plan(frame.shape[0], frame.shape[1], np.shape(psf)[0])
+    print("TV : fidelity %g, penalty %g, %d iterations, %s, %d × %d transform" % (fidelity, _TV_PENALTY, iterations, coupling, plan.Py, plan.Px))
+    return utils.tv_deconvolve(frame, psf, fidelity, _TV_PENALTY, iterations, coupling)
 
 
 def _wiener_phase(frame, psf, balance):
@@ -511,7 +548,7 @@ def _level_shape(i, M, N):
 
 def _deblur_device(pic, filename, dest_path, blur_width, confidence, tolerance, quality, bits, mask, display, blur, preview, p, order, norm,
                    priority, mask_size, iterations, refocus, pyramid, save, despeckle=None, sharpen=None, denoise=None, local_contrast=None,
-                   detail=None, clarity=None, wiener_balance=None):
+                   detail=None, clarity=None, fast_phase=None):
     """`deblur_module` (deconvolve.py:65-368) with every frame resident in HBM: one upload of the picture,
     one download of the result; pad_image, gamma, the window views, the resize between pyramid levels and the solver all
     work on `lib._native.DeviceImage`s.  Line references as in `deblur_module` above."""
@@ -572,8 +609,8 @@ def _deblur_device(pic, filename, dest_path, blur_width, confidence, tolerance, 
         for case in ["blind", "non-blind"]:
             _native.Context.get().synchronize()
             t_case = time.perf_counter()
-            if case == "non-blind" and wiener_balance is not None:
-                deb, old = _wiener_phase(pic_d, psf, wiener_balance), deb
+            if case == "non-blind" and fast_phase is not None:
+                deb, old = _fast_phase(pic_d, psf, fast_phase), deb
                 old.close()
                 _native.Context.get().synchronize()
                 phases[case] = time.perf_counter() - t_case

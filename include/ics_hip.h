@@ -551,6 +551,29 @@ int ics_img_window_scores(const ics_img *src, int y0, int y1, int x0, int x1, in
 #define ICS_IMG_WIENER_MAX 8192
 int ics_img_wiener(const ics_img *src, const float *psf, int K, float balance, ics_img **out);
 int ics_img_wiener_plan(int H, int W, int K, int *Py, int *Px, size_t *workspace_bytes);
+/* TV-regularised deconvolution of a device image by a known PSF: minimise sum |Du| + (fidelity / 2) |h * u - f|^2, total variation
+ * plus a quadratic data term, by variable splitting (FTVd, Wang, Yang, Yin, Zhang 2008, in its split-Bregman / ADMM form, Goldstein and
+ * Osher 2009): every iteration is one shrinkage of the gradient per pixel and one linear solve that is diagonal under the 2-D
+ * transform.  The method between ics_img_wiener (no image prior) and the Richardson-Lucy loop.  psf, K, Py, Px, ext, Hc, L as for
+ * ics_img_wiener (L itself, not its square: it is the transfer of D^T D for periodic forward differences); everything runs on the
+ * periodic Py x Px domain.  mu = fidelity > 0, beta = penalty > 0, n = iterations, 1 .. ICS_IMG_TVD_MAX_ITERATIONS (a fixed count, no
+ * stopping rule); coupling 0: every channel is shrunk by its own gradient magnitude, 1: the three by their common one.
+ *   N0c = mu conj(Hc) transform(ext_c),  Gc = 1 / (mu |Hc|^2 + beta L),  u = ext, bx = by = 0;  n times (indices mod Px, Py):
+ *     vx = u[y, x+1] - u[y, x] + bx,  vy = u[y+1, x] - u[y, x] + by
+ *     m = sqrt(vx^2 + vy^2) (coupling 1: summed over the three channels too);  s = (m - 1 / beta) / m where m > 1 / beta, else 0
+ *     wx = s vx, wy = s vy;  bx = vx - wx, by = vy - wy;  px = wx - bx, py = wy - by
+ *     z = (px[y, x-1] - px[y, x]) + (py[y-1, x] - py[y, x]);  u_c = real(inverse transform((N0c + beta transform(z_c)) Gc))
+ *   out = u[:H, :W].  Nothing is clipped.
+ * float32 throughout, every operation of the shrinkage rounded once, no atomics: two runs give identical bits (restated in float64
+ * in tests/tv_deconv_ref.py).  A NaN spreads over the whole frame.  Queued like the other image filters, its kernels bracketed for
+ * ics_ctx_last_kernel_ms; src is not written.  ICS_EINVAL (*out NULL): src, psf or out NULL, K even or outside 3 .. 255 or above
+ * min(H, W), fidelity or penalty not finite or <= 0, iterations outside 1 .. ICS_IMG_TVD_MAX_ITERATIONS, coupling neither 0 nor 1.
+ * ICS_ENOSUP: H + K - 1 or W + K - 1 above ICS_IMG_WIENER_MAX.
+ * ics_img_tv_deconvolve_plan: the transform sizes and the device bytes such a call takes from the context's pool, 11 floats per
+ * transform point and channel and the tables (no device needed); same checks on H, W, K. */
+#define ICS_IMG_TVD_MAX_ITERATIONS 500
+int ics_img_tv_deconvolve(const ics_img *src, const float *psf, int K, float fidelity, float penalty, int iterations, int coupling, ics_img **out);
+int ics_img_tv_deconvolve_plan(int H, int W, int K, int *Py, int *Px, size_t *workspace_bytes);
 /* richardson_lucy_MM(image[iy:iy+M, ix:ix+N], u[uy:uy+uM, ux:ux+uN], psf, ...) with both windows taken from device
  * images (deconvolve.py:277-313 passes such views); psf is a host MK*MK*3 array as in ics_rl_upload. */
 int ics_rl_upload_img(ics_rl *job, const ics_img *image, int iy, int ix, const ics_img *u, int uy, int ux, const float *psf);

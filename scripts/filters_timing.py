@@ -1,6 +1,6 @@
 """Timing of the lib/utils.py filters on one seeded SIZE x SIZE RGB float32 picture (GPU box), one JSON line:
 
-    python scripts/filters_timing.py [SIZE=4096] [guided | llf | noise | despeckle | blurwidth | mask | wiener]       (a section name: that section alone)
+    python scripts/filters_timing.py [SIZE=4096] [guided | llf | noise | despeckle | blurwidth | mask | wiener | tvdeconv]       (a section name: that section alone)
 
   resident   the filters on a DeviceImage in HBM (csrc/ics_img_filters.hip): device time of the kernels (HIP events around them,
              ics_ctx_last_kernel_ms; warm, median of 25) and wall time of the queued call up to a stream synchronise
@@ -59,6 +59,13 @@
              transits of 8 B per transform point and channel; beside each frame DeviceImage.copy() of it as in the despeckle section.
              "driver": `deblur_module` on the 8-bit picture of the blurwidth section at 2048^2 and 4096^2 (blur 15, frames resident,
              iterations 20, the second call) with nonblind="rl" and nonblind="wiener": `last_phase_seconds` of both phases
+  tvdeconv   DeviceImage.tv_deconvolve (csrc/ics_img_tvdeconv.hip), fidelity 2000, penalty 10, K = 15 (a Gaussian PSF), on frames of its
+             own: SIZE x SIZE and 4000 x 6000, both couplings: kernel ms of a call of 10 iterations and of one of 1 iteration (median
+             and minimum of 5 rounds), ms per iteration as their difference over 9, the pool bytes, and TB/s on the model of 13.5
+             transits of 8 B per transform point and channel an iteration; beside each frame DeviceImage.wiener on it
+             (balance 0.01) and DeviceImage.copy() of it as in the despeckle section.  "driver": `deblur_module` on the 8-bit picture of
+             the blurwidth section at SIZE^2 (blur 15, mask_size 255, frames resident, iterations 20, the second call) with
+             nonblind="rl", "wiener" and "tv": `last_phase_seconds` of both phases
   checks     the resident USM must not take longer than the three float64 calls, in kernel time and in wall time (a guard against a
              broken kernel, not a target); the exit status is 1 if one of them fails
 Starts no child process; a job script puts its own time limit around it."""
@@ -343,9 +350,61 @@ def wiener_section(ctx):
     return res
 
 
+TVD_K, TVD_FIDELITY, TVD_PENALTY, TVD_ITERATIONS, TVD_REPS, TVD_TRANSITS = 15, 2000.0, 10.0, 10, 5, 13.5
+
+
+def tvdeconv_section(ctx, size):
+    import contextlib
+    import io
+    sys.path.insert(0, os.path.join(ROOT, "image-cases-studies_amd"))
+    import deconvolve as dv
+
+    def kernel_ms(fn):
+        fn().close()                                       # warm: code objects, LDS attribute, pool blocks
+        ctx.synchronize()
+        ms = []
+        for _ in range(TVD_REPS):
+            out = fn()
+            ctx.synchronize()
+            ms.append(ctx.last_kernel_ms())
+            out.close()
+        return float(np.median(ms)), float(np.min(ms))
+
+    res = {"K": TVD_K, "fidelity": TVD_FIDELITY, "penalty": TVD_PENALTY, "iterations": TVD_ITERATIONS}
+    psf = utils.gaussian_kernel(TVD_K, TVD_K / 6.0)
+    for H, W in ((size, size), (4000, 6000)):
+        img = _native.DeviceImage.from_host(np.random.default_rng(0).random((H, W, 3), dtype=np.float32), ctx)
+        plan = _native.tv_deconvolve_plan(H, W, TVD_K)
+        row = res["%dx%d" % (H, W)] = {"transform": [plan.Py, plan.Px], "pool_mb": round(plan.workspace_bytes / 2 ** 20, 1), "copy": copy_row(img, ctx)}
+        med, low = kernel_ms(lambda: img.wiener(psf, WIENER_BALANCE))
+        row["wiener"] = {"kernel_ms": round(med, 4), "min_ms": round(low, 4)}
+        for coupling in ("vector", "channel"):
+            full, full_min = kernel_ms(lambda: img.tv_deconvolve(psf, TVD_FIDELITY, TVD_PENALTY, TVD_ITERATIONS, coupling))
+            one, one_min = kernel_ms(lambda: img.tv_deconvolve(psf, TVD_FIDELITY, TVD_PENALTY, 1, coupling))
+            per = (full - one) / (TVD_ITERATIONS - 1)
+            row[coupling] = {"kernel_ms": round(full, 4), "min_ms": round(full_min, 4), "one_iteration_ms": round(one, 4), "ms_per_iteration": round(per, 4),
+                             "tb_per_s": round(TVD_TRANSITS * 8 * 3 * plan.Py * plan.Px / (per * 1e-3) / 1e12, 3)}
+        img.close()
+    drv = res["driver"] = {}
+    coarse = np.random.default_rng(0).random((size // 8 + 2, size // 8 + 2, 3))
+    pic = (np.repeat(np.repeat(coarse, 8, 0), 8, 1)[:size, :size] * 200 + 20).astype(np.uint8)
+    for mode in ("rl", "wiener", "tv"):
+        for _ in range(2):                                 # the first call builds the jobs
+            with contextlib.redirect_stdout(io.StringIO()):
+                t0 = time.perf_counter()
+                dv.deblur_module(pic, "t", ".", 15, mask=[size // 2, size // 2], mask_size=255, display=False, iterations=20, save=False,
+                                 device_resident=True, nonblind=mode)
+                dt = time.perf_counter() - t0
+        drv["%d_%s" % (size, mode)] = {"seconds": round(dt, 4), **{k: round(v, 5) for k, v in dv.deblur_module.last_phase_seconds.items()}}
+    return res
+
+
 def main():
     size = int(sys.argv[1]) if len(sys.argv) > 1 else 4096
     ctx = _native.Context.get()
+    if sys.argv[2:] == ["tvdeconv"]:
+        print(json.dumps({"size": size, "device": ctx.name, "tvdeconv": tvdeconv_section(ctx, size)}))
+        return 0
     if sys.argv[2:] == ["wiener"]:
         print(json.dumps({"device": ctx.name, "wiener": wiener_section(ctx)}))
         return 0
@@ -444,6 +503,7 @@ def main():
     res["blurwidth"] = blurwidth_section(img, ctx, size)
     res["mask"] = mask_section(img, ctx, size)
     res["wiener"] = wiener_section(ctx)
+    res["tvdeconv"] = tvdeconv_section(ctx, size)
     res["checks"] = {"%s_%s" % (name, what): res["resident"][name][what] <= res["per_channel_f64"][name][what]
                      for name in ("usm_gauss15", "usm_bessel15") for what in ("kernel_ms", "wall_ms")}
     print(json.dumps(res))
