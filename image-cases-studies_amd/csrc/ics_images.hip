@@ -1,5 +1,5 @@
 // ics_images.hip -- the ics_img_* entries of the C ABI (include/ics_hip.h).  Host side only; kernels live in ics_img.hip / ics_img_filters.hip /
-// ics_img_tvdenoise.hip / ics_img_wavelet.hip / ics_img_noise.hip / ics_img_despeckle.hip / ics_img_blurwidth.hip / ics_img_mask.hip / ics_img_guided.hip / ics_img_llf.hip (what these nine share: ics_img_px.h) / ics_img_wiener.hip / ics_img_tvdeconv.hip / ics_resize.hip.
+// ics_img_tvdenoise.hip / ics_img_wavelet.hip / ics_img_noise.hip / ics_img_despeckle.hip / ics_img_blurwidth.hip / ics_img_mask.hip / ics_img_guided.hip / ics_img_llf.hip (what these nine share: ics_img_px.h) / ics_img_wiener.hip / ics_img_tvdeconv.hip / ics_img_tvmdeconv.hip / ics_resize.hip.
 #include "ics_host.h"
 
 using namespace ics_host;
@@ -535,6 +535,58 @@ extern "C" int ics_img_tv_deconvolve(const ics_img* src, const float* psf, int K
   if (e == hipSuccess) e = op.begin();
   if (e == hipSuccess) e = ics_launch_img_tv_deconvolve(src->d, H, W, K, fidelity, penalty, iterations, coupling, Py, Px, ws, (*out)->d, c->stream);
   return op.finish(e);
+}
+
+// ---- TV deconvolution of a device image with a masked data term (csrc/ics_img_tvmdeconv.hip) ---------------------------------------
+// One route.  The shapes and the limits are those of ics_img_tv_deconvolve; one workspace from the pool, carved by the launcher, the
+// caller's mask inside it.  Only the count comes back; the frame stays where it is.
+extern "C" int ics_img_tv_deconvolve_masked_plan(int H, int W, int K, int* Py, int* Px, size_t* workspace_bytes) {
+  int py = 0, px = 0;
+  RC(wiener_shape(H, W, K, &py, &px));
+  if (Py) *Py = py;
+  if (Px) *Px = px;
+  if (workspace_bytes) *workspace_bytes = ics_img_tvm_workspace_bytes(K, py, px);
+  return ICS_OK;
+}
+extern "C" int ics_img_tv_deconvolve_masked(const ics_img* src, const float* psf, int K, const unsigned char* observed, float clip, float fidelity, float penalty,
+                                            float data_penalty, int iterations, int coupling, long long* unobserved, ics_img** out) {
+  RC(check_new(src, out));
+  if (!psf) return ics_set_error(ICS_EINVAL, "psf is NULL");
+  if (!(clip > 0.f)) return ics_set_error(ICS_EINVAL, "clip = %g (above 0; inf keeps every finite pixel)", (double)clip);
+  if (!std::isfinite(fidelity) || !(fidelity > 0.f)) return ics_set_error(ICS_EINVAL, "fidelity = %g (must be finite and > 0)", (double)fidelity);
+  if (!std::isfinite(penalty) || !(penalty > 0.f)) return ics_set_error(ICS_EINVAL, "penalty = %g (must be finite and > 0)", (double)penalty);
+  if (!std::isfinite(data_penalty) || !(data_penalty > 0.f)) return ics_set_error(ICS_EINVAL, "data_penalty = %g (must be finite and > 0)", (double)data_penalty);
+  if (iterations < 1 || iterations > ICS_IMG_TVD_MAX_ITERATIONS) return ics_set_error(ICS_EINVAL, "iterations = %d (1 .. %d)", iterations, ICS_IMG_TVD_MAX_ITERATIONS);
+  RC(check_coupling(coupling));
+  const int H = src->H, W = src->W;
+  int Py = 0, Px = 0;
+  RC(wiener_shape(H, W, K, &Py, &Px));
+  ics_ctx* c = src->ctx;
+  HIPCHK(hipSetDevice(c->device));
+  std::vector<float> planar((size_t)3 * K * K);
+  for (int ch = 0; ch < 3; ++ch)
+    for (int i = 0; i < K * K; ++i) planar[(size_t)ch * K * K + i] = psf[(size_t)3 * i + ch];
+  ImgOp op(c, out, "img_tv_deconvolve_masked");
+  RC(img_new(c, H, W, out));
+  void* ws = nullptr;
+  long long got = 0;
+  hipError_t e = op.alloc(&ws, ics_img_tvm_workspace_bytes(K, Py, Px));
+  if (e == hipSuccess) e = put_table(c, ics_img_wiener_psf_slot(ics_img_tvm_tables(ws, Py, Px), K, Py, Px), planar);
+  if (e == hipSuccess && observed) {
+    e = hipMemcpyAsync(ics_img_tvm_mask_slot(ws, K, Py, Px), observed, (size_t)H * W, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);   // the host buffer may be released by the caller
+  }
+  if (e == hipSuccess) e = op.begin();
+  if (e == hipSuccess)
+    e = ics_launch_img_tv_deconvolve_masked(src->d, H, W, K, observed != nullptr, clip, fidelity, penalty, data_penalty, iterations, coupling, Py, Px, ws, (*out)->d, c->stream);
+  if (e == hipSuccess && unobserved) {                 // the count and nothing else
+    e = op.end();
+    if (e == hipSuccess) e = hipMemcpyAsync(&got, ics_img_tvm_total(ws, Py, Px), sizeof got, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  }
+  RC(op.finish(e));
+  if (unobserved) *unobserved = got;
+  return ICS_OK;
 }
 
 // ---- guided filter of a device image (csrc/ics_img_guided.hip) ------------------------------------------------------------------

@@ -392,3 +392,16 @@ size_t ics_img_tvd_workspace_bytes(int K, int Py, int Px);
 void* ics_img_tvd_tables(void* workspace, int Py, int Px);
 hipError_t ics_launch_img_tv_deconvolve(const float* f, int H, int W, int K, float mu, float beta, int iterations, int coupling, int Py, int Px, void* workspace, float* out,
                                         hipStream_t s);
+
+// ---- TV deconvolution with a masked data term (ics_img_tvmdeconv.hip): the iterations of ics_img_tvdeconv.hip with the extension of the
+// frame, clipped and non-finite pixels and the caller's zeros declared unobserved, one more splitting variable keeping the solve
+// diagonal.  workspace: ics_img_tvm_workspace_bytes, one block; ics_img_tvm_tables: the tables inside it, laid out as
+// ics_img_wiener_table_bytes, their ics_img_wiener_psf_slot holding the PSF as [3][K][K] (every channel of sum 1) before the launch;
+// ics_img_tvm_mask_slot: H W bytes of the caller's mask before the launch where observed is true; ics_img_tvm_total: the count of
+// unobserved frame pixels after it.  clip: +inf for none.  coupling as above.  One route; f is only read.
+size_t ics_img_tvm_workspace_bytes(int K, int Py, int Px);
+void* ics_img_tvm_tables(void* workspace, int Py, int Px);
+long long* ics_img_tvm_total(void* workspace, int Py, int Px);
+unsigned char* ics_img_tvm_mask_slot(void* workspace, int K, int Py, int Px);
+hipError_t ics_launch_img_tv_deconvolve_masked(const float* f, int H, int W, int K, bool observed, float clip, float mu, float beta, float gamma, int iterations, int coupling,
+                                               int Py, int Px, void* workspace, float* out, hipStream_t s);

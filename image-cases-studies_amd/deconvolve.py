@@ -138,7 +138,13 @@ def deblur_module(pic, filename, dest_path, blur_width, confidence=10, tolerance
     iterations, coupling "vector" unless given; the penalty is 10): likewise, the second phase being one `utils.tv_deconvolve` -- the
     loop's total-variation prior on `wiener`'s transform, tens of milliseconds, lower fidelity for noisier frames;
     "===== TV DECONVOLUTION =====" and one line "TV : fidelity 2000, penalty 10, 10 iterations, vector, 8192 × 8192 transform" are
-    printed."""
+    printed.
+    `nonblind="tv-masked"` or `("tv-masked", fidelity[, iterations[, coupling[, clip]]])` (fidelity 2000, 10 iterations, coupling
+    "vector", clip 0.99 unless given; the penalties are 10 and the fidelity): likewise, the second phase being one
+    `utils.tv_deconvolve_masked` -- "tv" with the pixels beyond the frame's edges and those with a channel at or above `clip` (None:
+    none) unobserved instead of fitted; the edges pay at once, the clipped highlights only from about 30 iterations;
+    "===== MASKED TV DECONVOLUTION =====" and one line "TV-masked : fidelity 2000, penalties 10 / 2000, 10 iterations, vector, clip
+    0.99, 8192 × 8192 transform, 1.72 % unobserved" are printed."""
     fast_phase = _nonblind_args(nonblind)
     despeckle = _despeckle_args(despeckle)
     auto_width = _blur_width_args(blur_width)
@@ -299,17 +305,27 @@ def deblur_module(pic, filename, dest_path, blur_width, confidence=10, tolerance
 
 
 def _nonblind_args(nonblind):
-    """`nonblind` of deblur_module -> None for "rl" (the loop), the balance of "wiener" / ("wiener", balance), or
-    ("tv", fidelity, iterations, coupling) of "tv" / ("tv", fidelity[, iterations[, coupling]]), checked (ValueError)"""
-    form = ("nonblind takes \"rl\", \"wiener\", (\"wiener\", balance), \"tv\" or (\"tv\", fidelity[, iterations[, coupling]]), got %r"
-            % (nonblind,))
+    """`nonblind` of deblur_module -> None for "rl" (the loop), the balance of "wiener" / ("wiener", balance),
+    ("tv", fidelity, iterations, coupling) of "tv" / ("tv", fidelity[, iterations[, coupling]]), or
+    ("tv-masked", fidelity, iterations, coupling, clip) of "tv-masked" / ("tv-masked", fidelity[, iterations[, coupling[, clip]]]),
+    checked (ValueError)"""
+    form = ("nonblind takes \"rl\", \"wiener\", (\"wiener\", balance), \"tv\", (\"tv\", fidelity[, iterations[, coupling]]), "
+            "\"tv-masked\" or (\"tv-masked\", fidelity[, iterations[, coupling[, clip]]]), got %r" % (nonblind,))
     if isinstance(nonblind, str):
-        if nonblind not in ("rl", "wiener", "tv"):
+        if nonblind not in ("rl", "wiener", "tv", "tv-masked"):
             raise ValueError(form)
-        return {"rl": None, "wiener": 0.01, "tv": ("tv",) + _TV_PHASE}[nonblind]
+        return {"rl": None, "wiener": 0.01, "tv": ("tv",) + _TV_PHASE, "tv-masked": ("tv-masked",) + _TVM_PHASE}[nonblind]
     if not isinstance(nonblind, (tuple, list)) or len(nonblind) < 2 or not isinstance(nonblind[0], str):
         raise ValueError(form)
     from lib import _native
+    if nonblind[0] == "tv-masked" and len(nonblind) <= 5:
+        fidelity, iterations, coupling, clip = tuple(nonblind[1:]) + _TVM_PHASE[len(nonblind) - 1:]
+        try:                                      # (the PSF is the blind phase's: a stand-in passes its checks here)
+            _, _, clip, fidelity, _, _, iterations, coupling = _native.tv_deconvolve_masked_args(np.ones((3, 3)), None, clip, fidelity, _TV_PENALTY, None, iterations,
+                                                                                                 coupling, (3, 3))
+        except ValueError as exc:
+            raise ValueError("nonblind: %s" % exc)
+        return ("tv-masked", fidelity, iterations, coupling, clip)
     if nonblind[0] == "tv" and len(nonblind) <= 4:
         fidelity, iterations, coupling = tuple(nonblind[1:]) + _TV_PHASE[len(nonblind) - 1:]
         try:                                      # (the PSF is the blind phase's: a stand-in passes its checks here)
@@ -326,13 +342,27 @@ def _nonblind_args(nonblind):
 
 _TV_PHASE = (2000.0, 10, "vector")      # fidelity, iterations, coupling of nonblind="tv" where not given
 _TV_PENALTY = 10.0
+_TVM_PHASE = _TV_PHASE + (0.99,)        # ... and clip of nonblind="tv-masked"
 
 
 def _fast_phase(frame, psf, choice):
     """the second phase of deblur_module where `nonblind` is not the loop (`choice`: what _nonblind_args returned)"""
     if isinstance(choice, tuple):
-        return _tv_phase(frame, psf, *choice[1:])
+        return (_tvm_phase if choice[0] == "tv-masked" else _tv_phase)(frame, psf, *choice[1:])
     return _wiener_phase(frame, psf, choice)
+
+
+def _tvm_phase(frame, psf, fidelity, iterations, coupling, clip):
+    """the second phase of deblur_module(nonblind="tv-masked") on the full-resolution gamma-encoded frame (an array or a DeviceImage):
+    its two printed lines (the second once the count is back), the deconvolved frame"""
+    from lib import _native
+    print("\n===== MASKED TV DECONVOLUTION =====")
+    plan = _native.tv_deconvolve_masked_plan(frame.shape[0], frame.shape[1], np.shape(psf)[0])
+    out, unobserved = utils.tv_deconvolve_masked(frame, psf, None, clip, fidelity, _TV_PENALTY, None, iterations, coupling, count=True)
+    print("TV-masked : fidelity %g, penalties %g / %g, %d iterations, %s, clip %s, %d × %d transform, %.2f %% unobserved"
+          % (fidelity, _TV_PENALTY, fidelity, iterations, coupling, "none" if clip == float("inf") else "%g" % clip, plan.Py, plan.Px,
+             100.0 * unobserved / (frame.shape[0] * frame.shape[1])))
+    return out
 
 
 def _tv_phase(frame, psf, fidelity, iterations, coupling):

@@ -190,6 +190,8 @@ def load():
     lib.ics_img_wiener_plan.argtypes = [ci, ci, ci, C.POINTER(ci), C.POINTER(ci), C.POINTER(C.c_size_t)]
     lib.ics_img_tv_deconvolve.argtypes = [vp, vp, ci, cf, cf, ci, ci, C.POINTER(vp)]
     lib.ics_img_tv_deconvolve_plan.argtypes = [ci, ci, ci, C.POINTER(ci), C.POINTER(ci), C.POINTER(C.c_size_t)]
+    lib.ics_img_tv_deconvolve_masked.argtypes = [vp, vp, ci, vp, cf, cf, cf, cf, ci, ci, C.POINTER(C.c_longlong), C.POINTER(vp)]
+    lib.ics_img_tv_deconvolve_masked_plan.argtypes = [ci, ci, ci, C.POINTER(ci), C.POINTER(ci), C.POINTER(C.c_size_t)]
     lib.ics_rl_upload_img.argtypes = [vp, vp, ci, ci, vp, ci, ci, vp]
     lib.ics_rl_download_img.argtypes = [vp, vp, ci, ci]
     lib.ics_group_create.argtypes = [ci, ci, ci, C.c_char_p, ci, C.POINTER(vp)]
@@ -211,7 +213,7 @@ def load():
                  "ics_rl_download", "ics_rl_run", "ics_rl_stage", "ics_rl_read", "ics_rl_write", "ics_rl_read_rows", "ics_rl_write_rows", "ics_rl_copy_rows", "ics_normalize_kernel",
                  "ics_tv", "ics_conv2d_symm", "ics_usm", "ics_bilateral", "ics_resize_bicubic", "ics_img_create", "ics_img_shape",
                  "ics_img_upload", "ics_img_upload_int", "ics_img_download", "ics_img_pad_edge", "ics_img_crop", "ics_img_paste", "ics_img_gamma", "ics_img_resize",
-                 "ics_img_convolve", "ics_img_usm", "ics_img_bilateral", "ics_img_tv_denoise", "ics_img_wavelet_equalize", "ics_img_noise_estimate", "ics_img_blur_profile", "ics_img_window_scores", "ics_img_despeckle", "ics_img_guided", "ics_img_local_laplacian", "ics_img_wiener", "ics_img_wiener_plan", "ics_img_tv_deconvolve", "ics_img_tv_deconvolve_plan",
+                 "ics_img_convolve", "ics_img_usm", "ics_img_bilateral", "ics_img_tv_denoise", "ics_img_wavelet_equalize", "ics_img_noise_estimate", "ics_img_blur_profile", "ics_img_window_scores", "ics_img_despeckle", "ics_img_guided", "ics_img_local_laplacian", "ics_img_wiener", "ics_img_wiener_plan", "ics_img_tv_deconvolve", "ics_img_tv_deconvolve_plan", "ics_img_tv_deconvolve_masked", "ics_img_tv_deconvolve_masked_plan",
                  "ics_rl_upload_img", "ics_rl_download_img", "ics_group_create", "ics_group_info", "ics_group_barrier",
                  "ics_group_allreduce_max", "ics_group_allreduce_sum", "ics_group_describe", "ics_group_allgather"):
         getattr(lib, name).restype = ci
@@ -586,6 +588,48 @@ def tv_deconvolve_plan(H, W, K):
     per transform point and channel and the tables (no device needed).  NativeError: as wiener_plan."""
     py, px, ws = C.c_int(0), C.c_int(0), C.c_size_t(0)
     _check(load().ics_img_tv_deconvolve_plan(int(H), int(W), int(K), C.byref(py), C.byref(px), C.byref(ws)))
+    return TVDeconvolvePlan(py.value, px.value, int(ws.value))
+
+
+def tv_deconvolve_masked_args(psf, observed, clip, fidelity, penalty, data_penalty, iterations, coupling, shape):
+    """the arguments of DeviceImage.tv_deconvolve_masked checked (ValueError) and as (psf, observed, clip, fidelity, penalty,
+    data_penalty, iterations, coupling): psf, fidelity, penalty, iterations and coupling as tv_deconvolve_args gives them; observed
+    None or a contiguous H x W uint8 array of 0 / 1 with at least one 1; clip a float, inf for None; data_penalty a float, fidelity
+    for None; shape: (H, W, ...) of the frame"""
+    k, fidelity, penalty, iterations, coupling = tv_deconvolve_args(psf, fidelity, penalty, iterations, coupling, shape)
+    if observed is not None:
+        try:
+            m = np.asarray(observed) != 0
+        except (TypeError, ValueError):
+            m = None
+        if m is None or m.dtype != np.bool_ or m.shape != tuple(shape[:2]):
+            raise ValueError("observed of shape %s (None or an array of the frame's %d x %d)" % (np.shape(observed), shape[0], shape[1]))
+        if not m.any():
+            raise ValueError("observed holds no non-zero entry: nothing of the frame is data")
+        observed = np.ascontiguousarray(m, dtype=np.uint8)
+    if clip is None:
+        clip = float("inf")
+    else:
+        try:
+            ok = not isinstance(clip, (str, bool)) and float(clip) > 0 and (float(clip) == float("inf") or _finite32(clip, scalar=True))
+        except (TypeError, ValueError):
+            ok = False
+        if not ok:
+            raise ValueError("clip %r (None, inf or a finite number > 0)" % (clip,))
+    if data_penalty is None:
+        data_penalty = fidelity
+    elif not _finite32(data_penalty, scalar=True) or not np.float32(data_penalty) > 0:
+        raise ValueError("data_penalty %r (None or finite and > 0)" % (data_penalty,))
+    return k, observed, float(clip), fidelity, penalty, float(data_penalty), iterations, coupling
+
+
+def tv_deconvolve_masked_plan(H, W, K):
+    """ics_img_tv_deconvolve_masked_plan: TVDeconvolvePlan(Py, Px, workspace_bytes) of DeviceImage.tv_deconvolve_masked on an H x W
+    frame with a K x K PSF -- the transform sizes (those of wiener_plan) and the device bytes it takes from the pool beside the
+    result: 4 (43 Py Px + Py + 4) + Py Px and the tables, 14 1/3 floats per transform point and channel, the row counts and a byte per
+    point for the mask (no device needed).  NativeError: as wiener_plan."""
+    py, px, ws = C.c_int(0), C.c_int(0), C.c_size_t(0)
+    _check(load().ics_img_tv_deconvolve_masked_plan(int(H), int(W), int(K), C.byref(py), C.byref(px), C.byref(ws)))
     return TVDeconvolvePlan(py.value, px.value, int(ws.value))
 
 
@@ -975,6 +1019,31 @@ class DeviceImage:
         coupling.  NativeError (ICS_ENOSUP): H + K - 1 or W + K - 1 above IMG_WIENER_MAX."""
         psf, fidelity, penalty, iterations, coupling = tv_deconvolve_args(psf, fidelity, penalty, iterations, coupling, self.shape)
         return self._new(load().ics_img_tv_deconvolve, _ptr(psf), psf.shape[0], fidelity, penalty, iterations, _coupling(coupling))
+
+    def tv_deconvolve_masked(self, psf, observed=None, clip=None, fidelity=2000.0, penalty=10.0, data_penalty=None, iterations=10, coupling="vector",
+                             count=False):
+        """`tv_deconvolve` with a masked data term: minimise sum |Du| + (fidelity / 2) |M (h * u - self)|^2, M a 0/1 plane shared by
+        the three channels -- what is not data is not fitted.  Unobserved are always the extension of the frame to the transform size
+        (`tv_deconvolve` fits its ramp as if it were measured, though the pixels beyond the frame that the PSF mixed into its rim are
+        unknown) and every pixel with a non-finite channel (a NaN is simply no data here: no despeckle needed first); with `clip`,
+        every pixel with a channel at or above it (clipped highlights break the linear blur model, `best_mask` leaves them out too);
+        with `observed`, an H x W array, every pixel where it is 0.  The mask breaks the diagonal solve; one more splitting variable
+        with the penalty `data_penalty` (None: fidelity) restores it (Almeida and Figueiredo, IEEE TIP 2013), on the transform, the
+        shrink pass and the tables of `tv_deconvolve` (csrc/ics_img_tvmdeconv.hip; restated in float64 in tests/tvm_deconv_ref.py).
+        psf, fidelity, penalty, iterations, coupling as for `tv_deconvolve`.  On the synthetic frames of `tv_deconvolve` (box PSFs of
+        5, 9, 15 px, sigma 0.002) ten iterations leave an rms error of 0.0333 / 0.0501 / 0.0740 where `tv_deconvolve` leaves 0.0418 /
+        0.0552 / 0.0883, the unknown edges alone.  Near clipped highlights the mask pays only from about 30 iterations: six lights under
+        a 15-px box, rms around them 0.0925 against 0.1048 without clip at 30 iterations, but 0.1348 against 0.1260 at 10.  Nothing is
+        clipped and nothing keeps the result positive.  Two calls give identical bits.  count=True: (image, unobserved), the frame
+        pixels that were not data; the call then waits for the device.  ValueError (before any native call): whatever `tv_deconvolve`
+        refuses; observed not H x W or all zero; clip not None, inf or a finite number > 0; data_penalty not None or finite and > 0.
+        NativeError (ICS_ENOSUP): H + K - 1 or W + K - 1 above IMG_WIENER_MAX."""
+        psf, observed, clip, fidelity, penalty, data_penalty, iterations, coupling = tv_deconvolve_masked_args(
+            psf, observed, clip, fidelity, penalty, data_penalty, iterations, coupling, self.shape)
+        got = C.c_longlong(0)
+        img = self._new(lambda h, *a: load().ics_img_tv_deconvolve_masked(h, *a[:-1], C.byref(got) if count else None, a[-1]), _ptr(psf), psf.shape[0],
+                        None if observed is None else _ptr(observed), clip, fidelity, penalty, data_penalty, iterations, _coupling(coupling))
+        return (img, int(got.value)) if count else img
 
     def close(self):
         if self._h:

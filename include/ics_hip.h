@@ -574,6 +574,30 @@ int ics_img_wiener_plan(int H, int W, int K, int *Py, int *Px, size_t *workspace
 #define ICS_IMG_TVD_MAX_ITERATIONS 500
 int ics_img_tv_deconvolve(const ics_img *src, const float *psf, int K, float fidelity, float penalty, int iterations, int coupling, ics_img **out);
 int ics_img_tv_deconvolve_plan(int H, int W, int K, int *Py, int *Px, size_t *workspace_bytes);
+/* ics_img_tv_deconvolve with a masked data term: minimise sum |Du| + (fidelity / 2) |M (h * u - f)|^2, M a 0/1 plane shared by the
+ * three channels.  What is not data is not fitted: the extension of the frame to the transform size (the pixels beyond the frame that
+ * the PSF mixed into its rim are unknown), clipped highlights, non-finite pixels, and whatever the caller marks.  The mask breaks the
+ * diagonal solve; one more splitting variable v = h * u with its multiplier d and its penalty gamma = data_penalty restores it
+ * (Almeida and Figueiredo, "Deconvolving images with unknown boundaries using the alternating direction method of multipliers", IEEE
+ * TIP 2013).  psf, K, Py, Px, Hc, L, mu, beta, n, coupling as for ics_img_tv_deconvolve.  observed: H W host bytes, row-major, or
+ * NULL for all non-zero; clip: a pixel with a channel at or above it is unobserved, +inf for none.
+ *   m = observed != 0 and the three channels finite and the three channels < clip;  f0 = f with non-finite values 0
+ *   ext = the ramp extension of f0;  M = m on the frame, 0 on every extension pixel
+ *   Gc = 1 / (gamma |Hc|^2 + beta L),  u = ext, bx = by = d = 0, r_c = real(inverse transform(Hc transform(ext_c)));  n times:
+ *     u, bx, by -> bx, by, z: the shrinkage of ics_img_tv_deconvolve
+ *     t = r + d;  v = (mu M ext + gamma t) / (mu M + gamma);  d = t - v;  q = v - d
+ *     U_c = (gamma conj(Hc) transform(q_c) + beta transform(z_c)) Gc;  u_c = real(inverse transform(U_c)),  r_c = real(inverse transform(Hc U_c))
+ *   out = u[:H, :W].  Nothing is clipped.  *unobserved (where not NULL): the frame pixels with m false.
+ * float32 throughout, no atomics, every sum in one order: two runs give identical bits (restated in float64 in
+ * tests/tvm_deconv_ref.py).  Near clipped highlights the mask pays from about 30 iterations, not at 10; nothing keeps the result
+ * positive.  Queued like the other image filters, its kernels bracketed for ics_ctx_last_kernel_ms; with unobserved given the call
+ * waits for the count.  src is not written.  ICS_EINVAL (*out NULL): as ics_img_tv_deconvolve, and clip not above 0 (NaN included),
+ * data_penalty not finite or <= 0.  ICS_ENOSUP: H + K - 1 or W + K - 1 above ICS_IMG_WIENER_MAX.
+ * ics_img_tv_deconvolve_masked_plan: the transform sizes and the device bytes such a call takes from the context's pool,
+ * 4 (43 Py Px + Py + 4) + Py Px and the tables of ics_img_wiener (14 1/3 floats per transform point and channel, the row counts, a
+ * byte per point for the caller's mask); no device needed; same checks on H, W, K. */
+int ics_img_tv_deconvolve_masked(const ics_img *src, const float *psf, int K, const unsigned char *observed, float clip, float fidelity, float penalty, float data_penalty, int iterations, int coupling, long long *unobserved, ics_img **out);
+int ics_img_tv_deconvolve_masked_plan(int H, int W, int K, int *Py, int *Px, size_t *workspace_bytes);
 /* richardson_lucy_MM(image[iy:iy+M, ix:ix+N], u[uy:uy+uM, ux:ux+uN], psf, ...) with both windows taken from device
  * images (deconvolve.py:277-313 passes such views); psf is a host MK*MK*3 array as in ics_rl_upload. */
 int ics_rl_upload_img(ics_rl *job, const ics_img *image, int iy, int ix, const ics_img *u, int uy, int ux, const float *psf);

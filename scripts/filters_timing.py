@@ -1,6 +1,6 @@
 """Timing of the lib/utils.py filters on one seeded SIZE x SIZE RGB float32 picture (GPU box), one JSON line:
 
-    python scripts/filters_timing.py [SIZE=4096] [guided | llf | noise | despeckle | blurwidth | mask | wiener | tvdeconv]       (a section name: that section alone)
+    python scripts/filters_timing.py [SIZE=4096] [guided | llf | noise | despeckle | blurwidth | mask | wiener | tvdeconv | tvmasked]       (a section name: that section alone)
 
   resident   the filters on a DeviceImage in HBM (csrc/ics_img_filters.hip): device time of the kernels (HIP events around them,
              ics_ctx_last_kernel_ms; warm, median of 25) and wall time of the queued call up to a stream synchronise
@@ -66,6 +66,12 @@
              (balance 0.01) and DeviceImage.copy() of it as in the despeckle section.  "driver": `deblur_module` on the 8-bit picture of
              the blurwidth section at SIZE^2 (blur 15, mask_size 255, frames resident, iterations 20, the second call) with
              nonblind="rl", "wiener" and "tv": `last_phase_seconds` of both phases
+  tvmasked   DeviceImage.tv_deconvolve_masked (csrc/ics_img_tvmdeconv.hip), fidelity 2000, penalties 10 and 2000, clip 0.99, K = 15 (a
+             Gaussian PSF), on the frames of the tvdeconv section, both couplings: kernel ms of a call of 10 iterations and of one of 1
+             iteration (median and minimum of 5 rounds), ms per iteration as their difference over 9, the bytes an iteration moves and
+             TB/s on the model of 17 1/6 transits of 8 B per transform point and channel, the pool bytes; beside each
+             frame DeviceImage.tv_deconvolve on it, measured the same way, and the ratio of the two iterations.  "driver": `deblur_module`
+             as in the tvdeconv section with nonblind="rl", "wiener", "tv" and "tv-masked"
   checks     the resident USM must not take longer than the three float64 calls, in kernel time and in wall time (a guard against a
              broken kernel, not a target); the exit status is 1 if one of them fails
 Starts no child process; a job script puts its own time limit around it."""
@@ -399,9 +405,65 @@ def tvdeconv_section(ctx, size):
     return res
 
 
+TVM_CLIP, TVM_TRANSITS = 0.99, 17.0 + 1.0 / 6.0
+
+
+def tvmasked_section(ctx, size):
+    import contextlib
+    import io
+    sys.path.insert(0, os.path.join(ROOT, "image-cases-studies_amd"))
+    import deconvolve as dv
+
+    def kernel_ms(fn):
+        fn().close()                                       # warm: code objects, LDS attribute, pool blocks
+        ctx.synchronize()
+        ms = []
+        for _ in range(TVD_REPS):
+            out = fn()
+            ctx.synchronize()
+            ms.append(ctx.last_kernel_ms())
+            out.close()
+        return float(np.median(ms)), float(np.min(ms))
+
+    def per_iteration(call):
+        full, full_min = kernel_ms(lambda: call(TVD_ITERATIONS))
+        one, one_min = kernel_ms(lambda: call(1))
+        return {"kernel_ms": round(full, 4), "min_ms": round(full_min, 4), "one_iteration_ms": round(one, 4), "ms_per_iteration": round((full - one) / (TVD_ITERATIONS - 1), 4)}
+
+    res = {"K": TVD_K, "fidelity": TVD_FIDELITY, "penalty": TVD_PENALTY, "data_penalty": TVD_FIDELITY, "clip": TVM_CLIP, "iterations": TVD_ITERATIONS}
+    psf = utils.gaussian_kernel(TVD_K, TVD_K / 6.0)
+    for H, W in ((size, size), (4000, 6000)):
+        img = _native.DeviceImage.from_host(np.random.default_rng(0).random((H, W, 3), dtype=np.float32), ctx)
+        plan = _native.tv_deconvolve_masked_plan(H, W, TVD_K)
+        moved = TVM_TRANSITS * 8 * 3 * plan.Py * plan.Px
+        row = res["%dx%d" % (H, W)] = {"transform": [plan.Py, plan.Px], "pool_mb": round(plan.workspace_bytes / 2 ** 20, 1), "gb_per_iteration": round(moved / 1e9, 3)}
+        for coupling in ("vector", "channel"):
+            tv = per_iteration(lambda n: img.tv_deconvolve(psf, TVD_FIDELITY, TVD_PENALTY, n, coupling))
+            tvm = per_iteration(lambda n: img.tv_deconvolve_masked(psf, None, TVM_CLIP, TVD_FIDELITY, TVD_PENALTY, None, n, coupling))
+            tvm["tb_per_s"] = round(moved / (tvm["ms_per_iteration"] * 1e-3) / 1e12, 3)
+            tvm["iteration_over_tv"] = round(tvm["ms_per_iteration"] / tv["ms_per_iteration"], 3)
+            row[coupling] = {"tv": tv, "tv_masked": tvm}
+        img.close()
+    drv = res["driver"] = {}
+    coarse = np.random.default_rng(0).random((size // 8 + 2, size // 8 + 2, 3))
+    pic = (np.repeat(np.repeat(coarse, 8, 0), 8, 1)[:size, :size] * 200 + 20).astype(np.uint8)
+    for mode in ("rl", "wiener", "tv", "tv-masked"):
+        for _ in range(2):                                 # the first call builds the jobs
+            with contextlib.redirect_stdout(io.StringIO()):
+                t0 = time.perf_counter()
+                dv.deblur_module(pic, "t", ".", 15, mask=[size // 2, size // 2], mask_size=255, display=False, iterations=20, save=False,
+                                 device_resident=True, nonblind=mode)
+                dt = time.perf_counter() - t0
+        drv["%d_%s" % (size, mode)] = {"seconds": round(dt, 4), **{k: round(v, 5) for k, v in dv.deblur_module.last_phase_seconds.items()}}
+    return res
+
+
 def main():
     size = int(sys.argv[1]) if len(sys.argv) > 1 else 4096
     ctx = _native.Context.get()
+    if sys.argv[2:] == ["tvmasked"]:
+        print(json.dumps({"size": size, "device": ctx.name, "tvmasked": tvmasked_section(ctx, size)}))
+        return 0
     if sys.argv[2:] == ["tvdeconv"]:
         print(json.dumps({"size": size, "device": ctx.name, "tvdeconv": tvdeconv_section(ctx, size)}))
         return 0
@@ -504,6 +566,7 @@ def main():
     res["mask"] = mask_section(img, ctx, size)
     res["wiener"] = wiener_section(ctx)
     res["tvdeconv"] = tvdeconv_section(ctx, size)
+    res["tvmasked"] = tvmasked_section(ctx, size)
     res["checks"] = {"%s_%s" % (name, what): res["resident"][name][what] <= res["per_channel_f64"][name][what]
                      for name in ("usm_gauss15", "usm_bessel15") for what in ("kernel_ms", "wall_ms")}
     print(json.dumps(res))
