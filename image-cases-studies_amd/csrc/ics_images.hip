@@ -1,5 +1,5 @@
 // ics_images.hip -- the ics_img_* entries of the C ABI (include/ics_hip.h).  Host side only; kernels live in ics_img.hip / ics_img_filters.hip /
-// ics_img_tvdenoise.hip / ics_img_wavelet.hip / ics_img_noise.hip / ics_img_despeckle.hip / ics_img_blurwidth.hip / ics_img_mask.hip / ics_img_guided.hip / ics_img_llf.hip (what these nine share: ics_img_px.h) / ics_img_wiener.hip / ics_img_tvdeconv.hip / ics_img_tvmdeconv.hip / ics_resize.hip.
+// ics_img_tvdenoise.hip / ics_img_wavelet.hip / ics_img_noise.hip / ics_img_despeckle.hip / ics_img_blurwidth.hip / ics_img_mask.hip / ics_img_guided.hip / ics_img_llf.hip (what these nine share: ics_img_px.h) / ics_img_wiener.hip / ics_img_tvdeconv.hip / ics_img_tvmdeconv.hip / ics_img_psfest.hip / ics_resize.hip.
 #include "ics_host.h"
 
 using namespace ics_host;
@@ -586,6 +586,52 @@ extern "C" int ics_img_tv_deconvolve_masked(const ics_img* src, const float* psf
   }
   RC(op.finish(e));
   if (unobserved) *unobserved = got;
+  return ICS_OK;
+}
+
+// ---- PSF from a sharp / blurred pair of device images (csrc/ics_img_psfest.hip) ---------------------------------------------------------
+// One route.  The shapes and the limit are the Wiener filter's for the box; one workspace from the pool, carved by the launcher.  Only
+// the raw kernel and the energies come back; the projection to a PSF is a few lines on K K 3 numbers and lives on the host
+// (lib/_native.py psf_project).
+extern "C" int ics_img_psf_estimate_plan(int H, int W, int K, int* Py, int* Px, size_t* workspace_bytes) {
+  int py = 0, px = 0;
+  RC(wiener_shape(H, W, K, &py, &px));
+  if (Py) *Py = py;
+  if (Px) *Px = px;
+  if (workspace_bytes) *workspace_bytes = ics_img_pe_workspace_bytes(H, W, K, py, px);
+  return ICS_OK;
+}
+extern "C" int ics_img_psf_estimate(const ics_img* blurred, const ics_img* sharp, int y0, int y1, int x0, int x1, int K, float regularisation, int coupling, float* raw,
+                                    double energy[3]) {
+  if (!blurred || !sharp) return ics_set_error(ICS_EINVAL, "a frame (blurred, sharp) is NULL");
+  if (!raw || !energy) return ics_set_error(ICS_EINVAL, "an output (raw, energy) is NULL");
+  if (y0 < 0 || x0 < 0 || y0 >= y1 || x0 >= x1) return ics_set_error(ICS_EINVAL, "box [%d, %d) x [%d, %d) (not empty, no negative corner)", y0, y1, x0, x1);
+  if (!std::isfinite(regularisation) || !(regularisation > 0.f)) return ics_set_error(ICS_EINVAL, "regularisation = %g (must be finite and > 0)", (double)regularisation);
+  RC(check_coupling(coupling));
+  const int H = y1 - y0, W = x1 - x0;
+  int Py = 0, Px = 0;
+  RC(wiener_shape(H, W, K, &Py, &Px));
+  if (blurred->ctx != sharp->ctx) return ics_set_error(ICS_EINVAL, "the two frames belong to different contexts");
+  if (blurred->H != sharp->H || blurred->W != sharp->W)
+    return ics_set_error(ICS_EINVAL, "frames of different shapes: blurred %d x %d, sharp %d x %d", blurred->H, blurred->W, sharp->H, sharp->W);
+  if (y1 > sharp->H || x1 > sharp->W) return ics_set_error(ICS_EINVAL, "box [%d, %d) x [%d, %d) outside the %d x %d frames", y0, y1, x0, x1, sharp->H, sharp->W);
+  ics_ctx* c = sharp->ctx;
+  HIPCHK(hipSetDevice(c->device));
+  const long pitch = 3L * sharp->W, first = (long)y0 * pitch + 3L * x0;
+  ImgOp op(c, nullptr, "img_psf_estimate");
+  void* ws = nullptr;
+  std::vector<float> got((size_t)3 * K * K);
+  double s[3] = {0.0, 0.0, 0.0};
+  hipError_t e = op.alloc(&ws, ics_img_pe_workspace_bytes(H, W, K, Py, Px));
+  if (e == hipSuccess) e = op.begin();
+  if (e == hipSuccess) e = ics_launch_img_psf_estimate(sharp->d + first, blurred->d + first, pitch, H, W, K, regularisation, coupling, Py, Px, ws, c->stream);
+  if (e == hipSuccess) e = op.end();
+  if (e == hipSuccess) e = hipMemcpyAsync(got.data(), ics_img_pe_raw(ws, H, W, K, Py, Px), got.size() * sizeof(float), hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(s, ics_img_pe_energy(ws, H, W, K, Py, Px), sizeof s, hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  RC(op.finish(e));
+  std::copy(got.begin(), got.end(), raw);
+  for (int ch = 0; ch < 3; ++ch) energy[ch] = s[ch];
   return ICS_OK;
 }
 

@@ -405,3 +405,14 @@ long long* ics_img_tvm_total(void* workspace, int Py, int Px);
 unsigned char* ics_img_tvm_mask_slot(void* workspace, int K, int Py, int Px);
 hipError_t ics_launch_img_tv_deconvolve_masked(const float* f, int H, int W, int K, bool observed, float clip, float mu, float beta, float gamma, int iterations, int coupling,
                                                int Py, int Px, void* workspace, float* out, hipStream_t s);
+
+// ---- PSF from a sharp / blurred pair of device-resident images (ics_img_psfest.hip): the tapered derivatives of the two H x W windows
+// through one transform of the sizes of ics_img_wiener.hip, the cross-spectrum solve, the K x K crop of its inverse.  sharp, blurred:
+// the first pixel of the window in each frame, `pitch` floats a frame row.  workspace: ics_img_pe_workspace_bytes, one block;
+// ics_img_pe_raw (3 K K floats, [i][j][c]) and ics_img_pe_energy (3 doubles) inside it hold the results after the launch.  coupling: 0 a
+// PSF per channel, 1 one from the three.  One route; the frames are only read.
+size_t ics_img_pe_workspace_bytes(int H, int W, int K, int Py, int Px);
+float* ics_img_pe_raw(void* workspace, int H, int W, int K, int Py, int Px);
+double* ics_img_pe_energy(void* workspace, int H, int W, int K, int Py, int Px);
+hipError_t ics_launch_img_psf_estimate(const float* sharp, const float* blurred, long pitch, int H, int W, int K, float regularisation, int coupling, int Py, int Px,
+                                       void* workspace, hipStream_t s);

@@ -1,4 +1,4 @@
-// ics_wn_fft.h -- for ics_img_wiener.hip, ics_img_tvdeconv.hip and ics_img_tvmdeconv.hip only (everything here is local to the unit that includes it): the
+// ics_wn_fft.h -- for ics_img_wiener.hip, ics_img_tvdeconv.hip, ics_img_tvmdeconv.hip and ics_img_psfest.hip only (everything here is local to the unit that includes it): the
 // line transform of the frame-sized fp32 transforms, a Stockham autosort transform of one line of N = 2^n points in LDS, and the
 // layout of its twiddle table (ics_img_wiener.hip describes both).  Device functions only; the kernels stay in their units.
 #pragma once

@@ -192,6 +192,8 @@ def load():
     lib.ics_img_tv_deconvolve_plan.argtypes = [ci, ci, ci, C.POINTER(ci), C.POINTER(ci), C.POINTER(C.c_size_t)]
     lib.ics_img_tv_deconvolve_masked.argtypes = [vp, vp, ci, vp, cf, cf, cf, cf, ci, ci, C.POINTER(C.c_longlong), C.POINTER(vp)]
     lib.ics_img_tv_deconvolve_masked_plan.argtypes = [ci, ci, ci, C.POINTER(ci), C.POINTER(ci), C.POINTER(C.c_size_t)]
+    lib.ics_img_psf_estimate.argtypes = [vp, vp, ci, ci, ci, ci, ci, cf, ci, C.POINTER(cf), C.POINTER(cd)]
+    lib.ics_img_psf_estimate_plan.argtypes = [ci, ci, ci, C.POINTER(ci), C.POINTER(ci), C.POINTER(C.c_size_t)]
     lib.ics_rl_upload_img.argtypes = [vp, vp, ci, ci, vp, ci, ci, vp]
     lib.ics_rl_download_img.argtypes = [vp, vp, ci, ci]
     lib.ics_group_create.argtypes = [ci, ci, ci, C.c_char_p, ci, C.POINTER(vp)]
@@ -214,6 +216,7 @@ def load():
                  "ics_tv", "ics_conv2d_symm", "ics_usm", "ics_bilateral", "ics_resize_bicubic", "ics_img_create", "ics_img_shape",
                  "ics_img_upload", "ics_img_upload_int", "ics_img_download", "ics_img_pad_edge", "ics_img_crop", "ics_img_paste", "ics_img_gamma", "ics_img_resize",
                  "ics_img_convolve", "ics_img_usm", "ics_img_bilateral", "ics_img_tv_denoise", "ics_img_wavelet_equalize", "ics_img_noise_estimate", "ics_img_blur_profile", "ics_img_window_scores", "ics_img_despeckle", "ics_img_guided", "ics_img_local_laplacian", "ics_img_wiener", "ics_img_wiener_plan", "ics_img_tv_deconvolve", "ics_img_tv_deconvolve_plan", "ics_img_tv_deconvolve_masked", "ics_img_tv_deconvolve_masked_plan",
+                 "ics_img_psf_estimate", "ics_img_psf_estimate_plan",
                  "ics_rl_upload_img", "ics_rl_download_img", "ics_group_create", "ics_group_info", "ics_group_barrier",
                  "ics_group_allreduce_max", "ics_group_allreduce_sum", "ics_group_describe", "ics_group_allgather"):
         getattr(lib, name).restype = ci
@@ -633,6 +636,80 @@ def tv_deconvolve_masked_plan(H, W, K):
     return TVDeconvolvePlan(py.value, px.value, int(ws.value))
 
 
+PsfEstimatePlan = collections.namedtuple("PsfEstimatePlan", "Py Px workspace_bytes")
+
+
+def psf_estimate_args(size, regularisation, threshold, coupling, window, shape_blurred, shape_sharp):
+    """the arguments of DeviceImage.psf_raw / lib.utils.estimate_psf checked (ValueError) and as (size, regularisation, threshold,
+    coupling, (y0, y1, x0, x1)): an int, two floats, a string and the half-open window, the whole frame for None; shape_blurred,
+    shape_sharp: (H, W, ...) of the two frames"""
+    Hb, Wb, Hs, Ws = int(shape_blurred[0]), int(shape_blurred[1]), int(shape_sharp[0]), int(shape_sharp[1])
+    if (Hb, Wb) != (Hs, Ws):
+        raise ValueError("frames of different shapes: blurred %d x %d, sharp %d x %d" % (Hb, Wb, Hs, Ws))
+    try:
+        whole = int(size) == size and not isinstance(size, bool)
+    except (TypeError, ValueError, OverflowError):
+        whole = False
+    if not whole or not 3 <= int(size) <= 255 or int(size) % 2 == 0:
+        raise ValueError("size %r (an odd integer, 3 to 255)" % (size,))
+    if window is None:
+        window = (0, Hb, 0, Wb)
+    try:
+        y0, y1, x0, x1 = (int(v) for v in window)
+        exact = all(int(v) == v for v in window)
+    except (TypeError, ValueError):
+        y0 = y1 = x0 = x1 = 0
+        exact = False
+    if not exact or not (0 <= y0 < y1 <= Hb and 0 <= x0 < x1 <= Wb):
+        raise ValueError("window %r ((y0, y1, x0, x1), half-open, not empty, inside the %d x %d frames)" % (window, Hb, Wb))
+    if int(size) > min(y1 - y0, x1 - x0):
+        raise ValueError("size %d, larger than the %d x %d window" % (int(size), y1 - y0, x1 - x0))
+    if not _finite32(regularisation, scalar=True) or not np.float32(regularisation) > 0:
+        raise ValueError("regularisation %r (must be finite and > 0)" % (regularisation,))
+    try:
+        ok = not isinstance(threshold, (str, bool)) and 0 <= float(threshold) < 1
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError("threshold %r (a number in [0, 1))" % (threshold,))
+    _coupling(coupling)
+    return int(size), float(regularisation), float(threshold), coupling, (y0, y1, x0, x1)
+
+
+def psf_estimate_plan(H, W, K):
+    """ics_img_psf_estimate_plan: PsfEstimatePlan(Py, Px, workspace_bytes) of DeviceImage.psf_raw on an H x W window with a K x K PSF
+    -- the transform sizes (those of wiener_plan) and the device bytes it takes from the pool: twelve complex planes of Py Px points,
+    3 K Px complex values and the tables (no device needed).  NativeError: as wiener_plan."""
+    py, px, ws = C.c_int(0), C.c_int(0), C.c_size_t(0)
+    _check(load().ics_img_psf_estimate_plan(int(H), int(W), int(K), C.byref(py), C.byref(px), C.byref(ws)))
+    return PsfEstimatePlan(py.value, px.value, int(ws.value))
+
+
+def psf_project(raw, threshold):
+    """The raw kernel of DeviceImage.psf_raw made a PSF, per plane, in float64: the taps below threshold times the plane's maximum are
+    set to 0 (every negative tap with them), the rest is divided by its sum.  Returns (psf, rejected): the K x K x 3 float32 PSF and,
+    per channel, sum |raw - kept| / sum |raw|, the share of the raw kernel's weight that was cut.  ValueError: raw not K x K x 3;
+    threshold outside [0, 1); a raw kernel that is not finite (NaN or inf in a frame: despeckle first); a plane whose maximum is not
+    > 0."""
+    raw = np.asarray(raw, dtype=np.float64)
+    if raw.ndim != 3 or raw.shape[0] != raw.shape[1] or raw.shape[2] != 3:
+        raise ValueError("raw of shape %s (K x K x 3)" % (raw.shape,))
+    if not 0 <= float(threshold) < 1:
+        raise ValueError("threshold %r (a number in [0, 1))" % (threshold,))
+    if not np.isfinite(raw).all():
+        raise ValueError("the raw kernel is not finite: a frame holds NaN or inf (despeckle first)")
+    psf, rejected = np.empty(raw.shape, np.float64), []
+    for c in range(3):
+        p = raw[..., c]
+        m = p.max()
+        if not m > 0:
+            raise ValueError("the raw kernel of channel %d has no positive tap (maximum %g)" % (c, m))
+        kept = np.where(p < float(threshold) * m, 0.0, p)
+        rejected.append(float(np.abs(p - kept).sum() / np.abs(p).sum()))
+        psf[..., c] = kept / kept.sum()
+    return np.ascontiguousarray(psf, dtype=np.float32), tuple(rejected)
+
+
 def llf_levels(H, W):
     """levels=None of DeviceImage.local_laplacian: the halvings (n -> (n + 1) // 2) that bring the longer side of an H x W picture to
     16 or below, within 1 .. IMG_LLF_MAX_LEVELS"""
@@ -1044,6 +1121,33 @@ class DeviceImage:
         img = self._new(lambda h, *a: load().ics_img_tv_deconvolve_masked(h, *a[:-1], C.byref(got) if count else None, a[-1]), _ptr(psf), psf.shape[0],
                         None if observed is None else _ptr(observed), clip, fidelity, penalty, data_penalty, iterations, _coupling(coupling))
         return (img, int(got.value)) if count else img
+
+    def psf_raw(self, sharp, size, regularisation=1e-3, coupling="vector", window=None):
+        """The kernel that takes `sharp`, a DeviceImage of the same shape and scene, to this blurred frame: (raw, energy).  The linear
+        solve of the fast blind methods (Cho and Lee 2009; Xu and Jia 2010) on the derivatives of the pair, k = argmin sum |d s * k -
+        d b|^2 + regularisation S |k|^2, S the gradient energy of the sharp frame, diagonal under `wiener`'s transform: the forward
+        differences of both frames along x and y, tapered over `size` pixels at the border of the window (the pair obeys b = s * k
+        only away from it) and zero padded, N = sum conj(A) B and D = sum |A|^2 over the two directions ("vector": and the three
+        channels, one kernel three times), raw = the size x size taps around 0 of the inverse transform of N / (D + regularisation S)
+        (csrc/ics_img_psfest.hip; restated in float64 in tests/psf_est_ref.py).  raw: size x size x 3 float32, b ~ s * raw as a true
+        convolution, centre tap at (size // 2, size // 2), nothing clipped or normalised (psf_project does that); energy: three
+        float64.  window (y0, y1, x0, x1), half-open: the region of both frames to look at (None: all).  The sharp frame must be
+        registered to this one; a sharp frame that is itself blurred gives the relative PSF; a NaN spreads.  Two calls give identical
+        bits; only raw and energy cross PCIe; the call waits for them.  ValueError (before any native call): frames of different
+        shapes, size no odd integer in 3 .. 255 or above the window, a bad window, regularisation not finite or <= 0, unknown
+        coupling; after it: an energy that is not finite or not > 0 (a sharp frame with no gradients, or NaN or inf in it).
+        NativeError (ICS_ENOSUP): a window side + size - 1 above IMG_WIENER_MAX."""
+        if not isinstance(sharp, DeviceImage):
+            raise ValueError("sharp must be a DeviceImage like the blurred frame, got %s" % (type(sharp).__name__,))
+        size, regularisation, _, coupling, (y0, y1, x0, x1) = psf_estimate_args(size, regularisation, 0.0, coupling, window, self.shape, sharp.shape)
+        raw, energy = np.empty((size, size, 3), np.float32), np.empty(3, np.float64)
+        _check(load().ics_img_psf_estimate(self._h, sharp._h, y0, y1, x0, x1, size, regularisation, _coupling(coupling),
+                                           raw.ctypes.data_as(C.POINTER(C.c_float)), energy.ctypes.data_as(C.POINTER(C.c_double))))
+        if not np.isfinite(energy).all():
+            raise ValueError("the gradient energy of the sharp frame is not finite: it holds NaN or inf (despeckle first)")
+        if not (energy > 0).all():
+            raise ValueError("the sharp frame has no gradients (energy %s): nothing to estimate a PSF from" % (tuple(float(v) for v in energy),))
+        return raw, energy
 
     def close(self):
         if self._h:

@@ -390,6 +390,52 @@ def wiener(src, psf, balance=0.01):
         res.close()
 
 
+PsfEstimate = collections.namedtuple("PsfEstimate", "psf raw rejected")
+
+
+def estimate_psf(blurred, sharp, size, regularisation=1e-3, threshold=0.05, coupling="vector", window=None, info=False):
+    """Not in the reference's lib/utils.py, whose only way to a PSF is the blind loop: the PSF from a picture and a sharper rendering of
+    the same scene -- a test chart and its photograph, a frame stopped down and the same frame wide open, a synthetic target -- or the
+    check of a PSF the blind phase returned against the frame it produced.  The linear solve every fast blind method repeats (Cho and
+    Lee 2009; Xu and Jia 2010): k = argmin sum |d sharp * k - d blurred|^2 + regularisation S |k|^2 on the derivatives of the pair,
+    tapered at the border, diagonal under the transform of `wiener` (`DeviceImage.psf_raw`, csrc/ics_img_psfest.hip); the taps below
+    threshold times the largest are then cut and the rest normalised to sum 1 (`lib._native.psf_project`).  Returns the size x size x 3
+    float32 PSF, ready for `wiener` / `tv_deconvolve` / `tv_deconvolve_masked`; info=True: PsfEstimate(psf, raw, rejected), the raw
+    kernel and the share of its weight that the threshold cut, per channel.  size odd, 3 .. 255; coupling "vector": one PSF from the
+    three channels, "channel": one each; window (y0, y1, x0, x1), half-open: the region to look at (None: the whole frame).  Two
+    `lib._native.DeviceImage`s are read where they lie; two H x W x 3 arrays are uploaded once each; only the raw kernel and the energy
+    come back.  It cannot register the pair (`sharp` must lie on `blurred` to the pixel), gives the relative PSF where `sharp` is
+    itself blurred, leaves the PSF free along a direction in which `sharp` has no gradients, and a NaN spreads (despeckle first).
+    ValueError: a DeviceImage with an array, frames of different shapes, bad arguments (before anything is uploaded), a raw kernel or
+    energy that is not finite, a sharp frame with no gradients.  There is no CPU fallback."""
+    dev = [isinstance(v, _native.DeviceImage) for v in (blurred, sharp)]
+    if dev[0] != dev[1]:
+        raise ValueError("blurred and sharp must both be DeviceImages or both H x W x 3 arrays")
+    if all(dev):
+        b, s, own = blurred, sharp, False
+        size, regularisation, threshold, coupling, window = _native.psf_estimate_args(size, regularisation, threshold, coupling, window, b.shape, s.shape)
+    else:
+        ab, asharp = np.asarray(blurred), np.asarray(sharp)
+        for arr in (ab, asharp):
+            if arr.ndim != 3 or arr.shape[2] != 3:
+                raise ValueError("expected two DeviceImages or two H x W x 3 arrays, got shape %s" % (arr.shape,))
+        size, regularisation, threshold, coupling, window = _native.psf_estimate_args(size, regularisation, threshold, coupling, window, ab.shape, asharp.shape)   # refused before anything is uploaded
+        b = _native.DeviceImage.from_host(np.ascontiguousarray(ab, dtype=np.float32))
+        try:
+            s = _native.DeviceImage.from_host(np.ascontiguousarray(asharp, dtype=np.float32))
+        except Exception:
+            b.close()
+            raise
+        own = True
+    try:
+        raw, _ = b.psf_raw(s, size, regularisation, coupling, window)
+    finally:
+        if own:
+            b.close(); s.close()
+    psf, rejected = _native.psf_project(raw, threshold)
+    return PsfEstimate(psf, raw, rejected) if info else psf
+
+
 def tv_deconvolve(src, psf, fidelity=2000.0, penalty=10.0, iterations=10, coupling="vector"):
     """Not in the reference's lib/utils.py: deconvolution of a picture by a known PSF under the total-variation prior the loop itself
     uses, by the fast splitting method (FTVd, Wang, Yang, Yin, Zhang 2008; split Bregman, Goldstein and Osher 2009) -- `iterations`

@@ -598,6 +598,30 @@ int ics_img_tv_deconvolve_plan(int H, int W, int K, int *Py, int *Px, size_t *wo
  * byte per point for the caller's mask); no device needed; same checks on H, W, K. */
 int ics_img_tv_deconvolve_masked(const ics_img *src, const float *psf, int K, const unsigned char *observed, float clip, float fidelity, float penalty, float data_penalty, int iterations, int coupling, long long *unobserved, ics_img **out);
 int ics_img_tv_deconvolve_masked_plan(int H, int W, int K, int *Py, int *Px, size_t *workspace_bytes);
+/* The PSF that takes a sharp device image to a blurred one of the same scene, the linear solve of the fast blind methods (Cho and Lee
+ * 2009; Xu and Jia 2010) on image derivatives: k = argmin sum |d s * k - d b|^2 + gamma |k|^2, diagonal under the 2-D transform.
+ * (y0, y1, x0, x1): a half-open box inside both frames, H x W its sides; K odd, 3 .. 255, K <= min(H, W); regularisation > 0;
+ * coupling 0: a PSF per channel, 1: one PSF from the three channels, its plane three times in raw and its energy three times.
+ *   Py, Px = those of ics_img_wiener for H, W, K
+ *   wy[y] = 0.5 - 0.5 cos(pi (j + 0.5) / Ty) for j = min(y, H - 1 - y) < Ty = min(K, H / 2), else 1; wx likewise; w = wy (x) wx
+ *     (the pair obeys b = s * k only away from the border)
+ *   d_x f[y, x] = w[y, x] (f[y, x+1] - f[y, x]), 0 at x = W - 1; d_y f likewise; zero beyond H x W up to Py x Px (no ramp)
+ *   A = transform(d s_c), B = transform(d b_c);  N = sum conj(A) B,  D = sum |A|^2,  S = sum over the pixels of (d s_c)^2, over the
+ *     two directions (coupling 1: and the three channels)
+ *   full = real(inverse transform(N / (D + regularisation S)));  raw[i, j] = full[(i - K / 2) mod Py, (j - K / 2) mod Px]
+ * so that b ~ s * raw, a true convolution with the centre tap at (K / 2, K / 2): ics_img_wiener(b, raw normalised) undoes it.
+ * raw: K K 3 host floats (HWC), nothing clipped or normalised (the Python layer projects); energy: S per channel.  float32
+ * throughout, the energy summed in double, no atomics, every sum in one order: two runs give identical bits (restated in float64 in
+ * tests/psf_est_ref.py).  s must be registered to b; a NaN spreads; a sharp frame without gradients gives energy 0 and a raw that
+ * means nothing.  Its kernels are bracketed for ics_ctx_last_kernel_ms; the call waits for raw and energy; neither frame is written.
+ * ICS_EINVAL, before a frame is touched: a NULL pointer, an empty box or one with a negative corner, K even or outside 3 .. 255 or
+ * above the box, regularisation not finite or <= 0, coupling neither 0 nor 1; then: frames of different shape or context, a box
+ * outside them.  ICS_ENOSUP: H + K - 1 or W + K - 1 above ICS_IMG_WIENER_MAX.
+ * ics_img_psf_estimate_plan: the transform sizes and the device bytes such a call takes from the context's pool: twelve complex
+ * planes of Py Px points, 3 K Px complex values, the tables (no device needed); same checks on H, W, K. */
+int ics_img_psf_estimate(const ics_img *blurred, const ics_img *sharp, int y0, int y1, int x0, int x1, int K,
+                         float regularisation, int coupling, float *raw /* K*K*3 */, double energy[3]);
+int ics_img_psf_estimate_plan(int H, int W, int K, int *Py, int *Px, size_t *workspace_bytes);
 /* richardson_lucy_MM(image[iy:iy+M, ix:ix+N], u[uy:uy+uM, ux:ux+uN], psf, ...) with both windows taken from device
  * images (deconvolve.py:277-313 passes such views); psf is a host MK*MK*3 array as in ics_rl_upload. */
 int ics_rl_upload_img(ics_rl *job, const ics_img *image, int iy, int ix, const ics_img *u, int uy, int ux, const float *psf);

@@ -1,6 +1,6 @@
 """Timing of the lib/utils.py filters on one seeded SIZE x SIZE RGB float32 picture (GPU box), one JSON line:
 
-    python scripts/filters_timing.py [SIZE=4096] [guided | llf | noise | despeckle | blurwidth | mask | wiener | tvdeconv | tvmasked]       (a section name: that section alone)
+    python scripts/filters_timing.py [SIZE=4096] [guided | llf | noise | despeckle | blurwidth | mask | wiener | tvdeconv | tvmasked | psf]       (a section name: that section alone)
 
   resident   the filters on a DeviceImage in HBM (csrc/ics_img_filters.hip): device time of the kernels (HIP events around them,
              ics_ctx_last_kernel_ms; warm, median of 25) and wall time of the queued call up to a stream synchronise
@@ -72,6 +72,12 @@
              TB/s on the model of 17 1/6 transits of 8 B per transform point and channel, the pool bytes; beside each
              frame DeviceImage.tv_deconvolve on it, measured the same way, and the ratio of the two iterations.  "driver": `deblur_module`
              as in the tvdeconv section with nonblind="rl", "wiener", "tv" and "tv-masked"
+  psf        DeviceImage.psf_raw (csrc/ics_img_psfest.hip), regularisation 1e-3, both couplings, on a 4096 x 4096 pair of its own (SIZE is
+             not used; the blurred frame is a second random frame: the kernels do the same work on any data): the whole frame at K = 15
+             and the window of 1023 x 1023 pixels at (1537, 1539) at K = 31: the transform sizes, the pool bytes, kernel ms of the
+             eight launches (median and minimum of 9 rounds), the wall time of the call (it waits for the raw kernel and the energies),
+             and TB/s on the model of 42 transits of 8 B per transform point; beside each DeviceImage.wiener (balance 0.01, a
+             Gaussian PSF of the same K) on the frame, or on the crop of the window, and DeviceImage.copy() of the frame
   checks     the resident USM must not take longer than the three float64 calls, in kernel time and in wall time (a guard against a
              broken kernel, not a target); the exit status is 1 if one of them fails
 Starts no child process; a job script puts its own time limit around it."""
@@ -458,6 +464,47 @@ def tvmasked_section(ctx, size):
     return res
 
 
+PSF_REGULARISATION, PSF_TRANSITS = 1e-3, 42
+PSF_CASES = ((None, 15), ((1537, 2560, 1539, 2562), 31))
+
+
+def psf_section(ctx):
+    H = W = 4096
+    rng = np.random.default_rng(0)
+    sharp = _native.DeviceImage.from_host(rng.random((H, W, 3), dtype=np.float32), ctx)
+    blurred = _native.DeviceImage.from_host(rng.random((H, W, 3), dtype=np.float32), ctx)
+    res = {"regularisation": PSF_REGULARISATION, "frame": [H, W], "copy": copy_row(sharp, ctx)}
+    for window, K in PSF_CASES:
+        y0, y1, x0, x1 = window or (0, H, 0, W)
+        plan = _native.psf_estimate_plan(y1 - y0, x1 - x0, K)
+        row = res["%dx%d_K_%d" % (y1 - y0, x1 - x0, K)] = {"transform": [plan.Py, plan.Px], "pool_mb": round(plan.workspace_bytes / 2 ** 20, 1)}
+        for coupling in ("vector", "channel"):
+            blurred.psf_raw(sharp, K, PSF_REGULARISATION, coupling, window)       # warm: code objects, LDS attribute, pool blocks
+            kernel, wall = [], []
+            for _ in range(REPS_DESPECKLE):
+                t0 = time.perf_counter()
+                blurred.psf_raw(sharp, K, PSF_REGULARISATION, coupling, window)
+                wall.append((time.perf_counter() - t0) * 1e3)
+                kernel.append(ctx.last_kernel_ms())
+            med = float(np.median(kernel))
+            row[coupling] = {"kernel_ms": round(med, 4), "min_ms": round(float(np.min(kernel)), 4), "wall_ms": round(float(np.median(wall)), 4),
+                             "tb_per_s": round(PSF_TRANSITS * 8 * plan.Py * plan.Px / (med * 1e-3) / 1e12, 3)}
+        img = blurred.crop(y0, y1, x0, x1)
+        psf = utils.gaussian_kernel(K, K / 6.0)
+        img.wiener(psf, WIENER_BALANCE).close()            # warm
+        ctx.synchronize()
+        kernel = []
+        for _ in range(REPS_DESPECKLE):
+            out = img.wiener(psf, WIENER_BALANCE)
+            ctx.synchronize()
+            kernel.append(ctx.last_kernel_ms())
+            out.close()
+        row["wiener"] = {"kernel_ms": round(float(np.median(kernel)), 4), "min_ms": round(float(np.min(kernel)), 4)}
+        img.close()
+    sharp.close(); blurred.close()
+    return res
+
+
 def main():
     size = int(sys.argv[1]) if len(sys.argv) > 1 else 4096
     ctx = _native.Context.get()
@@ -466,6 +513,9 @@ def main():
         return 0
     if sys.argv[2:] == ["tvdeconv"]:
         print(json.dumps({"size": size, "device": ctx.name, "tvdeconv": tvdeconv_section(ctx, size)}))
+        return 0
+    if sys.argv[2:] == ["psf"]:
+        print(json.dumps({"device": ctx.name, "psf": psf_section(ctx)}))
         return 0
     if sys.argv[2:] == ["wiener"]:
         print(json.dumps({"device": ctx.name, "wiener": wiener_section(ctx)}))
@@ -567,6 +617,7 @@ def main():
     res["wiener"] = wiener_section(ctx)
     res["tvdeconv"] = tvdeconv_section(ctx, size)
     res["tvmasked"] = tvmasked_section(ctx, size)
+    res["psf"] = psf_section(ctx)
     res["checks"] = {"%s_%s" % (name, what): res["resident"][name][what] <= res["per_channel_f64"][name][what]
                      for name in ("usm_gauss15", "usm_bessel15") for what in ("kernel_ms", "wall_ms")}
     print(json.dumps(res))
