@@ -62,7 +62,7 @@ bool ics_host::rank1_factors(const double* k, int KH, int KW, std::vector<double
 static int conv2d_common(ics_ctx* c, const double* src, int H, int W, const double* kern, int KH, int KW, int usm, double amount, double* out) {
   if (!c || !src || !kern || !out) return ics_set_error(ICS_EINVAL, "NULL argument");
   if (H < 1 || W < 1 || KH < 1 || KW < 1) return ics_set_error(ICS_EINVAL, "bad sizes");
-  if ((size_t)(32 + KH - 1) * (32 + KW - 1) * 8 > 160 * 1024) return ics_set_error(ICS_ENOSUP, "kernel %d x %d too large for the LDS tile (up to 111 x 111)", KH, KW);
+  if ((size_t)(32 + KH - 1) * (32 + KW - 1) * 8 > 160 * 1024) return ics_set_error(ICS_ENOSUP, "kernel %d x %d too large for the LDS tile (up to 112 x 112: (31 + KH) * (31 + KW) doubles within 160 KB)", KH, KW);
   HIPCHK(hipSetDevice(c->device));
   const size_t n = (size_t)H * W, nk = (size_t)KH * KW;
   std::vector<double> col, row;
