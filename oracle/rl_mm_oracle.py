@@ -92,6 +92,13 @@ def _conv_scipy(a, b, mode):
     return convolve(a, b, mode=mode)
 
 
+def _conv_fft64(a, b, mode):
+    """The same sums through float64 FFTs: `conv="fft64"`, the float64 form for frames on which the direct sums take minutes
+    (within 1e-12 of them, tests/test_psf_gradient_ref.py)."""
+    from scipy.signal import fftconvolve
+    return fftconvolve(np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64), mode=mode)
+
+
 def _conv_direct(a, b, mode):
     """Direct float64 evaluation of scipy.signal.convolve(a, b, mode) for 2-D inputs."""
     a = np.asarray(a, dtype=np.float64)
@@ -217,6 +224,7 @@ class Trace:
     dof_max: list = field(default_factory=list)
     dt: list = field(default_factory=list)       # per inner iteration, 3 floats
     dtpsf: list = field(default_factory=list)    # per inner iteration (blind)
+    gradk: list = field(default_factory=list)    # per inner iteration (blind): a copy of the MK x MK x 3 PSF gradient (pyx:567-571)
     iterations: int = 0
     stopped: bool = False
     psf_final: np.ndarray | None = None          # the *local* psf (differs from caller's under correlation)
@@ -257,12 +265,12 @@ def richardson_lucy_MM(image, u, psf, top, bottom, left, right, tau, M, N, C, MK
     """Restatement of lib/deconvolution.pyx:341-675.  Mutates `u` (always) and `psf` (blind) in
     place and returns a view of `u`, exactly like the reference.
 
-    Extra keyword-only arguments (not in the reference): `conv` ("scipy" | "direct"), `trace`
-    (collects the printed scalars), `snapshot_at` (outer-iteration counts at which to copy u),
+    Extra keyword-only arguments (not in the reference): `conv` ("scipy" | "direct" | "fft64": the float64 sums through float64
+    FFTs | a function (a, b, mode) -> array, for tests that put a wrong convolution in), `trace` (collects the printed scalars and the PSF gradient of every inner iteration), `snapshot_at` (outer-iteration counts at which to copy u),
     `quiet` (suppress prints), `tv_mode` ("shipped" = TV term dead, as the reference behaves),
     `dof_zero_rule`: value of the ratio (g - f)/(g + f) of pyx:499 where g == f == 0 EXACTLY.  None -> IEEE (0/0 = NaN)
     with conv="scipy" -- the reference bit for bit, whatever its FFT's rounding makes of such a pixel -- and 1 with
-    conv="direct".  Why 1: in a region where image and u are exactly 0 the reference's g is the rounding noise of a complex64
+    conv="direct" / "fft64".  Why 1: in a region where image and u are exactly 0 the reference's g is the rounding noise of a complex64
     FFT (~1e-10, either sign), f is 0, and (g - 0)/(g + 0) = 1 for EVERY non-zero g; exact arithmetic (this branch, and the
     device kernels) produces g = 0 there and IEEE would turn the whole frame into NaN through the next convolution.  The
     rule touches nothing else: g + f == 0 with g != 0 stays +-inf as in the reference (include/ics_hip.h, "DoF ratio").
@@ -277,9 +285,9 @@ def richardson_lucy_MM(image, u, psf, top, bottom, left, right, tau, M, N, C, MK
                              {"float64": "double"}.get(arr.dtype.name, arr.dtype.name))
     if tv_mode != "shipped":
         raise NotImplementedError("extended TV modes live in oracle/rl_ext_oracle.py")
-    cv = _conv_scipy if conv == "scipy" else _conv_direct
+    cv = conv if callable(conv) else {"scipy": _conv_scipy, "direct": _conv_direct, "fft64": _conv_fft64}[conv]
     if dof_zero_rule is None:
-        dof_zero_rule = 1.0 if conv == "direct" else float("nan")
+        dof_zero_rule = float("nan") if conv == "scipy" else 1.0
     tr = trace if trace is not None else Trace()
 
     def say(s):
@@ -344,6 +352,7 @@ def richardson_lucy_MM(image, u, psf, top, bottom, left, right, tau, M, N, C, MK
                 # pyx:574 (A14): step_factor / MK is a C float division
                 dtpsf = F32(F32(step_factor / F32(MK)) * F32(np.amax(psf) + 0)) / F32(np.amax(np.abs(gradk)) + F32(1e-15))
                 tr.dtpsf.append(dtpsf)
+                tr.gradk.append(gradk.copy())
                 psf -= dtpsf * gradk                                      # pyx:577-581
                 if correlation:                                           # pyx:584-585  (A15, rebinding quirk)
                     m = np.mean(psf, axis=2)

@@ -11,6 +11,7 @@ behind the stage API, and everything here is held against it BIT FOR BIT:
 import numpy as np
 import pytest
 
+import psf_gradient_ref as pg
 import rl_mm_oracle as orc
 
 pytestmark = pytest.mark.gpu
@@ -32,8 +33,7 @@ def _case(M, N, MK):
             image = np.ascontiguousarray(np.kron(small, np.ones((8, 8, 1), np.float32))[:M, :N] * 0.8 + 0.1 * rng.random((M, N, 3), dtype=np.float32))
             pad = MK // 2
             u0 = np.ascontiguousarray(np.pad(image, ((pad, pad), (pad, pad), (0, 0)), mode="edge"))
-        psf = (orc.gaussian_psf(MK) * (0.5 + rng.random((MK, MK, 3), dtype=np.float32))).astype(np.float32)   # no symmetry: flips show
-        orc.normalize_kernel(psf, MK)
+        psf = pg.asymmetric_psf(MK, rng)   # no symmetry: flips show
         for a in (image, u0, psf):
             a.setflags(write=False)
         _cases[key] = (image, u0, psf)

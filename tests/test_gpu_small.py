@@ -81,7 +81,12 @@ def test_whole_run_against_the_oracle(M, N, MK, blind, corr, iters):
         assert np.allclose(g[name], ref, rtol=2e-3, atol=1e-7, equal_nan=True), (name, g[name], ref)
 
 
-@pytest.mark.parametrize("M,N,MK,blind,corr", [(255, 255, 15, True, 0), (255, 255, 15, True, 1), (160, 120, 21, False, 0), (64, 255, 9, True, 0), (255, 255, 31, True, 0)])
+# (the second row: with the first, every compiled PSF size 3 ... 31 blind, on frames of a few tiles -- ics_small_plan derives another
+#  decomposition for every size, and this is the only guard on A1 ... A10 of the sizes no other test runs)
+@pytest.mark.parametrize("M,N,MK,blind,corr", [(255, 255, 15, True, 0), (255, 255, 15, True, 1), (160, 120, 21, False, 0), (64, 255, 9, True, 0), (255, 255, 31, True, 0),
+                                               (97, 129, 3, True, 0), (96, 130, 5, True, 0), (98, 128, 7, True, 0), (129, 97, 11, True, 0), (97, 129, 13, True, 0),
+                                               (95, 131, 17, True, 0), (99, 127, 19, True, 0), (130, 96, 21, True, 0), (97, 129, 23, True, 0), (96, 128, 25, True, 0),
+                                               (98, 130, 27, True, 0), (127, 99, 29, True, 0)])
 def test_against_the_multi_launch_families(M, N, MK, blind, corr, debug_switch):
     case = orc.synth_case(M, N, MK, seed=5, blind=blind)
     win = orc.default_window(M, N, MK)
