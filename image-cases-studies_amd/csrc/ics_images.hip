@@ -1,5 +1,5 @@
 // ics_images.hip -- the ics_img_* entries of the C ABI (include/ics_hip.h).  Host side only; kernels live in ics_img.hip / ics_img_filters.hip /
-// ics_img_tvdenoise.hip / ics_img_wavelet.hip / ics_img_noise.hip / ics_img_despeckle.hip / ics_img_blurwidth.hip / ics_img_mask.hip / ics_img_guided.hip / ics_img_llf.hip (what these nine share: ics_img_px.h) / ics_img_wiener.hip / ics_img_tvdeconv.hip / ics_img_tvmdeconv.hip / ics_img_psfest.hip / ics_resize.hip.
+// ics_img_tvdenoise.hip / ics_img_wavelet.hip / ics_img_noise.hip / ics_img_despeckle.hip / ics_img_blurwidth.hip / ics_img_mask.hip / ics_img_guided.hip / ics_img_llf.hip (what these nine share: ics_img_px.h) / ics_img_wiener.hip / ics_img_tvdeconv.hip / ics_img_tvmdeconv.hip / ics_img_psfest.hip / ics_img_align.hip / ics_resize.hip.
 #include "ics_host.h"
 
 using namespace ics_host;
@@ -633,6 +633,292 @@ extern "C" int ics_img_psf_estimate(const ics_img* blurred, const ics_img* sharp
   std::copy(got.begin(), got.end(), raw);
   for (int ch = 0; ch < 3; ++ch) energy[ch] = s[ch];
   return ICS_OK;
+}
+
+// ---- registration of two device images and the warp of one (csrc/ics_img_align.hip) -----------------------------------------------------
+// One route.  The luma pyramids of both frames, the tiles' slots and the sums live in one workspace from the pool; a step is two launches
+// and one read-back of at most 67 doubles through the context's pinned area; the damping and the solve, a Cholesky of at most 10 x 10 in
+// double, run here.  The loop is restated in tests/align_ref.py (level_loop, align).
+namespace {
+const int AL_MIN_SIDE = 16, AL_AUTO_SIDE = 64, AL_MAX_LEVELS = ICS_IMG_ALIGN_MAX_LEVELS, AL_MAX_PARAMS = 10, AL_MAX_SUMS = 67;
+const double AL_MIN_COVERAGE = 0.25, AL_LAMBDA0 = 1e-6;
+
+struct Mat3 { double m[9]; };
+Mat3 al_mul3(const Mat3& a, const Mat3& b) {
+  Mat3 r;
+  for (int i = 0; i < 3; ++i)
+    for (int j = 0; j < 3; ++j) r.m[3 * i + j] = a.m[3 * i] * b.m[j] + a.m[3 * i + 1] * b.m[3 + j] + a.m[3 * i + 2] * b.m[6 + j];
+  return r;
+}
+double al_det3(const Mat3& a) {
+  return a.m[0] * (a.m[4] * a.m[8] - a.m[5] * a.m[7]) - a.m[1] * (a.m[3] * a.m[8] - a.m[5] * a.m[6]) + a.m[2] * (a.m[3] * a.m[7] - a.m[4] * a.m[6]);
+}
+Mat3 al_inv3(const Mat3& a) {   // (of a matrix whose determinant was checked, or of a frame / shift, which has one)
+  const double d = 1.0 / al_det3(a);
+  const double* m = a.m;
+  return Mat3{{(m[4] * m[8] - m[5] * m[7]) * d, (m[2] * m[7] - m[1] * m[8]) * d, (m[1] * m[5] - m[2] * m[4]) * d,
+               (m[5] * m[6] - m[3] * m[8]) * d, (m[0] * m[8] - m[2] * m[6]) * d, (m[2] * m[3] - m[0] * m[5]) * d,
+               (m[3] * m[7] - m[4] * m[6]) * d, (m[1] * m[6] - m[0] * m[7]) * d, (m[0] * m[4] - m[1] * m[3]) * d}};
+}
+Mat3 al_unit(Mat3 a) { const double w = a.m[8]; for (double& v : a.m) v /= w; return a; }
+Mat3 al_frame3(int H, int W) { const double s = (H > W ? H : W) / 2.0; return Mat3{{s, 0.0, (W - 1) / 2.0, 0.0, s, (H - 1) / 2.0, 0.0, 0.0, 1.0}}; }
+Mat3 al_shift3(double tx, double ty) { return Mat3{{1.0, 0.0, tx, 0.0, 1.0, ty, 0.0, 0.0, 1.0}}; }
+const Mat3 AL_UP = {{2.0, 0.0, 0.5, 0.0, 2.0, 0.5, 0.0, 0.0, 1.0}};   // level l + 1 -> level l: X = 2 (x + 0.5) - 0.5
+
+int al_check_matrix(const double* M) {
+  for (int k = 0; k < 9; ++k)
+    if (!std::isfinite(M[k])) return ics_set_error(ICS_EINVAL, "the matrix is not finite");
+  Mat3 a;
+  memcpy(a.m, M, sizeof a.m);
+  const double d = al_det3(a);
+  if (!(M[8] != 0.0) || !std::isfinite(d) || !(fabs(d) > 0.0)) return ics_set_error(ICS_EINVAL, "the matrix is singular (determinant %g, M[2][2] = %g)", d, M[8]);
+  return ICS_OK;
+}
+int al_check_model(int model) { return model >= 0 && model <= 2 ? ICS_OK : ics_set_error(ICS_EINVAL, "model %d (0 = translation, 1 = affine, 2 = homography)", model); }
+int al_check_box(const ics_img* fixed, int y0, int y1, int x0, int x1) {
+  if (y0 < 0 || x0 < 0 || y0 >= y1 || x0 >= x1) return ics_set_error(ICS_EINVAL, "box [%d, %d) x [%d, %d) (not empty, no negative corner)", y0, y1, x0, x1);
+  if (fixed && (y1 > fixed->H || x1 > fixed->W)) return ics_set_error(ICS_EINVAL, "box [%d, %d) x [%d, %d) outside the %d x %d frame", y0, y1, x0, x1, fixed->H, fixed->W);
+  return ICS_OK;
+}
+int al_levels(int side, int levels, int* used) {
+  int n = levels;
+  if (levels == 0) for (n = 1; n < AL_MAX_LEVELS && (side >> n) >= AL_AUTO_SIDE; ) ++n;
+  if (n < 1 || n > AL_MAX_LEVELS) return ics_set_error(ICS_EINVAL, "levels = %d (0 = automatic, 1 .. %d)", levels, AL_MAX_LEVELS);
+  if ((side >> (n - 1)) < AL_MIN_SIDE) return ics_set_error(ICS_EINVAL, "%d level(s) on planes of %d px: no level may be smaller than %d px a side", n, side, AL_MIN_SIDE);
+  *used = n;
+  return ICS_OK;
+}
+size_t al_workspace_floats(int Hf, int Wf, int Hm, int Wm, int levels) {
+  size_t n = 2 * AL_MAX_SUMS + (size_t)ics_img_al_tiles(Hf, Wf) * AL_MAX_SUMS;   // the sums (as doubles), the slots
+  for (int l = 0; l < levels; ++l) n += (size_t)(Hf >> l) * (Wf >> l) + (size_t)(Hm >> l) * (Wm >> l);
+  return n;
+}
+hipError_t al_pin(ics_ctx* c) {
+  if (c->pin) return hipSuccess;
+  hipError_t e = hipHostMalloc((void**)&c->pin, ics_ctx::PIN_DOUBLES * 8, hipHostMallocDefault);
+  if (e == hipSuccess) e = hipEventCreateWithFlags(&c->pin_ev, hipEventDisableTiming);
+  return e;
+}
+
+struct AlSums { double S[AL_MAX_PARAMS][AL_MAX_PARAMS], g[AL_MAX_PARAMS], rr, count; };
+struct AlLevel { const float *T, *I; int H, W, Hm, Wm; };
+struct AlRun {
+  ics_ctx* c; int model, photo, n; float* slots; double* out;
+  // one evaluation: two launches, the raw sums read back into the context's pinned area, waited for
+  hipError_t raw(const AlLevel& lv, const Mat3& A, double gain, double bias) {
+    hipError_t e = ics_launch_img_al_sums(lv.T, lv.H, lv.W, lv.I, lv.Hm, lv.Wm, model, photo, A.m, gain, bias, slots, out, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(c->pin, out, (size_t)ics_img_al_slot_floats(model, photo) * sizeof(double), hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    return e;
+  }
+  // ... checked and unpacked: ICS_OK, a refusal (ICS_EINVAL) or ICS_EHIP with *he set
+  int evaluate(const AlLevel& lv, const Mat3& A, double gain, double bias, AlSums* s, hipError_t* he) {
+    *he = raw(lv, A, gain, bias);
+    if (*he != hipSuccess) return ICS_EHIP;
+    const double* v = c->pin;
+    const int ns = ics_img_al_slot_floats(model, photo);
+    for (int k = 0; k < ns; ++k)
+      if (!std::isfinite(v[k])) return ics_set_error(ICS_EINVAL, "the frames are not finite: despeckle first");
+    int k = 0;
+    for (int i = 0; i < n; ++i)
+      for (int j = i; j < n; ++j, ++k) s->S[i][j] = s->S[j][i] = v[k];
+    for (int i = 0; i < n; ++i) s->g[i] = v[k++];
+    s->rr = v[k]; s->count = v[k + 1];
+    if (s->count < AL_MIN_COVERAGE * ((double)lv.H * lv.W)) return ics_set_error(ICS_EINVAL, "frames do not overlap enough (coverage %.3f)", s->count / ((double)lv.H * lv.W));
+    return ICS_OK;
+  }
+};
+// (S + lambda diag S) d = -g by Cholesky; false: a pivot that is not > 0
+bool al_solve(const AlSums& s, int n, double lambda, double* d) {
+  double L[AL_MAX_PARAMS][AL_MAX_PARAMS] = {}, y[AL_MAX_PARAMS];
+  for (int i = 0; i < n; ++i)
+    for (int j = 0; j <= i; ++j) {
+      double v = s.S[i][j] + (i == j ? lambda * s.S[i][i] : 0.0);
+      for (int k = 0; k < j; ++k) v -= L[i][k] * L[j][k];
+      if (i == j) {
+        if (!(v > 0.0) || !std::isfinite(v)) return false;
+        L[i][i] = sqrt(v);
+      } else L[i][j] = v / L[j][j];
+    }
+  for (int i = 0; i < n; ++i) { double v = -s.g[i]; for (int k = 0; k < i; ++k) v -= L[i][k] * y[k]; y[i] = v / L[i][i]; }
+  for (int i = n - 1; i >= 0; --i) { double v = y[i]; for (int k = i + 1; k < n; ++k) v -= L[k][i] * d[k]; d[i] = v / L[i][i]; }
+  return true;
+}
+// the largest motion, in pixels of the moving plane, of the fixed plane's four corners between A0 and A1
+double al_corner_motion(const Mat3& A0, const Mat3& A1, const AlLevel& lv) {
+  const Mat3 nf = al_frame3(lv.H, lv.W);
+  const double sm = al_frame3(lv.Hm, lv.Wm).m[0];
+  double worst = 0.0;
+  for (int k = 0; k < 4; ++k) {
+    const double x = ((k & 1 ? lv.W - 1 : 0) - nf.m[2]) / nf.m[0], y = ((k & 2 ? lv.H - 1 : 0) - nf.m[5]) / nf.m[0];
+    double p[2][2];
+    const Mat3* both[2] = {&A0, &A1};
+    for (int w = 0; w < 2; ++w) {
+      const double* a = both[w]->m;
+      const double D = a[6] * x + a[7] * y + a[8];
+      p[w][0] = (a[0] * x + a[1] * y + a[2]) / D; p[w][1] = (a[3] * x + a[4] * y + a[5]) / D;
+    }
+    const double dx = (p[0][0] - p[1][0]) * sm, dy = (p[0][1] - p[1][1]) * sm, m = sqrt(dx * dx + dy * dy);
+    if (!(m <= worst)) worst = m;
+  }
+  return worst;
+}
+const int AL_INDEX[3][8] = {{2, 5, 0, 0, 0, 0, 0, 0}, {0, 1, 2, 3, 4, 5, 0, 0}, {0, 1, 2, 3, 4, 5, 6, 7}};   // the entries of A a step moves
+}  // namespace
+
+extern "C" int ics_img_align_plan(int H, int W, int levels, int* used, size_t* workspace_bytes) {
+  if (H < 1 || W < 1) return ics_set_error(ICS_EINVAL, "bad frame size %d x %d", H, W);
+  int n = 0;
+  RC(al_levels(H < W ? H : W, levels, &n));
+  if (used) *used = n;
+  if (workspace_bytes) *workspace_bytes = al_workspace_floats(H, W, H, W, n) * sizeof(float);
+  return ICS_OK;
+}
+
+namespace {
+// what ics_img_align and ics_img_align_sums share: the checks on the pair, the workspace, the luma pyramids
+struct AlSetup {
+  AlLevel lv[AL_MAX_LEVELS];
+  int levels = 0;
+  AlRun run{};
+};
+int al_check_pair(const ics_img* moving, const ics_img* fixed, int y0, int y1, int x0, int x1, int model, const double* M, double gain, double bias) {
+  if (!moving || !fixed) return ics_set_error(ICS_EINVAL, "a frame (moving, fixed) is NULL");
+  if (!M) return ics_set_error(ICS_EINVAL, "the matrix is NULL");
+  RC(al_check_model(model));
+  RC(al_check_matrix(M));
+  if (!std::isfinite(gain) || !std::isfinite(bias) || gain == 0.0) return ics_set_error(ICS_EINVAL, "gain %g, bias %g (finite, gain not 0)", gain, bias);
+  return al_check_box(nullptr, y0, y1, x0, x1);
+}
+hipError_t al_setup(ImgOp& op, const ics_img* moving, const ics_img* fixed, int y0, int y1, int x0, int x1, int model, int photo, int levels, AlSetup* st) {
+  ics_ctx* c = fixed->ctx;
+  const int Hf = y1 - y0, Wf = x1 - x0;
+  void* ws = nullptr;
+  hipError_t e = op.alloc(&ws, al_workspace_floats(Hf, Wf, moving->H, moving->W, levels) * sizeof(float));
+  if (e == hipSuccess) e = al_pin(c);
+  if (e != hipSuccess) return e;
+  st->levels = levels;
+  st->run = AlRun{c, model, photo, ics_img_al_params(model, photo), nullptr, reinterpret_cast<double*>(ws)};
+  float* at = reinterpret_cast<float*>(ws) + 2 * AL_MAX_SUMS;
+  st->run.slots = at; at += (size_t)ics_img_al_tiles(Hf, Wf) * AL_MAX_SUMS;
+  e = op.begin();
+  for (int l = 0; l < levels && e == hipSuccess; ++l) {
+    AlLevel& v = st->lv[l];
+    v.H = Hf >> l; v.W = Wf >> l; v.Hm = moving->H >> l; v.Wm = moving->W >> l;
+    float* T = at; at += (size_t)v.H * v.W;
+    float* I = at; at += (size_t)v.Hm * v.Wm;
+    v.T = T; v.I = I;
+    if (l == 0) {
+      e = ics_launch_img_al_luma(fixed->d + ((size_t)y0 * fixed->W + x0) * 3, 3L * fixed->W, v.H, v.W, T, c->stream);
+      if (e == hipSuccess) e = ics_launch_img_al_luma(moving->d, 3L * moving->W, v.Hm, v.Wm, I, c->stream);
+    } else {
+      e = ics_launch_img_al_half(st->lv[l - 1].T, st->lv[l - 1].H, st->lv[l - 1].W, T, c->stream);
+      if (e == hipSuccess) e = ics_launch_img_al_half(st->lv[l - 1].I, st->lv[l - 1].Hm, st->lv[l - 1].Wm, I, c->stream);
+    }
+  }
+  return e;
+}
+}  // namespace
+
+extern "C" int ics_img_align_sums(const ics_img* moving, const ics_img* fixed, int y0, int y1, int x0, int x1, int model, int photometric, const double M[9], double gain,
+                                  double bias, double* sums, int count) {
+  RC(al_check_pair(moving, fixed, y0, y1, x0, x1, model, M, gain, bias));
+  const int ns = ics_img_al_slot_floats(model, photometric);
+  if (!sums || count != ns) return ics_set_error(ICS_EINVAL, "sums of %d entries (this model has %d)", sums ? count : 0, ns);
+  if (moving->ctx != fixed->ctx) return ics_set_error(ICS_EINVAL, "the two frames belong to different contexts");
+  RC(al_check_box(fixed, y0, y1, x0, x1));
+  ics_ctx* c = fixed->ctx;
+  HIPCHK(hipSetDevice(c->device));
+  ImgOp op(c, nullptr, "img_align_sums");
+  AlSetup st;
+  hipError_t e = al_setup(op, moving, fixed, y0, y1, x0, x1, model, photometric != 0, 1, &st);
+  if (e == hipSuccess) {
+    Mat3 m;
+    memcpy(m.m, M, sizeof m.m);
+    const Mat3 A = al_unit(al_mul3(al_mul3(al_inv3(al_frame3(moving->H, moving->W)), al_mul3(al_unit(m), al_shift3(x0, y0))), al_frame3(y1 - y0, x1 - x0)));
+    e = st.run.raw(st.lv[0], A, gain, bias);
+  }
+  RC(op.finish(e));
+  for (int k = 0; k < ns; ++k) sums[k] = c->pin[k];
+  return ICS_OK;
+}
+
+extern "C" int ics_img_align(const ics_img* moving, const ics_img* fixed, int y0, int y1, int x0, int x1, int model, int photometric, int levels, int iterations,
+                             double tolerance, double M[9], double gain_bias[2], double stats[5]) {
+  if (!gain_bias || !stats) return ics_set_error(ICS_EINVAL, "an argument (gain_bias, stats) is NULL");
+  RC(al_check_pair(moving, fixed, y0, y1, x0, x1, model, M, gain_bias[0], gain_bias[1]));
+  if (iterations < 1) return ics_set_error(ICS_EINVAL, "iterations = %d (at least 1)", iterations);
+  if (!std::isfinite(tolerance) || !(tolerance > 0.0)) return ics_set_error(ICS_EINVAL, "tolerance = %g (must be finite and > 0)", tolerance);
+  if (levels < 0 || levels > AL_MAX_LEVELS) return ics_set_error(ICS_EINVAL, "levels = %d (0 = automatic, 1 .. %d)", levels, AL_MAX_LEVELS);
+  if (moving->ctx != fixed->ctx) return ics_set_error(ICS_EINVAL, "the two frames belong to different contexts");
+  RC(al_check_box(fixed, y0, y1, x0, x1));
+  const int Hf = y1 - y0, Wf = x1 - x0;
+  int side = Hf < Wf ? Hf : Wf, used = 0;
+  if (moving->H < side) side = moving->H;
+  if (moving->W < side) side = moving->W;
+  RC(al_levels(side, levels, &used));
+  ics_ctx* c = fixed->ctx;
+  HIPCHK(hipSetDevice(c->device));
+  ImgOp op(c, nullptr, "img_align");
+  AlSetup st;
+  hipError_t e = al_setup(op, moving, fixed, y0, y1, x0, x1, model, photometric != 0, used, &st);
+  if (e != hipSuccess) return op.finish(e);
+  const bool photo = photometric != 0;
+  const int n = st.run.n, geo = n - (photo ? 2 : 0);
+  Mat3 m;
+  memcpy(m.m, M, sizeof m.m);
+  m = al_mul3(al_unit(m), al_shift3(x0, y0));
+  const Mat3 down = al_inv3(AL_UP);
+  for (int l = 1; l < used; ++l) m = al_mul3(al_mul3(down, m), AL_UP);
+  double gain = gain_bias[0], bias = gain_bias[1];
+  int total = 0, rc = ICS_OK;
+  double last = 0.0;                    // the corner motion of the last step taken at full resolution
+  AlSums cur, nxt;
+  for (int l = used - 1; l >= 0 && rc == ICS_OK; --l) {
+    const AlLevel& lv = st.lv[l];
+    const Mat3 nf = al_frame3(lv.H, lv.W), nm = al_frame3(lv.Hm, lv.Wm);
+    Mat3 A = al_unit(al_mul3(al_mul3(al_inv3(nm), m), nf));
+    rc = st.run.evaluate(lv, A, gain, bias, &cur, &e);
+    double lambda = AL_LAMBDA0;
+    for (int step = 0; step < iterations && rc == ICS_OK; ++step) {
+      double d[AL_MAX_PARAMS];
+      if (!al_solve(cur, n, lambda, d)) { rc = ics_set_error(ICS_EINVAL, "no texture to align on"); break; }
+      Mat3 A1 = A;
+      for (int k = 0; k < geo; ++k) A1.m[AL_INDEX[model][k]] += d[k];
+      const double g1 = photo ? gain + d[n - 2] : gain, b1 = photo ? bias + d[n - 1] : bias;
+      rc = st.run.evaluate(lv, A1, g1, b1, &nxt, &e);
+      if (rc != ICS_OK) break;
+      ++total;
+      const double motion = al_corner_motion(A, A1, lv);
+      if (l == 0) last = motion;
+      if (nxt.rr / nxt.count <= cur.rr / cur.count) { A = A1; gain = g1; bias = b1; cur = nxt; lambda /= 10.0; }
+      else lambda *= 10.0;
+      if (motion < tolerance) break;
+    }
+    m = al_unit(al_mul3(al_mul3(nm, A), al_inv3(nf)));
+    if (l) m = al_mul3(al_mul3(AL_UP, m), down);
+  }
+  if (rc == ICS_EHIP) return op.finish(e);
+  const int done = op.finish(hipSuccess);
+  if (rc != ICS_OK) return rc;          // (a refusal: its message stands)
+  RC(done);
+  m = al_unit(al_mul3(m, al_shift3(-x0, -y0)));
+  memcpy(M, m.m, sizeof m.m);
+  gain_bias[0] = gain; gain_bias[1] = bias;
+  stats[0] = sqrt(cur.rr / cur.count); stats[1] = cur.count / ((double)Hf * Wf); stats[2] = total; stats[3] = used; stats[4] = last;
+  return ICS_OK;
+}
+
+extern "C" int ics_img_warp(const ics_img* src, const double M[9], int oh, int ow, ics_img** out) {
+  RC(check_new(src, out));
+  if (!M) return ics_set_error(ICS_EINVAL, "the matrix is NULL");
+  RC(al_check_matrix(M));
+  if (oh < 1 || ow < 1) return ics_set_error(ICS_EINVAL, "bad output size %d x %d", oh, ow);
+  ImgOp op(src->ctx, out, "img_warp");
+  RC(img_new(src->ctx, oh, ow, out));
+  hipError_t e = op.begin();
+  if (e == hipSuccess) e = ics_launch_img_al_warp(src->d, src->H, src->W, M, (*out)->d, oh, ow, src->ctx->stream);
+  return op.finish(e);
 }
 
 // ---- guided filter of a device image (csrc/ics_img_guided.hip) ------------------------------------------------------------------

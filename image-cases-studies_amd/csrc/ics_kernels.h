@@ -416,3 +416,17 @@ float* ics_img_pe_raw(void* workspace, int H, int W, int K, int Py, int Px);
 double* ics_img_pe_energy(void* workspace, int H, int W, int K, int Py, int Px);
 hipError_t ics_launch_img_psf_estimate(const float* sharp, const float* blurred, long pitch, int H, int W, int K, float regularisation, int coupling, int Py, int Px,
                                        void* workspace, hipStream_t s);
+
+// ---- registration and warp of device-resident images (ics_img_align.hip): the luma plane of a window of an HWC frame (`pitch` floats a
+// frame row), its 2 x 2 mean, one evaluation of the Gauss-Newton sums of a fixed plane T (H x W) against a moving plane I (Hm x Wm), and
+// the projective warp of a frame.  model 0 translation, 1 affine, 2 homography; A: the 3 x 3 matrix between the planes' own frames
+// (coordinates from the centre, divided by half the longer side).  slots: ics_img_al_tiles(H, W) * ics_img_al_slot_floats floats; out:
+// that many doubles -- the upper triangle of J^T J row-major, J^T r, sum r^2, the count.  The planes and frames are only read.
+int ics_img_al_params(int model, int photometric);
+int ics_img_al_slot_floats(int model, int photometric);
+long ics_img_al_tiles(int H, int W);
+hipError_t ics_launch_img_al_luma(const float* f, long pitch, int H, int W, float* out, hipStream_t s);
+hipError_t ics_launch_img_al_half(const float* in, int H, int W, float* out, hipStream_t s);
+hipError_t ics_launch_img_al_sums(const float* T, int H, int W, const float* I, int Hm, int Wm, int model, int photometric, const double A[9], double gain, double bias,
+                                  float* slots, double* out, hipStream_t s);
+hipError_t ics_launch_img_al_warp(const float* src, int H, int W, const double M[9], float* out, int oh, int ow, hipStream_t s);

@@ -99,6 +99,7 @@ IMG_DESPECKLE_STRENGTH = 6.0     # include/ics_hip.h ICS_IMG_DESPECKLE_STRENGTH:
 IMG_BLURWIDTH_MAX_LAG = 128      # include/ics_hip.h ICS_IMG_BLURWIDTH_MAX_LAG: largest lag of DeviceImage.blur_profile
 IMG_WIENER_MAX = 8192            # include/ics_hip.h ICS_IMG_WIENER_MAX: longest line of DeviceImage.wiener's transform (H + K - 1, W + K - 1 at most)
 IMG_TVD_MAX_ITERATIONS = 500     # include/ics_hip.h ICS_IMG_TVD_MAX_ITERATIONS: most iterations of DeviceImage.tv_deconvolve
+IMG_ALIGN_MAX_LEVELS = 8         # include/ics_hip.h ICS_IMG_ALIGN_MAX_LEVELS: most pyramid levels of DeviceImage.align
 IMG_MASK_CELL = 16               # include/ics_hip.h ICS_IMG_MASK_CELL: DeviceImage.window_scores ranks boxes on this grid and scores whole cells of this side
 IMG_NOISE_STRENGTH = 3.0         # include/ics_hip.h ICS_IMG_NOISE_STRENGTH: thresholds="auto" cuts this many standard deviations
 IMG_NOISE_E = (0.89079631027875839, 0.20066385102441897, 0.085507504753369934, 0.041217444374316202,      # include/ics_hip.h ICS_IMG_NOISE_E: e_j, the L2
@@ -194,6 +195,10 @@ def load():
     lib.ics_img_tv_deconvolve_masked_plan.argtypes = [ci, ci, ci, C.POINTER(ci), C.POINTER(ci), C.POINTER(C.c_size_t)]
     lib.ics_img_psf_estimate.argtypes = [vp, vp, ci, ci, ci, ci, ci, cf, ci, C.POINTER(cf), C.POINTER(cd)]
     lib.ics_img_psf_estimate_plan.argtypes = [ci, ci, ci, C.POINTER(ci), C.POINTER(ci), C.POINTER(C.c_size_t)]
+    lib.ics_img_align.argtypes = [vp, vp, ci, ci, ci, ci, ci, ci, ci, ci, cd, C.POINTER(cd), C.POINTER(cd), C.POINTER(cd)]
+    lib.ics_img_align_sums.argtypes = [vp, vp, ci, ci, ci, ci, ci, ci, C.POINTER(cd), cd, cd, C.POINTER(cd), ci]
+    lib.ics_img_warp.argtypes = [vp, C.POINTER(cd), ci, ci, C.POINTER(vp)]
+    lib.ics_img_align_plan.argtypes = [ci, ci, ci, C.POINTER(ci), C.POINTER(C.c_size_t)]
     lib.ics_rl_upload_img.argtypes = [vp, vp, ci, ci, vp, ci, ci, vp]
     lib.ics_rl_download_img.argtypes = [vp, vp, ci, ci]
     lib.ics_group_create.argtypes = [ci, ci, ci, C.c_char_p, ci, C.POINTER(vp)]
@@ -217,6 +222,7 @@ def load():
                  "ics_img_upload", "ics_img_upload_int", "ics_img_download", "ics_img_pad_edge", "ics_img_crop", "ics_img_paste", "ics_img_gamma", "ics_img_resize",
                  "ics_img_convolve", "ics_img_usm", "ics_img_bilateral", "ics_img_tv_denoise", "ics_img_wavelet_equalize", "ics_img_noise_estimate", "ics_img_blur_profile", "ics_img_window_scores", "ics_img_despeckle", "ics_img_guided", "ics_img_local_laplacian", "ics_img_wiener", "ics_img_wiener_plan", "ics_img_tv_deconvolve", "ics_img_tv_deconvolve_plan", "ics_img_tv_deconvolve_masked", "ics_img_tv_deconvolve_masked_plan",
                  "ics_img_psf_estimate", "ics_img_psf_estimate_plan",
+                 "ics_img_align", "ics_img_align_sums", "ics_img_warp", "ics_img_align_plan",
                  "ics_rl_upload_img", "ics_rl_download_img", "ics_group_create", "ics_group_info", "ics_group_barrier",
                  "ics_group_allreduce_max", "ics_group_allreduce_sum", "ics_group_describe", "ics_group_allgather"):
         getattr(lib, name).restype = ci
@@ -710,6 +716,88 @@ def psf_project(raw, threshold):
     return np.ascontiguousarray(psf, dtype=np.float32), tuple(rejected)
 
 
+AlignPlan = collections.namedtuple("AlignPlan", "levels workspace_bytes")
+class Alignment(collections.namedtuple("Alignment", "matrix gain bias rms coverage steps")):
+    """what DeviceImage.align returns; beside the fields, as attributes of the instance (`_replace`, slicing and `==` do not carry
+    them): `levels`, the pyramid levels used, and `last_step`, the corner motion in px of the last step at full resolution"""
+    levels = None
+    last_step = None
+
+ALIGN_MODELS = ("translation", "affine", "homography")          # the library's 0, 1, 2; 2, 6 and 8 parameters
+ALIGN_REFUSALS = ("not finite: despeckle first", "frames do not overlap enough", "no texture to align on")
+
+
+def _matrix(m, what="matrix"):
+    """a 3 x 3 projective matrix as float64 with m[2][2] = 1; ValueError: another shape, not finite, singular"""
+    try:
+        a = np.array(m, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError("%s %r (3 x 3 numbers)" % (what, m))
+    if a.shape != (3, 3) or not np.isfinite(a).all():
+        raise ValueError("%s of shape %s (3 x 3, finite)" % (what, a.shape))
+    if a[2, 2] == 0 or not abs(np.linalg.det(a)) > 0:
+        raise ValueError("%s is singular" % (what,))
+    return np.ascontiguousarray(a / a[2, 2])
+
+
+def _box(window, shape, what="window"):
+    H, W = int(shape[0]), int(shape[1])
+    if window is None:
+        return (0, H, 0, W)
+    try:
+        y0, y1, x0, x1 = (int(v) for v in window)
+        exact = all(int(v) == v for v in window)
+    except (TypeError, ValueError):
+        y0 = y1 = x0 = x1 = 0
+        exact = False
+    if not exact or not (0 <= y0 < y1 <= H and 0 <= x0 < x1 <= W):
+        raise ValueError("%s %r ((y0, y1, x0, x1), half-open, not empty, inside the %d x %d frame)" % (what, window, H, W))
+    return (y0, y1, x0, x1)
+
+
+def align_args(model, photometric, levels, iterations, tolerance, init, window, shape_moving, shape_fixed):
+    """the arguments of DeviceImage.align / lib.utils.align checked (ValueError) and as (model number, photometric as 0 / 1, levels with 0
+    for None, iterations, tolerance, the start as a 3 x 3 float64 matrix, (y0, y1, x0, x1)); shape_moving, shape_fixed: (H, W, ...) of
+    the two frames, which may differ"""
+    if model not in ALIGN_MODELS:
+        raise ValueError("model %r (one of %s)" % (model, ", ".join(ALIGN_MODELS)))
+    if not isinstance(photometric, (bool, np.bool_)):
+        raise ValueError("photometric %r (True or False)" % (photometric,))
+
+    def whole(v, lo, hi):
+        try:
+            return not isinstance(v, (bool, str)) and int(v) == v and lo <= int(v) <= hi
+        except (TypeError, ValueError, OverflowError):
+            return False
+
+    if levels is not None and not whole(levels, 1, IMG_ALIGN_MAX_LEVELS):
+        raise ValueError("levels %r (None or an integer, 1 to %d)" % (levels, IMG_ALIGN_MAX_LEVELS))
+    if not whole(iterations, 1, 1 << 20):
+        raise ValueError("iterations %r (an integer, at least 1)" % (iterations,))
+    try:
+        ok = not isinstance(tolerance, (bool, str)) and math.isfinite(float(tolerance)) and float(tolerance) > 0
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError("tolerance %r (must be finite and > 0)" % (tolerance,))
+    box = _box(window, shape_fixed)
+    start = np.eye(3) if init is None else _matrix(init, "init")
+    side = min(box[1] - box[0], box[3] - box[2], int(shape_moving[0]), int(shape_moving[1]))
+    if side >> ((levels or 1) - 1) < 16:
+        raise ValueError("%d level(s) on planes of %d px: no level may be smaller than 16 px a side" % (levels or 1, side))
+    return ALIGN_MODELS.index(model), int(bool(photometric)), int(levels or 0), int(iterations), float(tolerance), start, box
+
+
+def align_plan(H, W, levels=None):
+    """ics_img_align_plan: AlignPlan(levels, workspace_bytes) of DeviceImage.align of an H x W window against an H x W moving frame --
+    the pyramid levels it uses (levels=None: halve while the smaller side of the next level stays >= 64, at most
+    IMG_ALIGN_MAX_LEVELS) and the device bytes it takes from the pool: both luma pyramids, 67 floats a 32 x 32 tile, the sums (no
+    device needed).  NativeError (ICS_EINVAL): H or W < 1, levels outside 1 .. IMG_ALIGN_MAX_LEVELS, a level below 16 px a side."""
+    used, ws = C.c_int(0), C.c_size_t(0)
+    _check(load().ics_img_align_plan(int(H), int(W), int(levels or 0), C.byref(used), C.byref(ws)))
+    return AlignPlan(used.value, int(ws.value))
+
+
 def llf_levels(H, W):
     """levels=None of DeviceImage.local_laplacian: the halvings (n -> (n + 1) // 2) that bring the longer side of an H x W picture to
     16 or below, within 1 .. IMG_LLF_MAX_LEVELS"""
@@ -1148,6 +1236,67 @@ class DeviceImage:
         if not (energy > 0).all():
             raise ValueError("the sharp frame has no gradients (energy %s): nothing to estimate a PSF from" % (tuple(float(v) for v in energy),))
         return raw, energy
+
+    def align(self, fixed, model="affine", photometric=True, levels=None, iterations=30, tolerance=1e-3, init=None, window=None, gain=1.0, bias=0.0):
+        """Registers this frame, the moving one, to `fixed`, a DeviceImage of the same context and of any shape: Alignment(matrix, gain,
+        bias, rms, coverage, steps).  matrix, 3 x 3 float64 with [2][2] = 1, takes a pixel (x, y, 1) of `fixed` to its position in this
+        frame, so that `self.warp(matrix, fixed.shape)` lies on `fixed`.  Coarse-to-fine Gauss-Newton on the luma of both frames
+        (forward-additive Lucas-Kanade with Levenberg's damping): model "translation" (2 parameters), "affine" (6) or "homography" (8);
+        photometric: and a gain and a bias, the residual gain I(M x) + bias - T(x).  levels None: halve while the smaller side of the
+        next level stays >= 64 px; a level ends when a step moves no corner by `tolerance` px, or after `iterations` steps.  init: the
+        start (None: the identity); window (y0, y1, x0, x1), half-open: the region of `fixed` to look at.  rms: of the residual at
+        full resolution; coverage: the share of the window's pixels that fall inside this frame; steps: over all levels
+        (csrc/ics_img_align.hip; restated in float64 in tests/align_ref.py).  Two calls give identical bits; per step 67 doubles
+        at most cross PCIe; neither frame is written.  ValueError: bad arguments (before any native call); "not finite: despeckle first",
+        "frames do not overlap enough", "no texture to align on" while it runs."""
+        if not isinstance(fixed, DeviceImage):
+            raise ValueError("fixed must be a DeviceImage like the moving frame, got %s" % (type(fixed).__name__,))
+        model, photometric, levels, iterations, tolerance, start, (y0, y1, x0, x1) = align_args(model, photometric, levels, iterations, tolerance, init, window,
+                                                                                                  self.shape, fixed.shape)
+        if not (_finite32(gain, scalar=True) and _finite32(bias, scalar=True) and float(gain) != 0):
+            raise ValueError("gain %r, bias %r (finite, gain not 0)" % (gain, bias))
+        M, gb, stats = start.copy(), np.array([gain, bias], np.float64), np.zeros(5, np.float64)
+        dp = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))
+        try:
+            _check(load().ics_img_align(self._h, fixed._h, y0, y1, x0, x1, model, photometric, levels, iterations, tolerance, dp(M), dp(gb), dp(stats)))
+        except NativeError as exc:
+            if exc.code == ICS_EINVAL and any(words in str(exc) for words in ALIGN_REFUSALS):
+                raise ValueError(str(exc).split(": ", 1)[1]) from None
+            raise
+        got = Alignment(M, float(gb[0]), float(gb[1]), float(stats[0]), float(stats[1]), int(stats[2]))
+        got.levels, got.last_step = int(stats[3]), float(stats[4])
+        return got
+
+    def align_sums(self, fixed, matrix, model="affine", photometric=True, gain=1.0, bias=0.0, window=None):
+        """One evaluation of the sums of a Gauss-Newton step of `align` at full resolution, for the given matrix, gain and bias: (S, g,
+        sum r^2, count) -- the n x n matrix sum J^T J, sum J^T r, the squared residual and the number of pixels that counted, in the
+        normalised coordinates of include/ics_hip.h (tests/align_ref.py sums_on_window).  Nothing is refused for what the sums hold."""
+        if not isinstance(fixed, DeviceImage):
+            raise ValueError("fixed must be a DeviceImage like the moving frame, got %s" % (type(fixed).__name__,))
+        if model not in ALIGN_MODELS:
+            raise ValueError("model %r (one of %s)" % (model, ", ".join(ALIGN_MODELS)))
+        y0, y1, x0, x1 = _box(window, fixed.shape)
+        M = _matrix(matrix)
+        n = (2, 6, 8)[ALIGN_MODELS.index(model)] + (2 if photometric else 0)
+        raw = np.zeros(n * (n + 1) // 2 + n + 2, np.float64)
+        _check(load().ics_img_align_sums(self._h, fixed._h, y0, y1, x0, x1, ALIGN_MODELS.index(model), int(bool(photometric)), M.ctypes.data_as(C.POINTER(C.c_double)),
+                                         float(gain), float(bias), raw.ctypes.data_as(C.POINTER(C.c_double)), raw.size))
+        S = np.zeros((n, n))
+        S[np.triu_indices(n)] = raw[:n * (n + 1) // 2]
+        S = S + np.triu(S, 1).T
+        return S, raw[n * (n + 1) // 2:n * (n + 1) // 2 + n].copy(), float(raw[-2]), int(raw[-1])
+
+    def warp(self, matrix, shape=None):
+        """A new image of `shape` (H, W[, 3]; None: this frame's): out[y][x] = this frame sampled at matrix (x, y, 1), by Keys' cubic
+        convolution (a = -0.5) over 4 x 4 taps whose coordinates are clamped to the frame -- beyond it the edge repeats.  float32, every
+        operation rounded once (csrc/ics_img_align.hip k_img_al_warp; tests/align_ref.py warp): the identity and an integer shift copy
+        finite pixels bit for bit.  With the matrix of `moving.align(fixed)`, `moving.warp(matrix, fixed.shape)` lies on `fixed`.
+        ValueError: a matrix that is not 3 x 3, not finite or singular, a bad shape."""
+        M = _matrix(matrix)
+        H, W = self.shape[:2] if shape is None else (shape[0], shape[1])
+        if int(H) != H or int(W) != W or H < 1 or W < 1:
+            raise ValueError("shape %r (H, W at least 1)" % (shape,))
+        return self._new(load().ics_img_warp, M.ctypes.data_as(C.POINTER(C.c_double)), int(H), int(W))
 
     def close(self):
         if self._h:

@@ -390,10 +390,89 @@ def wiener(src, psf, balance=0.01):
         res.close()
 
 
-PsfEstimate = collections.namedtuple("PsfEstimate", "psf raw rejected")
+class PsfEstimate(collections.namedtuple("PsfEstimate", "psf raw rejected")):
+    """what estimate_psf(info=True) returns; `matrix`: with register=, the 3 x 3 matrix that takes a pixel of `blurred` to its position in `sharp` (else None).  It is an attribute
+    of the instance, not a field: the three fields stay what they were, and `_replace`, `_make`, slicing and `==` do not carry or compare it"""
+    matrix = None
 
 
-def estimate_psf(blurred, sharp, size, regularisation=1e-3, threshold=0.05, coupling="vector", window=None, info=False):
+Alignment = _native.Alignment
+
+
+def _pair_on_device(a, b, names):
+    """two DeviceImages read where they lie, or two H x W x 3 arrays: (a, b, arrays or None) -- nothing is uploaded here"""
+    dev = [isinstance(v, _native.DeviceImage) for v in (a, b)]
+    if dev[0] != dev[1]:
+        raise ValueError("%s and %s must both be DeviceImages or both H x W x 3 arrays" % names)
+    if all(dev):
+        return a, b, None
+    arrays = (np.asarray(a), np.asarray(b))
+    for arr in arrays:
+        if arr.ndim != 3 or arr.shape[2] != 3:
+            raise ValueError("expected two DeviceImages or two H x W x 3 arrays, got shape %s" % (arr.shape,))
+    return arrays[0], arrays[1], arrays
+
+
+def _upload_pair(arrays):
+    a = _native.DeviceImage.from_host(np.ascontiguousarray(arrays[0], dtype=np.float32))
+    try:
+        b = _native.DeviceImage.from_host(np.ascontiguousarray(arrays[1], dtype=np.float32))
+    except Exception:
+        a.close()
+        raise
+    return a, b
+
+
+def align(moving, fixed, model="affine", photometric=True, levels=None, iterations=30, tolerance=1e-3, init=None, window=None, info=False):
+    """Not in the reference's lib/utils.py (its README lists "Lens PSF calibration" under what may come one day; `estimate_psf` is one half
+    of it, this the other): registers `moving` to `fixed` and returns the 3 x 3 float64 matrix that takes a pixel (x, y, 1) of `fixed`
+    to its position in `moving` -- `warp(moving, matrix, fixed.shape)` then lies on `fixed`.  Coarse-to-fine Gauss-Newton on the luma
+    (forward-additive Lucas-Kanade, Levenberg's damping; `DeviceImage.align`, csrc/ics_img_align.hip): model "translation", "affine"
+    or "homography"; photometric: a gain and a bias between the frames are estimated with it (two exposures); levels None: halve
+    while the smaller side stays >= 64 px; init: a start (None: the identity); window (y0, y1, x0, x1): the region of `fixed` to
+    look at.  info=True: Alignment(matrix, gain, bias, rms, coverage, steps).  Two `lib._native.DeviceImage`s are read where they
+    lie; two H x W x 3 arrays, which may differ in shape, are uploaded once each.  It cannot align through a blur so strong that no
+    level holds texture, a motion beyond about a tenth of the frame without `init`, periodic patterns (a local minimum), parallax,
+    rolling shutter or lens distortion; a strongly asymmetric PSF shifts the registration by its centroid.  ValueError: a DeviceImage
+    with an array, bad arguments (before anything is uploaded), frames that are not finite, do not overlap enough or hold no
+    texture.  There is no CPU fallback."""
+    m, f, arrays = _pair_on_device(moving, fixed, ("moving", "fixed"))
+    _native.align_args(model, photometric, levels, iterations, tolerance, init, window, m.shape, f.shape)      # refused before anything is uploaded
+    if arrays is not None:
+        m, f = _upload_pair(arrays)
+    try:
+        got = m.align(f, model, photometric, levels, iterations, tolerance, init, window)
+    finally:
+        if arrays is not None:
+            m.close(); f.close()
+    return got if info else got.matrix
+
+
+def warp(src, matrix, shape=None):
+    """Not in the reference's lib/utils.py: `src` seen through the 3 x 3 matrix, out[y][x] = src sampled at matrix (x, y, 1), by Keys'
+    cubic convolution over 4 x 4 taps, the edge repeated beyond the frame (`DeviceImage.warp`, csrc/ics_img_align.hip); shape (H, W):
+    that of the result (None: that of `src`).  A `lib._native.DeviceImage` gives a new DeviceImage, an H x W x 3 array is uploaded
+    once and gives a float32 array.  ValueError: a matrix that is not 3 x 3, not finite or singular.  There is no CPU fallback."""
+    if isinstance(src, _native.DeviceImage):
+        return src.warp(matrix, shape)
+    arr = np.asarray(src)
+    if arr.ndim != 3 or arr.shape[2] != 3:
+        raise ValueError("expected a DeviceImage or an H x W x 3 array, got shape %s" % (arr.shape,))
+    _native._matrix(matrix)                                           # refused before anything is uploaded
+    if shape is not None and (len(shape) < 2 or int(shape[0]) < 1 or int(shape[1]) < 1):
+        raise ValueError("shape %r (H, W at least 1)" % (shape,))
+    img = _native.DeviceImage.from_host(np.ascontiguousarray(arr, dtype=np.float32))
+    try:
+        res = img.warp(matrix, shape)
+    finally:
+        img.close()
+    try:
+        return res.to_host()
+    finally:
+        res.close()
+
+
+def estimate_psf(blurred, sharp, size, regularisation=1e-3, threshold=0.05, coupling="vector", window=None, info=False, register=None):
     """Not in the reference's lib/utils.py, whose only way to a PSF is the blind loop: the PSF from a picture and a sharper rendering of
     the same scene -- a test chart and its photograph, a frame stopped down and the same frame wide open, a synthetic target -- or the
     check of a PSF the blind phase returned against the frame it produced.  The linear solve every fast blind method repeats (Cho and
@@ -404,10 +483,15 @@ def estimate_psf(blurred, sharp, size, regularisation=1e-3, threshold=0.05, coup
     kernel and the share of its weight that the threshold cut, per channel.  size odd, 3 .. 255; coupling "vector": one PSF from the
     three channels, "channel": one each; window (y0, y1, x0, x1), half-open: the region to look at (None: the whole frame).  Two
     `lib._native.DeviceImage`s are read where they lie; two H x W x 3 arrays are uploaded once each; only the raw kernel and the energy
-    come back.  It cannot register the pair (`sharp` must lie on `blurred` to the pixel), gives the relative PSF where `sharp` is
+    come back.  Without `register=` (below) it cannot register the pair (`sharp` must lie on `blurred` to the pixel); it gives the relative PSF where `sharp` is
     itself blurred, leaves the PSF free along a direction in which `sharp` has no gradients, and a NaN spreads (despeckle first).
     ValueError: a DeviceImage with an array, frames of different shapes, bad arguments (before anything is uploaded), a raw kernel or
-    energy that is not finite, a sharp frame with no gradients.  There is no CPU fallback."""
+    energy that is not finite, a sharp frame with no gradients.  There is no CPU fallback.
+    register "translation", "affine" or "homography": `sharp`, of any shape, is first registered to `blurred` (`align`, on the window,
+    with a gain and a bias) and warped onto it, one line is printed, and the estimate proceeds on the warped frame; info=True then
+    carries the matrix as `PsfEstimate.matrix`.  None: the frames are taken as registered."""
+    if register is not None:
+        return _estimate_psf_registered(blurred, sharp, size, regularisation, threshold, coupling, window, info, register)
     dev = [isinstance(v, _native.DeviceImage) for v in (blurred, sharp)]
     if dev[0] != dev[1]:
         raise ValueError("blurred and sharp must both be DeviceImages or both H x W x 3 arrays")
@@ -434,6 +518,32 @@ def estimate_psf(blurred, sharp, size, regularisation=1e-3, threshold=0.05, coup
             b.close(); s.close()
     psf, rejected = _native.psf_project(raw, threshold)
     return PsfEstimate(psf, raw, rejected) if info else psf
+
+
+def _estimate_psf_registered(blurred, sharp, size, regularisation, threshold, coupling, window, info, register):
+    """estimate_psf(register=...): align `sharp` to `blurred`, warp it to the shape of `blurred`, estimate"""
+    b, s, arrays = _pair_on_device(blurred, sharp, ("blurred", "sharp"))
+    size, regularisation, threshold, coupling, window = _native.psf_estimate_args(size, regularisation, threshold, coupling, window, b.shape, b.shape)
+    _native.align_args(register, True, None, 30, 1e-3, None, window, s.shape, b.shape)                          # refused before anything is uploaded
+    if arrays is not None:
+        b, s = _upload_pair(arrays)
+    warped = None
+    try:
+        got = s.align(b, register, True, window=window)
+        print("Register : %s, %.2g px last step, rms %.4f, coverage %.0f %%" % (register, got.last_step, got.rms, 100.0 * got.coverage))
+        warped = s.warp(got.matrix, b.shape)
+        raw, _ = b.psf_raw(warped, size, regularisation, coupling, window)
+    finally:
+        if warped is not None:
+            warped.close()
+        if arrays is not None:
+            b.close(); s.close()
+    psf, rejected = _native.psf_project(raw, threshold)
+    if not info:
+        return psf
+    res = PsfEstimate(psf, raw, rejected)
+    res.matrix = got.matrix
+    return res
 
 
 def tv_deconvolve(src, psf, fidelity=2000.0, penalty=10.0, iterations=10, coupling="vector"):

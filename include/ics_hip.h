@@ -622,6 +622,47 @@ int ics_img_tv_deconvolve_masked_plan(int H, int W, int K, int *Py, int *Px, siz
 int ics_img_psf_estimate(const ics_img *blurred, const ics_img *sharp, int y0, int y1, int x0, int x1, int K,
                          float regularisation, int coupling, float *raw /* K*K*3 */, double energy[3]);
 int ics_img_psf_estimate_plan(int H, int W, int K, int *Py, int *Px, size_t *workspace_bytes);
+/* Registration of two device images and the projective warp of one.  M, 3 x 3 row-major with M[8] = 1, takes a pixel (x, y, 1) of
+ * `fixed` to the position (u, v) = (M0 . p, M1 . p) / (M2 . p) in `moving`.  ics_img_align finds it by coarse-to-fine Gauss-Newton on the
+ * luma of both frames (forward-additive Lucas-Kanade, Levenberg's damping), with a gain a and a bias b where photometric != 0: the
+ * residual is r = a I(M x) + b - T(x), T the luma of the box (y0, y1, x0, x1) of `fixed`, I that of all of `moving`.
+ *   luma     Y = ((R + G) + B) * (1 / 3), smoothed by the binomial 1 2 1 each way inside the box / frame (the edge repeated), so that
+ *            the bilinear sample and its central differences describe one surface on hard edges; pyramid level l + 1 = ((a + b) + (c + d)) * 0.25 of a 2 x 2 block, an odd last row or column
+ *            dropped, pixel centres X = 2 (x + 0.5) - 0.5.  levels 0: halve while the smaller side of the next level of either plane
+ *            stays >= 64, at most ICS_IMG_ALIGN_MAX_LEVELS; no level may be smaller than 16 px a side.
+ *   model    0 translation (2 parameters), 1 affine (6), 2 homography (8); photometric adds a and b.
+ *   a step   at a level: for every pixel of the fixed plane whose position (u, v) has 1 <= u < Wm - 2 and 1 <= v < Hm - 2, I and the
+ *            central differences of I sampled bilinearly, the row J = a grad I . d(u, v)/dp (and I, 1), with the coordinates of both
+ *            planes taken from their centres and divided by half their longer sides; S = sum J^T J, g = sum J^T r, sum r^2 and the
+ *            count, float32 inside a 32 x 32 tile, double across the tiles, every sum in one order; (S + lambda diag S) d = -g by
+ *            Cholesky in double on the host; lambda starts at 1e-6 at every level; a step that raises sum r^2 / count is rejected
+ *            and lambda multiplied by 10, an accepted one divides it by 10.  A level ends when the largest motion of its four corners
+ *            under a step is below `tolerance` px, or after `iterations` steps.
+ * M: in the start, out the result; gain_bias: in the start (1, 0 for none), out the result (unchanged where photometric == 0, though
+ * applied); stats: the rms of r at full resolution, count / pixels of the box, steps taken over all levels, levels used, the corner
+ * motion in px of the last step at full resolution (one entry more than first planned: the line estimate_psf prints needs it).  Restated in
+ * float64 in tests/align_ref.py.  Two runs give identical bits; neither frame is written; the frames may differ in shape; the call
+ * waits for one read-back of at most 67 doubles per step.
+ * ICS_EINVAL, before a frame is touched: a NULL pointer, model outside 0 .. 2, M not finite or singular, gain 0 or not finite, an empty
+ * box or one with a negative corner, iterations < 1, tolerance not finite or <= 0, levels outside 0 .. ICS_IMG_ALIGN_MAX_LEVELS; then:
+ * frames of different contexts, a box outside `fixed`, a level below 16 px; while it runs, with these words in ics_last_error: "not
+ * finite: despeckle first" (a sum that is NaN or inf), "frames do not overlap enough" (count below a quarter of the plane at any step),
+ * "no texture to align on" (the damped matrix is not positive definite).
+ * ics_img_align_sums: one evaluation of the sums at full resolution for the given M, gain and bias: the upper triangle of S row-major,
+ * g, sum r^2, the count -- n (n + 1) / 2 + n + 2 doubles for n parameters (`count` must say so), in the normalised coordinates above.
+ * ics_img_warp: *out[y][x][c] = src sampled at M (x, y, 1), oh x ow pixels, by Keys' cubic convolution (a = -0.5) over 4 x 4 taps whose
+ * coordinates are clamped to the frame; float32, every operation rounded once (tests/align_ref.py warp); an identity or an integer
+ * shift copies finite pixels bit for bit.  ICS_EINVAL: a NULL pointer, M not finite or singular, oh or ow < 1.
+ * ics_img_align_plan: the levels an H x W box against an H x W moving frame uses and the device bytes the call takes from the
+ * context's pool (both pyramids, 67 floats a tile, the sums); no device needed; same checks on H, W, levels. */
+#define ICS_IMG_ALIGN_MAX_LEVELS 8
+int ics_img_align(const ics_img *moving, const ics_img *fixed, int y0, int y1, int x0, int x1, int model, int photometric, int levels,
+                  int iterations, double tolerance, double M[9] /* in: start, out: result */, double gain_bias[2] /* in/out */,
+                  double stats[5] /* rms, coverage, steps taken, levels used, last step px */);
+int ics_img_align_sums(const ics_img *moving, const ics_img *fixed, int y0, int y1, int x0, int x1, int model, int photometric,
+                       const double M[9], double gain, double bias, double *sums, int count);
+int ics_img_warp(const ics_img *src, const double M[9], int oh, int ow, ics_img **out);
+int ics_img_align_plan(int H, int W, int levels, int *used, size_t *workspace_bytes);
 /* richardson_lucy_MM(image[iy:iy+M, ix:ix+N], u[uy:uy+uM, ux:ux+uN], psf, ...) with both windows taken from device
  * images (deconvolve.py:277-313 passes such views); psf is a host MK*MK*3 array as in ics_rl_upload. */
 int ics_rl_upload_img(ics_rl *job, const ics_img *image, int iy, int ix, const ics_img *u, int uy, int ux, const float *psf);

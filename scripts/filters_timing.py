@@ -1,6 +1,6 @@
 """Timing of the lib/utils.py filters on one seeded SIZE x SIZE RGB float32 picture (GPU box), one JSON line:
 
-    python scripts/filters_timing.py [SIZE=4096] [guided | llf | noise | despeckle | blurwidth | mask | wiener | tvdeconv | tvmasked | psf]       (a section name: that section alone)
+    python scripts/filters_timing.py [SIZE=4096] [guided | llf | noise | despeckle | blurwidth | mask | wiener | tvdeconv | tvmasked | psf | align]       (a section name: that section alone)
 
   resident   the filters on a DeviceImage in HBM (csrc/ics_img_filters.hip): device time of the kernels (HIP events around them,
              ics_ctx_last_kernel_ms; warm, median of 25) and wall time of the queued call up to a stream synchronise
@@ -78,6 +78,12 @@
              eight launches (median and minimum of 9 rounds), the wall time of the call (it waits for the raw kernel and the energies),
              and TB/s on the model of 42 transits of 8 B per transform point; beside each DeviceImage.wiener (balance 0.01, a
              Gaussian PSF of the same K) on the frame, or on the crop of the window, and DeviceImage.copy() of the frame
+  align      DeviceImage.align_sums / align / warp (csrc/ics_img_align.hip) on a 4096 x 4096 pair of its own (SIZE is not used): a smoothed
+             random field and the same field (3, -2) px off.  Per model, photometric on: one align_sums call -- the lumas of both frames
+             and one evaluation of the sums -- kernel ms (median and minimum of 9 rounds) and GB/s on the model of 40 B/px (2 x 16 for the
+             lumas, 8 for the pass); a whole align of the frame and of the window of 1023 x 1023 pixels at (1537, 1539): the levels, the
+             pool bytes, the steps taken, wall ms of the call and ms per step; a warp of the frame by a small homography: kernel ms and
+             TB/s on 24 B/px; beside them DeviceImage.copy() of the frame
   checks     the resident USM must not take longer than the three float64 calls, in kernel time and in wall time (a guard against a
              broken kernel, not a target); the exit status is 1 if one of them fails
 Starts no child process; a job script puts its own time limit around it."""
@@ -505,6 +511,58 @@ def psf_section(ctx):
     return res
 
 
+ALIGN_WINDOW = (1537, 2560, 1539, 2562)
+ALIGN_SUMS_BYTES, ALIGN_WARP_BYTES = 40, 24
+
+
+def align_section(ctx):
+    from scipy.ndimage import uniform_filter
+    H = W = 4096
+    rng = np.random.default_rng(0)
+    base = uniform_filter(rng.random((H + 16, W + 16, 3), dtype=np.float32), size=(5, 5, 1), mode="nearest")
+    fixed = _native.DeviceImage.from_host(np.ascontiguousarray(base[8:8 + H, 8:8 + W]), ctx)
+    moving = _native.DeviceImage.from_host(np.ascontiguousarray(base[6:6 + H, 11:11 + W]), ctx)      # fixed (x, y) lies at (x - 3, y + 2) in moving
+    del base
+    res = {"frame": [H, W], "copy": copy_row(fixed, ctx), "align_sums": {}, "align": {}}
+    near = np.array([[1.0, 0.0, -2.6], [0.0, 1.0, 1.7], [0.0, 0.0, 1.0]])
+    for model in _native.ALIGN_MODELS:
+        moving.align_sums(fixed, near, model)                # warm: code objects, pool blocks
+        kernel = []
+        for _ in range(REPS_DESPECKLE):
+            moving.align_sums(fixed, near, model)
+            kernel.append(ctx.last_kernel_ms())
+        med = float(np.median(kernel))
+        res["align_sums"][model] = {"kernel_ms": round(med, 4), "min_ms": round(float(np.min(kernel)), 4),
+                                    "gb_per_s": round(ALIGN_SUMS_BYTES * H * W / (med * 1e-3) / 1e9, 1)}
+    for window in (None, ALIGN_WINDOW):
+        y0, y1, x0, x1 = window or (0, H, 0, W)
+        plan = _native.align_plan(y1 - y0, x1 - x0)
+        row = res["align"]["%dx%d" % (y1 - y0, x1 - x0)] = {"levels": plan.levels, "pool_mb": round(plan.workspace_bytes / 2 ** 20, 1)}
+        for model in _native.ALIGN_MODELS:
+            got = moving.align(fixed, model, window=window)  # warm
+            wall = []
+            for _ in range(REPS_DESPECKLE):
+                t0 = time.perf_counter()
+                got = moving.align(fixed, model, window=window)
+                wall.append((time.perf_counter() - t0) * 1e3)
+            med = float(np.median(wall))
+            row[model] = {"wall_ms": round(med, 3), "min_ms": round(float(np.min(wall)), 3), "steps": got.steps, "ms_per_step": round(med / max(got.steps, 1), 4),
+                          "shift": [round(float(got.matrix[0, 2]), 4), round(float(got.matrix[1, 2]), 4)], "rms": round(got.rms, 6), "coverage": round(got.coverage, 4)}
+    M = np.array([[0.9995, -0.004, 9.0], [0.004, 0.9995, -7.0], [1e-6, -1e-6, 1.0]])
+    moving.warp(M).close()                                   # warm
+    ctx.synchronize()
+    kernel = []
+    for _ in range(REPS_DESPECKLE):
+        out = moving.warp(M)
+        ctx.synchronize()
+        kernel.append(ctx.last_kernel_ms())
+        out.close()
+    med = float(np.median(kernel))
+    res["warp"] = {"kernel_ms": round(med, 4), "min_ms": round(float(np.min(kernel)), 4), "tb_per_s": round(ALIGN_WARP_BYTES * H * W / (med * 1e-3) / 1e12, 3)}
+    fixed.close(); moving.close()
+    return res
+
+
 def main():
     size = int(sys.argv[1]) if len(sys.argv) > 1 else 4096
     ctx = _native.Context.get()
@@ -516,6 +574,9 @@ def main():
         return 0
     if sys.argv[2:] == ["psf"]:
         print(json.dumps({"device": ctx.name, "psf": psf_section(ctx)}))
+        return 0
+    if sys.argv[2:] == ["align"]:
+        print(json.dumps({"device": ctx.name, "align": align_section(ctx)}))
         return 0
     if sys.argv[2:] == ["wiener"]:
         print(json.dumps({"device": ctx.name, "wiener": wiener_section(ctx)}))
@@ -618,6 +679,7 @@ def main():
     res["tvdeconv"] = tvdeconv_section(ctx, size)
     res["tvmasked"] = tvmasked_section(ctx, size)
     res["psf"] = psf_section(ctx)
+    res["align"] = align_section(ctx)
     res["checks"] = {"%s_%s" % (name, what): res["resident"][name][what] <= res["per_channel_f64"][name][what]
                      for name in ("usm_gauss15", "usm_bessel15") for what in ("kernel_ms", "wall_ms")}
     print(json.dumps(res))
