@@ -469,13 +469,34 @@ static int wiener_shape(int H, int W, int K, int* Py, int* Px) {
                          H, W, K, K, H + K - 1, W + K - 1, ICS_IMG_WIENER_MAX);
   return ICS_OK;
 }
-extern "C" int ics_img_wiener_plan(int H, int W, int K, int* Py, int* Px, size_t* workspace_bytes) {
+// the four *_plan entry points: the transform sizes, and bytes(Py, Px) of workspace
+template <typename Bytes>
+static int wiener_plan(int H, int W, int K, int* Py, int* Px, size_t* workspace_bytes, Bytes bytes) {
   int py = 0, px = 0;
   RC(wiener_shape(H, W, K, &py, &px));
   if (Py) *Py = py;
   if (Px) *Px = px;
-  if (workspace_bytes) *workspace_bytes = 2 * ics_img_wiener_frame_bytes(py, px) + ics_img_wiener_table_bytes(K, py, px);
+  if (workspace_bytes) *workspace_bytes = bytes(py, px);
   return ICS_OK;
+}
+// the PSF, K x K x 3, as [3][K][K]
+static std::vector<float> planar_psf(const float* psf, int K) {
+  std::vector<float> planar((size_t)3 * K * K);
+  for (int ch = 0; ch < 3; ++ch)
+    for (int i = 0; i < K * K; ++i) planar[(size_t)ch * K * K + i] = psf[(size_t)3 * i + ch];
+  return planar;
+}
+// the scalars of the TV solvers; data_penalty: the masked solver's, nullptr without
+static int check_tv(float fidelity, float penalty, const float* data_penalty, int iterations, int coupling) {
+  if (!std::isfinite(fidelity) || !(fidelity > 0.f)) return ics_set_error(ICS_EINVAL, "fidelity = %g (must be finite and > 0)", (double)fidelity);
+  if (!std::isfinite(penalty) || !(penalty > 0.f)) return ics_set_error(ICS_EINVAL, "penalty = %g (must be finite and > 0)", (double)penalty);
+  if (data_penalty && (!std::isfinite(*data_penalty) || !(*data_penalty > 0.f)))
+    return ics_set_error(ICS_EINVAL, "data_penalty = %g (must be finite and > 0)", (double)*data_penalty);
+  if (iterations < 1 || iterations > ICS_IMG_TVD_MAX_ITERATIONS) return ics_set_error(ICS_EINVAL, "iterations = %d (1 .. %d)", iterations, ICS_IMG_TVD_MAX_ITERATIONS);
+  return check_coupling(coupling);
+}
+extern "C" int ics_img_wiener_plan(int H, int W, int K, int* Py, int* Px, size_t* workspace_bytes) {
+  return wiener_plan(H, W, K, Py, Px, workspace_bytes, [&](int py, int px) { return 2 * ics_img_wiener_frame_bytes(py, px) + IcsWnTables(nullptr, K, py, px).bytes; });
 }
 extern "C" int ics_img_wiener(const ics_img* src, const float* psf, int K, float balance, ics_img** out) {
   RC(check_new(src, out));
@@ -486,17 +507,14 @@ extern "C" int ics_img_wiener(const ics_img* src, const float* psf, int K, float
   RC(wiener_shape(H, W, K, &Py, &Px));
   ics_ctx* c = src->ctx;
   HIPCHK(hipSetDevice(c->device));
-  std::vector<float> planar((size_t)3 * K * K);
-  for (int ch = 0; ch < 3; ++ch)
-    for (int i = 0; i < K * K; ++i) planar[(size_t)ch * K * K + i] = psf[(size_t)3 * i + ch];
   ImgOp op(c, out, "img_wiener");
   RC(img_new(c, H, W, out));
   float2 *A = nullptr, *B = nullptr;
   void* tables = nullptr;
   hipError_t e = op.alloc((void**)&A, ics_img_wiener_frame_bytes(Py, Px));
   if (e == hipSuccess) e = op.alloc((void**)&B, ics_img_wiener_frame_bytes(Py, Px));
-  if (e == hipSuccess) e = op.alloc(&tables, ics_img_wiener_table_bytes(K, Py, Px));
-  if (e == hipSuccess) e = put_table(c, ics_img_wiener_psf_slot(tables, K, Py, Px), planar);
+  if (e == hipSuccess) e = op.alloc(&tables, IcsWnTables(nullptr, K, Py, Px).bytes);
+  if (e == hipSuccess) e = put_table(c, IcsWnTables(tables, K, Py, Px).psf, planar_psf(psf, K));
   if (e == hipSuccess) e = op.begin();
   if (e == hipSuccess) e = ics_launch_img_wiener(src->d, H, W, K, balance, Py, Px, A, B, tables, (*out)->d, c->stream);
   return op.finish(e);
@@ -505,33 +523,22 @@ extern "C" int ics_img_wiener(const ics_img* src, const float* psf, int K, float
 // ---- TV-regularised deconvolution of a device image (csrc/ics_img_tvdeconv.hip) ------------------------------------------------------
 // One route.  The shapes and the limit are the Wiener filter's; one workspace from the pool, carved by the launcher.
 extern "C" int ics_img_tv_deconvolve_plan(int H, int W, int K, int* Py, int* Px, size_t* workspace_bytes) {
-  int py = 0, px = 0;
-  RC(wiener_shape(H, W, K, &py, &px));
-  if (Py) *Py = py;
-  if (Px) *Px = px;
-  if (workspace_bytes) *workspace_bytes = ics_img_tvd_workspace_bytes(K, py, px);
-  return ICS_OK;
+  return wiener_plan(H, W, K, Py, Px, workspace_bytes, [&](int py, int px) { return ics_img_tvd_workspace_bytes(K, py, px); });
 }
 extern "C" int ics_img_tv_deconvolve(const ics_img* src, const float* psf, int K, float fidelity, float penalty, int iterations, int coupling, ics_img** out) {
   RC(check_new(src, out));
   if (!psf) return ics_set_error(ICS_EINVAL, "psf is NULL");
-  if (!std::isfinite(fidelity) || !(fidelity > 0.f)) return ics_set_error(ICS_EINVAL, "fidelity = %g (must be finite and > 0)", (double)fidelity);
-  if (!std::isfinite(penalty) || !(penalty > 0.f)) return ics_set_error(ICS_EINVAL, "penalty = %g (must be finite and > 0)", (double)penalty);
-  if (iterations < 1 || iterations > ICS_IMG_TVD_MAX_ITERATIONS) return ics_set_error(ICS_EINVAL, "iterations = %d (1 .. %d)", iterations, ICS_IMG_TVD_MAX_ITERATIONS);
-  RC(check_coupling(coupling));
+  RC(check_tv(fidelity, penalty, nullptr, iterations, coupling));
   const int H = src->H, W = src->W;
   int Py = 0, Px = 0;
   RC(wiener_shape(H, W, K, &Py, &Px));
   ics_ctx* c = src->ctx;
   HIPCHK(hipSetDevice(c->device));
-  std::vector<float> planar((size_t)3 * K * K);
-  for (int ch = 0; ch < 3; ++ch)
-    for (int i = 0; i < K * K; ++i) planar[(size_t)ch * K * K + i] = psf[(size_t)3 * i + ch];
   ImgOp op(c, out, "img_tv_deconvolve");
   RC(img_new(c, H, W, out));
   void* ws = nullptr;
   hipError_t e = op.alloc(&ws, ics_img_tvd_workspace_bytes(K, Py, Px));
-  if (e == hipSuccess) e = put_table(c, ics_img_wiener_psf_slot(ics_img_tvd_tables(ws, Py, Px), K, Py, Px), planar);
+  if (e == hipSuccess) e = put_table(c, IcsWnTables(ics_img_tvd_tables(ws, Py, Px), K, Py, Px).psf, planar_psf(psf, K));
   if (e == hipSuccess) e = op.begin();
   if (e == hipSuccess) e = ics_launch_img_tv_deconvolve(src->d, H, W, K, fidelity, penalty, iterations, coupling, Py, Px, ws, (*out)->d, c->stream);
   return op.finish(e);
@@ -541,37 +548,25 @@ extern "C" int ics_img_tv_deconvolve(const ics_img* src, const float* psf, int K
 // One route.  The shapes and the limits are those of ics_img_tv_deconvolve; one workspace from the pool, carved by the launcher, the
 // caller's mask inside it.  Only the count comes back; the frame stays where it is.
 extern "C" int ics_img_tv_deconvolve_masked_plan(int H, int W, int K, int* Py, int* Px, size_t* workspace_bytes) {
-  int py = 0, px = 0;
-  RC(wiener_shape(H, W, K, &py, &px));
-  if (Py) *Py = py;
-  if (Px) *Px = px;
-  if (workspace_bytes) *workspace_bytes = ics_img_tvm_workspace_bytes(K, py, px);
-  return ICS_OK;
+  return wiener_plan(H, W, K, Py, Px, workspace_bytes, [&](int py, int px) { return ics_img_tvm_workspace_bytes(K, py, px); });
 }
 extern "C" int ics_img_tv_deconvolve_masked(const ics_img* src, const float* psf, int K, const unsigned char* observed, float clip, float fidelity, float penalty,
                                             float data_penalty, int iterations, int coupling, long long* unobserved, ics_img** out) {
   RC(check_new(src, out));
   if (!psf) return ics_set_error(ICS_EINVAL, "psf is NULL");
   if (!(clip > 0.f)) return ics_set_error(ICS_EINVAL, "clip = %g (above 0; inf keeps every finite pixel)", (double)clip);
-  if (!std::isfinite(fidelity) || !(fidelity > 0.f)) return ics_set_error(ICS_EINVAL, "fidelity = %g (must be finite and > 0)", (double)fidelity);
-  if (!std::isfinite(penalty) || !(penalty > 0.f)) return ics_set_error(ICS_EINVAL, "penalty = %g (must be finite and > 0)", (double)penalty);
-  if (!std::isfinite(data_penalty) || !(data_penalty > 0.f)) return ics_set_error(ICS_EINVAL, "data_penalty = %g (must be finite and > 0)", (double)data_penalty);
-  if (iterations < 1 || iterations > ICS_IMG_TVD_MAX_ITERATIONS) return ics_set_error(ICS_EINVAL, "iterations = %d (1 .. %d)", iterations, ICS_IMG_TVD_MAX_ITERATIONS);
-  RC(check_coupling(coupling));
+  RC(check_tv(fidelity, penalty, &data_penalty, iterations, coupling));
   const int H = src->H, W = src->W;
   int Py = 0, Px = 0;
   RC(wiener_shape(H, W, K, &Py, &Px));
   ics_ctx* c = src->ctx;
   HIPCHK(hipSetDevice(c->device));
-  std::vector<float> planar((size_t)3 * K * K);
-  for (int ch = 0; ch < 3; ++ch)
-    for (int i = 0; i < K * K; ++i) planar[(size_t)ch * K * K + i] = psf[(size_t)3 * i + ch];
   ImgOp op(c, out, "img_tv_deconvolve_masked");
   RC(img_new(c, H, W, out));
   void* ws = nullptr;
   long long got = 0;
   hipError_t e = op.alloc(&ws, ics_img_tvm_workspace_bytes(K, Py, Px));
-  if (e == hipSuccess) e = put_table(c, ics_img_wiener_psf_slot(ics_img_tvm_tables(ws, Py, Px), K, Py, Px), planar);
+  if (e == hipSuccess) e = put_table(c, IcsWnTables(ics_img_tvm_tables(ws, Py, Px), K, Py, Px).psf, planar_psf(psf, K));
   if (e == hipSuccess && observed) {
     e = hipMemcpyAsync(ics_img_tvm_mask_slot(ws, K, Py, Px), observed, (size_t)H * W, hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);   // the host buffer may be released by the caller
@@ -594,12 +589,7 @@ extern "C" int ics_img_tv_deconvolve_masked(const ics_img* src, const float* psf
 // the raw kernel and the energies come back; the projection to a PSF is a few lines on K K 3 numbers and lives on the host
 // (lib/_native.py psf_project).
 extern "C" int ics_img_psf_estimate_plan(int H, int W, int K, int* Py, int* Px, size_t* workspace_bytes) {
-  int py = 0, px = 0;
-  RC(wiener_shape(H, W, K, &py, &px));
-  if (Py) *Py = py;
-  if (Px) *Px = px;
-  if (workspace_bytes) *workspace_bytes = ics_img_pe_workspace_bytes(H, W, K, py, px);
-  return ICS_OK;
+  return wiener_plan(H, W, K, Py, Px, workspace_bytes, [&](int py, int px) { return ics_img_pe_workspace_bytes(H, W, K, py, px); });
 }
 extern "C" int ics_img_psf_estimate(const ics_img* blurred, const ics_img* sharp, int y0, int y1, int x0, int x1, int K, float regularisation, int coupling, float* raw,
                                     double energy[3]) {

@@ -29,7 +29,6 @@
 
 namespace {
 
-#define PE_LANES 1024                          // lanes of a line's workgroup at most (N / 4 below 4096 points, 64 at least)
 #define PE_PLANES 6                            // derivative planes: plane 2 c + d, d = 0 along x, 1 along y
 
 __global__ __launch_bounds__(256) void k_img_pe_tables(float2* __restrict__ twy, float2* __restrict__ twx, float* __restrict__ wy, float* __restrict__ wx, int Py, int Px,
@@ -44,11 +43,11 @@ __global__ __launch_bounds__(256) void k_img_pe_tables(float2* __restrict__ twy,
 }
 
 // grid (6, Py): row blockIdx.y of plane blockIdx.x.  s, b: the first pixel of the window in the two frames, `pitch` floats a frame row
-__global__ __launch_bounds__(PE_LANES) void k_img_pe_rows(const float* __restrict__ s, const float* __restrict__ b, long pitch, int H, int W, int Py, int Px, int logPx,
+__global__ __launch_bounds__(WN_LANES) void k_img_pe_rows(const float* __restrict__ s, const float* __restrict__ b, long pitch, int H, int W, int Py, int Px, int logPx,
                                                           const float2* __restrict__ tw, const float* __restrict__ wy, const float* __restrict__ wx,
                                                           float2* __restrict__ Z, float* __restrict__ slot) {
   extern __shared__ __attribute__((aligned(16))) float2 sm[];
-  __shared__ float red[PE_LANES];
+  __shared__ float red[WN_LANES];
   const int p = blockIdx.x, y = blockIdx.y, tid = threadIdx.x, nthr = blockDim.x, c = p >> 1, d = p & 1;
   float2* o = Z + ((long)p * Py + y) * Px;
   if (y >= H) {                                  // (the whole workgroup)
@@ -76,19 +75,15 @@ __global__ __launch_bounds__(PE_LANES) void k_img_pe_rows(const float* __restric
     __syncthreads();
   }
   if (tid == 0) slot[(long)p * H + y] = red[0];
-  const float2* r = wn_fft<false>(sm, sm + Px, Px, logPx, tw);
-  for (int j = tid; j < Px; j += nthr) o[j] = r[j];
+  wn_store(o, wn_fft<false>(sm, sm + Px, Px, logPx, tw), Px);
 }
 
 // grid (Px, 6): the line Z[p][kx][:] forward, in place
-__global__ __launch_bounds__(PE_LANES) void k_img_pe_cols(float2* __restrict__ Z, int Py, int logPy, const float2* __restrict__ tw) {
+__global__ __launch_bounds__(WN_LANES) void k_img_pe_cols(float2* __restrict__ Z, int Py, int logPy, const float2* __restrict__ tw) {
   extern __shared__ __attribute__((aligned(16))) float2 sm[];
-  const int tid = threadIdx.x, nthr = blockDim.x;
   float2* l = Z + ((long)blockIdx.y * gridDim.x + blockIdx.x) * Py;
-  for (int j = tid; j < Py; j += nthr) sm[j] = l[j];
-  __syncthreads();
-  const float2* r = wn_fft<false>(sm, sm + Py, Py, logPy, tw);
-  for (int j = tid; j < Py; j += nthr) l[j] = r[j];
+  wn_load(sm, l, Py);
+  wn_store(l, wn_fft<false>(sm, sm + Py, Py, logPy, tw), Py);
 }
 
 // one workgroup: S of channel c = the slots of planes 2 c and 2 c + 1 (2 H floats in a row), summed in double in one fixed order
@@ -115,7 +110,7 @@ __global__ __launch_bounds__(256) void k_img_pe_energy(const float* __restrict__
 }
 
 // grid (Px, nq), nq = 3 (coupling 0: plane pair q) or 1 (coupling 1: all six): line kx of Q, inverse along y, the K rows around 0 -> R[q][i][kx]
-__global__ __launch_bounds__(PE_LANES) void k_img_pe_solve(const float2* __restrict__ Z, int Py, int Px, int logPy, const float2* __restrict__ tw, int K, int coupling,
+__global__ __launch_bounds__(WN_LANES) void k_img_pe_solve(const float2* __restrict__ Z, int Py, int Px, int logPy, const float2* __restrict__ tw, int K, int coupling,
                                                            float regularisation, float scale, const double* __restrict__ S, float2* __restrict__ R) {
   extern __shared__ __attribute__((aligned(16))) float2 sm[];
   const int kx = blockIdx.x, q = blockIdx.y, tid = threadIdx.x, nthr = blockDim.x;
@@ -141,13 +136,11 @@ __global__ __launch_bounds__(PE_LANES) void k_img_pe_solve(const float2* __restr
 }
 
 // grid (K, nq): row i of R[q] inverse along x, the real part of the K columns around 0 -> raw[i][j][q] (coupling 1: the three channels)
-__global__ __launch_bounds__(PE_LANES) void k_img_pe_crop(const float2* __restrict__ R, int Px, int logPx, const float2* __restrict__ tw, int K, int coupling,
+__global__ __launch_bounds__(WN_LANES) void k_img_pe_crop(const float2* __restrict__ R, int Px, int logPx, const float2* __restrict__ tw, int K, int coupling,
                                                           float* __restrict__ raw) {
   extern __shared__ __attribute__((aligned(16))) float2 sm[];
   const int i = blockIdx.x, q = blockIdx.y, tid = threadIdx.x, nthr = blockDim.x;
-  const float2* l = R + ((long)q * K + i) * Px;
-  for (int j = tid; j < Px; j += nthr) sm[j] = l[j];
-  __syncthreads();
+  wn_load(sm, R + ((long)q * K + i) * Px, Px);
   const float2* r = wn_fft<true>(sm, sm + Px, Px, logPx, tw);
   for (int j = tid; j < K; j += nthr) {
     const float v = r[(j - K / 2 + Px) & (Px - 1)].x;
@@ -156,9 +149,6 @@ __global__ __launch_bounds__(PE_LANES) void k_img_pe_crop(const float2* __restri
     else o[q] = v;
   }
 }
-
-int pe_log2(int v) { int k = 0; while ((1 << k) < v) ++k; return k; }
-int pe_lanes(int P) { const int t = P / 4; return t < 64 ? 64 : (t > PE_LANES ? PE_LANES : t); }
 
 // the workspace: Za, Zb (6 Py Px float2 each), R (3 K Px float2), the twiddles (Py + Px float2), S (4 doubles, one unused), then floats:
 // wy (H), wx (W), the slots (6 H), raw (3 K K)
@@ -191,32 +181,22 @@ double* ics_img_pe_energy(void* workspace, int H, int W, int K, int Py, int Px) 
 
 hipError_t ics_launch_img_psf_estimate(const float* sharp, const float* blurred, long pitch, int H, int W, int K, float regularisation, int coupling, int Py, int Px,
                                        void* workspace, hipStream_t s) {
-  if (!sharp || !blurred || !workspace || H < 1 || W < 1 || K < 3 || !(K & 1) || K > H || K > W || pitch < 3L * W) return hipErrorInvalidValue;
-  if (Py < H + K - 1 || Px < W + K - 1 || Py > ICS_IMG_WIENER_MAX || Px > ICS_IMG_WIENER_MAX || (Py & (Py - 1)) || (Px & (Px - 1))) return hipErrorInvalidValue;
+  if (!sharp || !blurred || !workspace || !wn_shape_ok(H, W, K, Py, Px) || pitch < 3L * W) return hipErrorInvalidValue;
   if (!(regularisation > 0.f) || (coupling != 0 && coupling != 1)) return hipErrorInvalidValue;
-  const int logPy = pe_log2(Py), logPx = pe_log2(Px), nq = coupling ? 1 : 3;
+  const int logPy = wn_log2(Py), logPx = wn_log2(Px), nq = coupling ? 1 : 3;
   const PeCarve m(workspace, H, W, K, Py, Px);
   const size_t ldsy = ics_img_wiener_lds(Py), ldsx = ics_img_wiener_lds(Px);
-  if (ldsy > 64 * 1024 || ldsx > 64 * 1024) {    // lines of 8192 points: 128 KB of dynamic LDS
-    static std::atomic<bool> cfg[4][ICS_MAX_DEVICES];
-    const int dev = ics_current_device();
-    const size_t top = ics_img_wiener_lds(ICS_IMG_WIENER_MAX);
-    hipError_t e = ics_configure_lds(cfg[0], dev, k_img_pe_rows, top);
-    if (e == hipSuccess) e = ics_configure_lds(cfg[1], dev, k_img_pe_cols, top);
-    if (e == hipSuccess) e = ics_configure_lds(cfg[2], dev, k_img_pe_solve, top);
-    if (e == hipSuccess) e = ics_configure_lds(cfg[3], dev, k_img_pe_crop, top);
-    if (e != hipSuccess) return e;
-  }
+  if (hipError_t e = wn_raise_lds<k_img_pe_rows, k_img_pe_cols, k_img_pe_solve, k_img_pe_crop>(Py, Px); e != hipSuccess) return e;
   const int P0 = Py > Px ? Py : Px;
   const size_t half = (size_t)3 * Py * Px;       // the transpose takes three planes a launch
   const float scale = 1.f / ((float)Py * (float)Px);
   hipLaunchKernelGGL(k_img_pe_tables, dim3((unsigned)((P0 + 255) / 256)), dim3(256), 0, s, m.twy, m.twx, m.wy, m.wx, Py, Px, logPy, logPx, H, W, K);
-  hipLaunchKernelGGL(k_img_pe_rows, dim3(PE_PLANES, (unsigned)Py), dim3(pe_lanes(Px)), ldsx, s, sharp, blurred, pitch, H, W, Py, Px, logPx, m.twx, m.wy, m.wx, m.Za, m.slot);
+  hipLaunchKernelGGL(k_img_pe_rows, dim3(PE_PLANES, (unsigned)Py), dim3(wn_lanes(Px)), ldsx, s, sharp, blurred, pitch, H, W, Py, Px, logPx, m.twx, m.wy, m.wx, m.Za, m.slot);
   ics_launch_img_wiener_transpose(m.Za, Py, Px, Px, m.Zb, s);
   ics_launch_img_wiener_transpose(m.Za + half, Py, Px, Px, m.Zb + half, s);
-  hipLaunchKernelGGL(k_img_pe_cols, dim3((unsigned)Px, PE_PLANES), dim3(pe_lanes(Py)), ldsy, s, m.Zb, Py, logPy, m.twy);
+  hipLaunchKernelGGL(k_img_pe_cols, dim3((unsigned)Px, PE_PLANES), dim3(wn_lanes(Py)), ldsy, s, m.Zb, Py, logPy, m.twy);
   hipLaunchKernelGGL(k_img_pe_energy, dim3(1), dim3(256), 0, s, m.slot, H, coupling, m.S);
-  hipLaunchKernelGGL(k_img_pe_solve, dim3((unsigned)Px, (unsigned)nq), dim3(pe_lanes(Py)), ldsy, s, m.Zb, Py, Px, logPy, m.twy, K, coupling, regularisation, scale, m.S, m.R);
-  hipLaunchKernelGGL(k_img_pe_crop, dim3((unsigned)K, (unsigned)nq), dim3(pe_lanes(Px)), ldsx, s, m.R, Px, logPx, m.twx, K, coupling, m.raw);
+  hipLaunchKernelGGL(k_img_pe_solve, dim3((unsigned)Px, (unsigned)nq), dim3(wn_lanes(Py)), ldsy, s, m.Zb, Py, Px, logPy, m.twy, K, coupling, regularisation, scale, m.S, m.R);
+  hipLaunchKernelGGL(k_img_pe_crop, dim3((unsigned)K, (unsigned)nq), dim3(wn_lanes(Px)), ldsx, s, m.R, Px, logPx, m.twx, K, coupling, m.raw);
   return hipGetLastError();
 }

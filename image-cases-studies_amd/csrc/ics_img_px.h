@@ -1,4 +1,4 @@
-// ics_img_px.h -- for ics_img_filters.hip, ics_img_tvdenoise.hip, ics_img_wavelet.hip, ics_img_guided.hip, ics_img_llf.hip, ics_img_noise.hip, ics_img_despeckle.hip, ics_img_blurwidth.hip, ics_img_mask.hip, ics_img_align.hip, ics_img_tvdeconv.hip (the launch by coupling) and ics_img_tvmdeconv.hip (that and the pixel load) only (everything here is local to
+// ics_img_px.h -- for ics_img_filters.hip, ics_img_tvdenoise.hip, ics_img_wavelet.hip, ics_img_guided.hip, ics_img_llf.hip, ics_img_noise.hip, ics_img_despeckle.hip, ics_img_blurwidth.hip, ics_img_mask.hip, ics_img_align.hip and ics_img_tvmdeconv.hip (the pixel load) only (everything here is local to
 // the unit that includes it): what their kernels and launchers share, the 12-byte pixel access, the luma, the symmetric fold, the B3-spline pass, two launch helpers.
 #pragma once
 #include "ics_kernels.h"

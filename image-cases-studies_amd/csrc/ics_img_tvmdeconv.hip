@@ -24,59 +24,45 @@
 // is 2 Px floats, u[c][y][:] its first Px and z[c][y][:] its second Px, so the row kernels work in place (a workgroup reads its row
 // into LDS before it writes it) and the frames swap roles every iteration.  b ping-pongs as in ics_img_tvdeconv.hip.
 //
-// Setup: the tables, k_img_tvm_setup (ext, M, 0 -> b, d, the row counts), k_img_tvm_count, k_img_tvm_psf_rows, k_img_tvm_psf_cols
+// The tables, the tiled transpose and the rows of the PSF are the Wiener unit's (ics_launch_img_wiener_*), the shrink pass the TV unit's
+// (ics_launch_img_tvd_shrink, in its form for the row halves of this unit).
+// Setup: the tables, k_img_tvm_setup (ext, M, 0 -> b, d, the row counts), k_img_tvm_count, the rows of the PSF, k_img_tvm_psf_cols
 // (Hc, Gc / (Py Px)), k_img_tvm_rows (ext -> A), a transpose, k_img_tvm_blur_cols (forward, Hc / (Py Px), inverse), a transpose,
 // k_img_tvm_inv_rows (ext -> u, real part -> r).
-// An iteration, u in X: k_img_tvm_shrink (u, b -> b', z), k_img_tvm_rows (r, d, M, ext, z -> d, X), a transpose (X -> Y),
+// An iteration, u in X: the shrink pass (u, b -> b', z), k_img_tvm_rows (r, d, M, ext, z -> d, X), a transpose (X -> Y),
 // k_img_tvm_cols (lines kx, Px - kx of Y -> line kx of X), a transpose (X -> Y; the last iteration the rows below H only),
 // k_img_tvm_inv_rows (Y -> u, r in place; the last iteration the first W points of the rows below H -> out).
+#include <utility>
 #include "ics_img_px.h"
 #include "ics_wn_fft.h"
 
 namespace {
 
-#define TVM_LANES 1024                         // lanes of a line's workgroup at most (N / 4 below 4096 points, 64 at least)
-#define TVM_PER 8                              // points of a line per lane at most (ICS_IMG_WIENER_MAX / TVM_LANES)
-#define TVM_TW 64                              // the shrink pass: pixels of a tile along x
-#define TVM_TH 16                              //                  and along y; 256 lanes, four pixels each
+#define TVM_PER 8                              // points of a line per lane at most
+static_assert(TVM_PER * WN_LANES == WN_MAX, "the column kernel holds a whole line in its lanes");
 
-__device__ __forceinline__ float tvm_finite(float v) { return isfinite(v) ? v : 0.f; }
-
-// grid (Py): row y of the extended frame -> ext[c][y][:] (the arithmetic of the Wiener unit's row kernel on f0), M[y][:], zeros ->
+// grid (Py): row y of the extended frame -> ext[c][y][:] (of f0), M[y][:], zeros ->
 // bx, by, d; the unobserved pixels of the row -> rowcount[y] (lane sums, then a tree in LDS: one order)
 __global__ __launch_bounds__(256) void k_img_tvm_setup(const float* __restrict__ f, const unsigned char* __restrict__ observed, float clip, int H, int W, int Py, int Px,
                                                        float* __restrict__ ext, float* __restrict__ bx, float* __restrict__ by, float* __restrict__ d, float* __restrict__ M,
                                                        int* __restrict__ rowcount) {
   __shared__ int cnt[256];
   const int y = blockIdx.x, tid = threadIdx.x;
-  const long pitch = 3L * W, plane = (long)Py * Px;
-  const bool below = y >= H;
-  const float* r0 = f + (long)(below ? H - 1 : y) * pitch;   // the row itself, or the last one
-  const float* r1 = f;                                       // the first one
-  const float ty = below ? (float)(y - H + 1) / (float)(Py - H + 1) : 0.f;
-  const auto px = [&](int x, int c) {
-    const float a = tvm_finite(r0[3L * x + c]);
-    return below ? (1.f - ty) * a + ty * tvm_finite(r1[3L * x + c]) : a;
-  };
-  const float gx = (float)(Px - W + 1);
-  float last[3], first[3];
-#pragma unroll
-  for (int c = 0; c < 3; ++c) { last[c] = px(W - 1, c); first[c] = px(0, c); }
+  const long plane = (long)Py * Px;
   int n = 0;
   for (int j = tid; j < Px; j += 256) {
-    const float t = (float)(j - W + 1) / gx;
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
       const long at = c * plane + (long)y * Px + j;
-      ext[at] = j < W ? px(j, c) : (1.f - t) * last[c] + t * first[c];
+      ext[at] = wn_ext<true>(f, c, y, j, H, W, Py, Px);
       bx[at] = 0.f;
       by[at] = 0.f;
       d[at] = 0.f;
     }
     bool m = false;
-    if (!below && j < W) {
+    if (y < H && j < W) {
       float v[3];
-      ld3(r0 + 3L * j, v);
+      ld3(f + ((long)y * W + j) * 3, v);
       m = isfinite(v[0]) && isfinite(v[1]) && isfinite(v[2]) && v[0] < clip && v[1] < clip && v[2] < clip && (!observed || observed[(long)y * W + j] != 0);
       n += m ? 0 : 1;
     }
@@ -106,38 +92,15 @@ __global__ __launch_bounds__(256) void k_img_tvm_count(const int* __restrict__ r
   if (tid == 0) total[0] = cnt[0];
 }
 
-// grid (K, 3): row r of channel c of the PSF (planar, [3][K][K]), zero padded to Px points, tap K / 2 at point 0 -> Hr[c][r][:]
-__global__ __launch_bounds__(TVM_LANES) void k_img_tvm_psf_rows(const float* __restrict__ psf, int K, int Px, int logPx, const float2* __restrict__ tw,
-                                                                float2* __restrict__ Hr) {
-  extern __shared__ __attribute__((aligned(16))) float2 sm[];
-  const int r = blockIdx.x, c = blockIdx.y, tid = threadIdx.x, nthr = blockDim.x;
-  const float* p = psf + ((long)c * K + r) * K;
-  for (int j = tid; j < Px; j += nthr) {
-    int t = j + K / 2;
-    if (t >= Px) t -= Px;
-    sm[j] = make_float2(t < K ? p[t] : 0.f, 0.f);
-  }
-  __syncthreads();
-  const float2* q = wn_fft<false>(sm, sm + Px, Px, logPx, tw);
-  float2* o = Hr + ((long)c * K + r) * Px;
-  for (int j = tid; j < Px; j += nthr) o[j] = q[j];
-}
-
 // grid (Px, 3): column kx of Hc -> Hc[c][kx][:], scale / (gamma |Hc|^2 + beta L) -> G[c][kx][:] (scale = 1 / (Py Px), a power of two:
 // exact.  The denominator is gamma at (0, 0), where L is 0 and Hc the channel's sum, and positive everywhere)
-__global__ __launch_bounds__(TVM_LANES) void k_img_tvm_psf_cols(const float2* __restrict__ Hr, int K, int Py, int Px, int logPy, const float2* __restrict__ tw,
+__global__ __launch_bounds__(WN_LANES) void k_img_tvm_psf_cols(const float2* __restrict__ Hr, int K, int Py, int Px, int logPy, const float2* __restrict__ tw,
                                                                 const float* __restrict__ lamy, const float* __restrict__ lamx, float gamma, float beta, float scale,
                                                                 float2* __restrict__ Hc, float* __restrict__ G) {
   extern __shared__ __attribute__((aligned(16))) float2 sm[];
   const int kx = blockIdx.x, c = blockIdx.y, tid = threadIdx.x, nthr = blockDim.x;
   const float2* h = Hr + (long)c * K * Px + kx;
-  for (int j = tid; j < Py; j += nthr) {
-    int t = j + K / 2;
-    if (t >= Py) t -= Py;
-    sm[j] = t < K ? h[(long)t * Px] : make_float2(0.f, 0.f);
-  }
-  __syncthreads();
-  const float2* q = wn_fft<false>(sm, sm + Py, Py, logPy, tw);
+  const float2* q = wn_psf_line(sm, Py, logPy, K, tw, [&](int t) { return h[(long)t * Px]; });
   const float lx = lamx[kx];
   const long line = ((long)c * Px + kx) * Py;
   for (int j = tid; j < Py; j += nthr) {
@@ -150,7 +113,7 @@ __global__ __launch_bounds__(TVM_LANES) void k_img_tvm_psf_cols(const float2* __
 
 // grid (3, Py): row y of channel c -> its transform X[c][y][:], in place over the row's u and z.  r == nullptr (the setup): the row of
 // ext alone.  Otherwise the v, d, q update of the row (d in place), q in the real and z in the imaginary part
-__global__ __launch_bounds__(TVM_LANES) void k_img_tvm_rows(float2* X, const float* __restrict__ ext, const float* __restrict__ r, float* __restrict__ d,
+__global__ __launch_bounds__(WN_LANES) void k_img_tvm_rows(float2* X, const float* __restrict__ ext, const float* __restrict__ r, float* __restrict__ d,
                                                             const float* __restrict__ M, float mu, float gamma, int Py, int Px, int logPx, const float2* __restrict__ tw) {
   extern __shared__ __attribute__((aligned(16))) float2 sm[];
   const int y = blockIdx.y, tid = threadIdx.x, nthr = blockDim.x;
@@ -170,32 +133,29 @@ __global__ __launch_bounds__(TVM_LANES) void k_img_tvm_rows(float2* X, const flo
     }
   }
   __syncthreads();
-  const float2* q = wn_fft<false>(sm, sm + Px, Px, logPx, tw);
-  for (int j = tid; j < Px; j += nthr) line[j] = q[j];
+  wn_store(line, wn_fft<false>(sm, sm + Px, Px, logPx, tw), Px);
 }
 
 // grid (Px, 3), the setup: the line B[c][kx][:] forward, times Hc (scale = 1 / (Py Px)), inverse, in place
-__global__ __launch_bounds__(TVM_LANES) void k_img_tvm_blur_cols(float2* __restrict__ B, const float2* __restrict__ Hc, float scale, int Py, int logPy,
+__global__ __launch_bounds__(WN_LANES) void k_img_tvm_blur_cols(float2* __restrict__ B, const float2* __restrict__ Hc, float scale, int Py, int logPy,
                                                                  const float2* __restrict__ tw) {
   extern __shared__ __attribute__((aligned(16))) float2 sm[];
   const int tid = threadIdx.x, nthr = blockDim.x;
   const long line = ((long)blockIdx.y * gridDim.x + blockIdx.x) * Py;
-  for (int j = tid; j < Py; j += nthr) sm[j] = B[line + j];
-  __syncthreads();
+  wn_load(sm, B + line, Py);
   float2* r = wn_fft<false>(sm, sm + Py, Py, logPy, tw);
   for (int j = tid; j < Py; j += nthr) {
     const float2 v = wn_mul(Hc[line + j], r[j]);
     r[j] = make_float2(__fmul_rn(v.x, scale), __fmul_rn(v.y, scale));
   }
   __syncthreads();
-  const float2* q = wn_fft<true>(r, r == sm ? sm + Py : sm, Py, logPy, tw);
-  for (int j = tid; j < Py; j += nthr) B[line + j] = q[j];
+  wn_store(B + line, wn_fft<true>(r, r == sm ? sm + Py : sm, Py, logPy, tw), Py);
 }
 
 // grid (Px, 3): lines kx and Px - kx of Y (the transposed row transforms of q + i z) -> the row spectra of q and of z at kx, both
 // forward (z waits in registers, then the transform of q does), U = (gamma conj(Hc) Q + beta Z) G, U + i Hc U inverse -> line kx of X.
 // A lane holds points tid + i blockDim.x, i < TVM_PER
-__global__ __launch_bounds__(TVM_LANES) void k_img_tvm_cols(const float2* __restrict__ Y, float2* __restrict__ X, const float2* __restrict__ Hc, const float* __restrict__ G,
+__global__ __launch_bounds__(WN_LANES) void k_img_tvm_cols(const float2* __restrict__ Y, float2* __restrict__ X, const float2* __restrict__ Hc, const float* __restrict__ G,
                                                             float gamma, float beta, int Py, int logPy, const float2* __restrict__ tw) {
   extern __shared__ __attribute__((aligned(16))) float2 sm[];
   const int kx = blockIdx.x, Px = gridDim.x, tid = threadIdx.x, nthr = blockDim.x;
@@ -251,13 +211,12 @@ __global__ __launch_bounds__(TVM_LANES) void k_img_tvm_cols(const float2* __rest
 // grid (3, rows): Y[c][y][:] inverse; the real part of the first n points -> dst[c * chan + y * pitch + j * step] (u in place: dst the
 // frame itself, chan 2 Py Px, pitch 2 Px, step 1, n Px on all Py rows; the result image: chan 1, pitch 3 W, step 3, n W on the rows
 // below H).  r given: the imaginary part -> r[c][y][:]; uinit given too (the setup): the row of uinit -> dst, the real part -> r
-__global__ __launch_bounds__(TVM_LANES) void k_img_tvm_inv_rows(const float2* Y, int Py, int Px, int logPx, const float2* __restrict__ tw, float* dst, long chan, long pitch,
+__global__ __launch_bounds__(WN_LANES) void k_img_tvm_inv_rows(const float2* Y, int Py, int Px, int logPx, const float2* __restrict__ tw, float* dst, long chan, long pitch,
                                                                 int step, int n, const float* __restrict__ uinit, float* __restrict__ r) {
   extern __shared__ __attribute__((aligned(16))) float2 sm[];
   const int c = blockIdx.x, y = blockIdx.y, tid = threadIdx.x, nthr = blockDim.x;
   const long row = ((long)c * Py + y) * Px;
-  for (int j = tid; j < Px; j += nthr) sm[j] = Y[row + j];
-  __syncthreads();
+  wn_load(sm, Y + row, Px);
   const float2* q = wn_fft<true>(sm, sm + Px, Px, logPx, tw);
   float* o = dst + c * chan + y * pitch;
   for (int j = tid; j < n; j += nthr) {
@@ -267,77 +226,24 @@ __global__ __launch_bounds__(TVM_LANES) void k_img_tvm_inv_rows(const float2* Y,
   }
 }
 
-// grid (ceil(Px / TVM_TW), ceil(Py / TVM_TH)): the shrinkage of one tile and its z, the pass of ics_img_tvdeconv.hip on the planes of
-// this unit: u[c][y][x] at uz[(c Py + y) 2 Px + x], z[c][y][x] Px floats further.  bx0, by0 -> bx1, by1
-template <bool VEC>
-__global__ __launch_bounds__(256) void k_img_tvm_shrink(float* uz, const float* __restrict__ bx0, const float* __restrict__ by0, float* __restrict__ bx1,
-                                                        float* __restrict__ by1, int Py, int Px, float thr) {
-  constexpr int UW = TVM_TW + 2, UH = TVM_TH + 2, PW = TVM_TW + 1, PH = TVM_TH + 1;
-  __shared__ float su[3][UH][UW];              // u at (y0 - 1 + r, x0 - 1 + q)
-  __shared__ float sp[2][3][PH][PW];           // px, py at (y0 - 1 + r, x0 - 1 + q)
-  const int x0 = blockIdx.x * TVM_TW, y0 = blockIdx.y * TVM_TH, tid = threadIdx.x;
-  const long plane = (long)Py * Px;
-  for (int i = tid; i < 3 * UH * UW; i += 256) {
-    const int c = i / (UH * UW), k = i - c * (UH * UW), r = k / UW, q = k - r * UW;
-    su[c][r][q] = uz[((long)c * Py + ((y0 - 1 + r) & (Py - 1))) * 2 * Px + ((x0 - 1 + q) & (Px - 1))];
-  }
-  __syncthreads();
-  for (int i = tid; i < PH * PW; i += 256) {
-    const int r = i / PW, q = i - r * PW;
-    const int y = y0 - 1 + r, x = x0 - 1 + q;
-    const long at = (long)(y & (Py - 1)) * Px + (x & (Px - 1));
-    const bool own = r > 0 && q > 0 && y < Py && x < Px;
-    float vx[3], vy[3], mm[3];
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      const float here = su[c][r][q];
-      vx[c] = __fadd_rn(__fsub_rn(su[c][r][q + 1], here), bx0[c * plane + at]);
-      vy[c] = __fadd_rn(__fsub_rn(su[c][r + 1][q], here), by0[c * plane + at]);
-      mm[c] = __fadd_rn(__fmul_rn(vx[c], vx[c]), __fmul_rn(vy[c], vy[c]));
-    }
-    if (VEC) mm[0] = mm[1] = mm[2] = __fadd_rn(__fadd_rn(mm[0], mm[1]), mm[2]);
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      const float m = __fsqrt_rn(mm[c]);
-      const float s = m > thr ? __fdiv_rn(__fsub_rn(m, thr), m) : 0.f;
-      const float wx = __fmul_rn(s, vx[c]), wy = __fmul_rn(s, vy[c]);
-      const float bx = __fsub_rn(vx[c], wx), by = __fsub_rn(vy[c], wy);
-      sp[0][c][r][q] = __fsub_rn(wx, bx);
-      sp[1][c][r][q] = __fsub_rn(wy, by);
-      if (own) { bx1[c * plane + at] = bx; by1[c * plane + at] = by; }
-    }
-  }
-  __syncthreads();
-  for (int i = tid; i < 3 * TVM_TH * TVM_TW; i += 256) {
-    const int c = i / (TVM_TH * TVM_TW), k = i - c * (TVM_TH * TVM_TW), r = k / TVM_TW + 1, q = (k & (TVM_TW - 1)) + 1;
-    const int y = y0 - 1 + r, x = x0 - 1 + q;
-    if (y < Py && x < Px)
-      uz[((long)c * Py + y) * 2 * Px + Px + x] = __fadd_rn(__fsub_rn(sp[0][c][r][q - 1], sp[0][c][r][q]), __fsub_rn(sp[1][c][r - 1][q], sp[1][c][r][q]));
-  }
-}
-
-int tvm_log2(int v) { int k = 0; while ((1 << k) < v) ++k; return k; }
-int tvm_lanes(int P) { const int t = P / 4; return t < 64 ? 64 : (t > TVM_LANES ? TVM_LANES : t); }
-
 }  // namespace
 
 // the one block of a call, in floats of a transform plane (Py Px): A, B, Hc (6 each), G, bx0, by0, bx1, by1, d, ext, r (3 each), M (1)
 // = 43; then Py row counts and the total (4 words), the tables, and Py Px bytes for the caller's mask (H W of them used)
 size_t ics_img_tvm_workspace_bytes(int K, int Py, int Px) {
-  return ((size_t)43 * Py * Px + Py + 4) * sizeof(float) + ics_img_wiener_table_bytes(K, Py, Px) + (size_t)Py * Px;
+  return ((size_t)43 * Py * Px + Py + 4) * sizeof(float) + IcsWnTables(nullptr, K, Py, Px).bytes + (size_t)Py * Px;
 }
 void* ics_img_tvm_tables(void* workspace, int Py, int Px) { return reinterpret_cast<float*>(workspace) + (size_t)43 * Py * Px + Py + 4; }
 long long* ics_img_tvm_total(void* workspace, int Py, int Px) { return reinterpret_cast<long long*>(reinterpret_cast<float*>(workspace) + (size_t)43 * Py * Px + Py); }
 unsigned char* ics_img_tvm_mask_slot(void* workspace, int K, int Py, int Px) {
-  return reinterpret_cast<unsigned char*>(ics_img_tvm_tables(workspace, Py, Px)) + ics_img_wiener_table_bytes(K, Py, Px);
+  return reinterpret_cast<unsigned char*>(ics_img_tvm_tables(workspace, Py, Px)) + IcsWnTables(nullptr, K, Py, Px).bytes;
 }
 
 hipError_t ics_launch_img_tv_deconvolve_masked(const float* f, int H, int W, int K, bool observed, float clip, float mu, float beta, float gamma, int iterations, int coupling,
                                                int Py, int Px, void* workspace, float* out, hipStream_t s) {
-  if (!f || !workspace || !out || H < 1 || W < 1 || K < 3 || !(K & 1) || K > H || K > W || iterations < 1) return hipErrorInvalidValue;
-  if (Py < H + K - 1 || Px < W + K - 1 || Py > ICS_IMG_WIENER_MAX || Px > ICS_IMG_WIENER_MAX || (Py & (Py - 1)) || (Px & (Px - 1))) return hipErrorInvalidValue;
-  if (Py > TVM_PER * tvm_lanes(Py)) return hipErrorInvalidValue;
-  const int logPy = tvm_log2(Py), logPx = tvm_log2(Px);
+  if (!f || !workspace || !out || !wn_shape_ok(H, W, K, Py, Px) || iterations < 1) return hipErrorInvalidValue;
+  if (Py > TVM_PER * wn_lanes(Py)) return hipErrorInvalidValue;
+  const int logPy = wn_log2(Py), logPx = wn_log2(Px);
   const size_t plane3 = (size_t)3 * Py * Px;                  // floats of three real planes; a spectrum frame is two of them
   float* w = reinterpret_cast<float*>(workspace);
   float2 *X = reinterpret_cast<float2*>(w), *Y = reinterpret_cast<float2*>(w + 2 * plane3), *Hc = reinterpret_cast<float2*>(w + 4 * plane3);
@@ -345,53 +251,37 @@ hipError_t ics_launch_img_tv_deconvolve_masked(const float* f, int H, int W, int
   float *bx[2] = {w + 7 * plane3, w + 9 * plane3}, *by[2] = {w + 8 * plane3, w + 10 * plane3};
   float *d = w + 11 * plane3, *ext = w + 12 * plane3, *r = w + 13 * plane3, *M = w + 14 * plane3;
   int* rowcount = reinterpret_cast<int*>(M + (size_t)Py * Px);
-  float2* Hr = reinterpret_cast<float2*>(ics_img_tvm_tables(workspace, Py, Px));
-  float2* twy = Hr + (size_t)3 * K * Px;
-  float2* twx = twy + Py;
-  float* lamy = reinterpret_cast<float*>(twx + Px);
-  float* lamx = lamy + Py;
-  const float* psf = lamx + Px;                  // (== ics_img_wiener_psf_slot of the tables: uploaded by the caller)
+  const IcsWnTables t(ics_img_tvm_tables(workspace, Py, Px), K, Py, Px);   // (t.psf: uploaded by the caller)
   const unsigned char* mask = observed ? ics_img_tvm_mask_slot(workspace, K, Py, Px) : nullptr;   // (uploaded by the caller too)
   const size_t ldsy = ics_img_wiener_lds(Py), ldsx = ics_img_wiener_lds(Px);
-  if (ldsy > 64 * 1024 || ldsx > 64 * 1024) {    // lines of 8192 points: 128 KB of dynamic LDS
-    static std::atomic<bool> cfg[6][ICS_MAX_DEVICES];
-    const int dev = ics_current_device();
-    const size_t top = ics_img_wiener_lds(ICS_IMG_WIENER_MAX);
-    hipError_t e = ics_configure_lds(cfg[0], dev, k_img_tvm_rows, top);
-    if (e == hipSuccess) e = ics_configure_lds(cfg[1], dev, k_img_tvm_psf_rows, top);
-    if (e == hipSuccess) e = ics_configure_lds(cfg[2], dev, k_img_tvm_psf_cols, top);
-    if (e == hipSuccess) e = ics_configure_lds(cfg[3], dev, k_img_tvm_blur_cols, top);
-    if (e == hipSuccess) e = ics_configure_lds(cfg[4], dev, k_img_tvm_cols, top);
-    if (e == hipSuccess) e = ics_configure_lds(cfg[5], dev, k_img_tvm_inv_rows, top);
-    if (e != hipSuccess) return e;
-  }
+  hipError_t e = wn_raise_lds<k_img_tvm_rows, k_img_tvm_psf_cols, k_img_tvm_blur_cols, k_img_tvm_cols, k_img_tvm_inv_rows>(Py, Px);
+  if (e != hipSuccess) return e;
   const float scale = 1.f / ((float)Py * (float)Px), thr = 1.f / beta;
-  const dim3 rows(3, (unsigned)Py), cols((unsigned)Px, 3), shrink((unsigned)((Px + TVM_TW - 1) / TVM_TW), (unsigned)((Py + TVM_TH - 1) / TVM_TH));
-  const dim3 lx((unsigned)tvm_lanes(Px)), ly((unsigned)tvm_lanes(Py));
+  const dim3 rows(3, (unsigned)Py), cols((unsigned)Px, 3), lx((unsigned)wn_lanes(Px)), ly((unsigned)wn_lanes(Py));
   const long uchan = 2L * Py * Px, upitch = 2L * Px;         // u inside a spectrum frame
-  ics_launch_img_wiener_tables(twy, twx, lamy, lamx, Py, Px, s);
+  ics_launch_img_wiener_tables(t.twy, t.twx, t.lamy, t.lamx, Py, Px, s);
   hipLaunchKernelGGL(k_img_tvm_setup, dim3((unsigned)Py), dim3(256), 0, s, f, mask, clip, H, W, Py, Px, ext, bx[0], by[0], d, M, rowcount);
   hipLaunchKernelGGL(k_img_tvm_count, dim3(1), dim3(256), 0, s, rowcount, H, ics_img_tvm_total(workspace, Py, Px));
-  hipLaunchKernelGGL(k_img_tvm_psf_rows, dim3((unsigned)K, 3), lx, ldsx, s, psf, K, Px, logPx, twx, Hr);
-  hipLaunchKernelGGL(k_img_tvm_psf_cols, cols, ly, ldsy, s, Hr, K, Py, Px, logPy, twy, lamy, lamx, gamma, beta, scale, Hc, G);
-  hipLaunchKernelGGL(k_img_tvm_rows, rows, lx, ldsx, s, X, ext, (const float*)nullptr, (float*)nullptr, (const float*)nullptr, mu, gamma, Py, Px, logPx, twx);
+  if ((e = ics_launch_img_wiener_psf_rows(t.psf, K, Px, t.twx, t.Hr, s)) != hipSuccess) return e;
+  hipLaunchKernelGGL(k_img_tvm_psf_cols, cols, ly, ldsy, s, t.Hr, K, Py, Px, logPy, t.twy, t.lamy, t.lamx, gamma, beta, scale, Hc, G);
+  hipLaunchKernelGGL(k_img_tvm_rows, rows, lx, ldsx, s, X, ext, (const float*)nullptr, (float*)nullptr, (const float*)nullptr, mu, gamma, Py, Px, logPx, t.twx);
   ics_launch_img_wiener_transpose(X, Py, Px, Px, Y, s);
-  hipLaunchKernelGGL(k_img_tvm_blur_cols, cols, ly, ldsy, s, Y, Hc, scale, Py, logPy, twy);
+  hipLaunchKernelGGL(k_img_tvm_blur_cols, cols, ly, ldsy, s, Y, Hc, scale, Py, logPy, t.twy);
   ics_launch_img_wiener_transpose(Y, Px, Py, Py, X, s);
-  hipLaunchKernelGGL(k_img_tvm_inv_rows, rows, lx, ldsx, s, X, Py, Px, logPx, twx, reinterpret_cast<float*>(X), uchan, upitch, 1, Px, ext, r);
+  hipLaunchKernelGGL(k_img_tvm_inv_rows, rows, lx, ldsx, s, X, Py, Px, logPx, t.twx, reinterpret_cast<float*>(X), uchan, upitch, 1, Px, ext, r);
   for (int it = 0; it < iterations; ++it) {
     const int from = it & 1, to = from ^ 1;
     const bool last = it == iterations - 1;
-    ICS_LAUNCH_VEC(coupling, k_img_tvm_shrink, shrink, dim3(256), 0, s, reinterpret_cast<float*>(X), bx[from], by[from], bx[to], by[to], Py, Px, thr);
-    hipLaunchKernelGGL(k_img_tvm_rows, rows, lx, ldsx, s, X, ext, r, d, M, mu, gamma, Py, Px, logPx, twx);
+    ics_launch_img_tvd_shrink(coupling, true, reinterpret_cast<float*>(X), reinterpret_cast<float*>(X) + Px, bx[from], by[from], bx[to], by[to], Py, Px, thr, s);
+    hipLaunchKernelGGL(k_img_tvm_rows, rows, lx, ldsx, s, X, ext, r, d, M, mu, gamma, Py, Px, logPx, t.twx);
     ics_launch_img_wiener_transpose(X, Py, Px, Px, Y, s);
-    hipLaunchKernelGGL(k_img_tvm_cols, cols, ly, ldsy, s, Y, X, Hc, G, gamma, beta, Py, logPy, twy);
+    hipLaunchKernelGGL(k_img_tvm_cols, cols, ly, ldsy, s, Y, X, Hc, G, gamma, beta, Py, logPy, t.twy);
     ics_launch_img_wiener_transpose(X, Px, Py, last ? H : Py, Y, s);
     if (last)
-      hipLaunchKernelGGL(k_img_tvm_inv_rows, dim3(3, (unsigned)H), lx, ldsx, s, Y, Py, Px, logPx, twx, out, 1L, 3L * W, 3, W, (const float*)nullptr, (float*)nullptr);
+      hipLaunchKernelGGL(k_img_tvm_inv_rows, dim3(3, (unsigned)H), lx, ldsx, s, Y, Py, Px, logPx, t.twx, out, 1L, 3L * W, 3, W, (const float*)nullptr, (float*)nullptr);
     else
-      hipLaunchKernelGGL(k_img_tvm_inv_rows, rows, lx, ldsx, s, Y, Py, Px, logPx, twx, reinterpret_cast<float*>(Y), uchan, upitch, 1, Px, (const float*)nullptr, r);
-    float2* t = X; X = Y; Y = t;                 // u is in the frame the inverse rows ran on
+      hipLaunchKernelGGL(k_img_tvm_inv_rows, rows, lx, ldsx, s, Y, Py, Px, logPx, t.twx, reinterpret_cast<float*>(Y), uchan, upitch, 1, Px, (const float*)nullptr, r);
+    std::swap(X, Y);                             // u is in the frame the inverse rows ran on
   }
   return hipGetLastError();
 }

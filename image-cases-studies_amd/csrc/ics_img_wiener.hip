@@ -9,7 +9,7 @@
 //   L(ky,kx) = 4 sin^2(pi ky / Py) + 4 sin^2(pi kx / Px)  (= 4 - 2 cos(2 pi ky / Py) - 2 cos(2 pi kx / Px), the Laplacian's transfer)
 //   G        = conj(Hc) / (|Hc|^2 + balance L^2);  out_c = real(inverse transform(G * transform(ext_c)))[:H, :W], nothing clipped
 //
-// The line transform (wn_fft, ics_wn_fft.h, shared with ics_img_tvdeconv.hip): a Stockham autosort transform of one line of N = 2^n points in LDS, radix 4 with one leading radix-2
+// The line transform (wn_fft, ics_wn_fft.h): a Stockham autosort transform of one line of N = 2^n points in LDS, radix 4 with one leading radix-2
 // stage where n is odd, N / 4 butterflies a stage over the workgroup's lanes, the line ping-ponging between two buffers of N float2.
 // Stage reads are four runs of consecutive float2 (conflict free), its writes go out at a stride of p float2.  A lane takes two
 // butterflies of a stage at a time, all their loads before the arithmetic.  Twiddles come from one table per axis, laid out by stage:
@@ -31,12 +31,11 @@
 //   k_img_wn_cols      : the line B[c][kx][:] forward, times G, inverse, the line staying in LDS in between; written back in place
 //   k_img_wn_transpose : B[c][kx][y < H] -> A[c][y][kx]
 //   k_img_wn_inv_rows  : rows y < H inverse, the real part of the first W points -> out
+// The tables, the transpose, the PSF rows and the inverse rows serve the other units on this transform too (ics_launch_img_wiener_*).
 #include "ics_wn_fft.h"
 
 namespace {
 
-#define WN_MAX ICS_IMG_WIENER_MAX              // longest line: two buffers of it are 128 KB of the 160 KB of LDS
-#define WN_LANES 1024                          // lanes of a line's workgroup at most (N / 4 below 4096 points, 64 at least)
 #define WN_TILE 32                             // the transposes' tile side
 
 __global__ __launch_bounds__(256) void k_img_wn_tables(float2* __restrict__ twy, float2* __restrict__ twx, float* __restrict__ lamy, float* __restrict__ lamx, int Py, int Px,
@@ -55,23 +54,9 @@ __global__ __launch_bounds__(WN_LANES) void k_img_wn_rows(const float* __restric
                                                           float2* __restrict__ A) {
   extern __shared__ __attribute__((aligned(16))) float2 sm[];
   const int c = blockIdx.x, y = blockIdx.y, tid = threadIdx.x, nthr = blockDim.x;
-  const long pitch = 3L * W;
-  const bool ext = y >= H;
-  const float* r0 = f + (long)(ext ? H - 1 : y) * pitch + c;   // the row itself, or the last one
-  const float* r1 = f + c;                                     // the first one
-  const float ty = ext ? (float)(y - H + 1) / (float)(Py - H + 1) : 0.f;
-  const auto px = [&](int x) { return ext ? (1.f - ty) * r0[3L * x] + ty * r1[3L * x] : r0[3L * x]; };
-  const float last = px(W - 1), first = px(0), gx = (float)(Px - W + 1);
-  for (int j = tid; j < Px; j += nthr) {
-    float v;
-    if (j < W) v = px(j);
-    else { const float t = (float)(j - W + 1) / gx; v = (1.f - t) * last + t * first; }
-    sm[j] = make_float2(v, 0.f);
-  }
+  for (int j = tid; j < Px; j += nthr) sm[j] = make_float2(wn_ext<false>(f, c, y, j, H, W, Py, Px), 0.f);
   __syncthreads();
-  const float2* r = wn_fft<false>(sm, sm + Px, Px, logPx, tw);
-  float2* o = A + ((long)c * Py + y) * Px;
-  for (int j = tid; j < Px; j += nthr) o[j] = r[j];
+  wn_store(A + ((long)c * Py + y) * Px, wn_fft<false>(sm, sm + Px, Px, logPx, tw), Px);
 }
 
 // grid (ceil(clim / 32), ceil(R / 32), 3): in[plane][R][C] -> out[plane][C][R] for the columns below clim
@@ -96,17 +81,9 @@ __global__ __launch_bounds__(256) void k_img_wn_transpose(const float2* __restri
 __global__ __launch_bounds__(WN_LANES) void k_img_wn_psf_rows(const float* __restrict__ psf, int K, int Px, int logPx, const float2* __restrict__ tw,
                                                               float2* __restrict__ Hr) {
   extern __shared__ __attribute__((aligned(16))) float2 sm[];
-  const int r = blockIdx.x, c = blockIdx.y, tid = threadIdx.x, nthr = blockDim.x;
-  const float* p = psf + ((long)c * K + r) * K;
-  for (int j = tid; j < Px; j += nthr) {
-    int t = j + K / 2;
-    if (t >= Px) t -= Px;
-    sm[j] = make_float2(t < K ? p[t] : 0.f, 0.f);
-  }
-  __syncthreads();
-  const float2* q = wn_fft<false>(sm, sm + Px, Px, logPx, tw);
-  float2* o = Hr + ((long)c * K + r) * Px;
-  for (int j = tid; j < Px; j += nthr) o[j] = q[j];
+  const long row = (long)blockIdx.y * K + blockIdx.x;
+  const float* p = psf + row * K;
+  wn_store(Hr + row * Px, wn_psf_line(sm, Px, logPx, K, tw, [&](int t) { return make_float2(p[t], 0.f); }), Px);
 }
 
 // grid (Px, 3): column kx of Hc, then G scaled by `scale` = 1 / (Py Px) (a power of two: exact) -> G[c][kx][:]
@@ -116,13 +93,7 @@ __global__ __launch_bounds__(WN_LANES) void k_img_wn_psf_cols(const float2* __re
   extern __shared__ __attribute__((aligned(16))) float2 sm[];
   const int kx = blockIdx.x, c = blockIdx.y, tid = threadIdx.x, nthr = blockDim.x;
   const float2* h = Hr + (long)c * K * Px + kx;
-  for (int j = tid; j < Py; j += nthr) {
-    int t = j + K / 2;
-    if (t >= Py) t -= Py;
-    sm[j] = t < K ? h[(long)t * Px] : make_float2(0.f, 0.f);
-  }
-  __syncthreads();
-  const float2* q = wn_fft<false>(sm, sm + Py, Py, logPy, tw);
+  const float2* q = wn_psf_line(sm, Py, logPy, K, tw, [&](int t) { return h[(long)t * Px]; });
   const float lx = lamx[kx];
   float2* o = G + ((long)c * Px + kx) * Py;
   for (int j = tid; j < Py; j += nthr) {
@@ -140,30 +111,24 @@ __global__ __launch_bounds__(WN_LANES) void k_img_wn_cols(float2* __restrict__ B
   const long line = ((long)blockIdx.y * gridDim.x + blockIdx.x) * Py;
   float2* l = B + line;
   const float2* g = G + line;
-  for (int j = tid; j < Py; j += nthr) sm[j] = l[j];
-  __syncthreads();
+  wn_load(sm, l, Py);
   float2* r = wn_fft<false>(sm, sm + Py, Py, logPy, tw);
   for (int j = tid; j < Py; j += nthr) r[j] = wn_mul(r[j], g[j]);
   __syncthreads();
-  const float2* q = wn_fft<true>(r, r == sm ? sm + Py : sm, Py, logPy, tw);
-  for (int j = tid; j < Py; j += nthr) l[j] = q[j];
+  wn_store(l, wn_fft<true>(r, r == sm ? sm + Py : sm, Py, logPy, tw), Py);
 }
 
-// grid (3, H): A[c][y][:] inverse, the real part of the first W points -> out[y][:][c]
-__global__ __launch_bounds__(WN_LANES) void k_img_wn_inv_rows(const float2* __restrict__ A, int W, int Py, int Px, int logPx, const float2* __restrict__ tw,
-                                                              float* __restrict__ out) {
+// grid (3, rows): A[c][y][:] inverse, the real part of the first n points -> dst[c * chan + y * pitch + j * step] (an HWC image: chan 1,
+// pitch 3 W, step 3, n W on the rows below H; planes [3][Py][Px]: chan Py Px, pitch Px, step 1, n Px on all Py rows)
+__global__ __launch_bounds__(WN_LANES) void k_img_wn_inv_rows(const float2* __restrict__ A, int Py, int Px, int logPx, const float2* __restrict__ tw, float* __restrict__ dst,
+                                                              long chan, long pitch, int step, int n) {
   extern __shared__ __attribute__((aligned(16))) float2 sm[];
   const int c = blockIdx.x, y = blockIdx.y, tid = threadIdx.x, nthr = blockDim.x;
-  const float2* l = A + ((long)c * Py + y) * Px;
-  for (int j = tid; j < Px; j += nthr) sm[j] = l[j];
-  __syncthreads();
+  wn_load(sm, A + ((long)c * Py + y) * Px, Px);
   const float2* q = wn_fft<true>(sm, sm + Px, Px, logPx, tw);
-  float* o = out + (long)y * 3 * W + c;
-  for (int j = tid; j < W; j += nthr) o[3L * j] = q[j].x;
+  float* o = dst + c * chan + y * pitch;
+  for (int j = tid; j < n; j += nthr) o[(long)j * step] = q[j].x;
 }
-
-int wn_log2(int v) { int k = 0; while ((1 << k) < v) ++k; return k; }
-int wn_lanes(int P) { const int t = P / 4; return t < 64 ? 64 : (t > WN_LANES ? WN_LANES : t); }
 
 }  // namespace
 
@@ -174,17 +139,10 @@ int ics_img_wiener_sizes(int H, int W, int K, int* Py, int* Px) {
   return 1;
 }
 size_t ics_img_wiener_frame_bytes(int Py, int Px) { return (size_t)3 * Py * Px * sizeof(float2); }
-// the small block: Hr (3 K Px float2), the twiddles of the two axes (Py and Px float2, a few unused), 4 sin^2 along y and x, the planar PSF
-size_t ics_img_wiener_table_bytes(int K, int Py, int Px) {
-  return ((size_t)3 * K * Px + Py + Px) * sizeof(float2) + ((size_t)Py + Px + (size_t)3 * K * K) * sizeof(float);
-}
-float* ics_img_wiener_psf_slot(void* tables, int K, int Py, int Px) {
-  return reinterpret_cast<float*>(reinterpret_cast<float2*>(tables) + (size_t)3 * K * Px + Py + Px) + Py + Px;
-}
 size_t ics_img_wiener_lds(int P) { return (size_t)2 * P * sizeof(float2); }
 
-// the two passes ics_img_tvdeconv.hip shares with this unit: the tables of the two axes, and in[plane][R][C] -> out[plane][C][R] for the
-// columns below clim on three planes
+// the passes the other units on this transform share with this one: the tables of the two axes; in[plane][R][C] -> out[plane][C][R] for
+// the columns below clim on three planes; the rows of the PSF; the inverse rows
 void ics_launch_img_wiener_tables(float2* twy, float2* twx, float* lamy, float* lamx, int Py, int Px, hipStream_t s) {
   const int P0 = Py > Px ? Py : Px;
   hipLaunchKernelGGL(k_img_wn_tables, dim3((unsigned)((P0 + 255) / 256)), dim3(256), 0, s, twy, twx, lamy, lamx, Py, Px, wn_log2(Py), wn_log2(Px));
@@ -192,37 +150,32 @@ void ics_launch_img_wiener_tables(float2* twy, float2* twx, float* lamy, float* 
 void ics_launch_img_wiener_transpose(const float2* in, int R, int C, int clim, float2* out, hipStream_t s) {
   hipLaunchKernelGGL(k_img_wn_transpose, dim3((unsigned)((clim + WN_TILE - 1) / WN_TILE), (unsigned)((R + WN_TILE - 1) / WN_TILE), 3), dim3(256), 0, s, in, R, C, clim, out);
 }
+hipError_t ics_launch_img_wiener_psf_rows(const float* psf, int K, int Px, const float2* twx, float2* Hr, hipStream_t s) {
+  if (hipError_t e = wn_raise_lds<k_img_wn_psf_rows>(Px, Px); e != hipSuccess) return e;
+  hipLaunchKernelGGL(k_img_wn_psf_rows, dim3((unsigned)K, 3), dim3(wn_lanes(Px)), ics_img_wiener_lds(Px), s, psf, K, Px, wn_log2(Px), twx, Hr);
+  return hipSuccess;
+}
+hipError_t ics_launch_img_wiener_inv_rows(const float2* A, int rows, int Py, int Px, const float2* twx, float* dst, long chan, long pitch, int step, int n, hipStream_t s) {
+  if (hipError_t e = wn_raise_lds<k_img_wn_inv_rows>(Px, Px); e != hipSuccess) return e;
+  hipLaunchKernelGGL(k_img_wn_inv_rows, dim3(3, (unsigned)rows), dim3(wn_lanes(Px)), ics_img_wiener_lds(Px), s, A, Py, Px, wn_log2(Px), twx, dst, chan, pitch, step, n);
+  return hipSuccess;
+}
 
 hipError_t ics_launch_img_wiener(const float* f, int H, int W, int K, float balance, int Py, int Px, float2* A, float2* B, void* tables, float* out, hipStream_t s) {
-  if (!f || !A || !B || !tables || !out || H < 1 || W < 1 || K < 3 || !(K & 1) || K > H || K > W) return hipErrorInvalidValue;
-  if (Py < H + K - 1 || Px < W + K - 1 || Py > WN_MAX || Px > WN_MAX || (Py & (Py - 1)) || (Px & (Px - 1))) return hipErrorInvalidValue;
+  if (!f || !A || !B || !tables || !out || !wn_shape_ok(H, W, K, Py, Px)) return hipErrorInvalidValue;
   const int logPy = wn_log2(Py), logPx = wn_log2(Px);
-  float2* Hr = reinterpret_cast<float2*>(tables);
-  float2* twy = Hr + (size_t)3 * K * Px;
-  float2* twx = twy + Py;
-  float* lamy = reinterpret_cast<float*>(twx + Px);
-  float* lamx = lamy + Py;
-  const float* psf = lamx + Px;                  // (== ics_img_wiener_psf_slot: uploaded by the caller)
+  const IcsWnTables t(tables, K, Py, Px);        // (t.psf: uploaded by the caller)
   const size_t ldsy = ics_img_wiener_lds(Py), ldsx = ics_img_wiener_lds(Px);
-  if (ldsy > 64 * 1024 || ldsx > 64 * 1024) {    // lines of 8192 points: 128 KB of dynamic LDS
-    static std::atomic<bool> cfg[5][ICS_MAX_DEVICES];
-    const int dev = ics_current_device();
-    const size_t top = ics_img_wiener_lds(WN_MAX);
-    hipError_t e = ics_configure_lds(cfg[0], dev, k_img_wn_rows, top);
-    if (e == hipSuccess) e = ics_configure_lds(cfg[1], dev, k_img_wn_psf_rows, top);
-    if (e == hipSuccess) e = ics_configure_lds(cfg[2], dev, k_img_wn_psf_cols, top);
-    if (e == hipSuccess) e = ics_configure_lds(cfg[3], dev, k_img_wn_cols, top);
-    if (e == hipSuccess) e = ics_configure_lds(cfg[4], dev, k_img_wn_inv_rows, top);
-    if (e != hipSuccess) return e;
-  }
+  hipError_t e = wn_raise_lds<k_img_wn_rows, k_img_wn_psf_cols, k_img_wn_cols>(Py, Px);
+  if (e != hipSuccess) return e;
   const float scale = 1.f / ((float)Py * (float)Px);
-  ics_launch_img_wiener_tables(twy, twx, lamy, lamx, Py, Px, s);
-  hipLaunchKernelGGL(k_img_wn_rows, dim3(3, (unsigned)Py), dim3(wn_lanes(Px)), ldsx, s, f, H, W, Py, Px, logPx, twx, A);
+  ics_launch_img_wiener_tables(t.twy, t.twx, t.lamy, t.lamx, Py, Px, s);
+  hipLaunchKernelGGL(k_img_wn_rows, dim3(3, (unsigned)Py), dim3(wn_lanes(Px)), ldsx, s, f, H, W, Py, Px, logPx, t.twx, A);
   ics_launch_img_wiener_transpose(A, Py, Px, Px, B, s);
-  hipLaunchKernelGGL(k_img_wn_psf_rows, dim3((unsigned)K, 3), dim3(wn_lanes(Px)), ldsx, s, psf, K, Px, logPx, twx, Hr);
-  hipLaunchKernelGGL(k_img_wn_psf_cols, dim3((unsigned)Px, 3), dim3(wn_lanes(Py)), ldsy, s, Hr, K, Py, Px, logPy, twy, lamy, lamx, balance, scale, A);
-  hipLaunchKernelGGL(k_img_wn_cols, dim3((unsigned)Px, 3), dim3(wn_lanes(Py)), ldsy, s, B, A, Py, logPy, twy);
+  if ((e = ics_launch_img_wiener_psf_rows(t.psf, K, Px, t.twx, t.Hr, s)) != hipSuccess) return e;
+  hipLaunchKernelGGL(k_img_wn_psf_cols, dim3((unsigned)Px, 3), dim3(wn_lanes(Py)), ldsy, s, t.Hr, K, Py, Px, logPy, t.twy, t.lamy, t.lamx, balance, scale, A);
+  hipLaunchKernelGGL(k_img_wn_cols, dim3((unsigned)Px, 3), dim3(wn_lanes(Py)), ldsy, s, B, A, Py, logPy, t.twy);
   ics_launch_img_wiener_transpose(B, Px, Py, H, A, s);
-  hipLaunchKernelGGL(k_img_wn_inv_rows, dim3(3, (unsigned)H), dim3(wn_lanes(Px)), ldsx, s, A, W, Py, Px, logPx, twx, out);
+  if ((e = ics_launch_img_wiener_inv_rows(A, H, Py, Px, t.twx, out, 1L, 3L * W, 3, W, s)) != hipSuccess) return e;
   return hipGetLastError();
 }

@@ -367,36 +367,56 @@ hipError_t ics_launch_img_mask(const float* f, int H, int W, int y0, int y1, int
 
 // ---- Wiener deconvolution of device-resident images (ics_img_wiener.hip): one 2-D transform of the periodically extended frame, the
 // filter conj(Hc) / (|Hc|^2 + balance L^2) per channel, the inverse.  ics_img_wiener_sizes: the transform sizes (powers of two >=
-// H + K - 1, W + K - 1), 0 where one would be above ICS_IMG_WIENER_MAX.  A, B: ics_img_wiener_frame_bytes each; tables:
-// ics_img_wiener_table_bytes, its ics_img_wiener_psf_slot holding the PSF as [3][K][K] (every channel of sum 1) before the launch.
-// ics_img_wiener_lds: dynamic LDS of a line kernel at P points.  One route; f is only read.
+// H + K - 1, W + K - 1), 0 where one would be above ICS_IMG_WIENER_MAX.  A, B: ics_img_wiener_frame_bytes each; tables: the block of
+// IcsWnTables, its psf holding the PSF as [3][K][K] (every channel of sum 1) before the launch.  ics_img_wiener_lds: dynamic LDS of a
+// line kernel at P points.  One route; f is only read.
 #define ICS_IMG_WIENER_MAX 8192           // (== include/ics_hip.h)
 int ics_img_wiener_sizes(int H, int W, int K, int* Py, int* Px);
 size_t ics_img_wiener_frame_bytes(int Py, int Px);
-size_t ics_img_wiener_table_bytes(int K, int Py, int Px);
-float* ics_img_wiener_psf_slot(void* tables, int K, int Py, int Px);
 size_t ics_img_wiener_lds(int P);
 hipError_t ics_launch_img_wiener(const float* f, int H, int W, int K, float balance, int Py, int Px, float2* A, float2* B, void* tables, float* out,
                                  hipStream_t s);
-// two of its passes, for ics_img_tvdeconv.hip: the twiddle tables of the two axes (Py, Px float2, a few unused) with 4 sin^2 along y and
-// x, and the tiled transpose in[plane][R][C] -> out[plane][C][R] of three planes for the columns below clim
+// the small block of the operators that take a PSF: Hr (the transformed rows of the PSF, 3 K Px float2), the twiddles of the two axes
+// (Py and Px float2, a few unused), 4 sin^2 along y and x, the planar PSF.  block == nullptr: the size alone
+struct IcsWnTables {
+  float2 *Hr = nullptr, *twy = nullptr, *twx = nullptr;
+  float *lamy = nullptr, *lamx = nullptr, *psf = nullptr;
+  size_t bytes;
+  IcsWnTables(void* block, int K, int Py, int Px) {
+    bytes = ((size_t)3 * K * Px + Py + Px) * sizeof(float2) + ((size_t)Py + Px + (size_t)3 * K * K) * sizeof(float);
+    if (!block) return;
+    Hr = reinterpret_cast<float2*>(block); twy = Hr + (size_t)3 * K * Px; twx = twy + Py;
+    lamy = reinterpret_cast<float*>(twx + Px); lamx = lamy + Py; psf = lamx + Px;
+  }
+};
+// the passes its kernels do for the other units on this transform: the twiddle tables of the two axes with 4 sin^2 along y and x; the
+// tiled transpose in[plane][R][C] -> out[plane][C][R] of three planes for the columns below clim; the K non-zero rows of the rolled PSF
+// (planar, [3][K][K]) transformed -> Hr[c][r][:]; and the rows A[c][y][:], y < rows, inverse, the real part of their first n points ->
+// dst[c * chan + y * pitch + j * step]
 void ics_launch_img_wiener_tables(float2* twy, float2* twx, float* lamy, float* lamx, int Py, int Px, hipStream_t s);
 void ics_launch_img_wiener_transpose(const float2* in, int R, int C, int clim, float2* out, hipStream_t s);
+hipError_t ics_launch_img_wiener_psf_rows(const float* psf, int K, int Px, const float2* twx, float2* Hr, hipStream_t s);
+hipError_t ics_launch_img_wiener_inv_rows(const float2* A, int rows, int Py, int Px, const float2* twx, float* dst, long chan, long pitch, int step, int n, hipStream_t s);
 
 // ---- TV-regularised deconvolution of device-resident images (ics_img_tvdeconv.hip): split-Bregman iterations on the transform of
 // ics_img_wiener.hip (its sizes, its extension, its tables), a shrinkage of the gradient per pixel and a solve that is diagonal under
-// the transform.  workspace: ics_img_tvd_workspace_bytes, one block; ics_img_tvd_tables: the tables inside it, laid out as
-// ics_img_wiener_table_bytes, their ics_img_wiener_psf_slot holding the PSF as [3][K][K] (every channel of sum 1) before the launch.
+// the transform.  workspace: ics_img_tvd_workspace_bytes, one block; ics_img_tvd_tables: the block of IcsWnTables inside it, its psf
+// holding the PSF as [3][K][K] (every channel of sum 1) before the launch.
 // coupling: 0 every channel by its own gradient magnitude, 1 the three by their common one.  One route; f is only read.
 size_t ics_img_tvd_workspace_bytes(int K, int Py, int Px);
 void* ics_img_tvd_tables(void* workspace, int Py, int Px);
 hipError_t ics_launch_img_tv_deconvolve(const float* f, int H, int W, int K, float mu, float beta, int iterations, int coupling, int Py, int Px, void* workspace, float* out,
                                         hipStream_t s);
+// its shrink pass, for ics_img_tvmdeconv.hip too: u, bx0, by0 -> bx1, by1, z on three Py x Px planes.  halves false: u and z planes
+// [3][Py][Px]; true: u[c][y][:] the first and z[c][y][:] the second Px floats of row y of channel c of a spectrum frame (z = u + Px); the
+// b planes contiguous
+void ics_launch_img_tvd_shrink(int coupling, bool halves, const float* u, float* z, const float* bx0, const float* by0, float* bx1, float* by1, int Py, int Px, float thr,
+                               hipStream_t s);
 
 // ---- TV deconvolution with a masked data term (ics_img_tvmdeconv.hip): the iterations of ics_img_tvdeconv.hip with the extension of the
 // frame, clipped and non-finite pixels and the caller's zeros declared unobserved, one more splitting variable keeping the solve
-// diagonal.  workspace: ics_img_tvm_workspace_bytes, one block; ics_img_tvm_tables: the tables inside it, laid out as
-// ics_img_wiener_table_bytes, their ics_img_wiener_psf_slot holding the PSF as [3][K][K] (every channel of sum 1) before the launch;
+// diagonal.  workspace: ics_img_tvm_workspace_bytes, one block; ics_img_tvm_tables: the block of IcsWnTables inside it, its psf holding
+// the PSF as [3][K][K] (every channel of sum 1) before the launch;
 // ics_img_tvm_mask_slot: H W bytes of the caller's mask before the launch where observed is true; ics_img_tvm_total: the count of
 // unobserved frame pixels after it.  clip: +inf for none.  coupling as above.  One route; f is only read.
 size_t ics_img_tvm_workspace_bytes(int K, int Py, int Px);

@@ -1,10 +1,15 @@
-// ics_wn_fft.h -- for ics_img_wiener.hip, ics_img_tvdeconv.hip, ics_img_tvmdeconv.hip and ics_img_psfest.hip only (everything here is local to the unit that includes it): the
-// line transform of the frame-sized fp32 transforms, a Stockham autosort transform of one line of N = 2^n points in LDS, and the
-// layout of its twiddle table (ics_img_wiener.hip describes both).  Device functions only; the kernels stay in their units.
+// ics_wn_fft.h -- for ics_img_wiener.hip, ics_img_tvdeconv.hip, ics_img_tvmdeconv.hip and ics_img_psfest.hip only (everything here is local to the unit that includes it): what
+// the operators on the frame-sized fp32 2-D transform share.  Device side: the line transform, a Stockham autosort transform of one line
+// of N = 2^n points in LDS, and the layout of its twiddle table (ics_img_wiener.hip describes both); a line into LDS and out of it; the
+// K values of a PSF at their rolled places in a line; a pixel of the frame extended to the transform size.  Host side: the lanes of a
+// line's workgroup, the shape check and the dynamic-LDS limit of the line kernels.  The kernels stay in their units.
 #pragma once
 #include "ics_kernels.h"
 
 namespace {
+
+#define WN_MAX ICS_IMG_WIENER_MAX              // longest line: two buffers of it are 128 KB of the 160 KB of LDS
+#define WN_LANES 1024                          // lanes of a line's workgroup at most (N / 4 below 4096 points, 64 at least)
 
 __device__ __forceinline__ float2 wn_add(float2 a, float2 b) { return make_float2(a.x + b.x, a.y + b.y); }
 __device__ __forceinline__ float2 wn_sub(float2 a, float2 b) { return make_float2(a.x - b.x, a.y - b.y); }
@@ -72,6 +77,78 @@ __device__ __forceinline__ float2 wn_table(int i, int logN) {
   const int r = i - off, k = r / 3, m = r - 3 * k + 1;
   const double a = (double)(k * m) / (double)(2 * p);            // exp(-2 pi i k m / 4p)
   return make_float2((float)cospi(a), (float)-sinpi(a));
+}
+
+// the line l of n points -> sm, a barrier passed (a real line: its values as the real parts)
+__device__ __forceinline__ void wn_load(float2* sm, const float2* l, int n) {
+  const int tid = threadIdx.x, nthr = blockDim.x;
+  for (int j = tid; j < n; j += nthr) sm[j] = l[j];
+  __syncthreads();
+}
+__device__ __forceinline__ void wn_load(float2* sm, const float* l, int n) {
+  const int tid = threadIdx.x, nthr = blockDim.x;
+  for (int j = tid; j < n; j += nthr) sm[j] = make_float2(l[j], 0.f);
+  __syncthreads();
+}
+// the first n points of the line r in LDS -> l
+__device__ __forceinline__ void wn_store(float2* l, const float2* r, int n) {
+  const int tid = threadIdx.x, nthr = blockDim.x;
+  for (int j = tid; j < n; j += nthr) l[j] = r[j];
+}
+
+// a line of P points of a PSF, its K values v(0) .. v(K - 1) zero padded, tap K / 2 rolled to point 0 -> its transform (sm or sm + P)
+template <typename V>
+__device__ __forceinline__ const float2* wn_psf_line(float2* sm, int P, int logP, int K, const float2* __restrict__ tw, V v) {
+  const int tid = threadIdx.x, nthr = blockDim.x;
+  for (int j = tid; j < P; j += nthr) {
+    int t = j + K / 2;
+    if (t >= P) t -= P;
+    sm[j] = t < K ? v(t) : make_float2(0.f, 0.f);
+  }
+  __syncthreads();
+  return wn_fft<false>(sm, sm + P, P, logP, tw);
+}
+
+// pixel (y, x) of channel c of the H x W frame f (HWC) extended to Py x Px so that the wrap-around carries no step: along y, for every
+// column, rows H .. Py - 1 are (1 - t / g) f[H - 1] + (t / g) f[0], g = Py - H + 1, t = 1 .. g - 1; then the same along x on all Py rows.
+// ZERO_NONFINITE: a non-finite value of f counts as 0
+template <bool ZERO_NONFINITE>
+__device__ __forceinline__ float wn_ext(const float* __restrict__ f, int c, int y, int x, int H, int W, int Py, int Px) {
+  const bool below = y >= H;
+  const float* r0 = f + (long)(below ? H - 1 : y) * (3L * W) + c;   // the row itself, or the last one
+  const float* r1 = f + c;                                          // the first one
+  const float ty = below ? (float)(y - H + 1) / (float)(Py - H + 1) : 0.f;
+  const auto at = [&](const float* r, int i) { const float v = r[3L * i]; return ZERO_NONFINITE && !isfinite(v) ? 0.f : v; };
+  const auto px = [&](int i) { return below ? (1.f - ty) * at(r0, i) + ty * at(r1, i) : at(r0, i); };
+  const float last = px(W - 1), first = px(0);                      // (read on every path: uniform over a row's workgroup, scalar loads in the gfx950 code)
+  if (x < W) return px(x);
+  const float t = (float)(x - W + 1) / (float)(Px - W + 1);
+  return (1.f - t) * last + t * first;
+}
+
+inline int wn_log2(int v) { int k = 0; while ((1 << k) < v) ++k; return k; }
+inline int wn_lanes(int P) { const int t = P / 4; return t < 64 ? 64 : (t > WN_LANES ? WN_LANES : t); }
+
+// an H x W frame, a K x K PSF and transform sizes that hold them (ics_img_wiener_sizes)
+inline bool wn_shape_ok(int H, int W, int K, int Py, int Px) {
+  return H >= 1 && W >= 1 && K >= 3 && (K & 1) && K <= H && K <= W && Py >= H + K - 1 && Px >= W + K - 1 && Py <= WN_MAX && Px <= WN_MAX && !(Py & (Py - 1)) &&
+         !(Px & (Px - 1));
+}
+
+// before the launches of the line kernels Kern...: lines of 8192 points take 128 KB of dynamic LDS, more than a kernel gets unasked.
+// Raises the limit of each to the longest line, once per kernel and device
+template <auto Kern>
+hipError_t wn_raise_lds_of(int dev) {
+  static std::atomic<bool> done[ICS_MAX_DEVICES];
+  return ics_configure_lds(done, dev, Kern, ics_img_wiener_lds(WN_MAX));
+}
+template <auto... Kern>
+hipError_t wn_raise_lds(int Py, int Px) {
+  if (ics_img_wiener_lds(Py > Px ? Py : Px) <= 64 * 1024) return hipSuccess;
+  const int dev = ics_current_device();
+  hipError_t e = hipSuccess;
+  ((e = e == hipSuccess ? wn_raise_lds_of<Kern>(dev) : e), ...);
+  return e;
 }
 
 }  // namespace

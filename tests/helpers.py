@@ -112,6 +112,33 @@ def compare_samples(z, meta, tag, u, psf, gate, sums_tol):
     return max(errs.values()), ep
 
 
+def lds_table(tmp_path, prefix):
+    """static LDS bytes of every gfx950 kernel of the cross-compiled library whose name holds `prefix`, by demangled name (read from the
+    AMDGPU metadata as tests/test_mask_isa.py reads it: the size stands in front of the name)"""
+    import re
+    import shutil
+    import subprocess
+    from test_isa import LLVM
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    work = tmp_path / "lds"
+    work.mkdir()
+    shutil.copy(os.path.join(root, "image-cases-studies_amd", "libics_hip.so"), work / "lib.so")
+    subprocess.check_call([os.path.join(LLVM, "llvm-objdump"), "--offloading", "lib.so"], cwd=work, stdout=subprocess.DEVNULL)
+    rows = {}
+    for f in sorted(os.listdir(work)):
+        if not f.endswith("gfx950"):
+            continue
+        pending = None
+        for line in subprocess.check_output([os.path.join(LLVM, "llvm-readelf"), "--notes", f], cwd=work, text=True).splitlines():
+            m = re.match(r"    \.(group_segment_fixed_size|name):\s+(\S+)", line)
+            if m and m.group(1) == "group_segment_fixed_size":
+                pending = int(m.group(2))
+            elif m and prefix in m.group(2):
+                rows[m.group(2)] = pending
+    names = subprocess.check_output(["c++filt"], input="\n".join(rows), text=True).splitlines()
+    return {nice.replace("(anonymous namespace)::", "").replace("void ", "").split("(")[0]: rows[mangled] for mangled, nice in zip(rows, names)}
+
+
 def log_numbers(line):
     return [float(t) for t in line.replace("|", " ").replace("=", " ").split() if t.replace(".", "").replace("-", "").isdigit()]
 

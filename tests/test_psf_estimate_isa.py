@@ -5,38 +5,15 @@ energy kernel 256 doubles; the transpose is the Wiener unit's kernel (read from 
 tests/test_wiener_isa.py: metadata only, no instruction is searched for)."""
 import os
 import re
-import shutil
-import subprocess
 
 import wiener_ref as wr
+from helpers import lds_table
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LDS_PER_CU = 160 * 1024
 LINE_KERNELS = ["k_img_pe_cols", "k_img_pe_crop", "k_img_pe_rows", "k_img_pe_solve"]
 OTHER_KERNELS = ["k_img_pe_energy", "k_img_pe_tables"]
 STATIC_LDS = {"k_img_pe_rows": 4096, "k_img_pe_energy": 2048}
-
-
-def lds_table(tmp_path):
-    """static LDS bytes per kernel of this unit (as tests/test_wiener_isa.py reads them: the size stands in front of the name)"""
-    from test_isa import LLVM
-    work = tmp_path / "lds"
-    work.mkdir()
-    shutil.copy(os.path.join(ROOT, "image-cases-studies_amd", "libics_hip.so"), work / "lib.so")
-    subprocess.check_call([os.path.join(LLVM, "llvm-objdump"), "--offloading", "lib.so"], cwd=work, stdout=subprocess.DEVNULL)
-    rows = {}
-    for f in sorted(os.listdir(work)):
-        if not f.endswith("gfx950"):
-            continue
-        pending = None
-        for line in subprocess.check_output([os.path.join(LLVM, "llvm-readelf"), "--notes", f], cwd=work, text=True).splitlines():
-            m = re.match(r"    \.(group_segment_fixed_size|name):\s+(\S+)", line)
-            if m and m.group(1) == "group_segment_fixed_size":
-                pending = int(m.group(2))
-            elif m and "k_img_pe_" in m.group(2):
-                rows[m.group(2)] = pending
-    names = subprocess.check_output(["c++filt"], input="\n".join(rows), text=True).splitlines()
-    return {nice.replace("(anonymous namespace)::", "").replace("void ", "").split("(")[0]: rows[mangled] for mangled, nice in zip(rows, names)}
 
 
 def test_psf_estimate_kernels_use_no_scratch_and_the_stated_lds(tmp_path):
@@ -64,12 +41,17 @@ def test_psf_estimate_kernels_use_no_scratch_and_the_stated_lds(tmp_path):
         assert found[k]["vgpr_count"] <= 128, (k, found[k])
     # LDS: every line kernel takes 2 P float2 at launch; static are one float a lane of the row kernel (the row's share of the energy)
     # and 256 doubles of the energy kernel
-    d = {m: int(v) for m, v in re.findall(r"#define (PE_LANES|PE_PLANES) (\d+)", src)}
-    assert d == {"PE_LANES": 1024, "PE_PLANES": 6}
-    lds = lds_table(tmp_path)
+    shared = open(os.path.join(ROOT, "image-cases-studies_amd", "csrc", "ics_wn_fft.h")).read()
+    d = {m: int(v) for m, v in re.findall(r"#define (WN_LANES|PE_PLANES) (\d+)", shared + src)}
+    assert d == {"WN_LANES": 1024, "PE_PLANES": 6}
+    assert "_LANES 1024" not in src                                                    # the lanes of a line's workgroup are the shared header's
+    lds = lds_table(tmp_path, "k_img_pe_")
     assert lds == {k: STATIC_LDS.get(k, 0) for k in declared}, lds
-    assert 4 * d["PE_LANES"] == STATIC_LDS["k_img_pe_rows"] and 8 * 256 == STATIC_LDS["k_img_pe_energy"]
+    assert 4 * d["WN_LANES"] == STATIC_LDS["k_img_pe_rows"] and 8 * 256 == STATIC_LDS["k_img_pe_energy"]
     assert "`16 P` bytes" in section and "4 096 B" in section and "2 048 B" in section
-    assert "ics_img_wiener_lds(Py)" in src and "ics_img_wiener_lds(ICS_IMG_WIENER_MAX)" in src        # the line kernels' launch-time LDS
+    assert "ics_img_wiener_lds(Py)" in src and "ics_img_wiener_lds(WN_MAX)" in shared                 # the line kernels' launch-time LDS
+    raised = re.search(r"wn_raise_lds<([^>]*)>\(Py, Px\)", src).group(1)                # ... its limit raised for every line kernel
+    assert sorted(k.strip() for k in raised.split(",")) == LINE_KERNELS
+    assert "ics_launch_img_wiener_transpose(" in src and not re.search(r"\bvoid\s+ics_launch_img_wiener_transpose", src)
     assert 16 * wr.MAX_SIDE + STATIC_LDS["k_img_pe_rows"] == 132 * 1024 <= LDS_PER_CU                  # the row kernel at 8192 points
     assert "getenv" not in src

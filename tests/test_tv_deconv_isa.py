@@ -1,41 +1,20 @@
 """CPU: the gfx950 code of csrc/ics_img_tvdeconv.hip declares exactly the kernels DESIGN.md names ("TV deconvolution on a resident
 frame"), uses no scratch memory and spills nothing, its line kernels fit four waves a SIMD, and its LDS is what DESIGN.md states: the
-line kernels take theirs at launch (two buffers of one line), the shrink pass static tiles of u and p; the tables and the transposes
-are the Wiener unit's kernels (read from the AMDGPU metadata of the cross-compiled library like tests/test_wiener_isa.py: metadata only, no instruction is
+line kernels take theirs at launch (two buffers of one line), the shrink pass static tiles of u and p; the tables, the transposes, the
+rows of the PSF and the inverse rows are the Wiener unit's kernels, checked in tests/test_wiener_isa.py; the shrink pass serves the masked
+unit too and is checked here (read from the AMDGPU metadata of the cross-compiled library like tests/test_wiener_isa.py: metadata only, no instruction is
 searched for)."""
 import os
 import re
-import shutil
-import subprocess
 
 import wiener_ref as wr
+from helpers import lds_table
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LDS_PER_CU = 160 * 1024
-LINE_KERNELS = ["k_img_tvd_cols", "k_img_tvd_inv_rows", "k_img_tvd_n0", "k_img_tvd_psf_cols", "k_img_tvd_psf_rows", "k_img_tvd_rows"]
-OTHER_KERNELS = ["k_img_tvd_extend", "k_img_tvd_shrink"]              # (the tables and the transposes are the Wiener unit's kernels)
-
-
-def lds_table(tmp_path):
-    """static LDS bytes per kernel of this unit (as tests/test_wiener_isa.py reads them: the size stands in front of the name)"""
-    from test_isa import LLVM
-    work = tmp_path / "lds"
-    work.mkdir()
-    shutil.copy(os.path.join(ROOT, "image-cases-studies_amd", "libics_hip.so"), work / "lib.so")
-    subprocess.check_call([os.path.join(LLVM, "llvm-objdump"), "--offloading", "lib.so"], cwd=work, stdout=subprocess.DEVNULL)
-    rows = {}
-    for f in sorted(os.listdir(work)):
-        if not f.endswith("gfx950"):
-            continue
-        pending = None
-        for line in subprocess.check_output([os.path.join(LLVM, "llvm-readelf"), "--notes", f], cwd=work, text=True).splitlines():
-            m = re.match(r"    \.(group_segment_fixed_size|name):\s+(\S+)", line)
-            if m and m.group(1) == "group_segment_fixed_size":
-                pending = int(m.group(2))
-            elif m and "k_img_tvd_" in m.group(2):
-                rows[m.group(2)] = pending
-    names = subprocess.check_output(["c++filt"], input="\n".join(rows), text=True).splitlines()
-    return {nice.replace("(anonymous namespace)::", "").replace("void ", "").split("(")[0]: rows[mangled] for mangled, nice in zip(rows, names)}
+LINE_KERNELS = ["k_img_tvd_cols", "k_img_tvd_n0", "k_img_tvd_psf_cols", "k_img_tvd_rows"]
+OTHER_KERNELS = ["k_img_tvd_extend", "k_img_tvd_shrink"]
+WIENER_LAUNCHES = ["ics_launch_img_wiener_tables", "ics_launch_img_wiener_transpose", "ics_launch_img_wiener_psf_rows", "ics_launch_img_wiener_inv_rows"]
 
 
 def test_tv_deconvolve_kernels_use_no_scratch_and_the_stated_lds(tmp_path):
@@ -49,10 +28,15 @@ def test_tv_deconvolve_kernels_use_no_scratch_and_the_stated_lds(tmp_path):
     assert declared == sorted(LINE_KERNELS + OTHER_KERNELS)
     assert sorted(set(re.findall(r"`(k_img_tvd_\w+)`", section))) == declared          # DESIGN.md names these and no other
     assert "k_img_wn_" not in src                                                      # tests/test_wiener_isa.py collects that unit's kernels by this
+    for name in WIENER_LAUNCHES:                                                       # ... this unit launches them and redeclares none
+        assert name + "(" in src and not re.search(r"\b(void|hipError_t)\s+" + name, src), name
+    assert "k_img_tvd_psf_rows" not in src and "k_img_tvd_inv_rows" not in src
+    assert re.search(r"\bvoid\s+ics_launch_img_tvd_shrink\(", src)                     # the one launcher of the shrink pass, the masked unit's too
     tab = kernel_table(tmp_path)
     found = {k: v for k, v in tab.items() if k.split("<")[0] in declared}
     assert sorted(set(k.split("<")[0] for k in found)) == declared, sorted(found)
-    assert sorted(k for k in found if "<" in k) == ["k_img_tvd_shrink<false>", "k_img_tvd_shrink<true>"]
+    # the coupling, and the layout of u and z: planes (this unit) or the halves of a spectrum row (the masked unit)
+    assert sorted(k for k in found if "<" in k) == ["k_img_tvd_shrink<%s, %s>" % (v, h) for v in ("false", "true") for h in ("false", "true")]
     for k, v in found.items():
         assert v.get("private_segment_fixed_size", 0) == 0 and v.get("vgpr_spill_count", 0) == 0 and v.get("sgpr_spill_count", 0) == 0, (k, v)
     print({k: (v["vgpr_count"], v["sgpr_count"]) for k, v in found.items()})
@@ -61,16 +45,20 @@ def test_tv_deconvolve_kernels_use_no_scratch_and_the_stated_lds(tmp_path):
         assert found[k]["vgpr_count"] <= 128, (k, found[k])
     # LDS: the shrink pass holds u on its 16 x 64 tile and one pixel around it and px, py on the
     # tile and one pixel above and left of it, three channels each; every line kernel takes 2 P float2 at launch and nothing static
-    d = {m: int(v) for m, v in re.findall(r"#define (TVD_LANES|TVD_TW|TVD_TH) (\d+)", src)}
-    assert d == {"TVD_LANES": 1024, "TVD_TW": 64, "TVD_TH": 16}
+    shared = open(os.path.join(ROOT, "image-cases-studies_amd", "csrc", "ics_wn_fft.h")).read()
+    d = {m: int(v) for m, v in re.findall(r"#define (WN_LANES|TVD_TW|TVD_TH) (\d+)", shared + src)}
+    assert d == {"WN_LANES": 1024, "TVD_TW": 64, "TVD_TH": 16}
+    assert "_LANES 1024" not in src                                                    # the lanes of a line's workgroup are the shared header's
     shrink = 4 * 3 * (18 * 66 + 2 * 17 * 65)
     assert shrink == 40776
-    lds = lds_table(tmp_path)
+    lds = lds_table(tmp_path, "k_img_tvd_")
     assert sorted(lds) == sorted(found)
     for k, v in lds.items():                                                           # (the code object rounds the two arrays up to 16 bytes)
         want = (shrink + 15) // 16 * 16 if k.startswith("k_img_tvd_shrink") else 0
         assert v == want, (k, v)
     assert "`12 · (18 · 66 + 2 · 17 · 65) = 40 776 B`" in section and "`16 P` bytes" in section
-    assert "ics_img_wiener_lds(Py)" in src and "ics_img_wiener_lds(ICS_IMG_WIENER_MAX)" in src        # the line kernels' launch-time LDS
+    assert "ics_img_wiener_lds(Py)" in src and "ics_img_wiener_lds(WN_MAX)" in shared                 # the line kernels' launch-time LDS
+    raised = re.search(r"wn_raise_lds<([^>]*)>\(Py, Px\)", src).group(1)                # ... its limit raised for every line kernel
+    assert sorted(k.strip() for k in raised.split(",")) == LINE_KERNELS
     assert 16 * wr.MAX_SIDE == 128 * 1024 <= LDS_PER_CU
     assert "getenv" not in src

@@ -1,50 +1,30 @@
 """CPU: the gfx950 code of csrc/ics_img_wiener.hip declares exactly the kernels DESIGN.md names ("Wiener filter on a resident frame"),
 uses no scratch memory and spills nothing, and its LDS is what DESIGN.md states: the line kernels take theirs at launch (two buffers
 of one line), the transpose a static padded tile (read from the AMDGPU metadata of the cross-compiled library like tests/test_isa.py
-and tests/test_mask_isa.py: metadata only, no instruction is searched for)."""
+and tests/test_mask_isa.py: metadata only, no instruction is searched for).  Four of the kernels -- the tables, the transpose, the rows
+of the PSF, the inverse rows -- serve the TV, masked TV and PSF-estimate units too and are checked here, once."""
 import os
 import re
-import shutil
-import subprocess
 
 import wiener_ref as wr
+from helpers import lds_table
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LDS_PER_CU = 160 * 1024
 KERNELS = ["k_img_wn_cols", "k_img_wn_inv_rows", "k_img_wn_psf_cols", "k_img_wn_psf_rows", "k_img_wn_rows", "k_img_wn_tables", "k_img_wn_transpose"]
 
 
-def lds_table(tmp_path):
-    """static LDS bytes per kernel of this unit (as tests/test_mask_isa.py reads them)"""
-    from test_isa import LLVM
-    work = tmp_path / "lds"
-    work.mkdir()
-    shutil.copy(os.path.join(ROOT, "image-cases-studies_amd", "libics_hip.so"), work / "lib.so")
-    subprocess.check_call([os.path.join(LLVM, "llvm-objdump"), "--offloading", "lib.so"], cwd=work, stdout=subprocess.DEVNULL)
-    rows = {}
-    for f in sorted(os.listdir(work)):
-        if not f.endswith("gfx950"):
-            continue
-        pending = None
-        for line in subprocess.check_output([os.path.join(LLVM, "llvm-readelf"), "--notes", f], cwd=work, text=True).splitlines():
-            m = re.match(r"    \.(group_segment_fixed_size|name):\s+(\S+)", line)
-            if m and m.group(1) == "group_segment_fixed_size":
-                pending = int(m.group(2))
-            elif m and "k_img_wn_" in m.group(2):
-                rows[m.group(2)] = pending
-    names = subprocess.check_output(["c++filt"], input="\n".join(rows), text=True).splitlines()
-    return {nice.replace("(anonymous namespace)::", "").replace("void ", "").split("(")[0]: rows[mangled] for mangled, nice in zip(rows, names)}
-
-
 def test_wiener_kernels_use_no_scratch_and_the_stated_lds(tmp_path):
     from test_isa import kernel_table
     assert os.path.isfile(os.path.join(ROOT, "image-cases-studies_amd", "libics_hip.so")), "libics_hip.so is not built"
     src = open(os.path.join(ROOT, "image-cases-studies_amd", "csrc", "ics_img_wiener.hip")).read()
+    shared = open(os.path.join(ROOT, "image-cases-studies_amd", "csrc", "ics_wn_fft.h")).read()
     design = open(os.path.join(ROOT, "DESIGN.md")).read()
     section = design[design.index("**Wiener filter on a resident frame"):]
     section = section[:section.index("\n**", 10)] if "\n**" in section[10:] else section
     declared = sorted(set(re.findall(r"__global__[^;{]*?\bvoid\s+(k_\w+)\s*\(", src)))
     assert declared == KERNELS
+    assert "__global__" not in shared                                                  # the shared header holds device functions, no kernel
     assert sorted(set(re.findall(r"`(k_img_wn_\w+)`", section))) == KERNELS            # DESIGN.md names these and no other
     tab = kernel_table(tmp_path)
     found = {k: v for k, v in tab.items() if k in declared}
@@ -57,16 +37,17 @@ def test_wiener_kernels_use_no_scratch_and_the_stated_lds(tmp_path):
         if k not in ("k_img_wn_tables", "k_img_wn_transpose"):
             assert found[k]["vgpr_count"] <= 128, (k, found[k])
     # LDS: the transpose holds a 32 x 33 tile of float2, static; every line kernel takes 2 P float2 at launch and nothing static
-    d = {m: int(v) for m, v in re.findall(r"#define (WN_LANES|WN_TILE) (\d+)", src)}
+    d = {m: int(v) for m, v in re.findall(r"#define (WN_LANES|WN_TILE) (\d+)", shared + src)}
     assert d == {"WN_LANES": 1024, "WN_TILE": 32}
     tile = 8 * 32 * 33
     assert tile == 8448
-    lds = lds_table(tmp_path)
+    lds = lds_table(tmp_path, "k_img_wn_")
     assert lds == {k: (tile if k == "k_img_wn_transpose" else 0) for k in KERNELS}, lds
     assert "size_t ics_img_wiener_lds(int P) { return (size_t)2 * P * sizeof(float2); }" in src
+    assert "ics_img_wiener_lds(WN_MAX)" in shared                                      # wn_raise_lds: the limit every unit's line kernels get
     assert "`8 · 32 · 33 = 8 448 B`" in section and "`16 P` bytes" in section
     assert 16 * wr.MAX_SIDE == 128 * 1024 <= LDS_PER_CU
-    assert "#define WN_MAX ICS_IMG_WIENER_MAX" in src
+    assert "#define WN_MAX ICS_IMG_WIENER_MAX" in shared
     for header in (os.path.join(ROOT, "include", "ics_hip.h"), os.path.join(ROOT, "image-cases-studies_amd", "csrc", "ics_kernels.h")):
         assert int(re.search(r"#define ICS_IMG_WIENER_MAX (\d+)", open(header).read()).group(1)) == wr.MAX_SIDE
-    assert "getenv" not in src
+    assert "getenv" not in src and "getenv" not in shared
