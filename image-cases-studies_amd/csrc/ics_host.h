@@ -160,6 +160,12 @@ struct ics_img {
   float* d;
 };
 
+struct ics_mask {              // byte planes of a device image's size (ics_img_edge_mask): planes x H x W, 0 or 1
+  ics_ctx* ctx;
+  int H, W, planes;
+  unsigned char* d;
+};
+
 // ---- everything below is internal to the host units -----------------------------------------------------------------------------
 namespace ics_host {
 

@@ -1,5 +1,5 @@
 // ics_images.hip -- the ics_img_* entries of the C ABI (include/ics_hip.h).  Host side only; kernels live in ics_img.hip / ics_img_filters.hip /
-// ics_img_tvdenoise.hip / ics_img_wavelet.hip / ics_img_noise.hip / ics_img_despeckle.hip / ics_img_blurwidth.hip / ics_img_mask.hip / ics_img_guided.hip / ics_img_llf.hip (what these nine share: ics_img_px.h) / ics_img_wiener.hip / ics_img_tvdeconv.hip / ics_img_tvmdeconv.hip / ics_img_psfest.hip / ics_img_align.hip / ics_resize.hip.
+// ics_img_tvdenoise.hip / ics_img_wavelet.hip / ics_img_noise.hip / ics_img_despeckle.hip / ics_img_blurwidth.hip / ics_img_mask.hip / ics_img_guided.hip / ics_img_llf.hip (what these nine share: ics_img_px.h) / ics_img_wiener.hip / ics_img_tvdeconv.hip / ics_img_tvmdeconv.hip / ics_img_psfest.hip / ics_img_edges.hip / ics_img_align.hip / ics_resize.hip.
 #include "ics_host.h"
 
 using namespace ics_host;
@@ -390,6 +390,112 @@ extern "C" int ics_img_despeckle(const ics_img* src, int radius, const float thr
   return ICS_OK;
 }
 
+// ---- edge prediction on a device image (csrc/ics_img_edges.hip) ------------------------------------------------------------------------
+// route 0 of the shock filter: the blocked route from 511^2 pixels on.  Measured ("Edge prediction"; 4 steps, vector / channel):
+// at 255^2 a launch per step takes 0.018 / 0.019 ms against 0.024 / 0.035 (64 tiles leave three quarters of the compute units idle), at
+// 511^2 the blocked route 0.025 / 0.038 against 0.034 / 0.037, at 1023^2 0.062 / 0.095 against 0.097 / 0.104, at 4096^2 0.78 / 1.31
+// against 1.38 / 1.53.  The threshold is the smallest size at which the blocked route was measured ahead or level.
+static const long SHOCK_BLOCK_MIN_PIXELS = 511L * 511L;
+extern "C" int ics_img_shock(const ics_img* src, int iterations, float dt, float flat, int coupling, int route, ics_img** out) {
+  RC(check_new(src, out));
+  if (iterations < 0) return ics_set_error(ICS_EINVAL, "iterations = %d", iterations);
+  if (!std::isfinite(dt)) return ics_set_error(ICS_EINVAL, "dt = %g (must be finite)", (double)dt);
+  if (!(flat > 0.f) || !std::isfinite(flat)) return ics_set_error(ICS_EINVAL, "flat = %g (must be positive and finite)", (double)flat);
+  const float inv_flat = (float)(1.0 / (double)flat);
+  if (!std::isfinite(inv_flat)) return ics_set_error(ICS_EINVAL, "flat = %g (1 / flat is not finite)", (double)flat);
+  RC(check_coupling(coupling));
+  RC(check_route(route, "per step", "blocked"));
+  ics_ctx* c = src->ctx;
+  HIPCHK(hipSetDevice(c->device));
+  const int H = src->H, W = src->W;
+  if (route == 0) route = (long)H * W >= SHOCK_BLOCK_MIN_PIXELS ? 2 : 1;
+  ImgOp op(c, out, "img_shock");
+  RC(img_new(c, H, W, out));
+  float* tmp[2] = {nullptr, nullptr};
+  hipError_t e = hipSuccess;
+  const int frames = ics_img_shock_frames(iterations, route);
+  for (int i = 0; i < frames && e == hipSuccess; ++i) e = op.alloc((void**)&tmp[i], (size_t)H * W * 12);
+  if (e == hipSuccess) e = op.begin();
+  if (e == hipSuccess) {
+    if (iterations == 0) e = hipMemcpyAsync((*out)->d, src->d, (size_t)H * W * 12, hipMemcpyDeviceToDevice, c->stream);
+    else e = ics_launch_img_shock(src->d, H, W, iterations, dt, inv_flat, coupling, route, tmp, (*out)->d, c->stream);
+  }
+  return op.finish(e);
+}
+
+// ---- byte masks of a device image's size (ics_mask): what ics_img_edge_mask makes and ics_img_psf_estimate_masked reads
+extern "C" void ics_mask_destroy(ics_mask* m) {
+  if (!m) return;
+  m->ctx->pool.release(m->d);
+  delete m;
+}
+extern "C" int ics_mask_create(ics_ctx* c, int H, int W, int planes, const unsigned char* host, ics_mask** out) {
+  if (out) *out = nullptr;
+  if (!c || !host || !out) return ics_set_error(ICS_EINVAL, "NULL argument");
+  if (H < 1 || W < 1 || (planes != 1 && planes != 3)) return ics_set_error(ICS_EINVAL, "bad mask size %d x %d x %d (planes: 1 or 3)", planes, H, W);
+  HIPCHK(hipSetDevice(c->device));
+  ics_mask* m = new (std::nothrow) ics_mask{c, H, W, planes, nullptr};
+  if (!m) return ics_set_error(ICS_ENOMEM, "host allocation failed");
+  hipError_t e = c->pool.alloc((void**)&m->d, (size_t)planes * H * W);
+  if (e != hipSuccess) { delete m; return ics_set_error(ICS_ENOMEM, "device allocation of a %d x %d mask: %s", H, W, hipGetErrorString(e)); }
+  e = hipMemcpyAsync(m->d, host, (size_t)planes * H * W, hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);   // the host buffer may be released by the caller
+  if (e != hipSuccess) { ics_mask_destroy(m); return ics_set_error(ICS_EHIP, "mask_create: %s", hipGetErrorString(e)); }
+  *out = m;
+  return ICS_OK;
+}
+extern "C" int ics_mask_shape(const ics_mask* m, int* H, int* W, int* planes) {
+  if (!m) return ics_set_error(ICS_EINVAL, "mask is NULL");
+  if (H) *H = m->H;
+  if (W) *W = m->W;
+  if (planes) *planes = m->planes;
+  return ICS_OK;
+}
+extern "C" int ics_mask_download(const ics_mask* m, unsigned char* host) {
+  if (!m || !host) return ics_set_error(ICS_EINVAL, "NULL argument");
+  HIPCHK(hipSetDevice(m->ctx->device));
+  HIPCHK(hipMemcpyAsync(host, m->d, (size_t)m->planes * m->H * m->W, hipMemcpyDeviceToHost, m->ctx->stream));
+  HIPCHK(hipStreamSynchronize(m->ctx->stream));
+  return ICS_OK;
+}
+// route 0 of the mask: the keys route at every size.  Measured (vector / channel): 0.26 / 1.05 ms against 0.36 / 1.33 at 4096^2, 0.165 /
+// 0.425 against 0.172 / 0.438 at 1023^2, 0.067 / 0.149 against 0.066 / 0.147 at 255^2, where the eight launches are all there is: no
+// crossover worth a rule.  It borrows 4 bytes per pixel and plane from the pool; route 1 needs only the 98 KB block and stays callable.
+extern "C" int ics_img_edge_mask(const ics_img* src, unsigned per_sector, int coupling, int route, ics_mask** out, float threshold[3], unsigned kept[3]) {
+  if (out) *out = nullptr;
+  if (!src || !out || !threshold || !kept) return ics_set_error(ICS_EINVAL, "NULL argument");
+  if (per_sector < 1) return ics_set_error(ICS_EINVAL, "per_sector = %u (at least 1)", per_sector);
+  RC(check_coupling(coupling));
+  RC(check_route(route, "recompute", "keys"));
+  ics_ctx* c = src->ctx;
+  HIPCHK(hipSetDevice(c->device));
+  const int H = src->H, W = src->W, planes = coupling ? 1 : 3;
+  if (route == 0) route = 2;
+  ics_mask* m = new (std::nothrow) ics_mask{c, H, W, planes, nullptr};
+  if (!m) return ics_set_error(ICS_ENOMEM, "host allocation failed");
+  if (hipError_t e = c->pool.alloc((void**)&m->d, (size_t)planes * H * W); e != hipSuccess) {
+    delete m;
+    return ics_set_error(ICS_ENOMEM, "device allocation of a %d x %d mask: %s", H, W, hipGetErrorString(e));
+  }
+  ImgOp op(c, nullptr, "img_edge_mask");
+  unsigned *blk = nullptr, *keys = nullptr, res[6] = {0u, 0u, 0u, 0u, 0u, 0u};
+  hipError_t e = op.alloc((void**)&blk, ics_img_edge_block_words() * sizeof(unsigned));
+  if (const size_t words = ics_img_edge_key_words(H, W, coupling, route); e == hipSuccess && words) e = op.alloc((void**)&keys, words * sizeof(unsigned));
+  if (e == hipSuccess) e = op.begin();
+  if (e == hipSuccess) e = ics_launch_img_edge_mask(src->d, H, W, per_sector, coupling, route, c->cus, blk, keys, m->d, c->stream);
+  if (e == hipSuccess) e = op.end();
+  if (e == hipSuccess) e = hipMemcpyAsync(res, blk + ics_img_edge_result_word(), sizeof(res), hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  if (const int rc = op.finish(e); rc != ICS_OK) { ics_mask_destroy(m); return rc; }
+  // (a plane without a pixel of g > 0 has nothing to select: its threshold comes back as the NaN 0xFFFFFFFF, its mask empty, its count 0)
+  for (int i = 0; i < 3; ++i) {
+    memcpy(&threshold[i], &res[coupling ? 0 : i], sizeof(float));
+    kept[i] = res[3 + (coupling ? 0 : i)];
+  }
+  *out = m;
+  return ICS_OK;
+}
+
 // ---- blur profile of a device image (csrc/ics_img_blurwidth.hip) --------------------------------------------------------------------
 // One route (a second summation order would buy nothing).  The rule that turns the profiles into a width is twenty lines on
 // 2 (max_lag + 1) numbers and lives on the host (lib/_native.py blur_extent).
@@ -591,8 +697,8 @@ extern "C" int ics_img_tv_deconvolve_masked(const ics_img* src, const float* psf
 extern "C" int ics_img_psf_estimate_plan(int H, int W, int K, int* Py, int* Px, size_t* workspace_bytes) {
   return wiener_plan(H, W, K, Py, Px, workspace_bytes, [&](int py, int px) { return ics_img_pe_workspace_bytes(H, W, K, py, px); });
 }
-extern "C" int ics_img_psf_estimate(const ics_img* blurred, const ics_img* sharp, int y0, int y1, int x0, int x1, int K, float regularisation, int coupling, float* raw,
-                                    double energy[3]) {
+static int psf_estimate(const ics_img* blurred, const ics_img* sharp, const ics_mask* mask, int y0, int y1, int x0, int x1, int K, float regularisation,
+                        int coupling, float* raw, double energy[3]) {
   if (!blurred || !sharp) return ics_set_error(ICS_EINVAL, "a frame (blurred, sharp) is NULL");
   if (!raw || !energy) return ics_set_error(ICS_EINVAL, "an output (raw, energy) is NULL");
   if (y0 < 0 || x0 < 0 || y0 >= y1 || x0 >= x1) return ics_set_error(ICS_EINVAL, "box [%d, %d) x [%d, %d) (not empty, no negative corner)", y0, y1, x0, x1);
@@ -605,6 +711,11 @@ extern "C" int ics_img_psf_estimate(const ics_img* blurred, const ics_img* sharp
   if (blurred->H != sharp->H || blurred->W != sharp->W)
     return ics_set_error(ICS_EINVAL, "frames of different shapes: blurred %d x %d, sharp %d x %d", blurred->H, blurred->W, sharp->H, sharp->W);
   if (y1 > sharp->H || x1 > sharp->W) return ics_set_error(ICS_EINVAL, "box [%d, %d) x [%d, %d) outside the %d x %d frames", y0, y1, x0, x1, sharp->H, sharp->W);
+  if (mask) {
+    if (mask->ctx != sharp->ctx) return ics_set_error(ICS_EINVAL, "the mask belongs to a different context");
+    if (mask->H != sharp->H || mask->W != sharp->W) return ics_set_error(ICS_EINVAL, "a %d x %d mask for %d x %d frames", mask->H, mask->W, sharp->H, sharp->W);
+    if (mask->planes != (coupling ? 1 : 3)) return ics_set_error(ICS_EINVAL, "a mask of %d planes with coupling %d (one plane: vector, three: channel)", mask->planes, coupling);
+  }
   ics_ctx* c = sharp->ctx;
   HIPCHK(hipSetDevice(c->device));
   const long pitch = 3L * sharp->W, first = (long)y0 * pitch + 3L * x0;
@@ -614,7 +725,10 @@ extern "C" int ics_img_psf_estimate(const ics_img* blurred, const ics_img* sharp
   double s[3] = {0.0, 0.0, 0.0};
   hipError_t e = op.alloc(&ws, ics_img_pe_workspace_bytes(H, W, K, Py, Px));
   if (e == hipSuccess) e = op.begin();
-  if (e == hipSuccess) e = ics_launch_img_psf_estimate(sharp->d + first, blurred->d + first, pitch, H, W, K, regularisation, coupling, Py, Px, ws, c->stream);
+  if (e == hipSuccess && !mask) e = ics_launch_img_psf_estimate(sharp->d + first, blurred->d + first, pitch, H, W, K, regularisation, coupling, Py, Px, ws, c->stream);
+  if (e == hipSuccess && mask)
+    e = ics_launch_img_psf_estimate_masked(sharp->d + first, blurred->d + first, pitch, mask->d + (long)y0 * sharp->W + x0, sharp->W,
+                                           mask->planes == 3 ? (long)sharp->H * sharp->W : 0, H, W, K, regularisation, coupling, Py, Px, ws, c->stream);
   if (e == hipSuccess) e = op.end();
   if (e == hipSuccess) e = hipMemcpyAsync(got.data(), ics_img_pe_raw(ws, H, W, K, Py, Px), got.size() * sizeof(float), hipMemcpyDeviceToHost, c->stream);
   if (e == hipSuccess) e = hipMemcpyAsync(s, ics_img_pe_energy(ws, H, W, K, Py, Px), sizeof s, hipMemcpyDeviceToHost, c->stream);
@@ -623,6 +737,15 @@ extern "C" int ics_img_psf_estimate(const ics_img* blurred, const ics_img* sharp
   std::copy(got.begin(), got.end(), raw);
   for (int ch = 0; ch < 3; ++ch) energy[ch] = s[ch];
   return ICS_OK;
+}
+extern "C" int ics_img_psf_estimate(const ics_img* blurred, const ics_img* sharp, int y0, int y1, int x0, int x1, int K, float regularisation, int coupling, float* raw,
+                                    double energy[3]) {
+  return psf_estimate(blurred, sharp, nullptr, y0, y1, x0, x1, K, regularisation, coupling, raw, energy);
+}
+extern "C" int ics_img_psf_estimate_masked(const ics_img* blurred, const ics_img* sharp, const ics_mask* mask, int y0, int y1, int x0, int x1, int K,
+                                           float regularisation, int coupling, float* raw, double energy[3]) {
+  if (!mask) return ics_set_error(ICS_EINVAL, "mask is NULL");
+  return psf_estimate(blurred, sharp, mask, y0, y1, x0, x1, K, regularisation, coupling, raw, energy);
 }
 
 // ---- registration of two device images and the warp of one (csrc/ics_img_align.hip) -----------------------------------------------------

@@ -43,6 +43,8 @@ __global__ __launch_bounds__(256) void k_img_pe_tables(float2* __restrict__ twy,
 }
 
 // grid (6, Py): row blockIdx.y of plane blockIdx.x.  s, b: the first pixel of the window in the two frames, `pitch` floats a frame row
+// (k_img_ed_rows of ics_img_edges.hip is this kernel with the sharp derivative under a mask: a change here belongs there too; an all-ones
+//  mask must keep giving this kernel's bits, tests/test_gpu_blind_psf.py)
 __global__ __launch_bounds__(WN_LANES) void k_img_pe_rows(const float* __restrict__ s, const float* __restrict__ b, long pitch, int H, int W, int Py, int Px, int logPx,
                                                           const float2* __restrict__ tw, const float* __restrict__ wy, const float* __restrict__ wx,
                                                           float2* __restrict__ Z, float* __restrict__ slot) {
@@ -179,8 +181,11 @@ size_t ics_img_pe_workspace_bytes(int H, int W, int K, int Py, int Px) { return 
 float* ics_img_pe_raw(void* workspace, int H, int W, int K, int Py, int Px) { return PeCarve(workspace, H, W, K, Py, Px).raw; }
 double* ics_img_pe_energy(void* workspace, int H, int W, int K, int Py, int Px) { return PeCarve(workspace, H, W, K, Py, Px).S; }
 
-hipError_t ics_launch_img_psf_estimate(const float* sharp, const float* blurred, long pitch, int H, int W, int K, float regularisation, int coupling, int Py, int Px,
-                                       void* workspace, hipStream_t s) {
+// tables -> the rows of the six planes -> transposes, columns, energy, solve, crop, on the carved workspace.  rows == nullptr: k_img_pe_rows
+// on the two frames; else the caller's row kernel (ics_img_edges.hip: the sharp frame's derivatives under a mask), launched by `rows`
+// with what k_img_pe_rows gets -- it has to write every row of Za and every slot
+hipError_t ics_launch_img_psf_estimate_rows(ics_pe_rows_fn rows, void* user, const float* sharp, const float* blurred, long pitch, int H, int W, int K,
+                                            float regularisation, int coupling, int Py, int Px, void* workspace, hipStream_t s) {
   if (!sharp || !blurred || !workspace || !wn_shape_ok(H, W, K, Py, Px) || pitch < 3L * W) return hipErrorInvalidValue;
   if (!(regularisation > 0.f) || (coupling != 0 && coupling != 1)) return hipErrorInvalidValue;
   const int logPy = wn_log2(Py), logPx = wn_log2(Px), nq = coupling ? 1 : 3;
@@ -191,7 +196,11 @@ hipError_t ics_launch_img_psf_estimate(const float* sharp, const float* blurred,
   const size_t half = (size_t)3 * Py * Px;       // the transpose takes three planes a launch
   const float scale = 1.f / ((float)Py * (float)Px);
   hipLaunchKernelGGL(k_img_pe_tables, dim3((unsigned)((P0 + 255) / 256)), dim3(256), 0, s, m.twy, m.twx, m.wy, m.wx, Py, Px, logPy, logPx, H, W, K);
-  hipLaunchKernelGGL(k_img_pe_rows, dim3(PE_PLANES, (unsigned)Py), dim3(wn_lanes(Px)), ldsx, s, sharp, blurred, pitch, H, W, Py, Px, logPx, m.twx, m.wy, m.wx, m.Za, m.slot);
+  if (rows) {
+    const IcsPeRows r = {sharp, blurred, pitch, H, W, Py, Px, logPx, m.twx, m.wy, m.wx, m.Za, m.slot, wn_lanes(Px), ldsx};
+    if (hipError_t e = rows(r, user, s); e != hipSuccess) return e;
+  } else
+    hipLaunchKernelGGL(k_img_pe_rows, dim3(PE_PLANES, (unsigned)Py), dim3(wn_lanes(Px)), ldsx, s, sharp, blurred, pitch, H, W, Py, Px, logPx, m.twx, m.wy, m.wx, m.Za, m.slot);
   ics_launch_img_wiener_transpose(m.Za, Py, Px, Px, m.Zb, s);
   ics_launch_img_wiener_transpose(m.Za + half, Py, Px, Px, m.Zb + half, s);
   hipLaunchKernelGGL(k_img_pe_cols, dim3((unsigned)Px, PE_PLANES), dim3(wn_lanes(Py)), ldsy, s, m.Zb, Py, logPy, m.twy);
@@ -199,4 +208,9 @@ hipError_t ics_launch_img_psf_estimate(const float* sharp, const float* blurred,
   hipLaunchKernelGGL(k_img_pe_solve, dim3((unsigned)Px, (unsigned)nq), dim3(wn_lanes(Py)), ldsy, s, m.Zb, Py, Px, logPy, m.twy, K, coupling, regularisation, scale, m.S, m.R);
   hipLaunchKernelGGL(k_img_pe_crop, dim3((unsigned)K, (unsigned)nq), dim3(wn_lanes(Px)), ldsx, s, m.R, Px, logPx, m.twx, K, coupling, m.raw);
   return hipGetLastError();
+}
+
+hipError_t ics_launch_img_psf_estimate(const float* sharp, const float* blurred, long pitch, int H, int W, int K, float regularisation, int coupling, int Py, int Px,
+                                       void* workspace, hipStream_t s) {
+  return ics_launch_img_psf_estimate_rows(nullptr, nullptr, sharp, blurred, pitch, H, W, K, regularisation, coupling, Py, Px, workspace, s);
 }

@@ -311,6 +311,23 @@ size_t ics_img_noise_key_words(int H, int W, int coupling, int route);
 size_t ics_img_noise_keys_lds(int coupling);
 hipError_t ics_launch_img_noise(const float* f, int H, int W, int coupling, int route, int cus, unsigned* blk, unsigned* keys, hipStream_t s);
 
+// ---- edge prediction on device-resident images (ics_img_edges.hip): the shock filter and the orientation-balanced gradient mask -----
+// shock: tmp: ics_img_shock_frames frames of H W 3 floats the launches ping-pong through; route 1: a launch per step, 2:
+// ICS_IMG_SHOCK_BLOCK steps per launch on LDS tiles.  edge mask: blk: ics_img_edge_block_words words (zeroed by the launcher), afterwards
+// the words from ics_img_edge_result_word on hold three threshold bit patterns (0xFFFFFFFF: the plane has no gradients) and three counts;
+// keys: ics_img_edge_key_words words (route 2); mask: H W bytes per plane, 1 ("vector") or 3 ("channel") planes.  src / f are only read.
+#define ICS_IMG_SHOCK_BLOCK 4   // (== include/ics_hip.h)
+size_t ics_img_shock_block_lds();
+int ics_img_shock_frames(int iterations, int route);
+hipError_t ics_launch_img_shock(const float* src, int H, int W, int iterations, float dt, float inv_flat, int coupling, int route, float* const tmp[2],
+                                float* out, hipStream_t s);
+size_t ics_img_edge_block_words();
+size_t ics_img_edge_result_word();
+size_t ics_img_edge_key_words(int H, int W, int coupling, int route);
+size_t ics_img_edge_hist_lds(int coupling);
+hipError_t ics_launch_img_edge_mask(const float* f, int H, int W, unsigned per_sector, int coupling, int route, int cus, unsigned* blk, unsigned* keys,
+                                    unsigned char* mask, hipStream_t s);
+
 // ---- guided filter of device-resident images (ics_img_guided.hip): box means, a solve per pixel, base layer + detail * (src - base) --
 // route 1: coefficients to the planar frame `coef` (ics_img_guided_coef_floats floats), then the output; 2: one launch, coefficients
 // in LDS, radius <= ICS_IMG_GUIDED_FUSED_RADIUS, coef unused.  coupling 0: per channel, 1: the RGB pixel as the guide.
@@ -436,6 +453,21 @@ float* ics_img_pe_raw(void* workspace, int H, int W, int K, int Py, int Px);
 double* ics_img_pe_energy(void* workspace, int H, int W, int K, int Py, int Px);
 hipError_t ics_launch_img_psf_estimate(const float* sharp, const float* blurred, long pitch, int H, int W, int K, float regularisation, int coupling, int Py, int Px,
                                        void* workspace, hipStream_t s);
+// ... with the rows of the six planes formed by the caller's kernel: `rows` gets what k_img_pe_rows gets (tables already queued on s) and
+// has to write every row of Za ([6][Py][Px], rows H .. Py - 1 zero) and every slot ([6][H], the row's sum of the sharp derivative's
+// squares); grid (6, Py) of `lanes` lanes with `lds` bytes at launch is k_img_pe_rows's shape.  rows == nullptr: k_img_pe_rows.
+// ics_launch_img_psf_estimate_masked (ics_img_edges.hip): the sharp frame's derivatives multiplied by mask[y][x] before the taper;
+// mask: the window's first byte of the plane of channel 0, `mask_pitch` bytes a row, `mask_plane` bytes from a channel's plane to the
+// next (0: one plane for all).
+struct IcsPeRows {
+  const float *sharp, *blurred; long pitch; int H, W, Py, Px, logPx;
+  const float2* twx; const float *wy, *wx; float2* Za; float* slot; int lanes; size_t lds;
+};
+typedef hipError_t (*ics_pe_rows_fn)(const IcsPeRows& r, void* user, hipStream_t s);
+hipError_t ics_launch_img_psf_estimate_rows(ics_pe_rows_fn rows, void* user, const float* sharp, const float* blurred, long pitch, int H, int W, int K,
+                                            float regularisation, int coupling, int Py, int Px, void* workspace, hipStream_t s);
+hipError_t ics_launch_img_psf_estimate_masked(const float* sharp, const float* blurred, long pitch, const unsigned char* mask, long mask_pitch, long mask_plane,
+                                              int H, int W, int K, float regularisation, int coupling, int Py, int Px, void* workspace, hipStream_t s);
 
 // ---- registration and warp of device-resident images (ics_img_align.hip): the luma plane of a window of an HWC frame (`pitch` floats a
 // frame row), its 2 x 2 mean, one evaluation of the Gauss-Newton sums of a fixed plane T (H x W) against a moving plane I (Hm x Wm), and

@@ -1,4 +1,4 @@
-// ics_wn_fft.h -- for ics_img_wiener.hip, ics_img_tvdeconv.hip, ics_img_tvmdeconv.hip and ics_img_psfest.hip only (everything here is local to the unit that includes it): what
+// ics_wn_fft.h -- for ics_img_wiener.hip, ics_img_tvdeconv.hip, ics_img_tvmdeconv.hip, ics_img_psfest.hip and ics_img_edges.hip (the rows of the masked pair solve) only (everything here is local to the unit that includes it): what
 // the operators on the frame-sized fp32 2-D transform share.  Device side: the line transform, a Stockham autosort transform of one line
 // of N = 2^n points in LDS, and the layout of its twiddle table (ics_img_wiener.hip describes both); a line into LDS and out of it; the
 // K values of a PSF at their rolled places in a line; a pixel of the frame extended to the transform size.  Host side: the lanes of a

@@ -88,6 +88,7 @@ def describe(M, N, MK, params):
 
 FRAME_LIMIT_BYTES = 1 << 31      # include/ics_hip.h ICS_FRAME_LIMIT_BYTES
 IMG_TV_BLOCK = 4                 # include/ics_hip.h ICS_IMG_TV_BLOCK: iterations per launch of the blocked TV denoise route
+IMG_SHOCK_BLOCK = 4              # include/ics_hip.h ICS_IMG_SHOCK_BLOCK: steps per launch of the blocked shock-filter route
 IMG_WAVELET_MAX_SCALES = 8       # include/ics_hip.h ICS_IMG_WAVELET_MAX_SCALES: detail scales of the wavelet equaliser
 IMG_WAVELET_FUSED = 3            # include/ics_hip.h ICS_IMG_WAVELET_FUSED: scales the fused route runs in one launch on LDS tiles
 IMG_GUIDED_MAX_RADIUS = 32       # include/ics_hip.h ICS_IMG_GUIDED_MAX_RADIUS: largest window radius of the guided filter
@@ -195,6 +196,13 @@ def load():
     lib.ics_img_tv_deconvolve_masked_plan.argtypes = [ci, ci, ci, C.POINTER(ci), C.POINTER(ci), C.POINTER(C.c_size_t)]
     lib.ics_img_psf_estimate.argtypes = [vp, vp, ci, ci, ci, ci, ci, cf, ci, C.POINTER(cf), C.POINTER(cd)]
     lib.ics_img_psf_estimate_plan.argtypes = [ci, ci, ci, C.POINTER(ci), C.POINTER(ci), C.POINTER(C.c_size_t)]
+    lib.ics_img_shock.argtypes = [vp, ci, cf, cf, ci, ci, C.POINTER(vp)]
+    lib.ics_img_edge_mask.argtypes = [vp, C.c_uint, ci, ci, C.POINTER(vp), C.POINTER(cf), C.POINTER(C.c_uint)]
+    lib.ics_mask_shape.argtypes = [vp, C.POINTER(ci), C.POINTER(ci), C.POINTER(ci)]
+    lib.ics_mask_download.argtypes = [vp, vp]
+    lib.ics_mask_destroy.argtypes = [vp]; lib.ics_mask_destroy.restype = None
+    lib.ics_mask_create.argtypes = [vp, ci, ci, ci, vp, C.POINTER(vp)]
+    lib.ics_img_psf_estimate_masked.argtypes = [vp, vp, vp, ci, ci, ci, ci, ci, cf, ci, C.POINTER(cf), C.POINTER(cd)]
     lib.ics_img_align.argtypes = [vp, vp, ci, ci, ci, ci, ci, ci, ci, ci, cd, C.POINTER(cd), C.POINTER(cd), C.POINTER(cd)]
     lib.ics_img_align_sums.argtypes = [vp, vp, ci, ci, ci, ci, ci, ci, C.POINTER(cd), cd, cd, C.POINTER(cd), ci]
     lib.ics_img_warp.argtypes = [vp, C.POINTER(cd), ci, ci, C.POINTER(vp)]
@@ -222,6 +230,7 @@ def load():
                  "ics_img_upload", "ics_img_upload_int", "ics_img_download", "ics_img_pad_edge", "ics_img_crop", "ics_img_paste", "ics_img_gamma", "ics_img_resize",
                  "ics_img_convolve", "ics_img_usm", "ics_img_bilateral", "ics_img_tv_denoise", "ics_img_wavelet_equalize", "ics_img_noise_estimate", "ics_img_blur_profile", "ics_img_window_scores", "ics_img_despeckle", "ics_img_guided", "ics_img_local_laplacian", "ics_img_wiener", "ics_img_wiener_plan", "ics_img_tv_deconvolve", "ics_img_tv_deconvolve_plan", "ics_img_tv_deconvolve_masked", "ics_img_tv_deconvolve_masked_plan",
                  "ics_img_psf_estimate", "ics_img_psf_estimate_plan",
+                 "ics_img_shock", "ics_img_edge_mask", "ics_mask_shape", "ics_mask_download", "ics_mask_create", "ics_img_psf_estimate_masked",
                  "ics_img_align", "ics_img_align_sums", "ics_img_warp", "ics_img_align_plan",
                  "ics_rl_upload_img", "ics_rl_download_img", "ics_group_create", "ics_group_info", "ics_group_barrier",
                  "ics_group_allreduce_max", "ics_group_allreduce_sum", "ics_group_describe", "ics_group_allgather"):
@@ -297,6 +306,27 @@ def _route(route, names):
 
 
 NoiseEstimate = collections.namedtuple("NoiseEstimate", "median level sigma")
+EdgeMask = collections.namedtuple("EdgeMask", "mask threshold kept")
+
+
+def shock_args(iterations=4, dt=0.4, flat=0.01, coupling="vector", route=0):
+    """the arguments of DeviceImage.shock checked (ValueError) and as (iterations, dt, flat, coupling, route)"""
+    if isinstance(iterations, bool) or int(iterations) != iterations or iterations < 0:
+        raise ValueError("iterations %r (a whole number, 0 or more)" % (iterations,))
+    if not _finite32(dt, scalar=True):
+        raise ValueError("dt %r (a finite number)" % (dt,))
+    if not _finite32(flat, scalar=True) or not float(np.float32(flat)) > 0 or not np.isfinite(np.float32(1.0 / float(np.float32(flat)))):
+        raise ValueError("flat %r (positive, finite, and so its inverse)" % (flat,))
+    _coupling(coupling)
+    return int(iterations), float(dt), float(flat), coupling, _route(route, "1: a launch per step, 2: IMG_SHOCK_BLOCK steps per launch on LDS tiles")
+
+
+def edge_mask_args(per_sector, coupling="vector", route=0):
+    """the arguments of DeviceImage.edge_mask checked (ValueError) and as (per_sector, coupling, route)"""
+    if isinstance(per_sector, bool) or int(per_sector) != per_sector or not 1 <= per_sector < 2 ** 31:
+        raise ValueError("per_sector %r (a whole number, 1 or more)" % (per_sector,))
+    _coupling(coupling)
+    return int(per_sector), coupling, _route(route, "1: every pass forms the gradients from the frame, 2: the first pass stores keys and sectors")
 
 
 def noise_args(coupling="vector", route=0):
@@ -643,6 +673,80 @@ def tv_deconvolve_masked_plan(H, W, K):
 
 
 PsfEstimatePlan = collections.namedtuple("PsfEstimatePlan", "Py Px workspace_bytes")
+BlindPsfPlan = collections.namedtuple("BlindPsfPlan", "levels peak_bytes")
+
+
+def blind_psf_levels(H, W, K):
+    """the levels of lib.utils.blind_psf on an H x W window, [(K_l, H_l, W_l)], coarsest first: K_0 = K, K_{l+1} = max(3, (K_l // 2) | 1)
+    until 3, level l on ceil(H / 2^l) x ceil(W / 2^l); levels whose smaller side is below 4 K_l are dropped"""
+    Ks = [int(K)]
+    while Ks[-1] > 3:
+        Ks.append(max(3, (Ks[-1] // 2) | 1))
+    out = []
+    for l, k in enumerate(Ks):
+        hl, wl = -(-int(H) // 2 ** l), -(-int(W) // 2 ** l)
+        if min(hl, wl) >= 4 * k:
+            out.append((k, hl, wl))
+    return out[::-1]
+
+
+def blind_psf_args(size, iterations, shock, keep, regularisation, threshold, balance, coupling, window, shape):
+    """the arguments of lib.utils.blind_psf checked (ValueError) and as (size, iterations, shock, keep, regularisation, threshold, balance,
+    coupling, (y0, y1, x0, x1), levels)"""
+    size, regularisation, threshold, coupling, window = psf_estimate_args(size, regularisation, threshold, coupling, window, shape, shape)
+    if isinstance(iterations, bool) or int(iterations) != iterations or iterations < 1:
+        raise ValueError("iterations %r (a whole number, 1 or more)" % (iterations,))
+    try:
+        shock = tuple(shock)
+    except TypeError:
+        shock = ()
+    if len(shock) != 3:
+        raise ValueError("shock %r ((iterations, dt, flat))" % (shock,))
+    shock = shock_args(*shock, coupling)[:3]
+    if not _finite32(keep, scalar=True) or not keep > 0:
+        raise ValueError("keep %r (must be finite and > 0)" % (keep,))
+    if not _finite32(balance, scalar=True) or not np.float32(balance) > 0:
+        raise ValueError("balance %r (must be finite and > 0)" % (balance,))
+    y0, y1, x0, x1 = window
+    levels = blind_psf_levels(y1 - y0, x1 - x0, size)
+    if not levels or levels[-1][0] != size:
+        raise ValueError("a window of %d x %d is smaller than 4 x size = %d" % (y1 - y0, x1 - x0, 4 * size))
+    return size, int(iterations), shock, float(keep), regularisation, threshold, float(balance), coupling, window, levels
+
+
+def blind_psf_plan(H, W, K):
+    """BlindPsfPlan(levels, peak_bytes) of lib.utils.blind_psf on an H x W window with a K x K PSF: the levels as blind_psf_levels gives
+    them and the most device bytes the call holds at one time -- the window, and per level its frame, the latent frame, the predicted
+    frame and its mask beside the largest of the transients: the ping-pong frames of the shock filter, the keys and state block of the
+    mask, the workspace of `wiener` and that of the pair solve (no device needed).  ValueError: a window smaller than 4 K."""
+    levels = blind_psf_levels(H, W, K)
+    if not levels or levels[-1][0] != int(K):
+        raise ValueError("a window of %d x %d is smaller than 4 x size = %d" % (H, W, 4 * int(K)))
+    peak = 0
+    for k, hl, wl in levels:
+        frame = 12 * hl * wl
+        transient = max(2 * frame, 4 * hl * wl + 4 * (12 * 2048 + 30), wiener_plan(hl, wl, k).workspace_bytes, psf_estimate_plan(hl, wl, k).workspace_bytes)
+        peak = max(peak, 12 * int(H) * int(W) + 3 * frame + hl * wl + transient)
+    return BlindPsfPlan(levels, int(peak))
+
+
+def psf_centred(psf):
+    """every plane of a K x K x 3 PSF moved by whole pixels so that its centroid rounds to the centre tap, the taps that leave the support
+    dropped and the plane renormalised, in float64; float32 back.  The pair solve fixes a PSF only up to a shift it shares with the
+    predicted frame: without this the two drift together through the alternation of lib.utils.blind_psf."""
+    psf = np.asarray(psf, dtype=np.float64)
+    K = psf.shape[0]
+    r = np.arange(K, dtype=np.float64)
+    out = np.zeros_like(psf)
+    for c in range(3):
+        p = psf[..., c]
+        dy = K // 2 - int(np.floor((p.sum(axis=1) * r).sum() / p.sum() + 0.5))
+        dx = K // 2 - int(np.floor((p.sum(axis=0) * r).sum() / p.sum() + 0.5))
+        src_y, dst_y = (slice(0, K - dy), slice(dy, K)) if dy >= 0 else (slice(-dy, K), slice(0, K + dy))
+        src_x, dst_x = (slice(0, K - dx), slice(dx, K)) if dx >= 0 else (slice(-dx, K), slice(0, K + dx))
+        out[dst_y, dst_x, c] = p[src_y, src_x]
+        out[..., c] /= out[..., c].sum()
+    return np.ascontiguousarray(out, dtype=np.float32)
 
 
 def psf_estimate_args(size, regularisation, threshold, coupling, window, shape_blurred, shape_sharp):
@@ -1210,7 +1314,7 @@ class DeviceImage:
                         None if observed is None else _ptr(observed), clip, fidelity, penalty, data_penalty, iterations, _coupling(coupling))
         return (img, int(got.value)) if count else img
 
-    def psf_raw(self, sharp, size, regularisation=1e-3, coupling="vector", window=None):
+    def psf_raw(self, sharp, size, regularisation=1e-3, coupling="vector", window=None, mask=None):
         """The kernel that takes `sharp`, a DeviceImage of the same shape and scene, to this blurred frame: (raw, energy).  The linear
         solve of the fast blind methods (Cho and Lee 2009; Xu and Jia 2010) on the derivatives of the pair, k = argmin sum |d s * k -
         d b|^2 + regularisation S |k|^2, S the gradient energy of the sharp frame, diagonal under `wiener`'s transform: the forward
@@ -1224,13 +1328,24 @@ class DeviceImage:
         bits; only raw and energy cross PCIe; the call waits for them.  ValueError (before any native call): frames of different
         shapes, size no odd integer in 3 .. 255 or above the window, a bad window, regularisation not finite or <= 0, unknown
         coupling; after it: an energy that is not finite or not > 0 (a sharp frame with no gradients, or NaN or inf in it).
-        NativeError (ICS_ENOSUP): a window side + size - 1 above IMG_WIENER_MAX."""
+        NativeError (ICS_ENOSUP): a window side + size - 1 above IMG_WIENER_MAX.
+        mask: a DeviceMask of the frames' shape (one plane with "vector", three with "channel": what `sharp.edge_mask` returns with the
+        same coupling); the derivatives of `sharp` are multiplied by mask[y][x] before the taper, and the energy is summed over what
+        remains -- Cho and Lee's solve around a predicted frame; `blurred` is untouched.  None runs the unmasked code, whose bits an
+        all-ones mask reproduces.  ValueError: a mask that is no DeviceMask, of another shape or number of planes."""
         if not isinstance(sharp, DeviceImage):
             raise ValueError("sharp must be a DeviceImage like the blurred frame, got %s" % (type(sharp).__name__,))
         size, regularisation, _, coupling, (y0, y1, x0, x1) = psf_estimate_args(size, regularisation, 0.0, coupling, window, self.shape, sharp.shape)
         raw, energy = np.empty((size, size, 3), np.float32), np.empty(3, np.float64)
-        _check(load().ics_img_psf_estimate(self._h, sharp._h, y0, y1, x0, x1, size, regularisation, _coupling(coupling),
-                                           raw.ctypes.data_as(C.POINTER(C.c_float)), energy.ctypes.data_as(C.POINTER(C.c_double))))
+        out = (raw.ctypes.data_as(C.POINTER(C.c_float)), energy.ctypes.data_as(C.POINTER(C.c_double)))
+        if mask is None:
+            _check(load().ics_img_psf_estimate(self._h, sharp._h, y0, y1, x0, x1, size, regularisation, _coupling(coupling), *out))
+        else:
+            if not isinstance(mask, DeviceMask):
+                raise ValueError("mask must be a DeviceMask, got %s" % (type(mask).__name__,))
+            if mask.shape != (self.shape[:2] if coupling == "vector" else self.shape):
+                raise ValueError("a mask of shape %s for %s frames and coupling %r" % (mask.shape, self.shape, coupling))
+            _check(load().ics_img_psf_estimate_masked(self._h, sharp._h, mask._h, y0, y1, x0, x1, size, regularisation, _coupling(coupling), *out))
         if not np.isfinite(energy).all():
             raise ValueError("the gradient energy of the sharp frame is not finite: it holds NaN or inf (despeckle first)")
         if not (energy > 0).all():
@@ -1298,9 +1413,86 @@ class DeviceImage:
             raise ValueError("shape %r (H, W at least 1)" % (shape,))
         return self._new(load().ics_img_warp, M.ctypes.data_as(C.POINTER(C.c_double)), int(H), int(W))
 
+    def shock(self, iterations=4, dt=0.4, flat=0.01, coupling="vector", route=0):
+        """`iterations` steps of the shock filter (Osher and Rudin 1990) that Cho and Lee's edge prediction sharpens a latent frame
+        with: out = u - dt s |grad u|, the gradient by minmod of the one-sided differences per channel, the steer s = clamp(L / flat,
+        -1, 1) from the Laplacian L of the luma smoothed by the binomial 1 2 1 each way ("vector": the channels move together;
+        "channel": each by its own smoothed plane); every neighbour read with the edge repeated.  `flat` is the Laplacian at which
+        the steer saturates: below it a flat area moves proportionally less (and a rounding difference cannot flip a sign).  Returns
+        a new DeviceImage.  route 0: the library's choice, 1: a launch per step, 2: IMG_SHOCK_BLOCK steps per launch on LDS tiles;
+        all give identical bits, the float32 evaluation of tests/edges_ref.py (csrc/ics_img_edges.hip).  ValueError (before any
+        native call): iterations negative or no whole number, dt not finite, flat not positive and finite, unknown coupling or
+        route."""
+        iterations, dt, flat, coupling, route = shock_args(iterations, dt, flat, coupling, route)
+        return self._new(load().ics_img_shock, iterations, dt, flat, _coupling(coupling), route)
+
+    def edge_mask(self, per_sector, coupling="vector", route=0):
+        """The gradients of this frame worth trusting, by Cho and Lee's rule: the forward-difference gradients fall into four
+        orientation sectors of 45 degrees, every sector keeps its `per_sector` largest (all it has where it holds fewer), and the
+        smallest of the sectors' thresholds is applied to the whole frame: a picture dominated by one direction still keeps edges
+        across it.  Returns EdgeMask(mask, threshold, kept): a DeviceMask that stays on the device (H x W; "channel": three planes,
+        thresholds and counts, one selection per channel), the float32 threshold t of mask = g >= t, and the pixels kept.  An exact
+        radix select on the device (csrc/ics_img_edges.hip; restated in tests/edges_ref.py: identical bits for both routes).  The
+        call waits for the two numbers.  ValueError: per_sector below 1, unknown coupling or route (before any native call); "no
+        gradients to select" for a frame (or, "channel", a channel) that is constant."""
+        per_sector, coupling, route = edge_mask_args(per_sector, coupling, route)
+        h, t, k = C.c_void_p(), (C.c_float * 3)(), (C.c_uint * 3)()
+        _check(load().ics_img_edge_mask(self._h, per_sector, _coupling(coupling), route, C.byref(h), t, k))
+        mask = DeviceMask(h, self.ctx)
+        if any(math.isnan(v) for v in t):            # a plane without a gradient comes back with a NaN threshold
+            mask.close()
+            raise ValueError("no gradients to select")
+        if coupling == "vector":
+            return EdgeMask(mask, np.float32(t[0]), int(k[0]))
+        return EdgeMask(mask, np.array(list(t), np.float32), tuple(int(v) for v in k))
+
     def close(self):
         if self._h:
             load().ics_img_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class DeviceMask:
+    """ics_mask: byte planes (0 or 1) of a device image's size that live in HBM: what DeviceImage.edge_mask selects and the masked
+    pair solve reads where it lies.  to_host() is for tests and inspection."""
+
+    def __init__(self, handle, ctx):
+        self._h, self.ctx = handle, ctx
+
+    @classmethod
+    def from_host(cls, arr, ctx=None):
+        """a mask from an H x W or H x W x 3 array: non-zero entries are 1"""
+        ctx = ctx or Context.get()
+        arr = np.asarray(arr)
+        if arr.ndim not in (2, 3) or (arr.ndim == 3 and arr.shape[2] != 3) or arr.size == 0:
+            raise ValueError("DeviceMask needs an H x W or H x W x 3 array")
+        planes = np.ascontiguousarray((arr != 0).astype(np.uint8)[None] if arr.ndim == 2 else np.moveaxis((arr != 0).astype(np.uint8), 2, 0))
+        h = C.c_void_p()
+        _check(load().ics_mask_create(ctx._h, arr.shape[0], arr.shape[1], planes.shape[0], _ptr(planes), C.byref(h)))
+        return cls(h, ctx)
+
+    @property
+    def shape(self):
+        H, W, P = C.c_int(), C.c_int(), C.c_int()
+        _check(load().ics_mask_shape(self._h, C.byref(H), C.byref(W), C.byref(P)))
+        return (H.value, W.value) if P.value == 1 else (H.value, W.value, P.value)
+
+    def to_host(self):
+        """the mask as a bool array: H x W, or H x W x 3 for a mask per channel"""
+        shape = self.shape
+        raw = np.empty(((1,) if len(shape) == 2 else (shape[2],)) + shape[:2], np.uint8)
+        _check(load().ics_mask_download(self._h, _ptr(raw)))
+        return raw[0].astype(bool) if len(shape) == 2 else np.ascontiguousarray(np.moveaxis(raw, 0, 2)).astype(bool)
+
+    def close(self):
+        if self._h:
+            load().ics_mask_destroy(self._h)
             self._h = None
 
     def __del__(self):

@@ -520,6 +520,87 @@ def estimate_psf(blurred, sharp, size, regularisation=1e-3, threshold=0.05, coup
     return PsfEstimate(psf, raw, rejected) if info else psf
 
 
+BlindPsf = collections.namedtuple("BlindPsf", "psf levels kept rejected")
+
+
+def blind_psf(src, size, iterations=5, shock=(4, 0.4, 0.01), keep=2.0, regularisation=1e-3, threshold=0.05, balance=0.01, coupling="vector", window=None,
+              info=False):
+    """Not in the reference's lib/utils.py, whose only way to a PSF is the blind Richardson-Lucy loop: the PSF of one blurred picture by
+    the fast alternation of Cho and Lee (2009), milliseconds where the loop takes tenths of a second.  Coarse to fine -- K_0 = size,
+    K_{l+1} = max(3, (K_l // 2) | 1), level l on the window resized to ceil(H / 2^l) x ceil(W / 2^l), levels whose smaller side is below
+    4 K_l dropped -- and on every level `iterations` times: latent = `wiener`(frame, psf, balance) (the frame itself before there is a
+    PSF); p = latent.shock(*shock), the ramps of blurred edges steepened into steps; mask = p.edge_mask(per_sector), the gradients worth
+    trusting, the same number per orientation; raw = frame.psf_raw(p, K_l, regularisation, coupling, mask=mask), the linear solve
+    argmin sum |M d p * k - d frame|^2 + gamma |k|^2; psf = `lib._native.psf_project`(raw, threshold), moved by whole pixels so that its
+    centroid rounds to the centre (`lib._native.psf_centred`: the solve fixes the PSF only up to a shift it shares with p).  per_sector
+    starts at ceil(keep sqrt(H_l W_l) K_l / 4) and grows by 1 / 0.9 per iteration; between levels the PSF is resized like the driver's,
+    clipped at 0 and normalised.  Returns the size x size x 3 float32 PSF, every plane of sum 1; info=True: BlindPsf(psf, levels, kept,
+    rejected) with the (K, H, W) of every level, the pixels its last mask kept and the share of the raw kernel its last projection cut.
+    A `lib._native.DeviceImage` is read where it lies (window (y0, y1, x0, x1), half-open: the region to look at); an H x W x 3 array is
+    uploaded once; per iteration only the K x K x 3 raw kernel crosses to the host; every frame, mask and workspace goes back to the
+    context's pool on every way out.  tests/edges_ref.py restates it.  It serves compact PSFs: it does not recover one-pixel-wide motion
+    lines on small cluttered frames, structures smaller than the PSF, or a blur that varies over the window (README).  ValueError, before
+    anything is uploaded where the arguments show it: size even or outside 3 .. 255, a window smaller than 4 size, bad arguments, a frame
+    that is "not finite: despeckle first", "no gradients to select".  NativeError (ICS_ENOSUP): the transform limits of `wiener`.  There
+    is no CPU fallback."""
+    dev = isinstance(src, _native.DeviceImage)
+    if not dev:
+        arr = np.asarray(src)
+        if arr.ndim != 3 or arr.shape[2] != 3:
+            raise ValueError("expected a DeviceImage or an H x W x 3 array, got shape %s" % (arr.shape,))
+    shape = src.shape if dev else arr.shape
+    size, iterations, shock, keep, regularisation, threshold, balance, coupling, (y0, y1, x0, x1), levels = _native.blind_psf_args(
+        size, iterations, shock, keep, regularisation, threshold, balance, coupling, window, shape)
+    if not dev and not np.isfinite(arr[y0:y1, x0:x1]).all():
+        raise ValueError("the frame is not finite: despeckle first")
+    import contextlib
+    with contextlib.ExitStack() as held:
+        def hold(obj, stack=held):
+            stack.callback(obj.close)
+            return obj
+        if dev:
+            base = src if (y0, y1, x0, x1) == (0, shape[0], 0, shape[1]) else hold(src.crop(y0, y1, x0, x1))
+        else:
+            base = hold(_native.DeviceImage.from_host(np.ascontiguousarray(arr[y0:y1, x0:x1], dtype=np.float32)))
+        H, W = y1 - y0, x1 - x0
+        psf, kept, rejected = None, [], []
+        for K, Hl, Wl in levels:
+            with contextlib.ExitStack() as level:
+                frame = base if (Hl, Wl) == (H, W) else hold(base.resize(Hl, Wl), level)
+                if psf is not None:
+                    up = np.maximum(base.ctx.resize_bicubic(np.ascontiguousarray(psf, dtype=np.float64), (K, K)), 0.0)
+                    psf = np.ascontiguousarray(up / up.sum(axis=(0, 1)), dtype=np.float32)
+                per_sector = float(np.ceil(keep * np.sqrt(Hl * Wl) * K / 4))
+                for _ in range(iterations):
+                    with contextlib.ExitStack() as step:
+                        latent = frame if psf is None else hold(frame.wiener(psf, balance), step)
+                        p = hold(latent.shock(*shock, coupling), step)
+                        try:
+                            got = p.edge_mask(int(np.ceil(per_sector)), coupling)
+                        except ValueError:       # (a NaN spreads over a whole coarse level; on this way out only, the window is looked at)
+                            if not np.isfinite(base.to_host()).all():
+                                raise ValueError("the frame is not finite: despeckle first")
+                            raise
+                        hold(got.mask, step)
+                        try:
+                            raw, _ = frame.psf_raw(p, K, regularisation, coupling, mask=got.mask)
+                        except ValueError as exc:
+                            if "not finite" in str(exc):
+                                raise ValueError("the frame is not finite: despeckle first")
+                            raise
+                    try:
+                        projected, rej = _native.psf_project(raw, threshold)
+                    except ValueError as exc:
+                        if "not finite" in str(exc):
+                            raise ValueError("the frame is not finite: despeckle first")
+                        raise
+                    psf = _native.psf_centred(projected)
+                    per_sector /= 0.9
+                kept.append(got.kept)
+                rejected.append(rej)
+    return BlindPsf(psf, levels, kept, rejected) if info else psf
+
+
 def _estimate_psf_registered(blurred, sharp, size, regularisation, threshold, coupling, window, info, register):
     """estimate_psf(register=...): align `sharp` to `blurred`, warp it to the shape of `blurred`, estimate"""
     b, s, arrays = _pair_on_device(blurred, sharp, ("blurred", "sharp"))

@@ -622,6 +622,45 @@ int ics_img_tv_deconvolve_masked_plan(int H, int W, int K, int *Py, int *Px, siz
 int ics_img_psf_estimate(const ics_img *blurred, const ics_img *sharp, int y0, int y1, int x0, int x1, int K,
                          float regularisation, int coupling, float *raw /* K*K*3 */, double energy[3]);
 int ics_img_psf_estimate_plan(int H, int W, int K, int *Py, int *Px, size_t *workspace_bytes);
+/* Edge prediction on a device image (Cho and Lee 2009): the shock filter that turns the ramps of a blurred frame into steps, and the
+ * choice of the gradients worth trusting, the same number for every orientation (csrc/ics_img_edges.hip; restated in
+ * tests/edges_ref.py, whose float32 evaluation every route gives bit for bit: no FMA, IEEE square roots).
+ * ics_img_shock: `iterations` steps of (Osher and Rudin; every read of a neighbour through coordinates clamped to the picture)
+ *   Y   = ((R + G) + B) * float32(1 / 3) (coupling 1, vector; coupling 0, channel: Y = the channel itself, three times)
+ *   Ys  = the binomial 1 2 1 along x, then along y, of Y: ((a[-1] + a[+1]) + (a[0] + a[0])) * 0.25
+ *   s   = min(max((((Ys[x-1] + Ys[x+1]) + (Ys[y-1] + Ys[y+1])) - 4 Ys) * float32(1 / flat), -1), 1)
+ *   g   = sqrt(m(u - u[x-1], u[x+1] - u)^2 + m(u - u[y-1], u[y+1] - u)^2),  m(p, q) = p q > 0 ? copysign(min(|p|, |q|), p) : 0
+ *   out = u - (dt s) g                                        per channel u
+ * route 1: a launch per step; 2: ICS_IMG_SHOCK_BLOCK steps per launch on LDS tiles; 0: the library's choice.  Queued like
+ * the other image filters; src is not written.  ICS_EINVAL: iterations < 0, dt or flat not finite or flat <= 0, unknown coupling
+ * or route.
+ * ics_img_edge_mask: forward differences gx, gy per channel (0 in the last column / row);
+ *   coupling 1: g = sqrt((q0 + q1) + q2), q_c = gx_c^2 + gy_c^2, sx = (gx0 + gx1) + gx2, sy likewise: one mask;
+ *   coupling 0: g = sqrt(q_c), sx = gx_c, sy = gy_c: three independent masks;
+ *   sector: none where g is not > 0; 0 where |sy| <= 0.41421357f |sx|; 2 where |sx| <= 0.41421357f |sy|; else 1 if sx sy > 0, else 3;
+ *   t_b = the per_sector-th largest g of sector b, its smallest where it holds fewer; t = the smallest t_b of the sectors that hold
+ *   any; mask = g >= t.  An exact radix select on the device, as in ics_img_noise_estimate.
+ * *out: an ics_mask of H x W bytes per plane, one plane (coupling 1) or three (coupling 0), 0 or 1; threshold[c], kept[c]: t and the
+ * pixels of the mask per plane (coupling 1: in all three slots).  route 1: every pass forms g from the frame; 2: the first pass stores
+ * keys and sectors (4 + 1 bytes per pixel and plane, the bytes in the mask itself); 0: the library's choice.  The frame is taken to be
+ * finite.  Like ics_img_noise_estimate it copies its results back and waits.  A plane that has no pixel with g > 0 has nothing to
+ * select: its threshold comes back as NaN (the bits 0xFFFFFFFF), its mask all 0 and its count 0 -- the Python layer raises "no gradients
+ * to select" on it.  ICS_EINVAL: a NULL pointer, per_sector < 1, unknown coupling or route. */
+#define ICS_IMG_SHOCK_BLOCK 4
+typedef struct ics_mask ics_mask;
+int ics_img_shock(const ics_img *src, int iterations, float dt, float flat, int coupling, int route, ics_img **out);
+int ics_img_edge_mask(const ics_img *src, unsigned per_sector, int coupling, int route, ics_mask **out, float threshold[3], unsigned kept[3]);
+int ics_mask_create(ics_ctx *ctx, int H, int W, int planes /* 1 or 3 */, const unsigned char *host /* planes * H * W, 0 or 1 */, ics_mask **out);
+int ics_mask_shape(const ics_mask *m, int *H, int *W, int *planes);
+int ics_mask_download(const ics_mask *m, unsigned char *host /* planes * H * W */);
+void ics_mask_destroy(ics_mask *m);
+/* ics_img_psf_estimate with the sharp frame's derivatives multiplied by mask[y][x] before the taper (Cho and Lee's
+ * argmin sum |M d p * k - d b|^2 + gamma |k|^2 around a predicted frame p): the energy S is summed over what remains, `blurred` is
+ * untouched.  mask: of the frames' shape and context, one plane with coupling 1, three with coupling 0 (what ics_img_edge_mask makes
+ * with the same coupling); the window applies to it as to the frames.  An all-ones mask gives the bits of ics_img_psf_estimate.
+ * ICS_EINVAL: as ics_img_psf_estimate, and a NULL mask, one of another shape, context or number of planes. */
+int ics_img_psf_estimate_masked(const ics_img *blurred, const ics_img *sharp, const ics_mask *mask, int y0, int y1, int x0, int x1, int K,
+                                float regularisation, int coupling, float *raw /* K*K*3 */, double energy[3]);
 /* Registration of two device images and the projective warp of one.  M, 3 x 3 row-major with M[8] = 1, takes a pixel (x, y, 1) of
  * `fixed` to the position (u, v) = (M0 . p, M1 . p) / (M2 . p) in `moving`.  ics_img_align finds it by coarse-to-fine Gauss-Newton on the
  * luma of both frames (forward-additive Lucas-Kanade, Levenberg's damping), with a gain a and a bias b where photometric != 0: the

@@ -1,6 +1,6 @@
 """Timing of the lib/utils.py filters on one seeded SIZE x SIZE RGB float32 picture (GPU box), one JSON line:
 
-    python scripts/filters_timing.py [SIZE=4096] [guided | llf | noise | despeckle | blurwidth | mask | wiener | tvdeconv | tvmasked | psf | align]       (a section name: that section alone)
+    python scripts/filters_timing.py [SIZE=4096] [guided | llf | noise | despeckle | blurwidth | mask | wiener | tvdeconv | tvmasked | psf | align | blindfast]       (a section name: that section alone)
 
   resident   the filters on a DeviceImage in HBM (csrc/ics_img_filters.hip): device time of the kernels (HIP events around them,
              ics_ctx_last_kernel_ms; warm, median of 25) and wall time of the queued call up to a stream synchronise
@@ -84,6 +84,13 @@
              lumas, 8 for the pass); a whole align of the frame and of the window of 1023 x 1023 pixels at (1537, 1539): the levels, the
              pool bytes, the steps taken, wall ms of the call and ms per step; a warp of the frame by a small homography: kernel ms and
              TB/s on 24 B/px; beside them DeviceImage.copy() of the frame
+  blindfast  the parts of the fast blind PSF (csrc/ics_img_edges.hip) on a smoothed random SIZE x SIZE frame and on its windows of 255^2, 511^2 and
+             1023^2 pixels: DeviceImage.shock (4 steps, dt 0.4, flat 0.01) per route and coupling, DeviceImage.edge_mask (per_sector
+             = 2 sqrt(H W) 15 / 4) per route and coupling -- kernel ms, median and minimum of 9 rounds in which the routes alternate,
+             the mask's wall time (it waits for its threshold), "auto" what route=0 takes --, and on the 1023^2 window at K = 31 and the
+             255^2 window at K = 15 DeviceImage.psf_raw with the predictor's mask beside the plain one; a whole lib.utils.blind_psf on the
+             255^2 window at K = 15 and on the 1023^2 window at K = 31 (defaults: wall ms of the call, median and minimum of 5, its levels
+             and the peak device bytes of its plan); beside them DeviceImage.copy()
   checks     the resident USM must not take longer than the three float64 calls, in kernel time and in wall time (a guard against a
              broken kernel, not a target); the exit status is 1 if one of them fails
 Starts no child process; a job script puts its own time limit around it."""
@@ -511,6 +518,86 @@ def psf_section(ctx):
     return res
 
 
+BLINDFAST_SHOCK = (4, 0.4, 0.01)
+
+
+def blindfast_section(ctx, size):
+    from scipy.ndimage import uniform_filter
+    rng = np.random.default_rng(0)
+    pic = uniform_filter(rng.random((size, size, 3), dtype=np.float32), size=(7, 7, 1), mode="nearest")
+    img = _native.DeviceImage.from_host(pic, ctx)
+    del pic
+    res = {"shock": list(BLINDFAST_SHOCK), "copy": copy_row(img, ctx)}
+    names = {1: "route1", 2: "route2", 0: "auto"}
+    for side in (255, 511, 1023, size):
+        if side > size:
+            continue
+        o = (size - side) // 2 | 1
+        win = img.crop(o, o + side, o, o + side) if side < size else img
+        row = res["%dx%d" % (side, side)] = {}
+        per_sector = int(np.ceil(2.0 * side * 15 / 4))
+        for coupling in ("vector", "channel"):
+            times = {1: [], 2: [], 0: []}
+            for route in times:
+                win.shock(*BLINDFAST_SHOCK, coupling, route).close()          # warm
+            ctx.synchronize()
+            for _ in range(REPS_DESPECKLE):
+                for route in times:
+                    out = win.shock(*BLINDFAST_SHOCK, coupling, route)
+                    ctx.synchronize()
+                    times[route].append(ctx.last_kernel_ms())
+                    out.close()
+            for route, ms in times.items():
+                row["shock_%s_%s" % (coupling, names[route])] = {"kernel_ms": round(float(np.median(ms)), 4), "min_ms": round(float(np.min(ms)), 4)}
+            p = win.shock(*BLINDFAST_SHOCK, coupling)
+            times, wall = {1: [], 2: [], 0: []}, {1: [], 2: [], 0: []}
+            for route in times:
+                got = p.edge_mask(per_sector, coupling, route)                # warm
+                got.mask.close()
+            for _ in range(REPS_DESPECKLE):
+                for route in times:
+                    t0 = time.perf_counter()
+                    got = p.edge_mask(per_sector, coupling, route)
+                    wall[route].append((time.perf_counter() - t0) * 1e3)
+                    times[route].append(ctx.last_kernel_ms())
+                    got.mask.close()
+            for route, ms in times.items():
+                row["mask_%s_%s" % (coupling, names[route])] = {"kernel_ms": round(float(np.median(ms)), 4), "min_ms": round(float(np.min(ms)), 4),
+                                                              "wall_ms": round(float(np.median(wall[route])), 4)}
+            row["mask_%s_kept" % coupling] = got.kept
+            K = {255: 15, 1023: 31}.get(side)
+            if K:
+                m = p.edge_mask(per_sector, coupling)
+                for name, mask in (("psf_raw_masked", m.mask), ("psf_raw_plain", None)):
+                    win.psf_raw(p, K, 1e-3, coupling, mask=mask)              # warm
+                    kernel = []
+                    for _ in range(REPS_DESPECKLE):
+                        win.psf_raw(p, K, 1e-3, coupling, mask=mask)
+                        kernel.append(ctx.last_kernel_ms())
+                    row["%s_%s_K_%d" % (name, coupling, K)] = {"kernel_ms": round(float(np.median(kernel)), 4), "min_ms": round(float(np.min(kernel)), 4)}
+                m.mask.close()
+            p.close()
+        if win is not img:
+            win.close()
+    for side, K in ((255, 15), (1023, 31)):                     # a whole blind_psf on a window of the frame, read where it lies
+        if side > size:
+            continue
+        o = (size - side) // 2 | 1
+        window = (o, o + side, o, o + side)
+        got = utils.blind_psf(img, K, window=window, info=True)  # warm
+        wall = []
+        for _ in range(REPS_F64):
+            ctx.synchronize()
+            t0 = time.perf_counter()
+            utils.blind_psf(img, K, window=window)
+            wall.append((time.perf_counter() - t0) * 1e3)
+        res["blind_psf_%dx%d_K_%d" % (side, side, K)] = {"wall_ms": round(float(np.median(wall)), 3), "min_ms": round(float(np.min(wall)), 3),
+                                                       "levels": [list(v) for v in got.levels], "steps": 5 * len(got.levels),
+                                                       "peak_mb": round(_native.blind_psf_plan(side, side, K).peak_bytes / 2 ** 20, 1)}
+    img.close()
+    return res
+
+
 ALIGN_WINDOW = (1537, 2560, 1539, 2562)
 ALIGN_SUMS_BYTES, ALIGN_WARP_BYTES = 40, 24
 
@@ -577,6 +664,9 @@ def main():
         return 0
     if sys.argv[2:] == ["align"]:
         print(json.dumps({"device": ctx.name, "align": align_section(ctx)}))
+        return 0
+    if sys.argv[2:] == ["blindfast"]:
+        print(json.dumps({"size": size, "device": ctx.name, "blindfast": blindfast_section(ctx, size)}))
         return 0
     if sys.argv[2:] == ["wiener"]:
         print(json.dumps({"device": ctx.name, "wiener": wiener_section(ctx)}))
