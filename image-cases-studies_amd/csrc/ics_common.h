@@ -113,6 +113,12 @@ struct IcsDebug {
   std::atomic<int> fft_fused;         // ICS_FFT_FUSED         0 = the FFT-tile pipeline runs A11 and A13 as two kernels (k_conv_fft<0> + k_gradk_fft) instead of the fused three-transform unit
   std::atomic<int> fft_conv2;         // ICS_FFT_CONV2         0 = the FFT-tile pipeline runs A1 and A3 as two kernels; 1 (default) = as one unit per tile pair (k_conv_fft<2>) for the PSF sizes it pays for; 2 = wherever it is built
   std::atomic<int> fft_psf1;          // ICS_FFT_PSF1          0 = blind runs on the tiles step the PSF with k_psf + k_fft_spectrum instead of the one launch k_psf_spectra
+  std::atomic<int> fft_maxg;          // ICS_FFT_MAXG          0 = every mode-2 launch of the shipped loop reads u and ut in its epilogue (k_conv_fft<2>); 1 (default) = on frames of 6 Mpx and more, max u comes from the update pass and max |g| from k_maxg_select (k_conv_fft<3>); 2 = wherever mode 2 runs
+  std::atomic<int> key_trace;         // (test hook)           1 = ics_rl_run keeps a copy of the reduction keys of every inner iteration (queued device-to-device copies behind the update pass), read with ics_debug_key_trace
+  std::atomic<int> maxg_scanned;      // (read-only report)    (tile, channel) pairs the selection kernel of the last run's last operand-free launch scanned; -1: the run had none
+  std::atomic<int> maxg_pairs;        // (read-only report)    ... of this many; maxg_total / maxg_launches: the same summed over the run's launches, and their number
+  std::atomic<int> maxg_total;
+  std::atomic<int> maxg_launches;
   std::atomic<int> fft_rot;           // ICS_FFT_ROT           0 = mode 2 of the tiles walks its units from the first tile row (the last, partial round is then the bottom row's four-transform units)
   std::atomic<int> small_iter;        // ICS_SMALL_ITER        0 = small frames run the multi-launch families instead of the cooperative iteration kernel (ics_small.hip); 2 = 64-pixel tiles too; default 1, 0 under rocprofv3
   std::atomic<int> fail_small_launch; // (test hook)           1 = the next cooperative launch of the small-frame kernel is refused once (the job falls back to the multi-launch path)
@@ -138,6 +144,9 @@ struct IcsDebug {
     fft_conv2 = env_int("ICS_FFT_CONV2", 1);
     fft_rot = env_int("ICS_FFT_ROT", 1);
     fft_psf1 = env_int("ICS_FFT_PSF1", 1);
+    fft_maxg = env_int("ICS_FFT_MAXG", 1);
+    key_trace = 0;
+    maxg_scanned = -1; maxg_pairs = 0; maxg_total = 0; maxg_launches = 0;
     // (a process that has made a cooperative launch under rocprofv3 -- ROCm 7.2, rocprofiler-sdk tool library preloaded -- crashes in its exit handlers AFTER the
     //  profiler has written its output: exit code 139 for an otherwise complete run.  Under an attached profiler the small frames therefore stay on the
     //  multi-launch families unless ICS_SMALL_ITER=1 asks for the cooperative kernel explicitly)

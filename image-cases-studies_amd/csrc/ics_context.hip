@@ -22,7 +22,7 @@ static std::atomic<int>* debug_switch(const char* name) {
   const struct { const char* n; std::atomic<int>* v; } tab[] = {
       {"max_wgs", &d.max_wgs}, {"dynamic_tiles", &d.dynamic_tiles}, {"conv_rs", &d.conv_rs}, {"conv_path", &d.conv_path},
       {"fused_gradk", &d.fused_gradk}, {"update_kernel", &d.update_kernel}, {"fused_rs", &d.fused_rs},
-      {"planar_image", &d.planar_image}, {"pam_exact", &d.pam_exact}, {"fail_window_alloc", &d.fail_window_alloc}, {"pool_limit_mb", &d.pool_limit_mb}, {"overlap", &d.overlap}, {"fft_gradk", &d.fft_gradk}, {"fft_fused", &d.fft_fused}, {"fft_conv2", &d.fft_conv2}, {"fft_rot", &d.fft_rot}, {"fft_psf1", &d.fft_psf1}, {"small_iter", &d.small_iter}, {"small_trace", &d.small_trace}, {"fail_small_launch", &d.fail_small_launch},
+      {"planar_image", &d.planar_image}, {"pam_exact", &d.pam_exact}, {"fail_window_alloc", &d.fail_window_alloc}, {"pool_limit_mb", &d.pool_limit_mb}, {"overlap", &d.overlap}, {"fft_gradk", &d.fft_gradk}, {"fft_fused", &d.fft_fused}, {"fft_conv2", &d.fft_conv2}, {"fft_rot", &d.fft_rot}, {"fft_psf1", &d.fft_psf1}, {"fft_maxg", &d.fft_maxg}, {"key_trace", &d.key_trace}, {"maxg_scanned", &d.maxg_scanned}, {"maxg_pairs", &d.maxg_pairs}, {"maxg_total", &d.maxg_total}, {"maxg_launches", &d.maxg_launches}, {"small_iter", &d.small_iter}, {"small_trace", &d.small_trace}, {"fail_small_launch", &d.fail_small_launch},
       {"pool_check", &d.pool_check}, {"pool_overruns", &d.pool_overruns}, {"pool_selftest", &d.pool_selftest}};
   for (auto& t : tab)
     if (strcmp(t.n, name) == 0) return t.v;

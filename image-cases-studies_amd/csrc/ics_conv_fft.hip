@@ -1,7 +1,9 @@
-// ics_conv_fft.hip -- transform tiles (ics_fft_tile.h): the convolutions k_conv_fft<0|1|2> and, for wide PSFs, k_conv_fft_blk<0|1>, the image
+// ics_conv_fft.hip -- transform tiles (ics_fft_tile.h): the convolutions k_conv_fft<0|1|2> (and, built by ics_conv_fft_sel.hip from this file, the
+// operand-free mode-2 instance k_conv_fft<3>) and, for wide PSFs, k_conv_fft_blk<0|1>, the image
 // spectra of mode 2, the weight spectra (k_fft_spectrum; with the PSF step in front of them: k_psf_spectra), and the arguments every tile kernel is launched with (ics_conv_fft_fill_args).
 #include "ics_fft_tile.h"
 #include "ics_psf_step.h"
+#include "ics_maxg_select.h"
 #include <algorithm>
 #include <cassert>
 #include <mutex>
@@ -9,14 +11,18 @@
 
 namespace icsfft {
 
+// MODE 3 = mode 2 without the epilogue's operands (ics_maxg_select.h; instantiated in ics_conv_fft_sel.hip alone): the same units and the same
+// stored values; instead of the maxima of A6 / A7 it records max |gradu| per tile and wave (a.c.dofkeys: [unit][tile][wave]) and per channel
+// (a.c.sched: three words) -- two pointers of IcsConvArgs no tile kernel reads otherwise, so that IcsFftArgs keeps its layout.
 template <int MODE, bool TV>
 __global__ __launch_bounds__(ICS_FFT_THREADS) void k_conv_fft(IcsFftArgs a) {
+  constexpr bool M2 = MODE >= 2, SEL = MODE == 3;
   extern __shared__ __attribute__((aligned(16))) v2f lds[];
   v2f* const twl = lds + ICS_FFT_P * ICS_FFT_PITCH;
   const int tid = threadIdx.x;
   const int G = gridDim.x;
   if (tid < ICS_FFT_TW_ENTRIES) twl[tid] = tw128((tid / ICS_FFT_TWS) * (tid % ICS_FFT_TWS));
-  const Mem mem = make_mem(a, MODE);
+  const Mem mem = make_mem(a, M2 ? 2 : MODE);
   // workgroup b runs on XCD b % 8 (observed dispatch): consecutive unit slots q go to one XCD, so the three channel units of a tile pair
   // (n = 3 pair + c) share that XCD's L2.  Affects speed only.
   const int q = (G & 7) ? (int)blockIdx.x : (int)(blockIdx.x & 7) * (G >> 3) + (int)(blockIdx.x >> 3);
@@ -38,7 +44,7 @@ __global__ __launch_bounds__(ICS_FFT_THREADS) void k_conv_fft(IcsFftArgs a) {
     lds_barrier();
     stage_b<1>(lds, opaque(tid));
     lds_barrier();
-    if (MODE == 2) {
+    if (M2) {
       // A1 + A3 in one unit (see stage_d2_half): interior tiles stay in the frequency domain between the two convolutions
       if (!unit_is_border(a, u)) {
         v2f fs[2][8], s0[8], s1[8];
@@ -93,14 +99,14 @@ __global__ __launch_bounds__(ICS_FFT_THREADS) void k_conv_fft(IcsFftArgs a) {
     stage_d(sp, lds, opaque(tid));
     wave_sync();
     }
-    load_window(a, mem, decode_unit(a, walk_unit(a, k + G)), opaque(tid), pw, 0, MODE == 0 ? 2 : 1);   // next unit (beyond the last one: dropped accesses); mode 1 holds 64 operand registers through stage G and requests the second tile behind it
+    load_window(a, mem, decode_unit(a, walk_unit(a, k + G)), opaque(tid), pw, 0, (MODE == 0 || SEL) ? 2 : 1);   // next unit (beyond the last one: dropped accesses); mode 1 holds 64 operand registers through stage G and requests the second tile behind it
     stage_e(lds, lds, twl, opaque(tid));
     v4f fimg[2][4];
     Ops ops;
     if (MODE == 0) load_image(a, mem, u, opaque(tid), fimg);
-    else {
-      load_ops<TV, MODE == 2>(a, mem, u, opaque(tid), 0, ops);
-      load_ops<TV, MODE == 2>(a, mem, u, opaque(tid), 1, ops, 0, 1);   // (stages F and G leave registers for the first row group of tile 1's operands)
+    else if (!SEL) {
+      load_ops<TV, M2>(a, mem, u, opaque(tid), 0, ops);
+      load_ops<TV, M2>(a, mem, u, opaque(tid), 1, ops, 0, 1);   // (stages F and G leave registers for the first row group of tile 1's operands)
     }
     lds_barrier();
     stage_b<-1>(lds, opaque(tid));
@@ -110,7 +116,7 @@ __global__ __launch_bounds__(ICS_FFT_THREADS) void k_conv_fft(IcsFftArgs a) {
     // row-quad epilogue, row group by row group (at most one group's raw values alive beside the operands).  Mode 1 has two operand
     // frames: it requests those of the second tile here and takes its maxima in a second pass, and the second tile of the next unit's
     // window goes out between the passes (registers: 128 per thread with 1024 of them).
-    if (MODE >= 1) load_ops<TV, MODE == 2>(a, mem, u, opaque(tid), 1, ops, 1, 4);
+    if (MODE >= 1 && !SEL) load_ops<TV, M2>(a, mem, u, opaque(tid), 1, ops, 1, 4);
     Maxima mx; maxima_init(mx);
     v4f res[4][2];
     // lane address and row-group count of the two tiles ONCE per unit (as eight store_quad calls the address arithmetic of the epilogue
@@ -119,9 +125,22 @@ __global__ __launch_bounds__(ICS_FFT_THREADS) void k_conv_fft(IcsFftArgs a) {
     QuadOut qo[2];
     const int te = opaque(tid);
 #pragma unroll
-    for (int t = 0; t < 2; ++t) qo[t].vo = quad_lane<MODE == 2>(a, u, mem.lay, te, t, qo[t].rows, qo[t].X);
-    const bool edge = unit_is_edge<MODE == 2>(a, u);
-    if (MODE == 0) {
+    for (int t = 0; t < 2; ++t) qo[t].vo = quad_lane<M2>(a, u, mem.lay, te, t, qo[t].rows, qo[t].X);
+    const bool edge = unit_is_edge<M2>(a, u);
+    uint32_t tg[2] = {0u, 0u};   // (SEL) bits of max |gradu| over this thread's valid pixels of the two tiles
+    if (SEL) {
+      // no operands: a row group leaves as soon as its maximum is taken -- of the value that is stored, so a pixel outside the region counts as the 0 it is stored as
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        read_quads(lds, opaque(tid), i, res[i]);
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {
+          if (edge) { tg[t] = quad_absmax(a, qo[t], true, i, res[i][t], tg[t]); store_quad_at(a, mem, qo[t], true, i, res[i][t]); }
+          else { tg[t] = quad_absmax(a, qo[t], false, i, res[i][t], tg[t]); store_quad_at(a, mem, qo[t], false, i, res[i][t]); }
+        }
+        asm volatile("" ::: "memory");
+      }
+    } else if (MODE == 0) {
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         read_quads(lds, opaque(tid), i, res[i]);
@@ -164,7 +183,16 @@ __global__ __launch_bounds__(ICS_FFT_THREADS) void k_conv_fft(IcsFftArgs a) {
       lds_barrier();
       stage_a(lds, opaque(tid));
     }
-    if (MODE >= 1) {   // (u.c is uniform)
+    if (SEL) {   // the tile maxima of this wave: lane 0 stores them (no atomic inside the loop), the workgroup keeps the channel's
+#pragma unroll
+      for (int t = 0; t < 2; ++t) {
+        const uint32_t wg = ics_wave_max_u32(tg[t]);
+        store_wave_key(a.c.dofkeys, (tid & 63) == 0 ? (n * 2 + t) * (ICS_FFT_THREADS / 64) + (tid >> 6) : ICS_FFT_NONE, wg);
+#pragma unroll
+        for (int c = 0; c < 3; ++c)
+          if (u.c == c) accg[c] = accg[c] > wg ? accg[c] : wg;
+      }
+    } else if (MODE >= 1) {   // (u.c is uniform)
       uint32_t kg, ku;
       maxima_keys(mx, kg, ku);
 #pragma unroll
@@ -172,7 +200,11 @@ __global__ __launch_bounds__(ICS_FFT_THREADS) void k_conv_fft(IcsFftArgs a) {
         if (u.c == c) { accg[c] = accg[c] > kg ? accg[c] : kg; accu[c] = accu[c] > ku ? accu[c] : ku; }
     }
   }
-  if (MODE >= 1) {
+  if (SEL) {   // (accg is wave-uniform already)
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+      if ((tid & 63) == 0 && accg[c] > a.c.sched[c]) atomicMax(a.c.sched + c, accg[c]);
+  } else if (MODE >= 1) {
     // the workgroup's maxima: wave maxima -> one conditional atomic per wave, channel and value at the END of the kernel (inside the loop
     // the read of the running maximum waited for every store in flight)
 #pragma unroll
@@ -186,6 +218,16 @@ __global__ __launch_bounds__(ICS_FFT_THREADS) void k_conv_fft(IcsFftArgs a) {
   }
 }
 
+#ifdef ICS_FFT_SEL_UNIT
+// ics_conv_fft_sel.hip: this unit builds k_conv_fft<3, false> and its launcher, and nothing else.  An instance more in the unit of the
+// others moves their register allocation (ics_fft_tile.h, head), so the operand-free instance lives alone.
+}  // namespace icsfft
+hipError_t ics_launch_conv_fft_sel(const IcsFftArgs& a, hipStream_t s) {
+  static std::atomic<bool> configured[ICS_MAX_DEVICES];
+  if (!a.spec1 || !a.fspec || !a.c.dofkeys || !a.c.sched || a.c.tv) return hipErrorInvalidValue;
+  return ics_fft_launch(configured, icsfft::k_conv_fft<3, false>, ics_fft_grid(ics_device_cus(ics_current_device()), a.nunits), s, a);
+}
+#else
 // ---- PSF sizes above ICS_FFT_MAX_K: tap blocks on the tiles -----------------------------------------------------------------------------------
 // A tile keeps 128 - K + 1 of its 128 pixels a side: 32 at 97, nothing at 129.  A convolution is linear in its taps, so the K x K PSF is cut
 // into blk_n x blk_n blocks of blk_k x blk_k taps (blk_k <= 65) and block (qa, qb) is the blk_k x blk_k kernel on the window that starts
@@ -612,9 +654,12 @@ hipError_t ics_launch_fft_image_spectrum(const float* f, const IcsGeom& g, float
 }
 // c: in = u = the u mirror's origin, out = the back-projection's, f = the image's, ut, red, lambd as for mode 1; spec_conv / spec_corr = the two
 // weight spectra; fspec = the image spectra of THIS image and geometry
-hipError_t ics_launch_conv2_fft(const IcsConvArgs& c, const float* spec_conv, const float* spec_corr, const float* fspec, hipStream_t s) {
+// wkeys + gmax (both or neither): the operand-free instance k_conv_fft<3> (ics_conv_fft_sel.hip; shipped loop), which takes no maxima of g and u
+// but leaves max |gradu| per (unit, tile, wave) in wkeys -- ics_conv2_fft_units(g) * 2 * 16 words -- and raises the three words of gmax
+hipError_t ics_launch_conv2_fft(const IcsConvArgs& c, const float* spec_conv, const float* spec_corr, const float* fspec, hipStream_t s, uint32_t* wkeys, uint32_t* gmax) {
   IcsFftArgs a;
   ics_conv_fft_fill_args(2, c, spec_conv, &a);
+  if ((wkeys != nullptr) != (gmax != nullptr)) return hipErrorInvalidValue;
   a.spec1 = reinterpret_cast<const v2f*>(spec_corr); a.fspec = const_cast<float*>(fspec);
   // Where the static walk starts: the units of the outer ring take four transforms instead of two (about 1.6 of a unit's time), and a walk from
   // the first tile row ends on the last one -- the final, partial round of units is then made of the heaviest units (4096^2 / 15: 86 units of
@@ -657,8 +702,18 @@ hipError_t ics_launch_conv2_fft(const IcsConvArgs& c, const float* spec_conv, co
     }
   }
   if (a.rot < 0 || a.rot >= a.nunits) a.rot = 0;   // (a start point outside the list would drop units; any inside it only reorders the walk)
+  if (wkeys) { a.c.dofkeys = wkeys; a.c.sched = gmax; return ics_launch_conv_fft_sel(a, s); }
   return ics_launch_conv_fft_args(2, a, s);
 }
+// the tile grid of mode 2 on this geometry, for the selection kernel behind the operand-free instance (ics_maxg_select.h)
+void ics_conv2_fft_select_grid(const IcsGeom& g, IcsMaxgSelectArgs* m) {
+  IcsConvArgs c; memset(&c, 0, sizeof c); c.g = g;
+  IcsFftArgs a;
+  ics_conv_fft_fill_args(2, c, nullptr, &a);
+  m->ntiles = a.ntiles; m->tiles_x = a.tiles_x; m->Vy = a.Vy; m->V = a.V; m->ext_y = a.ext_y; m->ext_x = a.ext_x;
+  m->uM = g.uM; m->uN = g.uN; m->ppitch = ics_ppitch(g); m->plane = ics_plane_floats(g);
+}
+int ics_conv2_fft_units(const IcsGeom& g) { return (int)(ics_conv2_fft_fspec_floats(g) / ((size_t)8 * ICS_FFT_THREADS * 4)); }
 // ---- tap blocks (PSF sizes above ICS_FFT_MAX_K) ------------------------------------------------------------------------------------------------
 // the fewest blocks per axis whose size stays at 65 or below (2 to 129, 3 to 193, 4 to 255)
 bool ics_conv_fft_blk_supported(int K) { return K > ICS_FFT_MAX_K && K <= 255 && (K & 1); }
@@ -677,3 +732,4 @@ hipError_t ics_launch_conv_fft_blk(int mode, const IcsConvArgs& c, const float* 
   auto k1 = icsfft::k_conv_fft_blk<1>;
   return ics_fft_launch(configured[mode], mode == 0 ? k0 : k1, ics_fft_grid(ics_device_cus(ics_current_device()), a.nunits), s, a);
 }
+#endif   // ICS_FFT_SEL_UNIT

@@ -2,6 +2,7 @@
 // tile kernel shares (constants, buffer access, arguments, unit decode, loads, stages A-G, epilogues, the launch helper).  The kernels:
 //   ics_conv_fft.hip      k_conv_fft<0|1|2, TV>, k_conv_fft_blk<0|1> (tap blocks, PSF sizes above ICS_FFT_MAX_K), k_fft_image_spectrum,
 //                         k_fft_spectrum; ics_conv_fft_fill_args and the convolutions' launchers
+//   ics_conv_fft_sel.hip  k_conv_fft<3, false>: mode 2 without the epilogue's operands (ics_maxg_select.h), compiled from ics_conv_fft.hip in a unit of its own
 //   ics_gradk_fft.hip     k_gradk_fft, k_synth_gradk_fft, k_gradk_fft_reduce[_blk] and their launchers
 //   (k_conv_fft_blk stays in the unit of k_conv_fft: compiled in a unit of its own, both families came out with other registers and
 //    another instruction order -- the optimiser's result for a kernel depends on which other kernels share its module)
@@ -656,6 +657,20 @@ ICS_FFT_HD void store_quad_at(const IcsFftArgs& a, const Mem& mem, const QuadOut
   }
   st_f32x4(mem.out, i < q.rows ? q.vo : ICS_FFT_NONE, 32 * i * mem.lay.pitch, val);
 }
+// k_conv_fft<3>: `acc` raised to the largest |.| bits among the pixels of row group i that store_quad_at stores as they are (a pixel it stores as
+// zero, or a dropped row group, counts as nothing).  The integer maximum of the bits is Maxima::ag's: a NaN ranks above inf.
+ICS_FFT_HD uint32_t quad_absmax(const IcsFftArgs& a, const QuadOut& q, bool edge, int i, v4f val, uint32_t acc) {
+  if (edge) {
+    const int X = q.X;
+    val = (v4f){X >= a.ox0 ? val.x : 0.f, (X + 1 >= a.ox0 && X + 1 < a.ox1) ? val.y : 0.f, (X + 2 >= a.ox0 && X + 2 < a.ox1) ? val.z : 0.f, X + 3 < a.ox1 ? val.w : 0.f};
+  }
+  uint32_t m = 0u;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) m = __builtin_elementwise_max(m, fbits(val[e]) & 0x7FFFFFFFu);
+  return __builtin_elementwise_max(acc, i < q.rows ? m : 0u);
+}
+// ... and word `idx` of the launch's array of wave maxima (ICS_FFT_NONE: no access), unconditionally issued like every access of the unit loop
+ICS_FFT_HD void store_wave_key(uint32_t* keys, int idx, uint32_t v) { st_f32(make_gbuf(keys), idx, 0, __builtin_bit_cast(float, v)); }
 // Fused A11 + A13 unit: the residual of row group i, e' = r - image (pyx:563-565) on the tile's valid pixels inside the M x N interior and
 // exact zeros everywhere else of the 128 x 128 tile (what k_gradk_fft reads back from the residual frame), goes back into the slots it
 // was read from -- the operand of the second forward transform -- and, for tiles under the stop-test window, to the residual frame.
@@ -787,6 +802,7 @@ __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(
 // ---- host side: arguments, grid, launch ------------------------------------------------------------------------------------------------------
 // the region and valid part of `mode`, then ics_fft_tile_grid (ics_conv_fft.hip)
 void ics_conv_fft_fill_args(int mode, const IcsConvArgs& c, const float* spec, IcsFftArgs* a, int blk_n = 0, int blk_k = 0);
+hipError_t ics_launch_conv_fft_sel(const IcsFftArgs& a, hipStream_t s);   // k_conv_fft<3, false> (ics_conv_fft_sel.hip); `a` as ics_launch_conv2_fft fills it
 // One persistent workgroup per CU, capped by the max_wgs debug switch and by the number of units.  triples: the PSF-gradient kernels, whose
 // workgroups keep one channel each (blockIdx % 3) -- a multiple of three, three at least.
 static inline int ics_fft_grid(int cus, int nunits, bool triples = false) {

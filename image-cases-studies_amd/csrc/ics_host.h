@@ -143,6 +143,16 @@ struct ics_rl {
   float* fspec;         // mode 2 of the tile convolutions (A1 + A3 in one unit): the image windows' spectra, valid while fspec_valid
   bool fspec_valid;
   bool conv2_off;       // the spectra did not fit the device memory once: this job runs A1 and A3 as two kernels from then on
+  // mode 2 without the epilogue's operands (Route::maxg; ics_maxg_select.h): the device words of a run and the tile maxima of a launch, allocated
+  // by the first run that takes the route.  mgs_ready: an update pass of THIS run has recorded max u and Dmax into set mgs_set, so the next mode-2
+  // launch may be the operand-free one; cleared when a run starts (its first launch reads its operands) -- and a run that ends through undo() ends.
+  uint32_t *mgs, *mgs_wave;
+  bool mgs_ready;
+  int mgs_set;
+  // debug switch key_trace: the reduction slot every update pass of the last run read, one copy of ICS_RED_STRIDE words per inner iteration
+  // (the first ICS_KEY_TRACE_SLOTS of them), for ics_debug_key_trace
+  uint32_t* ktrace;
+  int ktrace_n;
   bool fft_on;
   bool plf_valid;                       // the mirror of the image frame still mirrors it (every writer of j->f calls image_changed)
   // small frames (ics_small.hip): the inner iterations of an outer one as a cooperative launch
@@ -203,6 +213,7 @@ static inline uint32_t* dof_of(ics_rl* j) { return j->dofkeys + 4 * j->par; }
 // the accumulator-order copies of the image follow the image frame: every writer of j->f calls this
 static inline void image_changed(ics_rl* j) { j->facc_valid[0] = j->facc_valid[1] = false; j->negf_valid = false; j->plf_valid = false; j->fspec_valid = false; }
 
+#define ICS_KEY_TRACE_SLOTS 64
 #define ICS_PSF_MAX 255   // PSF sizes: odd, 3 ... ICS_PSF_MAX (psf_supported, ics_route.hip)
 
 // Device allocation, zero-filled ON THE GIVEN STREAM: the job's stream is non-blocking, so a
@@ -298,6 +309,7 @@ struct Route {
   bool image_acc;       // the residual's epilogues read the accumulator-order copy of the image where their tile height has one (ics_image_acc.h)
   bool acc_order;       // ... and a run of these parameters does (ics_rl_route.image_in_accumulator_order)
   bool psf1;            // internal (not in ics_rl_route): blind inner iterations of a tile run step the PSF and build both spectra in one launch (k_psf_spectra)
+  bool maxg;            // internal (not in ics_rl_route): mode-2 launches behind an update pass of the run take no operands -- max u from that pass, max |g| from k_maxg_select
   bool overlap;         // the statistics of outer iteration i on the second stream beside iteration i + 1; else a drain at every outer boundary
 };
 

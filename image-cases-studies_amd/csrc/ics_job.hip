@@ -35,6 +35,9 @@ extern "C" void ics_rl_destroy(ics_rl* j) {
   if (j->spec_conv) j->ctx->pool.release(j->spec_conv);
   if (j->spec_corr) j->ctx->pool.release(j->spec_corr);
   if (j->fspec) j->ctx->pool.release(j->fspec);
+  if (j->mgs) j->ctx->pool.release(j->mgs);
+  if (j->mgs_wave) j->ctx->pool.release(j->mgs_wave);
+  if (j->ktrace) j->ctx->pool.release(j->ktrace);
   for (int i = 0; i < 2; ++i) { if (j->ev_body[i]) hipEventDestroy(j->ev_body[i]); if (j->ev_stats[i]) hipEventDestroy(j->ev_stats[i]); }
   if (j->h_scal) hipHostFree(j->h_scal);
   for (hipEvent_t e : j->ev) hipEventDestroy(e);
@@ -250,6 +253,19 @@ extern "C" int ics_rl_read(ics_rl* j, int which, float* host, size_t count) {
   }
   HIPCHK(hipStreamSynchronize(s));
   return ICS_OK;
+}
+
+// for the tests, beside ics_debug_set and like it outside the public header: the reduction keys (ICS_RED_STRIDE words per slot) the update
+// passes of the last ics_rl_run read, inner iteration by inner iteration, while the debug switch key_trace was on.  Returns the number of
+// slots written to `host` (at most `slots`), or a negative error code.
+extern "C" int ics_debug_key_trace(ics_rl* j, uint32_t* host, int slots) {
+  if (!j || !host || slots < 0) { (void)ics_set_error(ICS_EINVAL, "NULL argument"); return -1; }
+  int n = j->ktrace_n < ICS_KEY_TRACE_SLOTS ? j->ktrace_n : ICS_KEY_TRACE_SLOTS;
+  if (n > slots) n = slots;
+  if (!j->ktrace || n == 0) return 0;
+  if (hipSetDevice(j->ctx->device) != hipSuccess || hipStreamSynchronize(j->ctx->stream) != hipSuccess ||
+      hipMemcpy(host, j->ktrace, (size_t)n * ICS_RED_STRIDE * 4, hipMemcpyDeviceToHost) != hipSuccess) { (void)hipGetLastError(); (void)ics_set_error(ICS_EHIP, "key trace: copy failed"); return -1; }
+  return n;
 }
 
 extern "C" int ics_rl_write(ics_rl* j, int which, const float* host, size_t count) {

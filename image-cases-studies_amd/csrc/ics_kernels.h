@@ -98,7 +98,15 @@ hipError_t ics_launch_conv_fft_region(const IcsConvArgs& c, const float* spec, i
 size_t ics_conv2_fft_fspec_floats(const IcsGeom& g);
 bool ics_conv2_fft_supported(const IcsGeom& g);
 hipError_t ics_launch_fft_image_spectrum(const float* f, const IcsGeom& g, float* fspec, hipStream_t s);
-hipError_t ics_launch_conv2_fft(const IcsConvArgs& c, const float* spec_conv, const float* spec_corr, const float* fspec, hipStream_t s);
+hipError_t ics_launch_conv2_fft(const IcsConvArgs& c, const float* spec_conv, const float* spec_corr, const float* fspec, hipStream_t s, uint32_t* wkeys = nullptr, uint32_t* gmax = nullptr);
+// the operand-free form of mode 2 with the kernels beside it (ics_maxg_select.h; ics_conv_fft_sel.hip, ics_maxg_select.hip): the update pass that
+// records, into one set `rec` of the ICS_MGS_* words, the key of max u_c and the bits of max |(u_new - ut)/2| per channel over the frame it
+// writes (alias_next: the next majoriser is that frame, 0 recorded), and the selection kernel behind the launch
+hipError_t ics_launch_update_planar_rec(const IcsUpdateArgs& a, uint32_t* rec, int alias_next, hipStream_t s);
+struct IcsMaxgSelectArgs;
+int ics_conv2_fft_units(const IcsGeom& g);                                          // work units of mode 2 on this geometry
+void ics_conv2_fft_select_grid(const IcsGeom& g, IcsMaxgSelectArgs* m);             // fills the tile grid and the plane layout of *m
+hipError_t ics_launch_maxg_select(const IcsMaxgSelectArgs& m, hipStream_t s);
 // A12 + A13 on the same tiles (fp32): u, e = origins of planar mirrors; partial = ics_gradk_fft_blocks(cus) * K * K floats of scratch
 int ics_gradk_fft_blocks(int cus);
 hipError_t ics_launch_gradk_fft(const float* u, const float* e, const IcsGeom& g, float* partial, float* gradk, hipStream_t s);

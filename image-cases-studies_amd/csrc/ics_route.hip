@@ -13,7 +13,7 @@ bool ics_host::psf_supported(int K) { return ics_conv_supported(K) || ics_big_su
 // ---- routing ------------------------------------------------------------------------------------------------------------------------
 // Which kernels a run or a stage launches is decided in ONE place, resolve_route (below check_params), from the geometry, the parameters,
 // the weight tables the job owns, its sticky fallbacks and the routing switches (ics_common.h IcsDebug: conv_path, fused_gradk,
-// planar_image, fft_gradk, fft_fused, fft_conv2, fft_psf1, small_iter, overlap -- read nowhere else).  ics_rl_run and ics_rl_stage resolve it once and
+// planar_image, fft_gradk, fft_fused, fft_conv2, fft_psf1, fft_maxg, small_iter, overlap -- read nowhere else).  ics_rl_run and ics_rl_stage resolve it once and
 // hand it to the do_* helpers, which dispatch on it; ics_rl_describe copies it.  Family numbers: those of ics_rl_route (include/ics_hip.h); the Route itself: ics_host.h.
 
 // The FFT-tile pipeline (ics_conv_fft.hip; round 5): A1 / A3 / A11 as LDS-resident 128 x 128 overlap-save transforms on planar mirrors,
@@ -61,6 +61,7 @@ static bool fft_mirror_fits(const IcsGeom& g) { return ics_planar_floats(g) * si
 // 31: 0.184 -> 0.230 / 0.306 -> 0.351;  4096^2 9: 0.572 -> 0.470 / 0.775 -> 0.668;  15: 0.581 -> 0.518 / 0.797 -> 0.714 (another box: 0.576 -> 0.485 / 0.794 -> 0.686);
 // 21: 0.600 -> 0.561 / 0.828 -> 0.774;  25: level / 0.867 -> 0.859;  31: 0.636 -> 0.735 / 0.909 -> 0.990.
 static constexpr int ICS_CONV2_MAX_K = 25;
+static constexpr long ICS_MAXG_MIN_PX = 6000000L;   // mode 2 without the epilogue's operand reads (Route::maxg): u-frame pixels from which it is the default
 
 int ics_host::check_params(ics_rl* j, const ics_rl_params* p) {
   if (!p) return ics_set_error(ICS_EINVAL, "params is NULL");
@@ -148,6 +149,15 @@ Route ics_host::resolve_route(const ics_rl* j, const ics_rl_params* p, bool in_r
   // ics_rl_run, shipped loop, PSF sizes the tiles take whole.  Tap blocks, the two-kernel gradient, the PAM kinds, single stages and every other
   // route keep k_psf + k_fft_spectrum; ICS_FFT_PSF1=0 restores that pair here too.
   r.psf1 = in_run && r.tiles && shipped && r.gradk == GK_FUSED_TILES && ics_conv_fft_supported(K) && sw(d.fft_psf1) != 0;
+
+  // Mode 2 of the tiles without the epilogue's operand reads (ics_maxg_select.h): inside ics_rl_run, shipped loop -- the update pass in front of a
+  // launch records max u and max |(u - ut)/2|, the launch is the operand-free instance k_conv_fft<3>, and k_maxg_select behind it takes max |g| on the
+  // tiles that can hold it.  The PAM kinds, single stages and every other route keep k_conv_fft<2>; ICS_FFT_MAXG=0 restores it here too.
+  // By default from 6 Mpx on, where the launch is short of bytes: bench.py, parent -> this route, ms per inner iteration, 4096^2 / 15 blind 0.643 -> 0.613,
+  // non-blind 0.452 -> 0.425; at 2048^2 / 15 (--conv fft, blind) the launch is two and a half rounds of units and gains 1 us, the recording update pass
+  // costs 3.5 us more than k_update_planar: 0.237 -> 0.239.  ICS_FFT_MAXG=2: wherever mode 2 runs (the tests' small frames).
+  const int maxg_sw = sw(d.fft_maxg);
+  r.maxg = in_run && r.conv2 && shipped && !fuse && (maxg_sw == 2 || (maxg_sw == 1 && px >= ICS_MAXG_MIN_PX));
 
   // Small frames (ics_small.hip): every (tile, channel) of the u-frame on a compute unit of its own, the operands of the five inner iterations
   // resident in LDS, ONE cooperative launch per outer iteration instead of 25 - 30.  What ICS_CONV_AUTO picks for the shipped loop when the

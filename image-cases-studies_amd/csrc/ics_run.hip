@@ -8,6 +8,7 @@
 // Once per outer iteration: ut = u (D2D), window statistics + FFT whiteness metric (A18/A19), one
 // 64-byte D2H of the scalars, and the stop decision on the host (pyx:643-654).
 #include "ics_host.h"
+#include "ics_maxg_select.h"
 
 using namespace ics_host;
 
@@ -117,7 +118,9 @@ static int do_conv_fft(ics_rl* j, int mode, const ics_rl_params* p, int slot, Pr
 // which pays for small PSFs.  Inside ics_rl_run only (the residual frame is not produced: the statistics' window of it comes from a
 // window-sized launch of mode 0 where the loop does not rewrite it anyway), shipped loop only.
 // (Under AUTO up to ICS_CONV2_MAX_K, with the measurements it was set from: ics_route.hip.)
-static int do_conv2(ics_rl* j, const ics_rl_params* p, int slot, Prof& pr) {
+// Route::maxg: behind an update pass of the run (ics_rl::mgs_ready) the launch is the operand-free instance, with k_maxg_select behind it inside
+// the same bracket; the first launch of a run has no such pass in front of it and reads its operands like every launch did.
+static int do_conv2(ics_rl* j, const Route& r, const ics_rl_params* p, int slot, Prof& pr) {
   if (!j->fspec) RC(dalloc(j->ctx, &j->fspec, ics_conv2_fft_fspec_floats(j->g), false));
   if (!j->fspec_valid) {
     if (!porg(j, j->f)) return ics_set_error(ICS_ESTATE, "FFT pipeline: the image has no planar mirror");
@@ -136,6 +139,16 @@ static int do_conv2(ics_rl* j, const ics_rl_params* p, int slot, Prof& pr) {
   }
   if (!a.in || !a.out || !a.f || !a.ut) return ics_set_error(ICS_ESTATE, "FFT pipeline: a frame has no planar mirror");
   RC(pr.begin(ICS_K_SYNTH_BACKPROJECT));
+  if (r.maxg && j->mgs_ready) {
+    IcsMaxgSelectArgs m;
+    memset(&m, 0, sizeof m);
+    ics_conv2_fft_select_grid(j->g, &m);
+    m.gradu = a.out; m.u = a.u; m.ut = a.ut; m.wkeys = j->mgs_wave; m.state = j->mgs; m.red = a.red; m.lambd = p->lambd; m.set = j->mgs_set;
+    HIPCHK(ics_launch_conv2_fft(a, j->spec_conv, j->spec_corr, j->fspec, j->ctx->stream, j->mgs_wave, j->mgs + ICS_MGS_GMAX + 4 * j->mgs_set));
+    HIPCHK(ics_launch_maxg_select(m, j->ctx->stream));
+    j->mgs_set ^= 1;        // (the selection kernel has zeroed the other set: the update pass behind this launch records into it)
+    j->mgs_ready = false;
+  } else
   HIPCHK(ics_launch_conv2_fft(a, j->spec_conv, j->spec_corr, j->fspec, j->ctx->stream));
   RC(pr.end());
   return ICS_OK;
@@ -190,7 +203,8 @@ static int do_conv(ics_rl* j, const Route& r, int mode, const ics_rl_params* p, 
   return ICS_OK;
 }
 
-static int do_update(ics_rl* j, const Route& r, const ics_rl_params* p, int slot, int want_dof, Prof& pr) {
+// (alias_next: the next back-projection's majoriser will be the frame this pass writes -- the last inner iteration of an outer one)
+static int do_update(ics_rl* j, const Route& r, const ics_rl_params* p, int slot, int want_dof, Prof& pr, int alias_next = 0) {
   IcsUpdateArgs a;
   a.u = org(j, j->u); a.ut = org(j, ut_of(j)); a.g = org(j, j->gr); a.f = org(j, j->f);
   a.u_out = org(j, j->ut_is_u ? j->u2 : j->u);
@@ -203,10 +217,18 @@ static int do_update(ics_rl* j, const Route& r, const ics_rl_params* p, int slot
     a.u = porg(j, j->u); a.ut = porg(j, ut_of(j)); a.g = porg(j, j->gr); a.f = porg(j, j->f);
     a.u_out = porg(j, j->ut_is_u ? j->u2 : j->u); a.f_rw = nullptr;
     if (!a.u || !a.ut || !a.g || !a.f || !a.u_out) return ics_set_error(ICS_ESTATE, "FFT pipeline: a frame has no planar mirror");
+    if (r.maxg) {   // max u and Dmax of the frame this pass writes, for the operand-free mode-2 launch behind it (set mgs_set: zeroed)
+      HIPCHK(ics_launch_update_planar_rec(a, j->mgs + 8 * j->mgs_set, alias_next, j->ctx->stream));
+      j->mgs_ready = true;
+    } else
     HIPCHK(ics_launch_update_planar(a, j->ctx->stream));
   } else
   HIPCHK(ics_launch_update(a, j->ctx->stream));
   RC(pr.end());
+  if (j->ktrace && j->ktrace_n < ICS_KEY_TRACE_SLOTS) {   // (debug switch key_trace; outside the bracket: the chain of brackets breaks, as for every unbracketed launch)
+    HIPCHK(hipMemcpyAsync(j->ktrace + (size_t)j->ktrace_n++ * ICS_RED_STRIDE, a.red, ICS_RED_STRIDE * 4, hipMemcpyDeviceToDevice, j->ctx->stream));
+    pr.unchain();
+  }
   if (j->ut_is_u) {  // rotate: the untouched old u is the majoriser now, the stale ut frame becomes the spare
     float* old_ut = j->ut;
     j->ut = j->u; j->u = j->u2; j->u2 = old_ut;
@@ -448,6 +470,14 @@ static int prepare_route(ics_rl* j, const ics_rl_params* p, FftScope& fft_scope,
     // mode 2's image spectra are 1.6 frames more (128 KB per unit): when they do not fit, the run takes A1 and A3 as two kernels instead
     if (r.conv2 && !j->fspec && dalloc(j->ctx, &j->fspec, ics_conv2_fft_fspec_floats(j->g), false) != ICS_OK) { j->fspec = nullptr; j->conv2_off = true; r.conv2 = false; (void)hipGetLastError(); }
   }
+  // the operand-free mode-2 launches: a few state words and the tile maxima of a launch; where they do not fit, the run keeps k_conv_fft<2>
+  j->mgs_ready = false; j->mgs_set = 0;
+  if (r.maxg && !r.conv2) r.maxg = false;
+  if (r.maxg) {
+    if (!j->mgs && dalloc(j->ctx, &j->mgs, (size_t)ICS_MGS_WORDS, false) != ICS_OK) { j->mgs = nullptr; r.maxg = false; (void)hipGetLastError(); }
+    if (r.maxg && !j->mgs_wave && dalloc(j->ctx, &j->mgs_wave, (size_t)ics_conv2_fft_units(j->g) * 2 * ICS_MGS_WAVES, false) != ICS_OK) { j->mgs_wave = nullptr; r.maxg = false; (void)hipGetLastError(); }
+    if (r.maxg) HIPCHK(hipMemsetAsync(j->mgs, 0, (size_t)ICS_MGS_WORDS * sizeof(uint32_t), s));
+  }
   if (r.small && ensure_small(j, r.plan) != ICS_OK) { r.small = false; (void)hipGetLastError(); }   // (AUTO's choice: the multi-launch path needs nothing more)
   if (r.small) { HIPCHK(hipMemsetAsync(j->small_bar, 0, (size_t)ICS_SMALL_BAR_WORDS * sizeof(unsigned long long), s)); j->small_gen = 0; j->small_bak = false; }
   *out = r;
@@ -494,7 +524,7 @@ struct RunLoop {
       Prof& pr = (p->profile > 0 && inner_done % p->profile == 0) ? pr_on : pr_off;
       if (r.conv2) {
         if (tv) RC(do_tvterm(j, r, p, itt, pr));              // (PAM kinds: T of u, read by the back-projection's epilogue)
-        RC(do_conv2(j, p, itt, pr));                          // A1 + A2 + A3 (+A7) in one unit per tile pair; the residual frame is not written ...
+        RC(do_conv2(j, r, p, itt, pr));                       // A1 + A2 + A3 (+A7) in one unit per tile pair; the residual frame is not written ...
         if (!p->blind && last) RC(do_conv_fft_window(j, p, pr));   // ... so the statistics' window of it is (blind: A11 rewrites it, do_synth_gradk_fft)
       } else {
       if (!have_e) RC(do_conv(j, r, 0, p, itt, 0, pr));       // A1+A2
@@ -505,7 +535,7 @@ struct RunLoop {
       if (p->blind) {                                         // pyx:555
         if (fuse) RC(do_conv(j, r, 2, p, itt, last, pr));     // A5-A10 fused with A11
         else {
-          RC(do_update(j, r, p, itt, last, pr));
+          RC(do_update(j, r, p, itt, last, pr, last));
           if (fused_gk) RC(do_synth_gradk(j, r, p, 0, pr));   // A11 + A12 + A13, e' stays on chip
           else if (fused_fft) RC(do_synth_gradk_fft(j, p, 0, pr));   // the same on the transform tiles
           else RC(do_conv(j, r, 0, p, itt, 0, pr));
@@ -516,7 +546,7 @@ struct RunLoop {
         RC(do_conv(j, r, 2, p, itt, 0, pr));                  // A5-A10 fused with A1+A2 of itt+1
         have_e = true;
       } else {
-        RC(do_update(j, r, p, itt, last, pr));                // A5,A6,A8,A10 (outer boundary: stats need u and e)
+        RC(do_update(j, r, p, itt, last, pr, last));          // A5,A6,A8,A10 (outer boundary: stats need u and e)
       }
       ++inner_done;
     }
@@ -673,6 +703,10 @@ extern "C" int ics_rl_run(ics_rl* j, const ics_rl_params* p, ics_rl_stats* st) {
     st->trace_M_r = in.trace_M_r; st->trace_Hu = in.trace_Hu; st->trace_varu = in.trace_varu; st->trace_dof_min = in.trace_dof_min; st->trace_dof_max = in.trace_dof_max;
   }
   j->ut_is_u = false;
+  j->ktrace_n = 0;
+  if (ics_debug().key_trace.load(std::memory_order_relaxed)) {
+    if (!j->ktrace) RC(dalloc(j->ctx, &j->ktrace, (size_t)ICS_KEY_TRACE_SLOTS * ICS_RED_STRIDE));
+  } else if (j->ktrace) { j->ctx->pool.release(j->ktrace); j->ktrace = nullptr; }
   RunLoop run{j, p, st, r, s, tv, Prof{j, p->profile != 0}, Prof{j, false}};
   j->ev_used = 0; j->ev_pairs.clear(); j->ev_chain = -1;
   {   // the job's small state in one launch: flags, the tile counters (the kernels re-arm them; an aborted launch must not leak a count), the
@@ -693,7 +727,20 @@ extern "C" int ics_rl_run(ics_rl* j, const ics_rl_params* p, ics_rl_stats* st) {
   HIPCHK(hipEventRecord(j->ev_end, s));
   int hflags[4] = {0, 0, 0, 0};
   HIPCHK(hipMemcpyAsync(hflags, j->flags, sizeof hflags, hipMemcpyDeviceToHost, s));
+  uint32_t hmgs[4] = {0u, 0u, 0u, 0u};   // (Route::maxg: the selection kernel's counts, reported through the debug interface)
+  if (run.r.maxg) HIPCHK(hipMemcpyAsync(hmgs, j->mgs + ICS_MGS_SCANNED, sizeof hmgs, hipMemcpyDeviceToHost, s));
   HIPCHK(hipStreamSynchronize(s));
+  if (run.r.maxg) {
+    IcsDebug& d = ics_debug();
+    IcsMaxgSelectArgs m;
+    ics_conv2_fft_select_grid(j->g, &m);
+    d.maxg_scanned.store(hmgs[3] ? (int)hmgs[j->mgs_set ^ 1] : -1, std::memory_order_relaxed);      // (the set of the last launch: do_conv2 has moved on)
+    d.maxg_pairs.store(3 * m.ntiles, std::memory_order_relaxed);
+    d.maxg_total.store((int)hmgs[2], std::memory_order_relaxed); d.maxg_launches.store((int)hmgs[3], std::memory_order_relaxed);
+  } else if (run.r.conv2) {   // (a mode-2 run on the operand-reading launches)
+    IcsDebug& d = ics_debug();
+    d.maxg_scanned.store(-1, std::memory_order_relaxed); d.maxg_total.store(0, std::memory_order_relaxed); d.maxg_launches.store(0, std::memory_order_relaxed);
+  }
   float total = 0.f;
   HIPCHK(hipEventElapsedTime(&total, j->ev_begin, j->ev_end));
   st->iterations_done = run.it; st->stopped = run.stop; st->has_nan = hflags[1];
@@ -785,7 +832,7 @@ extern "C" int ics_rl_stage(ics_rl* j, int stage, const ics_rl_params* p) {
         return ics_set_error(ICS_ENOSUP, "ICS_STAGE_SYNTH_BACKPROJECT needs params.conv = ICS_CONV_FFT, tv_mode 0 and a PSF of at most 57 x 57");
       RC(pack_weights(j, 0, 0.f, 0, s));
       HIPCHK(hipMemsetAsync(j->red, 0, 8 * ICS_RED_STRIDE * sizeof(uint32_t), s));
-      RC(do_conv2(j, p, 0, pr));
+      RC(do_conv2(j, r, p, 0, pr));
       break;
     case ICS_STAGE_PSF_UPDATE: RC(do_psf(j, r, p, pr)); break;
     case ICS_STAGE_MAJORIZE: RC(do_majorize(j, pr)); break;
