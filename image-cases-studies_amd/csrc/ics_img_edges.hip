@@ -549,8 +549,10 @@ hipError_t ics_launch_img_edge_mask(const float* f, int H, int W, unsigned per_s
   // persistent workgroups, as many per CU as their histograms leave room for: 32 KB "vector", 96 KB "channel"
   const int per_cu = coupling ? 4 : 1;
   auto wgs = [&](long units, int k) {
-    const long cap = (long)(cus > 0 ? cus : 256) * k;
-    return dim3((unsigned)(units < cap ? units : cap));
+    long grid = (long)(cus > 0 ? cus : 256) * k;
+    if (units < grid) grid = units;
+    if (const int m = ics_debug().max_wgs.load(std::memory_order_relaxed); m > 0 && grid > m) grid = m;   // test hook: several tiles per workgroup on small frames
+    return dim3((unsigned)grid);
   };
   e = hipMemsetAsync(blk, 0, ics_img_edge_block_words() * sizeof(unsigned), s);
   if (e != hipSuccess) return e;

@@ -283,8 +283,10 @@ hipError_t ics_launch_img_noise(const float* f, int H, int W, int coupling, int 
   // 70 912 B in k_img_ns_keys, 24 576 B in k_img_ns_hist; no kernel needs more than 128 registers, four workgroups per CU
   const int rec_per_cu = coupling ? 4 : 3, keys_per_cu = coupling ? 4 : 2, hist_per_cu = 4;
   auto wgs = [&](long units, int per_cu) {
-    const long cap = (long)(cus > 0 ? cus : 256) * per_cu;
-    return dim3((unsigned)(units < cap ? units : cap));
+    long grid = (long)(cus > 0 ? cus : 256) * per_cu;
+    if (units < grid) grid = units;
+    if (const int m = ics_debug().max_wgs.load(std::memory_order_relaxed); m > 0 && grid > m) grid = m;   // test hook: several tiles per workgroup on small frames
+    return dim3((unsigned)grid);
   };
   hipError_t e = hipMemsetAsync(blk, 0, ics_img_noise_block_words() * sizeof(unsigned), s);
   if (e != hipSuccess) return e;

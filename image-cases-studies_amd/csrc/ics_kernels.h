@@ -312,7 +312,7 @@ hipError_t ics_launch_img_wavelet(const float* f, int H, int W, int scales, cons
 // ics_img_noise_block_words words (histograms and state; zeroed by the launcher); afterwards the words from
 // ics_img_noise_result_word on hold the medians' bit patterns, three ("channel") or one ("vector").  route 1: every pass recomputes
 // the detail from the frame, keys unused; 2: the first pass writes the keys (ics_img_noise_key_words words), the later ones read them.
-// cus: compute units of the device (the persistent grids are sized by it).  f is only read.
+// cus: compute units of the device (the persistent grids are sized by it and capped by the max_wgs switch).  f is only read.
 size_t ics_img_noise_block_words();
 size_t ics_img_noise_result_word();
 size_t ics_img_noise_key_words(int H, int W, int coupling, int route);
@@ -324,6 +324,7 @@ hipError_t ics_launch_img_noise(const float* f, int H, int W, int coupling, int 
 // ICS_IMG_SHOCK_BLOCK steps per launch on LDS tiles.  edge mask: blk: ics_img_edge_block_words words (zeroed by the launcher), afterwards
 // the words from ics_img_edge_result_word on hold three threshold bit patterns (0xFFFFFFFF: the plane has no gradients) and three counts;
 // keys: ics_img_edge_key_words words (route 2); mask: H W bytes per plane, 1 ("vector") or 3 ("channel") planes.  src / f are only read.
+// cus: compute units of the device (the persistent grids of the mask's kernels are sized by it and capped by the max_wgs switch).
 #define ICS_IMG_SHOCK_BLOCK 4   // (== include/ics_hip.h)
 size_t ics_img_shock_block_lds();
 int ics_img_shock_frames(int iterations, int route);

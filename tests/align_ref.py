@@ -45,6 +45,7 @@ from wiener_ref import dead_leaves
 MODELS = {"translation": 2, "affine": 6, "homography": 8}
 PARAMS = {"translation": (2, 5), "affine": (0, 1, 2, 3, 4, 5), "homography": (0, 1, 2, 3, 4, 5, 6, 7)}   # entries of A (row-major) a step moves
 TILE, LANES = 32, 64            # csrc/ics_img_align.hip ALT, ALLANES
+SUMS_BAND = 8 * TILE           # rows of a plane whose products `sums` holds at a time (the float64 sum over the tiles goes band by band)
 MIN_SIDE, AUTO_SIDE, MAX_LEVELS = 16, 64, 8
 MIN_COVERAGE = 0.25
 LAMBDA0 = 1e-6
@@ -177,9 +178,13 @@ def sums(T, I, A, model, photometric, gain=1.0, bias=0.0, dtype=np.float64):
     J, r, valid = rows(T, I, A, model, photometric, gain, bias, dtype)
     n = J.shape[-1]
     iu = np.triu_indices(n)
+    tot = None
     with np.errstate(all="ignore"):
-        prod = np.concatenate([J[..., iu[0]] * J[..., iu[1]], J * r[..., None], (r * r)[..., None]], axis=-1)
-        tot = _tile_sum(prod)
+        for y in range(0, J.shape[0], SUMS_BAND):                    # whole tile rows at a time: a large frame's products need not all exist at once
+            Jb, rb = J[y:y + SUMS_BAND], r[y:y + SUMS_BAND]
+            prod = np.concatenate([Jb[..., iu[0]] * Jb[..., iu[1]], Jb * rb[..., None], (rb * rb)[..., None]], axis=-1)
+            band = _tile_sum(prod)
+            tot = band if tot is None else tot + band
     S = np.zeros((n, n))
     S[iu] = tot[:len(iu[0])]
     S = S + np.triu(S, 1).T
@@ -426,6 +431,24 @@ def recovered(model, blur, dtype=np.float64):
 SUMS_CASES = [((31, 33), (31, 33), None), ((64, 96), (64, 96), None), ((97, 121), (97, 121), None), ((97, 121), (97, 121), (5, 90, 9, 108)),
               ((64, 96), (80, 100), None)]
 SUMS_GAIN, SUMS_BIAS = 1.1, -0.03
+# ... and where the reduction over the tiles (k_img_al_reduce: 1024 lanes, parts = 1024 // ns per slot entry, eight tiles a trip while
+# t + 7 parts < tiles, then one at a time) runs both loop forms: (frame, model, photometric), one per variant with 8 parts < tiles < 9 parts --
+# every lane makes one eight-wide trip, the lanes below tiles - 8 parts a tail step as well -- and one where the lanes make ten trips, or nine and a tail of seven.
+# ns = 7, 16, 29, 46, 46, 67; tests/test_trip_counts.py holds the shapes to this.
+SUMS_TRIP_CASES = [((1100, 1070), "translation", False), ((720, 710), "translation", True), ((530, 520), "affine", False), ((430, 400), "affine", True),
+                   ((430, 400), "homography", False), ((340, 330), "homography", True), ((1100, 1070), "homography", True)]
+
+
+@functools.lru_cache(maxsize=None)
+def sums_trip_reference(case, dtype=np.float64):
+    """(moving, fixed, M, (S, g, sum r^2, count)) of a trip case, computed once"""
+    shape, model, photometric = SUMS_TRIP_CASES[case]
+    moving, fixed = sums_pair(shape, shape)
+    M = sums_matrix(shape, shape, None)
+    ref = sums_on_window(moving, fixed, M, None, model, photometric, SUMS_GAIN, SUMS_BIAS, dtype)
+    for a in ref[:2]:
+        a.setflags(write=False)
+    return moving, fixed, M, ref
 
 
 def sums_matrix(shape_f, shape_m, window):

@@ -124,6 +124,21 @@ def test_the_float32_sums_stay_within_a_quarter_of_the_gate(case):
             assert eS <= ar.GATE / 4 and eg <= ar.GATE / 4 and er <= ar.GATE / 4
 
 
+@pytest.mark.parametrize("case", range(len(ar.SUMS_TRIP_CASES)))
+def test_the_float32_sums_of_the_trip_cases_stay_within_a_quarter_of_the_gate(case):
+    """the frames of up to 1190 tiles on which the device's reduction runs both loop forms: float32 sums per tile and a float64 sum over
+    the tiles do not grow with the frame, so the quarter holds as on the small ones"""
+    shape, model, photometric = ar.SUMS_TRIP_CASES[case]
+    _, _, _, (S, g, rr, n) = ar.sums_trip_reference(case)
+    _, _, _, (S32, g32, rr32, n32) = ar.sums_trip_reference(case, np.float32)
+    d = np.sqrt(np.diag(S))
+    assert (d > 0).all() and n > 0.5 * shape[0] * shape[1]
+    eS, eg, er = (np.abs(S32 - S) / np.outer(d, d)).max(), (np.abs(g32 - g) / (d * np.sqrt(rr))).max(), abs(rr32 / rr - 1)
+    print("%s, %s, photometric %s: S %.2g, g %.2g, r^2 %.2g of the gate's unit; count %d" % (shape, model, photometric, eS, eg, er, n))
+    assert n32 == n
+    assert eS <= ar.GATE / 4 and eg <= ar.GATE / 4 and er <= ar.GATE / 4
+
+
 @pytest.mark.parametrize("shape_s,shape_o", ar.WARP_CASES)
 def test_the_float32_warp_stays_within_a_quarter_of_the_gate(shape_s, shape_o):
     src = ar.warp_source(shape_s)

@@ -211,3 +211,46 @@ def test_device_image_operations_match_numpy():
         di = _native.DeviceImage.from_host(px)
         assert np.array_equal(di.to_host(), px.astype(np.float32))
         di.close()
+
+
+@pytest.mark.gpu
+def test_gamma_and_integer_upload_past_one_step_of_the_grid_stride_loop():
+    """k_img_gamma and k_int_to_f32 (csrc/ics_img.hip) run on at most 65 536 blocks of 256 lanes: above 16 777 216 values a lane takes a
+    second one, which deblur_module does on every picture of 5.6 Mpx and more.  2368 x 2368 x 3 = 16 822 272 values, 45 056 of them in the
+    second step; checked on the whole frame and on that tail by itself, which must also have been changed."""
+    import trips_ref as tr
+    from lib import _native
+    H, W = tr.STRIDE_FRAME
+    once = 65536 * 256
+    assert once < H * W * 3 < 2 * once
+    rng = np.random.default_rng(6)
+    for dt, top in ((np.uint8, 255), (np.uint16, 65535)):
+        px = rng.integers(0, top + 1, size=(H, W, 3), dtype=dt)
+        px.reshape(-1)[[once - 1, once, -1]] = top, top - 1, top
+        di = _native.DeviceImage.from_host(px)
+        got = di.to_host()
+        di.close()
+        assert got.dtype == np.float32 and got.shape == px.shape
+        assert np.array_equal(got.reshape(-1)[once:], px.reshape(-1)[once:].astype(np.float32)) and got.reshape(-1)[once:].min() >= 0 and got.reshape(-1)[once:].max() == top
+        assert np.array_equal(got, px.astype(np.float32))
+    # the driver's decode of that 16-bit picture, in place on the resident frame: (v / 65535) ^ (1 / 2.2)
+    d = _native.DeviceImage.from_host(px)
+    d.gamma(65535, 1 / 2.2)
+    dec, ref = d.to_host(), (got / np.float32(65535)) ** np.float32(1 / 2.2)
+    d.close()
+    tail = lambda v: v.reshape(-1)[once:]                                                # noqa: E731
+    err, err_tail = np.abs(dec - ref).max(), np.abs(tail(dec) - tail(ref)).max()
+    print("gamma(65535, 1 / 2.2) on %d values: max |device - numpy| %.3g, past value %d %.3g (gate %.3g)" % (dec.size, err, once, err_tail, GAMMA_GATE))
+    assert err < GAMMA_GATE and err_tail < GAMMA_GATE
+    assert (tail(dec) != tail(got)).mean() > 0.99                                        # the second step was taken (only 0 stays 0)
+    # ... and its encode, on a frame that gives the clip work on both sides: clip(v, 0, 1) ^ 2.2 x 65535
+    a = dec * np.float32(1.25) - np.float32(0.125)
+    d = _native.DeviceImage.from_host(a)
+    d.gamma(1.0, 2.2, 65535, clip01=True)
+    enc, ref = d.to_host(), np.clip(a / np.float32(1.0), 0, 1) ** np.float32(2.2) * np.float32(65535)
+    d.close()
+    err, err_tail = np.abs(enc - ref).max(), np.abs(tail(enc) - tail(ref)).max()
+    print("gamma(1, 2.2, 65535, clip) on %d values: max |device - numpy| %.3g, past value %d %.3g (gate %.3g)" % (enc.size, err, once, err_tail, GAMMA_CLIP_GATE))
+    assert (tail(a) < 0).any() and (tail(a) > 1).any() and tail(enc).min() == 0 and tail(enc).max() == 65535
+    assert err < GAMMA_CLIP_GATE and err_tail < GAMMA_CLIP_GATE
+    assert (tail(enc) != tail(a)).mean() > 0.99

@@ -57,6 +57,27 @@ def test_align_sums_match_the_float64_specification(case, model, photometric):
     assert eS <= ar.GATE and eg <= ar.GATE and er <= ar.GATE
 
 
+@pytest.mark.parametrize("case", range(len(ar.SUMS_TRIP_CASES)))
+def test_align_sums_where_the_reduction_runs_both_loop_forms(case):
+    """ar.SUMS_TRIP_CASES: per variant a frame whose tiles number between 8 and 9 times the reduction's parts, so that every lane makes
+    one eight-wide trip and some a tail step too, and the widest variant on 1190 tiles (ten trips, or nine and a tail of seven); the assertions
+    and the gate of the test above"""
+    shape, model, photometric = ar.SUMS_TRIP_CASES[case]
+    moving, fixed, M, (S, g, rr, n) = ar.sums_trip_reference(case)
+    dm, df = on_device(moving, fixed)
+    try:
+        Sd, gd, rrd, nd = dm.align_sums(df, M, model, photometric, ar.SUMS_GAIN, ar.SUMS_BIAS, None)
+    finally:
+        close(dm, df)
+    d = np.sqrt(np.diag(S))
+    eS, eg, er = (np.abs(Sd - S) / np.outer(d, d)).max(), (np.abs(gd - g) / (d * np.sqrt(rr))).max(), abs(rrd / rr - 1)
+    print("align_sums %s, %d tiles, %s, photometric %s: S %.3g, g %.3g, r^2 %.3g (gate %.3g); count %d" % (
+        shape, -(-shape[0] // ar.TILE) * -(-shape[1] // ar.TILE), model, photometric, eS, eg, er, ar.GATE, nd))
+    assert Sd.shape == S.shape and np.array_equal(Sd, Sd.T)
+    assert nd == n
+    assert eS <= ar.GATE and eg <= ar.GATE and er <= ar.GATE
+
+
 @pytest.mark.parametrize("shape_s,shape_o", ar.WARP_CASES)
 def test_warp_matches_the_float64_specification(shape_s, shape_o):
     from lib import utils

@@ -3,7 +3,12 @@
 tile of the blocked route and one pixel / three pixels over, a frame that is no multiple of anything, tile-exact 64 x 96 and one over,
 and a frame of three by five tiles whose last ones are partial.  Steps: 1, 4 (one launch of the blocked route), 5 (a remainder
 launch) and 9 (two full launches and a remainder, both ping-pong frames in use).  A wrong halo, clamp or region of the blocked route
-shows at a tile edge of exactly these shapes."""
+shows at a tile edge of exactly these shapes.
+
+The edge mask's kernels are persistent workgroups (at most cus x 1, x 4 or x 8) over 4 x 64 pixel tiles and units of 1024 or 256 keys: on
+these shapes and 256 CUs every workgroup makes one trip.  70 x 150 and 301 x 287 with the max_wgs switch at 2 and 1, and a frame past
+the launcher's own caps (tests/trips_ref.py past_the_caps: 1030 x 1100), make them add further tiles to a live LDS histogram and carry
+their kept counts from trip to trip."""
 import functools
 import gc
 
@@ -11,6 +16,7 @@ import numpy as np
 import pytest
 
 import edges_ref as er
+import trips_ref as tr
 
 pytestmark = pytest.mark.gpu
 
@@ -97,6 +103,56 @@ def test_edge_mask_of_the_devices_own_shock_frame_matches_the_specification(shap
             assert m.dtype == bool and m.shape == mask.shape
             assert np.array_equal(bits(np.asarray(th, np.float32)), bits(np.asarray(t, np.float32))), (route, per_sector, th, t)
             assert k == kept and np.array_equal(m, mask), (route, per_sector, k, kept)
+
+
+def assert_mask(got, want, what):
+    """(mask, threshold, kept) of the device against the specification's or another run's: every bit"""
+    assert got[0].dtype == bool and got[0].shape == want[0].shape, what
+    assert np.array_equal(bits(np.asarray(got[1], np.float32)), bits(np.asarray(want[1], np.float32))), (what, got[1], want[1])
+    assert np.array_equal(np.asarray(got[2]), np.asarray(want[2])) and np.array_equal(got[0], want[0]), (what, got[2], want[2])
+
+
+@pytest.mark.parametrize("coupling", er.COUPLINGS)
+@pytest.mark.parametrize("shape", [(70, 150), (301, 287)])
+def test_edge_mask_by_two_workgroups_and_by_one_that_walk_every_tile(debug_switch, shape, coupling):
+    """the max_wgs switch caps every persistent grid of the launcher: with 2 and with 1 workgroups each walks many tiles and key units
+    (54 and 11 on 70 x 150; 380, 85 and 338 on the ragged 301 x 287), adds them to a live LDS histogram and carries its kept count from
+    trip to trip.  The counts are integers: whoever walks the tiles, the bits are those of the specification and of the uncapped run."""
+    p = dev_shock(er.frame(shape), 4, coupling, 0)
+    for route in (1, 2):
+        assert all(units > 2 for units, _ in tr.edge_mask_grids(*shape, coupling, route).values())
+    for per_sector in per_sector_cases(shape):
+        want = er.edge_mask(p, per_sector, coupling, np.float32)
+        full = {route: dev_mask(p, per_sector, coupling, route) for route in (1, 2, 0)}
+        for cap in (2, 1):
+            debug_switch("max_wgs", cap)
+            capped = {route: dev_mask(p, per_sector, coupling, route) for route in (1, 2, 0)}
+            debug_switch("max_wgs", 0)
+            for route in (1, 2, 0):
+                what = "route %d, per_sector %d, max_wgs %d" % (route, per_sector, cap)
+                assert_mask(capped[route], want, what)
+                assert_mask(capped[route], full[route], what + " against the uncapped run")
+
+
+@pytest.mark.parametrize("coupling", er.COUPLINGS)
+def test_edge_mask_on_a_frame_with_more_units_than_workgroups(ctx, coupling):
+    """no switch: a frame large enough for the launcher's own caps (cus x 1 "channel", cus x 4 "vector" for the count passes, cus x 8
+    for the mask kernels), 1030 x 1100 on 256 CUs, no side a multiple of the 4 x 64 tile.  Every workgroup of every kernel takes a
+    second tile or key unit; asserted from the device's CU count, so that a larger device fails here instead of testing nothing."""
+    shape = tr.past_the_caps(ctx.compute_units)
+    assert shape[0] % 4 and shape[1] % 64
+    for route in (1, 2):
+        for kernel, (units, cap) in tr.edge_mask_grids(*shape, coupling, route, ctx.compute_units).items():
+            print("edge mask %s %d x %d on %d CUs, %s: %d units for %d workgroups" % ((coupling,) + shape + (ctx.compute_units, kernel, units, cap)))
+            assert units > cap, (kernel, units, cap)
+    with np.errstate(over="ignore"):                                     # (a sigmoid far from its edge: exp overflows to inf, the term is 0)
+        f = er.frame(shape)
+    p = dev_shock(f, 4, coupling, 0)
+    assert not np.array_equal(bits(p), bits(f))
+    for per_sector in per_sector_cases(shape):
+        want = er.edge_mask(p, per_sector, coupling, np.float32)
+        for route in (1, 2, 0):
+            assert_mask(dev_mask(p, per_sector, coupling, route), want, "route %d, per_sector %d" % (route, per_sector))
 
 
 def test_one_orientation_few_in_a_sector_and_ties_at_the_threshold():

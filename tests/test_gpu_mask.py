@@ -10,7 +10,10 @@ the best candidate a lead of at least twice the gate, asserted).
 
 Shapes (T = the cell kernel's tile side): one cell; 16 x 17 and 17 x 16 (the pixel that completes a difference); 31 (off = 7);
 33 x 49 with a box of 17 (2 x 3 candidates of one cell); T; T + 16 by T + 17 (a tile plus one cell, ragged); 2 T + 1 (two tiles per
-axis and one pixel past them); 70 x 200; 301 x 287 with boxes of 63 (also with the max_wgs switch at 2) and of 255 (n = 15)."""
+axis and one pixel past them); 70 x 200; 301 x 287 with boxes of 63 (also with the max_wgs switch at 2) and of 255 (n = 15); 1360 x 1360
+with a box of 16: 85 x 85 = 7225 candidates, between 7 and 8 times the pick's 1024 lanes, so that its lanes 0 .. 56 compare eight
+candidates in one unrolled trip and the others seven in the tail (the oracle leaves the best candidate of this picture 4800 times the
+lead the check asks for).  The tie rule across the two loop forms has a test of its own, on pictures whose ties are exact."""
 import ctypes as C
 import functools
 import os
@@ -30,7 +33,7 @@ T = mr.TILE
 CLIP = 0.99
 # (H, W, size, max_wgs switch)
 SHAPES = [(16, 16, 16, 0), (16, 17, 16, 0), (17, 16, 16, 0), (31, 31, 31, 0), (33, 49, 17, 0), (T, T, T, 0), (T + 16, T + 17, T, 0),
-          (2 * T + 1, 2 * T + 1, 48, 0), (70, 200, 63, 0), (301, 287, 63, 0), (301, 287, 63, 2), (301, 287, 255, 0)]
+          (2 * T + 1, 2 * T + 1, 48, 0), (70, 200, 63, 0), (301, 287, 63, 0), (301, 287, 63, 2), (301, 287, 255, 0), (1360, 1360, 16, 0)]
 WALL_CASE = ((200, 260), (13, 150, 7, 230), 63)
 POOL_CASE = (65, 97, 17)
 PATCH_CASE = (96, 112, 16)
@@ -93,7 +96,7 @@ def measure_f32_restatement():
 
 
 # Measured on the CPU by `python tests/test_gpu_mask.py`, without the code under test.
-F32_RESTATEMENT_ERROR = 4.518e-07
+F32_RESTATEMENT_ERROR = 8.133e-07     # (the one-cell boxes of 1360 x 1360; 4.518e-07 over the other frames)
 
 
 def gate():
@@ -154,6 +157,29 @@ def test_the_capped_grid_returns_the_bits_of_the_full_one(ctx, debug_switch):
     assert same(img.window_scores(63, scores=True), full)                            # the sums are per cell: who walks the tiles does not matter
     debug_switch("max_wgs", 1)
     assert same(img.window_scores(63, scores=True), full)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", [None] + list(tm.PICK_CASES))
+def test_the_pick_takes_the_first_of_equal_maxima_in_both_loop_forms(ctx, name):
+    """7225 candidates (tests/test_mask.py pick_picture): the pick's lanes 0 .. 56 compare eight candidates in one unrolled trip, the
+    others seven in the tail.  A unique maximum in either form, exact ties across the two, and the picture on which every candidate
+    ties.  The choice must be the first occurrence of the maximum in the device's own map: exact, whatever the rounding of a score."""
+    from lib._native import DeviceImage
+    raised = tm.PICK_CASES[name] if name else ()
+    img = DeviceImage.from_host(tm.pick_picture(raised), ctx)
+    try:
+        got = img.window_scores(16, scores=True)
+    finally:
+        img.close()
+    assert got.map.shape == (tm.PICK_N, tm.PICK_N) and 7 * 1024 < got.map.size < 8 * 1024
+    flat = got.map.ravel()
+    top = np.flatnonzero(flat == flat.max())
+    first = int(np.argmax(flat))
+    print("mask pick %s: maxima at candidates %s, chosen (%d, %d)" % (name or "every candidate equal", top.tolist() if top.size < 9 else "all %d" % top.size, got.box_y, got.box_x))
+    assert top.tolist() == (sorted(raised) if raised else list(range(flat.size)))              # the picture's ties are exact on the device too
+    assert first == (min(raised) if raised else 0)
+    assert (got.box_y, got.box_x) == (16 * (first // tm.PICK_N), 16 * (first % tm.PICK_N)) and got.score == flat[first] and got.clipped == 0
 
 
 @pytest.mark.gpu

@@ -11,7 +11,10 @@ below; `python tests/test_gpu_noise.py` prints it).
 
 Shapes: 1 x 1 (n = 1); 1 x 2 (n even: the lower median); 1 x 9, 9 x 1 and 5 x 7 fold every offset; 3 x 1030 and 1030 x 3 are thinner
 than tile and halo of the keys route; 32 x 128 sits exactly on two of its 16 x 64 tiles per axis and 33 x 129 one pixel past them;
-301 x 287 and 700 x 513 have ragged last tiles and give several persistent workgroups several tiles each."""
+301 x 287 and 700 x 513 have ragged last tiles and give several persistent workgroups of route 1 (4 x 64 tiles, at most cus x 3 or
+cus x 4 workgroups) several tiles each; route 2 (16 x 64 tiles and 1024-key units, 396 and 351 of them at most) stays below its caps on
+256 CUs there.  It wraps on 1030 x 1100 (tests/trips_ref.py BIG: 1170 tiles and 1107 key units for at most 1024 workgroups, asserted from
+the device's CU count), and on 301 x 287 with the max_wgs switch at 2 and at 1, where one workgroup walks every tile and unit."""
 import ctypes as C
 import functools
 import os
@@ -25,12 +28,13 @@ if __name__ == "__main__":
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     sys.path[:0] = [os.path.join(root, "oracle"), os.path.join(root, "tests"), os.path.join(root, "image-cases-studies_amd")]
 import noise_ref as nr
+import trips_ref as tr
 from test_noise import noisy_ramp
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TILE_H, TILE_W = 16, 64                                 # the keys route's tile (csrc/ics_img_noise.hip, asserted below)
 SIZES = [(1, 1), (1, 2), (1, 9), (9, 1), (5, 7), (3, 1030), (1030, 3), (2 * TILE_H, 2 * TILE_W), (2 * TILE_H + 1, 2 * TILE_W + 1), (301, 287),
-         (700, 513)]
+         (700, 513), tr.BIG]
 ROUTES = (0, 1, 2)
 
 
@@ -54,7 +58,7 @@ def measure_f32_restatement():
     return {coupling: max(abs(float(a) - float(b)) for H, W in SIZES for a, b in zip(*reference(H, W, coupling))) for coupling in nr.COUPLINGS}
 
 
-# Measured on the CPU by `python tests/test_gpu_noise.py`, without the code under test.
+# Measured on the CPU by `python tests/test_gpu_noise.py`, without the code under test (on 1030 x 1100 alone: 8.149e-09 and 1.303e-08).
 F32_RESTATEMENT_ERROR = {"channel": 4.843e-08, "vector": 4.641e-08}
 
 
@@ -81,6 +85,11 @@ def test_median_has_the_bits_of_the_restatement_by_every_route(ctx, H, W, coupli
     ref32, ref64 = reference(H, W, coupling)
     img = DeviceImage.from_host(pic, ctx)
     got = {}
+    if (H, W) == tr.BIG:                                 # the frame that is here for the caps: it must exceed them on this device
+        for route in (1, 2):
+            for kernel, (units, cap) in tr.noise_grids(H, W, coupling, route, ctx.compute_units).items():
+                print("noise %s %d x %d on %d CUs, %s: %d units for %d workgroups" % (coupling, H, W, ctx.compute_units, kernel, units, cap))
+                assert units > cap, (kernel, units, cap)
     for route in ROUTES:
         est = img.noise_estimate(coupling, route=route)
         assert isinstance(est, NoiseEstimate)
@@ -93,6 +102,31 @@ def test_median_has_the_bits_of_the_restatement_by_every_route(ctx, H, W, coupli
         assert img.noise_estimate(coupling, route=route) == est        # two runs, identical bits
         assert np.array_equal(img.to_host(), pic)                      # the source is never written
     assert got[1] == got[2] == got[0]                                  # the routes agree bit for bit
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("coupling", nr.COUPLINGS)
+def test_two_workgroups_and_one_that_walk_every_tile_give_the_same_bits(ctx, debug_switch, coupling):
+    """the max_wgs switch caps every persistent grid of the launcher: on 301 x 287 (380 tiles of route 1; 95 tiles and 85 key units of
+    route 2) two workgroups, then one, take every tile and unit in turn and add them to one live LDS histogram.  The counts are
+    integers: the median has the bits of the uncapped run and of the restatement whoever walks the tiles."""
+    from lib._native import DeviceImage
+    H, W = 301, 287
+    for route in (1, 2):
+        assert all(units > 2 for units, _ in tr.noise_grids(H, W, coupling, route).values())
+    pic = ns_picture(H, W)
+    ref32, _ = reference(H, W, coupling)
+    img = DeviceImage.from_host(pic, ctx)
+    full = {route: img.noise_estimate(coupling, route=route) for route in ROUTES}
+    for cap in (2, 1):
+        debug_switch("max_wgs", cap)
+        capped = {route: img.noise_estimate(coupling, route=route) for route in ROUTES}
+        debug_switch("max_wgs", 0)
+        for route in ROUTES:
+            assert bits(capped[route].median) == bits(ref32), (route, cap, capped[route].median, ref32)
+            assert capped[route] == full[route], (route, cap)
+            check(capped[route], pic, coupling)
+    assert np.array_equal(img.to_host(), pic)
 
 
 @pytest.mark.gpu

@@ -126,6 +126,44 @@ def test_cell_and_candidate_arithmetic():
     assert score[2, 3] == score[2, 1] == score.max() and mr.choice(pic, (0, 80, 0, 80), 16, 0.99)[:2] == (2, 1)
 
 
+# ---- exact ties over many candidates: the pictures of tests/test_gpu_mask.py's pick test ---------------------------------------------------
+# One 16 x 16 texture repeated over 1361 x 1361 (85 periods and the pixel that completes the last cells' differences): with a box of 16 a
+# candidate is one cell, 85 x 85 = 7225 of them, and every cell sees the same numbers in the same places, so all scores are one and the
+# same bits.  Raising the texture's contrast in the cell of candidate c makes that cell the maximum; two raised cells that do not touch
+# tie exactly.  k_img_mk_pick (1024 lanes, eight candidates a trip while c + 7 * 1024 < cand, then one at a time) gives lanes 0 .. 56 one
+# eight-wide trip and no tail, lanes 57 .. 1023 seven tail steps: the cases put a maximum in each class and a tie across them, both ways round.
+PICK_SIDE, PICK_N = 85 * 16 + 1, 85
+PICK_CASES = {"eight-wide, first slot": (23,), "eight-wide, fourth slot": (3 * 1024 + 31,), "tail only": (3450,),
+              "a tie, the eight-wide lane first": (3 * 1024 + 31, 3450), "a tie, the tail-only lane first": (500, 3 * 1024 + 31)}
+
+
+def pick_picture(raised=()):
+    """the periodic picture, the cells of the candidates `raised` at three times the contrast; float32, 1361 x 1361 x 3"""
+    tex = np.random.default_rng(77).random((16, 16, 3)) - 0.5
+    base, strong = (0.5 + 0.1 * tex).astype(np.float32), (0.5 + 0.3 * tex).astype(np.float32)
+    pic = np.tile(base, (PICK_N + 1, PICK_N + 1, 1))[:PICK_SIDE, :PICK_SIDE]
+    for c in raised:
+        i, j = divmod(c, PICK_N)
+        pic[16 * i:16 * i + 16, 16 * j:16 * j + 16] = strong
+    return np.ascontiguousarray(pic)
+
+
+def test_the_pick_pictures_tie_exactly_and_put_the_maximum_where_they_say():
+    whole = (0, PICK_SIDE, 0, PICK_SIDE)
+    assert mr.grid(whole, 16) == (1, 0, PICK_N, PICK_N)
+    score, trace, bad = mr.scores(pick_picture(), whole, 16, 0.99)
+    assert score.min() == score.max() > 0 and not bad.any() and mr.choice(pick_picture(), whole, 16, 0.99)[:2] == (0, 0)
+    plain = score[0, 0]
+    for name, raised in PICK_CASES.items():
+        score, trace, bad = mr.scores(pick_picture(raised), whole, 16, 0.99)
+        flat = score.ravel()
+        top = np.flatnonzero(flat == flat.max())
+        print("%s: maxima at %s, %.3e against %.3e elsewhere at most" % (name, top.tolist(), flat.max(), np.delete(flat, top).max()))
+        assert top.tolist() == sorted(raised) and int(np.argmax(flat)) == min(raised), name
+        assert np.delete(flat, top).max() < 0.5 * flat.max() and flat.max() > 4 * plain, name
+        assert mr.choice(pick_picture(raised), whole, 16, 0.99)[:2] == divmod(min(raised), PICK_N), name
+
+
 @pytest.mark.parametrize("seed", SEEDS)
 def test_properties_on_dead_leaves(seed):
     """what the score is for, by the float64 oracle alone"""
