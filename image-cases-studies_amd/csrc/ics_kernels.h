@@ -151,6 +151,7 @@ struct IcsRunResetArgs {
   uint32_t* red;       // [nred] := 0
   int nred;
   uint32_t* dofkeys;   // [8] := {0xFFFFFFFF, 0, 0, 0} x 2
+  float* scal;         // [ICS_SC_COUNT] := 0 (a non-blind run writes no dtpsf: a reused job must not report the one of the blind run before it)
 };
 hipError_t ics_launch_run_reset(const IcsRunResetArgs& a, hipStream_t s);
 

@@ -1079,6 +1079,7 @@ __global__ __launch_bounds__(256) void k_run_reset(IcsRunResetArgs a) {
   if (t < 8) a.dacc[t] = 0.0;
   if (t < 2) a.ukey[t] = 0u;
   if (t < 8) a.dofkeys[t] = (t & 3) == 0 ? 0xFFFFFFFFu : 0u;
+  if (t < ICS_SC_COUNT) a.scal[t] = 0.f;
   for (int i = t; i < a.nred; i += 256) a.red[i] = 0u;
 }
 }  // namespace

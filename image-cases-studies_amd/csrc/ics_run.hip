@@ -711,9 +711,11 @@ extern "C" int ics_rl_run(ics_rl* j, const ics_rl_params* p, ics_rl_stats* st) {
   j->ev_used = 0; j->ev_pairs.clear(); j->ev_chain = -1;
   {   // the job's small state in one launch: flags, the tile counters (the kernels re-arm them; an aborted launch must not leak a count), the
       // accumulators of the window statistics (likewise re-armed by their last kernel), both sets of reduction slots and DoF keys (later
-      // outer iterations: re-armed on the device by the kernel that writes the scalars)
+      // outer iterations: re-armed on the device by the kernel that writes the scalars), and the scalars: a run that writes no dtpsf (non-blind)
+      // reports 0 for it on a job whose last run was blind as on a fresh one (tests/test_gpu_job_reuse.py)
     IcsRunResetArgs ra;
     ra.flags = j->flags; ra.sched = j->sched; ra.dacc = j->dacc; ra.ukey = j->ukey; ra.red = j->red; ra.nred = 2 * 8 * ICS_RED_STRIDE; ra.dofkeys = j->dofkeys;
+    ra.scal = j->scal;
     HIPCHK(ics_launch_run_reset(ra, s));
   }
   // the caller's psf array is the local psf when the call starts (pyx:341)

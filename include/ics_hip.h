@@ -286,17 +286,25 @@ unsigned long long ics_rl_frame_bytes(int M, int N, int MK);
 int ics_rl_stage(ics_rl *job, int stage, const ics_rl_params *params);
 
 /* Reads one device frame back in the reference's shape. */
-#define ICS_BUF_U 0      /* uM x uN x 3  */
-#define ICS_BUF_UT 1     /* uM x uN x 3  */
+#define ICS_BUF_U 0      /* uM x uN x 3 : after ics_rl_run, what ics_rl_download returns, on every family */
+#define ICS_BUF_UT 1     /* uM x uN x 3 : the majoriser.  After ics_rl_run of n outer iterations: u as the last outer iteration found it (u after n - 1
+                            iterations; the upload for n = 1) on the multi-launch HWC families and the small-frame kernel (families 1 ... 4, 6).  On the
+                            transform tiles (family 5) the frames rotate as planar mirrors and only u and the residual are converted back: the buffer
+                            read here is then undefined from n = 2 on.  ics_rl_write and ICS_STAGE_MAJORIZE define it for single stages */
 #define ICS_BUF_GRADU 2  /* uM x uN x 3 : raw back-projection (A3), before A6.  After ics_rl_run: the last inner iteration's on the multi-launch families;
                             on the transform tiles (family 5) it lives in the frame's planar mirror and the buffer read here is not refreshed; the
                             cooperative small-frame kernel (family 6) never stores it (it stays in LDS) -- single stages (ics_rl_stage) always write it */
-#define ICS_BUF_IMAGE 3  /* M x N x 3    */
+#define ICS_BUF_IMAGE 3  /* M x N x 3 : the image as uploaded, on every family (tv_mode 1 steps it on the device, pyx:547-549).  Every writer -- ics_rl_upload,
+                            ics_rl_upload_img, ics_rl_write, ics_rl_write_rows, ics_rl_copy_rows, ics_rl_exchange_rows, that update -- drops the copies
+                            the kernels keep of it (accumulator order, negated, planar mirror, the spectra of mode 2): the next run rebuilds them */
 #define ICS_BUF_ERROR 4  /* M x N x 3    */
-#define ICS_BUF_PSF 5    /* MK x MK x 3  */
-#define ICS_BUF_GRADK 6  /* MK x MK x 3  */
+#define ICS_BUF_PSF 5    /* MK x MK x 3 : the local PSF (ics_rl_download's psf_local).  ics_rl_write of it repacks every weight table but, unlike
+                            ics_rl_upload, touches neither psf_caller nor the flag that says a run with correlation = 1 has detached it: while the
+                            flag is set, ICS_STAGE_PSF_UPDATE steps this buffer alone.  ics_rl_run resets the flag when it starts */
+#define ICS_BUF_GRADK 6  /* MK x MK x 3 : after a blind ics_rl_run, the gradient of its last inner iteration */
 #define ICS_BUF_TV 8      /* uM x uN x 3 : TV term T (tv_mode 1) */
-#define ICS_BUF_SCALARS 7 /* 16 floats: dt[3], maxu[3], maxg[3], dtpsf, M_r, Hu, varu, dof_min, dof_max, 0 */
+#define ICS_BUF_SCALARS 7 /* 16 floats: dt[3], maxu[3], maxg[3], dtpsf, M_r, Hu, varu, dof_min, dof_max, 0.  ics_rl_run zeroes them when it starts
+                             (dtpsf stays 0 behind a non-blind run, whatever ran on the job before) */
 #define ICS_BUF_RED 9     /* 16 words (bit patterns in float slots): reduction keys of stage calls -- [0..2] max|g_k|,
                              [3..5] max u_k as order-preserving uint32 keys (larger key = larger float; NaN = 0xFFC00000);
                              read only: [12] min key, [13] max key, [14] NaN flag of the DoF mask of the last update (pyx:593) */
