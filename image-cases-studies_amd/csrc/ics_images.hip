@@ -1,5 +1,5 @@
 // ics_images.hip -- the ics_img_* entries of the C ABI (include/ics_hip.h).  Host side only; kernels live in ics_img.hip / ics_img_filters.hip /
-// ics_img_tvdenoise.hip / ics_img_wavelet.hip / ics_img_noise.hip / ics_img_despeckle.hip / ics_img_blurwidth.hip / ics_img_mask.hip / ics_img_guided.hip / ics_img_llf.hip (what these nine share: ics_img_px.h) / ics_img_wiener.hip / ics_img_tvdeconv.hip / ics_img_tvmdeconv.hip / ics_img_psfest.hip / ics_img_edges.hip / ics_img_align.hip / ics_resize.hip.
+// ics_img_tvdenoise.hip / ics_img_wavelet.hip / ics_img_noise.hip / ics_img_despeckle.hip / ics_img_blurwidth.hip / ics_img_blurmap.hip / ics_img_mask.hip / ics_img_guided.hip / ics_img_llf.hip (what these ten share: ics_img_px.h) / ics_img_wiener.hip / ics_img_tvdeconv.hip / ics_img_tvmdeconv.hip / ics_img_psfest.hip / ics_img_edges.hip / ics_img_align.hip / ics_resize.hip.
 #include "ics_host.h"
 
 using namespace ics_host;
@@ -561,6 +561,54 @@ extern "C" int ics_img_window_scores(const ics_img* src, int y0, int y1, int x0,
   RC(op.finish(e));
   *box_y = y0 + ICS_IMG_MASK_CELL * (int)got[0]; *box_x = x0 + ICS_IMG_MASK_CELL * (int)got[1];
   *score = got[2]; *trace = got[3]; *clipped = (long long)got[4];
+  return ICS_OK;
+}
+
+// ---- blur map of a device image (csrc/ics_img_blurmap.hip) -----------------------------------------------------------------------
+// One route, one launch.  The taps go up through put_table; the cell grid and the workgroups' counts of non-finite pixels come back in
+// one copy, the sparse plane (where asked for) in a second.
+extern "C" int ics_img_blur_map(const ics_img* src, int y0, int y1, int x0, int x1, float sigma_a, float sigma_b, float edge, float max_sigma, float* weight,
+                                float* moment, int* count, long long* bad, float* sparse, int rows, int cols) {
+  if (!src) return ics_set_error(ICS_EINVAL, "src is NULL");
+  if (!weight || !moment || !count || !bad) return ics_set_error(ICS_EINVAL, "an output (weight, moment, count, bad) is NULL");
+  const int H = src->H, W = src->W;
+  if (y0 < 0 || x0 < 0 || y1 > H || x1 > W || y0 >= y1 || x0 >= x1)
+    return ics_set_error(ICS_EINVAL, "window [%d, %d) x [%d, %d) (not empty, inside the %d x %d frame)", y0, y1, x0, x1, H, W);
+  if (!(sigma_a >= 0.5f) || !(sigma_a < sigma_b) || !std::isfinite(sigma_b) || ics_img_blurmap_radius(sigma_b) > ICS_IMG_BLURMAP_MAX_RADIUS)
+    return ics_set_error(ICS_EINVAL, "sigmas = (%g, %g) (0.5 <= sigma_a < sigma_b, ceil(3 sigma_b) <= %d)", (double)sigma_a, (double)sigma_b, ICS_IMG_BLURMAP_MAX_RADIUS);
+  if (!(edge > 0.f)) return ics_set_error(ICS_EINVAL, "edge = %g (above 0)", (double)edge);
+  if (!(max_sigma > 0.f)) return ics_set_error(ICS_EINVAL, "max_sigma = %g (above 0)", (double)max_sigma);
+  const int hw = y1 - y0, ww = x1 - x0, cell = ICS_IMG_BLURMAP_CELL, nr = (hw + cell - 1) / cell, nc = (ww + cell - 1) / cell;
+  if (rows != nr || cols != nc) return ics_set_error(ICS_EINVAL, "grid of %d x %d cells (the window has %d x %d)", rows, cols, nr, nc);
+  ics_ctx* c = src->ctx;
+  HIPCHK(hipSetDevice(c->device));
+  const size_t cells = (size_t)nr * nc;
+  const int grid = ics_img_blurmap_grid(hw, ww, c->cus);
+  std::vector<float> taps(2 * (2 * ICS_IMG_BLURMAP_MAX_RADIUS + 1), 0.f);
+  ics_img_blurmap_taps(sigma_a, taps.data());
+  ics_img_blurmap_taps(sigma_b, taps.data() + 2 * ICS_IMG_BLURMAP_MAX_RADIUS + 1);
+  std::vector<float> got(3 * cells + grid);
+  ImgOp op(c, nullptr, "img_blur_map");
+  float *dtaps = nullptr, *block = nullptr, *plane = nullptr;
+  hipError_t e = op.alloc((void**)&dtaps, taps.size() * sizeof(float));
+  if (e == hipSuccess) e = op.alloc((void**)&block, got.size() * sizeof(float));
+  if (e == hipSuccess && sparse) e = op.alloc((void**)&plane, (size_t)hw * ww * sizeof(float));
+  if (e == hipSuccess) e = put_table(c, dtaps, taps);
+  if (e == hipSuccess) e = op.begin();
+  if (e == hipSuccess)
+    e = ics_launch_img_blurmap(src->d, H, W, y0, y1, x0, x1, sigma_a, sigma_b, edge, max_sigma, grid, dtaps, block, block + cells, reinterpret_cast<int*>(block + 2 * cells),
+                               reinterpret_cast<int*>(block + 3 * cells), plane, c->stream);
+  if (e == hipSuccess) e = op.end();
+  if (e == hipSuccess) e = hipMemcpyAsync(got.data(), block, got.size() * sizeof(float), hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess && sparse) e = hipMemcpyAsync(sparse, plane, (size_t)hw * ww * sizeof(float), hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  RC(op.finish(e));
+  memcpy(weight, got.data(), cells * sizeof(float));
+  memcpy(moment, got.data() + cells, cells * sizeof(float));
+  memcpy(count, got.data() + 2 * cells, cells * sizeof(int));
+  long long n = 0;
+  for (int i = 0; i < grid; ++i) { int v; memcpy(&v, got.data() + 3 * cells + i, sizeof v); n += v; }
+  *bad = n;
   return ICS_OK;
 }
 

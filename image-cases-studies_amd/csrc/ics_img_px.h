@@ -1,4 +1,4 @@
-// ics_img_px.h -- for ics_img_filters.hip, ics_img_tvdenoise.hip, ics_img_wavelet.hip, ics_img_guided.hip, ics_img_llf.hip, ics_img_noise.hip, ics_img_despeckle.hip, ics_img_blurwidth.hip, ics_img_mask.hip, ics_img_align.hip, ics_img_edges.hip and ics_img_tvmdeconv.hip (the pixel load) only (everything here is local to
+// ics_img_px.h -- for ics_img_filters.hip, ics_img_tvdenoise.hip, ics_img_wavelet.hip, ics_img_guided.hip, ics_img_llf.hip, ics_img_noise.hip, ics_img_despeckle.hip, ics_img_blurwidth.hip, ics_img_blurmap.hip, ics_img_mask.hip, ics_img_align.hip, ics_img_edges.hip and ics_img_tvmdeconv.hip (the pixel load) only (everything here is local to
 // the unit that includes it): what their kernels and launchers share, the 12-byte pixel access, the luma, the symmetric fold, the B3-spline pass, two launch helpers.
 #pragma once
 #include "ics_kernels.h"
@@ -16,7 +16,7 @@ __device__ __forceinline__ void st3(float* __restrict__ p, const float v[3]) {
   *reinterpret_cast<f3u*>(p) = t;
 }
 
-// the luma of one pixel (ics_img_blurwidth.hip, ics_img_mask.hip, ics_img_align.hip, ics_img_edges.hip): (R + G + B) * float32(1 / 3), every operation rounded once
+// the luma of one pixel (ics_img_blurwidth.hip, ics_img_blurmap.hip, ics_img_mask.hip, ics_img_align.hip, ics_img_edges.hip): (R + G + B) * float32(1 / 3), every operation rounded once
 __device__ __forceinline__ float px_luma(const float v[3]) { return __fmul_rn(__fadd_rn(__fadd_rn(v[0], v[1]), v[2]), 0.333333343267440796f); }
 
 // index of the symmetric extension ... x1 x0 | x0 x1 ... x(n-1) | x(n-1) x(n-2) ... (numpy.pad(mode="symmetric")), at any distance

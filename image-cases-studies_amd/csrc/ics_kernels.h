@@ -392,6 +392,22 @@ int ics_img_mask_cells(int extent, int size);
 hipError_t ics_launch_img_mask(const float* f, int H, int W, int y0, int y1, int x0, int x1, int size, float clip, int cus, float* cells, double* table, double* result,
                                hipStream_t s);
 
+// ---- blur map of device-resident images (ics_img_blurmap.hip): per 16 x 16 cell of the window [y0, y1) x [x0, x1) the sums of A and
+// A sigma and the number of the kept edge pixels (gradient ratio of the luma smoothed by sigma_a and sigma_b, include/ics_hip.h), one
+// launch.  ics_img_blurmap_radius: ceilf(3.f * sigma); ics_img_blurmap_taps: the 2 r + 1 normalised taps of sigma; taps (device): those of
+// sigma_a at [0], those of sigma_b at [2 ICS_IMG_BLURMAP_MAX_RADIUS + 1].  grid: ics_img_blurmap_grid workgroups (persistent, sized by
+// the compute units and capped by the max_wgs switch); weight, moment, count: a value per cell, every one written; bad: an integer per
+// workgroup, its pixels whose luma is not finite; sparse (or NULL): a float per pixel of the window.  One route; f is only read.
+#define ICS_IMG_BLURMAP_CELL 16           // (== include/ics_hip.h)
+#define ICS_IMG_BLURMAP_MAX_RADIUS 8      // (== include/ics_hip.h)
+size_t ics_img_blurmap_lds(int r);
+int ics_img_blurmap_radius(float sigma);
+long ics_img_blurmap_tiles(int hw, int ww);
+int ics_img_blurmap_grid(int hw, int ww, int cus);
+void ics_img_blurmap_taps(float sigma, float* g);
+hipError_t ics_launch_img_blurmap(const float* f, int H, int W, int y0, int y1, int x0, int x1, float sigma_a, float sigma_b, float edge, float max_sigma, int grid,
+                                  const float* taps, float* weight, float* moment, int* count, int* bad, float* sparse, hipStream_t s);
+
 // ---- Wiener deconvolution of device-resident images (ics_img_wiener.hip): one 2-D transform of the periodically extended frame, the
 // filter conj(Hc) / (|Hc|^2 + balance L^2) per channel, the inverse.  ics_img_wiener_sizes: the transform sizes (powers of two >=
 // H + K - 1, W + K - 1), 0 where one would be above ICS_IMG_WIENER_MAX.  A, B: ics_img_wiener_frame_bytes each; tables: the block of

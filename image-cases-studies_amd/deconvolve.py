@@ -129,6 +129,9 @@ def deblur_module(pic, filename, dest_path, blur_width, confidence=10, tolerance
     `despeckle`, before the automatic blur width (which is then read over the chosen box) and before the odd-size padding, among the
     boxes that lie inside the picture; one line "Mask : [95, 143] (score 2.93e-03, clipped 0.0 %)" is printed before "Mask size :" and
     everything runs as if that centre had been passed.  On the resident path the frame is read where it lies.
+    `mask=("auto", clip, (lo, hi))`: the same choice among the boxes whose local blur width (`utils.blur_map`, a Gaussian-equivalent
+    sigma in pixels) lies in [lo, hi] -- the subject under a defocus that varies over the frame, where the plain choice takes the zone
+    in focus; the line reads "Mask : [95, 143] (score 2.93e-03, clipped 0.0 %, blur 2.31)", ValueError where no box qualifies.
     `nonblind="rl"` (the default: the reference's second phase, the loop on the whole frame), `"wiener"` or `("wiener", balance)`
     (balance 0.01 unless given): the blind phase runs as ever, and the second phase is one `utils.wiener` of the full-resolution
     gamma-encoded frame with the PSF the blind phase returned -- milliseconds where the loop takes most of the run, to try a PSF on
@@ -484,10 +487,10 @@ def _auto_blur_width(frame, max_width, window):
 
 
 def _mask_args(mask):
-    """`mask` of deblur_module -> None for None or a centre [y, x] of two integers, the clip level of "auto" / ("auto", clip), checked
-    (ValueError)"""
+    """`mask` of deblur_module -> None for None or a centre [y, x] of two integers, the clip level of "auto" / ("auto", clip),
+    (clip, (lo, hi)) of ("auto", clip, (lo, hi)), checked (ValueError)"""
     from lib import _native
-    form = "mask takes None, a centre [y, x] of two integers, \"auto\" or (\"auto\", clip), got %r" % (mask,)
+    form = "mask takes None, a centre [y, x] of two integers, \"auto\", (\"auto\", clip) or (\"auto\", clip, (lo, hi)), got %r" % (mask,)
     if mask is None:
         return None
     if isinstance(mask, str):
@@ -497,11 +500,12 @@ def _mask_args(mask):
     if not isinstance(mask, (list, tuple, np.ndarray)):
         raise ValueError(form)
     pair = len(mask) == 2
-    if pair and isinstance(mask[0], str):
+    if len(mask) in (2, 3) and isinstance(mask[0], str):
         if mask[0] != "auto":
             raise ValueError(form)
         try:
-            return _native.window_scores_args(_native.IMG_MASK_CELL, None, mask[1], (_native.IMG_MASK_CELL, _native.IMG_MASK_CELL))[2]
+            clip = _native.window_scores_args(_native.IMG_MASK_CELL, None, mask[1], (_native.IMG_MASK_CELL, _native.IMG_MASK_CELL))[2]
+            return clip if pair else (clip, utils.mask_blur_args(mask[2]))
         except ValueError as exc:
             raise ValueError("mask: %s" % exc)
     if not pair or not all(isinstance(v, (int, np.integer)) and not isinstance(v, bool) for v in mask):
@@ -515,6 +519,10 @@ def _auto_mask(frame, mask_size, clip):
     M, N = frame.shape[0], frame.shape[1]
     if 2 * (mask_size // 2) + 1 > min(M, N) - 2:
         raise ValueError("The mask is outside the picture boundaries. Move its center inside or reduce the blur size.")
+    if isinstance(clip, tuple):                                             # ("auto", clip, (lo, hi)): the best box whose blur lies in the range
+        got = utils.best_mask(frame, mask_size, clip[0], (1, M - 1, 1, N - 1), blur=clip[1])
+        print("Mask : [%d, %d] (score %.2e, clipped %.1f %%, blur %.2f)" % (got.center_y, got.center_x, got.score, 100.0 * got.clipped, got.sigma))
+        return [got.center_y, got.center_x]
     got = utils.best_mask(frame, mask_size, clip, (1, M - 1, 1, N - 1))
     print("Mask : [%d, %d] (score %.2e, clipped %.1f %%)" % (got.center_y, got.center_x, got.score, 100.0 * got.clipped))
     return [got.center_y, got.center_x]

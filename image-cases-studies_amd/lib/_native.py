@@ -102,6 +102,8 @@ IMG_WIENER_MAX = 8192            # include/ics_hip.h ICS_IMG_WIENER_MAX: longest
 IMG_TVD_MAX_ITERATIONS = 500     # include/ics_hip.h ICS_IMG_TVD_MAX_ITERATIONS: most iterations of DeviceImage.tv_deconvolve
 IMG_ALIGN_MAX_LEVELS = 8         # include/ics_hip.h ICS_IMG_ALIGN_MAX_LEVELS: most pyramid levels of DeviceImage.align
 IMG_MASK_CELL = 16               # include/ics_hip.h ICS_IMG_MASK_CELL: DeviceImage.window_scores ranks boxes on this grid and scores whole cells of this side
+IMG_BLURMAP_CELL = 16            # include/ics_hip.h ICS_IMG_BLURMAP_CELL: DeviceImage.blur_map reads the blur width per cell of this side (the grid of IMG_MASK_CELL)
+IMG_BLURMAP_MAX_RADIUS = 8       # include/ics_hip.h ICS_IMG_BLURMAP_MAX_RADIUS: ceil(3 sigma_b) of DeviceImage.blur_map at most
 IMG_NOISE_STRENGTH = 3.0         # include/ics_hip.h ICS_IMG_NOISE_STRENGTH: thresholds="auto" cuts this many standard deviations
 IMG_NOISE_E = (0.89079631027875839, 0.20066385102441897, 0.085507504753369934, 0.041217444374316202,      # include/ics_hip.h ICS_IMG_NOISE_E: e_j, the L2
                0.020424966592781431, 0.01018975924921329, 0.0050920466808193074, 0.0025456694579151255)   # norm of the response of scale j to a unit impulse
@@ -185,6 +187,7 @@ def load():
     lib.ics_img_blur_profile.argtypes = [vp, ci, ci, ci, ci, ci, C.POINTER(cd), C.POINTER(cd), C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]
     lib.ics_img_window_scores.argtypes = [vp, ci, ci, ci, ci, ci, cf, C.POINTER(ci), C.POINTER(ci), C.POINTER(cd), C.POINTER(cd), C.POINTER(C.c_longlong),
                                           C.POINTER(cd), ci, ci]
+    lib.ics_img_blur_map.argtypes = [vp, ci, ci, ci, ci, cf, cf, cf, cf, C.POINTER(cf), C.POINTER(cf), C.POINTER(ci), C.POINTER(C.c_longlong), C.POINTER(cf), ci, ci]
     lib.ics_img_despeckle.argtypes = [vp, ci, C.POINTER(cf), ci, ci, C.POINTER(vp), C.POINTER(C.c_uint)]
     lib.ics_img_guided.argtypes = [vp, ci, cf, cf, ci, ci, C.POINTER(vp)]
     lib.ics_img_local_laplacian.argtypes = [vp, cf, cf, cf, ci, ci, ci, ci, C.POINTER(vp)]
@@ -228,7 +231,7 @@ def load():
                  "ics_rl_download", "ics_rl_run", "ics_rl_stage", "ics_rl_read", "ics_rl_write", "ics_rl_read_rows", "ics_rl_write_rows", "ics_rl_copy_rows", "ics_normalize_kernel",
                  "ics_tv", "ics_conv2d_symm", "ics_usm", "ics_bilateral", "ics_resize_bicubic", "ics_img_create", "ics_img_shape",
                  "ics_img_upload", "ics_img_upload_int", "ics_img_download", "ics_img_pad_edge", "ics_img_crop", "ics_img_paste", "ics_img_gamma", "ics_img_resize",
-                 "ics_img_convolve", "ics_img_usm", "ics_img_bilateral", "ics_img_tv_denoise", "ics_img_wavelet_equalize", "ics_img_noise_estimate", "ics_img_blur_profile", "ics_img_window_scores", "ics_img_despeckle", "ics_img_guided", "ics_img_local_laplacian", "ics_img_wiener", "ics_img_wiener_plan", "ics_img_tv_deconvolve", "ics_img_tv_deconvolve_plan", "ics_img_tv_deconvolve_masked", "ics_img_tv_deconvolve_masked_plan",
+                 "ics_img_convolve", "ics_img_usm", "ics_img_bilateral", "ics_img_tv_denoise", "ics_img_wavelet_equalize", "ics_img_noise_estimate", "ics_img_blur_profile", "ics_img_window_scores", "ics_img_blur_map", "ics_img_despeckle", "ics_img_guided", "ics_img_local_laplacian", "ics_img_wiener", "ics_img_wiener_plan", "ics_img_tv_deconvolve", "ics_img_tv_deconvolve_plan", "ics_img_tv_deconvolve_masked", "ics_img_tv_deconvolve_masked_plan",
                  "ics_img_psf_estimate", "ics_img_psf_estimate_plan",
                  "ics_img_shock", "ics_img_edge_mask", "ics_mask_shape", "ics_mask_download", "ics_mask_create", "ics_img_psf_estimate_masked",
                  "ics_img_align", "ics_img_align_sums", "ics_img_warp", "ics_img_align_plan",
@@ -439,6 +442,122 @@ def window_scores_args(size, region, clip, shape):
     if not level > 0:
         raise ValueError("clip %r (a number above 0; inf keeps every finite pixel)" % (clip,))
     return int(size), (y0, y1, x0, x1), level
+
+
+BlurMap = collections.namedtuple("BlurMap", "sigma weight count pixels", defaults=(None,))
+
+
+def _blur_map_radius(s):
+    return int(math.ceil(float(np.float32(3.0) * np.float32(s))))        # (the product in float32, as the library takes it: 8 / 3 gives 8)
+
+
+def blur_map_args(sigmas, edge, max_sigma, window, shape):
+    """the arguments of DeviceImage.blur_map checked (ValueError) and as ((sigma_a, sigma_b), edge, max_sigma, (y0, y1, x0, x1)), the
+    numbers as float32 carries them; shape: (H, W, ...) of the frame.  Runs without a device."""
+    def number(v):
+        try:
+            return float(np.float32(v)) if not isinstance(v, (bool, str)) else math.nan
+        except (TypeError, ValueError, OverflowError):
+            return math.nan
+    try:
+        sa, sb = (number(v) for v in sigmas)
+    except (TypeError, ValueError):
+        sa = sb = math.nan
+    if not (0.5 <= sa < sb < math.inf) or _blur_map_radius(sb) > IMG_BLURMAP_MAX_RADIUS:
+        raise ValueError("sigmas %r ((sigma_a, sigma_b), 0.5 <= sigma_a < sigma_b, ceil(3 sigma_b) <= %d)" % (sigmas, IMG_BLURMAP_MAX_RADIUS))
+    e, ms = number(edge), number(max_sigma)
+    if not 0 < e < math.inf:
+        raise ValueError("edge %r (a finite number above 0)" % (edge,))
+    if not 0 < ms < math.inf:
+        raise ValueError("max_sigma %r (a finite number above 0)" % (max_sigma,))
+    H, W = int(shape[0]), int(shape[1])
+    if window is None:
+        window = (0, H, 0, W)
+    try:
+        y0, y1, x0, x1 = (int(v) for v in window)
+        exact = all(int(v) == v for v in window)
+    except (TypeError, ValueError):
+        y0 = y1 = x0 = x1 = 0
+        exact = False
+    if not exact or not (0 <= y0 < y1 <= H and 0 <= x0 < x1 <= W):
+        raise ValueError("window %r ((y0, y1, x0, x1), half-open, not empty, inside the %d x %d frame)" % (window, H, W))
+    return (sa, sb), e, ms, (y0, y1, x0, x1)
+
+
+def _blur_map_taps64(sigma):
+    s = float(np.float32(sigma))
+    r = _blur_map_radius(s)
+    g = [math.exp(-(i * i) / (2.0 * s * s)) for i in range(-r, r + 1)]
+    tot = 0.0
+    for v in g:
+        tot += v
+    return np.array([v / tot for v in g], np.float64)
+
+
+def blur_map_taps(sigma):
+    """the normalised Gaussian taps the library hands its blur-map kernel for `sigma`: g[i] = exp(-i^2 / (2 s^2)), i = -r .. r,
+    r = ceil(3 s), s as float32 carries it; summed in ascending order and divided in double, rounded to float32"""
+    return _blur_map_taps64(sigma).astype(np.float32)
+
+
+def blur_map_edge(sigma_noise, sigma_a=1.0, strength=5.0):
+    """The `edge` of DeviceImage.blur_map from the picture's noise: `strength` times the standard deviation of one gradient component
+    of the luma smoothed by sigma_a under white noise of `sigma_noise` per channel (noise_estimate(...).sigma),
+    strength * (sigma_noise / sqrt(3)) * sqrt(sum_j g_j^2 * sum_i (0.5 (g_{i-1} - g_{i+1}))^2), g the taps in double."""
+    if not _finite32(sigma_noise, scalar=True) or not float(sigma_noise) >= 0:
+        raise ValueError("sigma_noise %r (must be finite and >= 0)" % (sigma_noise,))
+    strength = _strength(strength)
+    g = _blur_map_taps64(sigma_a)
+    gp = np.concatenate(([0.0, 0.0], g, [0.0, 0.0]))
+    d = 0.5 * (gp[:-2] - gp[2:])
+    return strength * (float(sigma_noise) / math.sqrt(3.0)) * math.sqrt(float((g * g).sum()) * float((d * d).sum()))
+
+
+def blur_map_fill(bmap):
+    """The cell grid of a BlurMap with its empty cells (sigma NaN) filled, float64: a normalised convolution on the grid -- an empty
+    cell takes the weight-weighted mean of the nearest ring of cells (Chebyshev distance 1, 2, ...) that holds any.  A grid without
+    a single reading stays NaN."""
+    sigma, weight = np.asarray(bmap.sigma, np.float64), np.asarray(bmap.weight, np.float64)
+    out = sigma.copy()
+    have = ~np.isnan(sigma)
+    if not have.any():
+        return out
+    rows, cols = sigma.shape
+    for i, j in zip(*np.nonzero(~have)):
+        for d in range(1, max(rows, cols)):
+            ya, yb, xa, xb = max(i - d, 0), min(i + d, rows - 1), max(j - d, 0), min(j + d, cols - 1)
+            num = den = 0.0
+            for y in range(ya, yb + 1):
+                for x in range(xa, xb + 1):
+                    if max(abs(y - i), abs(x - j)) == d and have[y, x]:
+                        num += weight[y, x] * sigma[y, x]
+                        den += weight[y, x]
+            if den > 0:
+                out[i, j] = num / den
+                break
+    return out
+
+
+def blur_map_box_sigma(bmap, side, extent):
+    """The blur width of every candidate box of DeviceImage.window_scores(side, region) from the BlurMap of the same region, float64:
+    box (i, j) has its origin 16 i, 16 j pixels from the region's origin and takes the weight-weighted mean of the cells
+    [i, i + n) x [j, j + n), n = side // 16, of the map -- same grid, same origin; NaN where a box holds no kept pixel.  extent:
+    (height, width) of the region, which fixes the number of boxes, (extent - side) // 16 + 1 a side."""
+    sigma, weight, count = np.asarray(bmap.sigma, np.float64), np.asarray(bmap.weight, np.float64), np.asarray(bmap.count)
+    n = int(side) // IMG_BLURMAP_CELL
+    nci, ncj = (int(extent[0]) - int(side)) // IMG_BLURMAP_CELL + 1, (int(extent[1]) - int(side)) // IMG_BLURMAP_CELL + 1
+    if n < 1 or nci < 1 or ncj < 1 or nci - 1 + n > sigma.shape[0] or ncj - 1 + n > sigma.shape[1]:
+        raise ValueError("boxes of side %r in a region of %r do not lie on a map of %d x %d cells" % (side, extent, sigma.shape[0], sigma.shape[1]))
+    have = count > 0
+    mom = np.where(have, weight * np.where(have, sigma, 0.0), 0.0)
+    wgt = np.where(have, weight, 0.0)
+    out = np.full((nci, ncj), np.nan)
+    for i in range(nci):
+        for j in range(ncj):
+            den = wgt[i:i + n, j:j + n].sum()
+            if have[i:i + n, j:j + n].any() and den > 0:
+                out[i, j] = mom[i:i + n, j:j + n].sum() / den
+    return out
 
 
 def _strength(strength):
@@ -1202,6 +1321,35 @@ class DeviceImage:
         if not (math.isfinite(sc.value) and math.isfinite(tr.value)) or (scores and not np.isfinite(grid).all()):
             raise ValueError("the window score is not finite: the frame holds values beyond float32's range (lower clip)")
         return WindowScores(by.value, bx.value, sc.value, tr.value, bad.value, grid)
+
+    def blur_map(self, sigmas=(1.0, 2.0), edge=0.02, max_sigma=8.0, window=None, sparse=False):
+        """The local blur width of the picture over the half-open window (y0, y1, x0, x1) (None: the whole frame), in one launch:
+        BlurMap(sigma, weight, count, pixels), grids of ceil(h / 16) x ceil(w / 16) cells from the window's origin.  Zhuo and Sim's
+        gradient ratio: the luma is smoothed by two Gaussians sigmas = (sigma_a, sigma_b); at an edge pixel of a step blurred by a
+        Gaussian of s the gradient magnitudes A and B stand in the ratio R = sqrt((s^2 + sigma_b^2) / (s^2 + sigma_a^2)), hence
+        s^2 = (sigma_b^2 - R^2 sigma_a^2) / (R^2 - 1).  An edge pixel is a local maximum of A along its gradient with A >= edge and a
+        reading of at most max_sigma.  sigma: float64, the A-weighted mean reading of the cell's edge pixels, NaN where it has none
+        (blur_map_fill fills them); weight: float32, the sum of A; count: int32, the edge pixels.  sparse=True: pixels is the h x w
+        float32 plane of the readings, -1 where there is none, written by the same launch; else None.  Every sum is float32 in
+        one fixed order: two calls give identical bits (csrc/ics_img_blurmap.hip, include/ics_hip.h; restated in
+        tests/blur_map_ref.py).  Only the grids (and the plane) cross PCIe; the call waits for them.  ValueError (before any native
+        call): sigmas outside 0.5 <= sigma_a < sigma_b, ceil(3 sigma_b) <= 8, edge or max_sigma not above 0, a window that is empty
+        or not inside the frame; after it: "... not finite: despeckle first" where the window holds a NaN or an inf."""
+        (sa, sb), edge, max_sigma, (y0, y1, x0, x1) = blur_map_args(sigmas, edge, max_sigma, window, self.shape)
+        h, w = y1 - y0, x1 - x0
+        rows, cols = -(-h // IMG_BLURMAP_CELL), -(-w // IMG_BLURMAP_CELL)
+        weight, moment, count = np.empty((rows, cols), np.float32), np.empty((rows, cols), np.float32), np.empty((rows, cols), np.int32)
+        plane = np.empty((h, w), np.float32) if sparse else None
+        bad = C.c_longlong()
+        fp = C.POINTER(C.c_float)
+        _check(load().ics_img_blur_map(self._h, y0, y1, x0, x1, sa, sb, edge, max_sigma, weight.ctypes.data_as(fp), moment.ctypes.data_as(fp),
+                                       count.ctypes.data_as(C.POINTER(C.c_int)), C.byref(bad), plane.ctypes.data_as(fp) if sparse else None, rows, cols))
+        if bad.value > 0:
+            raise ValueError("%d pixels of the window are not finite: despeckle first" % bad.value)
+        sigma = np.full((rows, cols), np.nan)
+        have = count > 0
+        sigma[have] = moment[have].astype(np.float64) / weight[have].astype(np.float64)
+        return BlurMap(sigma, weight, count, plane)
 
     def despeckle(self, threshold, radius=1, coupling="vector", route=0, count=False):
         """Thresholded median: removes impulses -- hot and dead sensor pixels, salt and pepper, NaN and inf -- and leaves every

@@ -32,6 +32,7 @@ Notes on reference quirks that are kept:
 from __future__ import annotations
 
 import collections
+import math
 import os
 import struct
 import time
@@ -256,7 +257,74 @@ def estimate_blur_width(src, max_width=63, window=None):
     return BlurWidth(width, ex, ey)
 
 
+BlurMap = _native.BlurMap
+
+
+def _blur_map_edge_form(edge):
+    """`edge` of blur_map -> (None, the number) or (strength, None) for "auto" / ("auto", strength), checked (ValueError)"""
+    if isinstance(edge, str):
+        if edge != "auto":
+            raise ValueError("edge %r (a number above 0, \"auto\" or (\"auto\", strength))" % (edge,))
+        return 5.0, None
+    if isinstance(edge, (tuple, list)):
+        if len(edge) != 2 or edge[0] != "auto":
+            raise ValueError("edge %r (a number above 0, \"auto\" or (\"auto\", strength))" % (edge,))
+        return _native._strength(edge[1]), None
+    return None, edge
+
+
+def blur_map(src, sigmas=(1.0, 2.0), edge=0.02, max_sigma=8.0, window=None, sparse=False, fill=False):
+    """Not in the reference, whose README lists local blur estimation first under what may come one day and motivates its mask with
+    "cases where the PSF varies spatially": a map of the local blur width of the picture, to see where the defocus lies before a
+    box is chosen for the PSF (`best_mask(blur=...)`).  Zhuo and Sim's gradient-ratio defocus map: the luma is smoothed by two
+    Gaussians sigmas = (sigma_a, sigma_b); at an edge pixel of a step blurred by a Gaussian of s the two gradient magnitudes stand in
+    the ratio R = sqrt((s^2 + sigma_b^2) / (s^2 + sigma_a^2)), which is solved for s.  Edge pixels are the local maxima of the
+    gradient along its direction at or above `edge`, readings above `max_sigma` are dropped, and the readings are averaged, weighted
+    by the gradient, over cells of 16 x 16 pixels from the window's origin (`DeviceImage.blur_map`, csrc/ics_img_blurmap.hip: one
+    launch, local, no PSF, a fixed cost).  Returns `lib._native.BlurMap(sigma, weight, count, pixels)`: sigma float64 per cell, NaN
+    where the cell holds no edge (fill=True: filled from the nearest cells that hold one, `lib._native.blur_map_fill`); weight the sum
+    of the gradient magnitudes; count the edge pixels; pixels the h x w plane of the readings (-1 where none) with sparse=True, else
+    None.  edge="auto" or ("auto", strength) (strength 5 unless given): `strength` standard deviations of the gradient under the
+    frame's noise (`noise_estimate(src, "vector")` on the same frame, `lib._native.blur_map_edge`).  window (y0, y1, x0, x1),
+    half-open: the region to map (None: the whole frame).  A `lib._native.DeviceImage` is read where it lies; an H x W x 3 array is
+    uploaded once and only the grid (and the plane) comes back.  It reports a sigma of Gaussian equivalence, not a PSF; it reads a
+    sharp edge as about 0.5 to 0.8, underestimates above about 2 sigma_b, assumes isolated step edges (texture finer than sigma_b
+    reads low) and is blind where no edge passes `edge`.  ValueError: sigmas outside 0.5 <= sigma_a < sigma_b with ceil(3 sigma_b) <=
+    8, edge or max_sigma not above 0, a bad window, a window with NaN or inf ("not finite: despeckle first")."""
+    strength, number = _blur_map_edge_form(edge)
+    if isinstance(src, _native.DeviceImage):
+        img, own = src, False
+        _native.blur_map_args(sigmas, 1.0 if number is None else number, max_sigma, window, img.shape)
+    else:
+        arr = np.asarray(src)
+        if arr.ndim != 3 or arr.shape[2] != 3:
+            raise ValueError("expected a DeviceImage or an H x W x 3 array, got shape %s" % (arr.shape,))
+        _native.blur_map_args(sigmas, 1.0 if number is None else number, max_sigma, window, arr.shape)   # refused before anything is uploaded
+        img, own = _native.DeviceImage.from_host(np.ascontiguousarray(arr, dtype=np.float32)), True
+    try:
+        if number is None:
+            number = _native.blur_map_edge(noise_estimate(img, "vector").sigma[0], sigmas[0], strength)
+        got = img.blur_map(sigmas, number, max_sigma, window, sparse)
+    finally:
+        if own:
+            img.close()
+    return got._replace(sigma=_native.blur_map_fill(got)) if fill else got
+
+
 MaskChoice = collections.namedtuple("MaskChoice", "center_y center_x score trace clipped")
+MaskChoiceBlur = collections.namedtuple("MaskChoiceBlur", "center_y center_x score trace clipped sigma")
+
+
+def mask_blur_args(blur):
+    """`blur` of best_mask checked (ValueError) and as (lo, hi): two finite numbers, 0 <= lo <= hi"""
+    try:
+        lo, hi = (float(v) for v in blur)
+        ok = not any(isinstance(v, (bool, str)) for v in blur) and 0 <= lo <= hi < math.inf
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError("blur %r ((lo, hi), two finite numbers, 0 <= lo <= hi: the range of the box's blur width)" % (blur,))
+    return lo, hi
 
 
 def best_mask_args(mask_size, clip, region, shape):
@@ -271,7 +339,7 @@ def best_mask_args(mask_size, clip, region, shape):
     return _native.window_scores_args(2 * (int(mask_size) // 2) + 1, region, clip, shape)
 
 
-def best_mask(src, mask_size=255, clip=0.99, region=None):
+def best_mask(src, mask_size=255, clip=0.99, region=None, blur=None):
     """Not in the reference, whose README has the user select "a specific zone to refine the PSF": the `mask` of `deblur_module` from
     the picture.  The blind phase estimates the PSF on one box of the frame; a box of sky or bokeh gives it nothing to estimate from,
     a box with one dominant edge direction leaves the PSF free along that direction, and clipped pixels break the linear blur model
@@ -283,7 +351,14 @@ def best_mask(src, mask_size=255, clip=0.99, region=None):
     (None: the whole frame).  A `lib._native.DeviceImage` is read where it lies; an H x W x 3 array is uploaded once and a few numbers
     come back.  It ranks boxes on a 16-px grid from the region's origin, scores the inner 16 (side // 16) pixels of a box, and
     prefers the sharpest textured zone: under a blur that varies over the frame that is the zone in focus, not necessarily the
-    subject.  ValueError: mask_size below 16, a bad region or one smaller than the box, clip not above 0."""
+    subject.  blur=(lo, hi) tells it which blur to look for: the candidates' scores (`window_scores(..., scores=True)`) and the
+    blur map of the same region (`blur_map` at its defaults, `lib._native.blur_map_box_sigma`: the weighted mean reading of the
+    box's cells) are taken, and the best-scoring box whose blur width lies in [lo, hi] is returned, ties as before, as
+    MaskChoiceBlur(center_y, center_x, score, trace, clipped, sigma), sigma being the box's blur width.  ValueError: mask_size
+    below 16, a bad region or one smaller than the box, clip not above 0, a bad blur range, "no box with a blur in ..." where none
+    qualifies."""
+    if blur is not None:
+        blur = mask_blur_args(blur)
     if isinstance(src, _native.DeviceImage):
         img, own = src, False
         size, region, clip = best_mask_args(mask_size, clip, region, img.shape)
@@ -294,11 +369,22 @@ def best_mask(src, mask_size=255, clip=0.99, region=None):
         size, region, clip = best_mask_args(mask_size, clip, region, arr.shape)   # refused before anything is uploaded
         img, own = _native.DeviceImage.from_host(np.ascontiguousarray(arr, dtype=np.float32)), True
     try:
-        got = img.window_scores(size, region, clip)
+        got = img.window_scores(size, region, clip, scores=blur is not None)
+        if blur is not None:
+            sig = _native.blur_map_box_sigma(img.blur_map(window=region), size, (region[1] - region[0], region[3] - region[2]))
+            ok = (sig >= blur[0]) & (sig <= blur[1])                        # (NaN: a box without an edge never qualifies)
+            if not ok.any():
+                raise ValueError("no box with a blur in [%g, %g] (the boxes read %s)" % (
+                    blur[0], blur[1], "nothing" if np.isnan(sig).all() else "%.2f to %.2f" % (np.nanmin(sig), np.nanmax(sig))))
+            i, j = divmod(int(np.argmax(np.where(ok, got.map, -1.0))), sig.shape[1])   # the largest score, ties to the lowest row, then column
+            by, bx, sigma = region[0] + _native.IMG_MASK_CELL * i, region[2] + _native.IMG_MASK_CELL * j, float(sig[i, j])
+            got = img.window_scores(size, (by, by + size, bx, bx + size), clip)        # the box alone: its score again, its trace and clipped count
     finally:
         if own:
             img.close()
     scored = float(_native.IMG_MASK_CELL * (size // _native.IMG_MASK_CELL)) ** 2
+    if blur is not None:
+        return MaskChoiceBlur(got.box_y + size // 2, got.box_x + size // 2, got.score, got.trace, got.clipped / scored, sigma)
     return MaskChoice(got.box_y + size // 2, got.box_x + size // 2, got.score, got.trace, got.clipped / scored)
 
 

@@ -540,6 +540,31 @@ int ics_img_blur_profile(const ics_img *src, int y0, int y1, int x0, int x1, int
 #define ICS_IMG_MASK_CELL 16
 int ics_img_window_scores(const ics_img *src, int y0, int y1, int x0, int x1, int size, float clip, int *box_y, int *box_x, double *score, double *trace,
                           long long *clipped, double *map, int map_rows, int map_cols);
+/* Blur map of a device image: the local blur width on a grid of 16 x 16 cells, in one launch (Zhuo and Sim's gradient ratio: the luma
+ * smoothed by two Gaussians sigma_a < sigma_b; at an edge pixel of a step blurred by a Gaussian of s the gradient magnitudes stand in
+ * the ratio R = sqrt((s^2 + sigma_b^2) / (s^2 + sigma_a^2))).  Over the half-open window [y0, y1) x [x0, x1), every coordinate clamped
+ * to the window, every operation rounded once to float32:
+ *   Y = (R + G + B) * (1 / 3)
+ *   taps g_s[i] = exp(-i^2 / (2 s^2)), i = -r .. r, r = ceilf(3.f * s), normalised in double on the host, rounded to float32
+ *   S_s = the rows pass, then the columns pass: acc = 0, acc = acc + g[i] * v for i ascending
+ *   gx = 0.5 * (S[y, x+1] - S[y, x-1]), gy likewise; A = sqrt(gx gx + gy gy) of S_sigma_a, B of S_sigma_b
+ *   sector of the gradient of S_sigma_a by ics_img_edge_mask's rule; neighbour offsets (dy, dx) = (0, 1), (1, 1), (1, 0), (1, -1)
+ *   kept: A > A[y+dy, x+dx], A >= A[y-dy, x-dx], A >= edge, B > 0, R = A / B > 1,
+ *     s2 = (sigma_b^2 - (R R) sigma_a^2) / (R R - 1) <= max_sigma^2; its value is sigma = sqrt(max(s2, 0))
+ *   cell (i, j) = the pixels [y0 + 16 i, y0 + 16 i + 16) x [x0 + 16 j, ...) of the window (ragged at the far edges): weight = sum A,
+ *     moment = sum A sigma, count, over its kept pixels -- a row left to right, the row sums top to bottom, a pixel that is not kept
+ *     adding exactly 0.  The cell's blur width is moment / weight.
+ * weight, moment, count: rows x cols entries, row-major, rows == ceil((y1 - y0) / 16), cols == ceil((x1 - x0) / 16).  *bad: the number
+ * of pixels of the window whose luma is not finite (the map around such a pixel means nothing: despeckle first).  sparse (may be NULL):
+ * (y1 - y0) x (x1 - x0) floats, sigma at the kept pixels and -1 elsewhere, written by the same launch.  No atomics: two runs give
+ * identical bits (restated in tests/blur_map_ref.py).  One route.  Queued on the context's stream, its kernel bracketed for
+ * ics_ctx_last_kernel_ms, then the grid (and the plane) is copied back and WAITED FOR.  src is not written.  ICS_EINVAL, the message
+ * naming the argument: src or an output NULL, a window that is empty or outside the frame, sigmas outside 0.5 <= sigma_a < sigma_b with
+ * ceilf(3.f * sigma_b) <= ICS_IMG_BLURMAP_MAX_RADIUS, edge or max_sigma not positive (or NaN), a grid of another shape. */
+#define ICS_IMG_BLURMAP_CELL 16
+#define ICS_IMG_BLURMAP_MAX_RADIUS 8
+int ics_img_blur_map(const ics_img *src, int y0, int y1, int x0, int x1, float sigma_a, float sigma_b, float edge, float max_sigma,
+                     float *weight, float *moment, int *count, long long *bad, float *sparse, int rows, int cols);
 /* Wiener deconvolution of a device image by a known PSF: a regularised inverse filter on one 2-D transform of the whole frame, the
  * fast non-blind step beside the Richardson-Lucy loop.  psf: K x K x 3 host floats (HWC like ics_rl_upload), K odd, 3 .. 255,
  * K <= min(H, W), every channel of sum 1 (the Python layer normalises); balance > 0.

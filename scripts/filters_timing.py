@@ -1,6 +1,6 @@
 """Timing of the lib/utils.py filters on one seeded SIZE x SIZE RGB float32 picture (GPU box), one JSON line:
 
-    python scripts/filters_timing.py [SIZE=4096] [guided | llf | noise | despeckle | blurwidth | mask | wiener | tvdeconv | tvmasked | psf | align | blindfast]       (a section name: that section alone)
+    python scripts/filters_timing.py [SIZE=4096] [guided | llf | noise | despeckle | blurwidth | blurmap | mask | wiener | tvdeconv | tvmasked | psf | align | blindfast]       (a section name: that section alone)
 
   resident   the filters on a DeviceImage in HBM (csrc/ics_img_filters.hip): device time of the kernels (HIP events around them,
              ics_ctx_last_kernel_ms; warm, median of 25) and wall time of the queued call up to a stream synchronise
@@ -49,6 +49,11 @@
              `deblur_module` end to end at blur 15 on the 8-bit picture bench.py uses (frames resident, iterations 20, the second
              call), which the estimate precedes; "one_nonblind_outer_ms" = 5 x the README's 0.47 ms per inner iteration at 4096^2 is
              what the estimate at max_width 63 is to stay under
+  blurmap    DeviceImage.blur_map on the resident frame (csrc/ics_img_blurmap.hip): the whole frame at sigmas (1, 2) (halo 8) and (1, 8 / 3)
+             (halo 10, the largest), with and without the sparse plane, and a window of 1023^2 with an odd origin (those that fit the
+             frame): kernel ms of the one launch (median and minimum of 9 rounds), the wall time of the call (it waits for its grid),
+             the cells, the edge pixels and the LDS bytes per workgroup; beside it DeviceImage.copy() of the same frame as in the
+             despeckle section (24 B/px against the 12 B/px this operator reads)
   mask       DeviceImage.window_scores on the resident frame (csrc/ics_img_mask.hip) at mask_size 63, 255 and 1023 (those that fit the
              frame), clip 0.99: kernel ms of the three launches (median and minimum of 9 rounds), the wall time of the call (it waits
              for its five numbers), the candidates, the cells per box and the LDS bytes per workgroup of the cell kernel; beside it
@@ -303,6 +308,32 @@ def blurwidth_section(img, ctx, size):
             dt = time.perf_counter() - t0
     res["deblur_module_blur15_seconds"] = round(dt, 4)
     res["one_nonblind_outer_ms"] = round(5 * 0.47, 2)
+    return res
+
+
+BLURMAP_CASES = (("frame", (1.0, 2.0), False, None), ("frame_sparse", (1.0, 2.0), True, None), ("frame_halo10", (1.0, 8 / 3), False, None),
+                 ("window_1023", (1.0, 2.0), False, 1023))
+
+
+def blurmap_section(img, ctx, size):
+    res = {"edge": 0.02}
+    for name, sigmas, sparse, side in BLURMAP_CASES:
+        if side is not None and side + 7 > size:
+            continue
+        window = None if side is None else (5, 5 + side, 7, 7 + side)
+        img.blur_map(sigmas, window=window, sparse=sparse)   # warm
+        ctx.synchronize()
+        kernel, wall = [], []
+        for _ in range(REPS_DESPECKLE):
+            t0 = time.perf_counter()
+            got = img.blur_map(sigmas, window=window, sparse=sparse)
+            wall.append((time.perf_counter() - t0) * 1e3)
+            kernel.append(ctx.last_kernel_ms())
+        r = int(np.ceil(float(np.float32(3.0) * np.float32(sigmas[1]))))
+        res[name] = {"sigmas": [round(v, 4) for v in sigmas], "halo": r + 2, "cells": int(got.count.size), "edge_pixels": int(got.count.sum()),
+                     "kernel_ms": round(float(np.median(kernel)), 4), "min_ms": round(float(np.min(kernel)), 4), "wall_ms": round(float(np.median(wall)), 4),
+                     "lds_bytes": 4 * ((36 + 2 * r) * (68 + 2 * r) + 2 * (36 + 2 * r) * 68 + 2 * 36 * 68 + 384 + 17)}
+    res["copy"] = copy_row(img, ctx)
     return res
 
 
@@ -686,6 +717,9 @@ def main():
     if sys.argv[2:] == ["blurwidth"]:
         print(json.dumps({"size": size, "device": ctx.name, "blurwidth": blurwidth_section(img, ctx, size)}))
         return 0
+    if sys.argv[2:] == ["blurmap"]:
+        print(json.dumps({"size": size, "device": ctx.name, "blurmap": blurmap_section(img, ctx, size)}))
+        return 0
     if sys.argv[2:] == ["mask"]:
         print(json.dumps({"size": size, "device": ctx.name, "mask": mask_section(img, ctx, size)}))
         return 0
@@ -764,6 +798,7 @@ def main():
     res["noise"] = noise_section(img, ctx, size)
     res["despeckle"] = despeckle_section(img, ctx, size)
     res["blurwidth"] = blurwidth_section(img, ctx, size)
+    res["blurmap"] = blurmap_section(img, ctx, size)
     res["mask"] = mask_section(img, ctx, size)
     res["wiener"] = wiener_section(ctx)
     res["tvdeconv"] = tvdeconv_section(ctx, size)
